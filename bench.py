@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: bipartite-graph edges/sec (fwd+bwd) per training step, setcov-500 batch=32 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,9 +14,14 @@ A step = forward + MSE + backward (+ one RCCL all-reduce of the flat gradient bu
 stacked synthetic batch already resident in HBM.  Weak scaling (default): 32 setcov-500 samples PER GPU.  Strong scaling:
 the global batch of 32 is split over the ranks by edge count (`parallel.shard_samples`).  Rank 0 prints ONE JSON line.
 
-Timing: a timed block is EXACTLY K steps bracketed by barrier + synchronize on both sides (max over ranks).  Blocks are
-repeated until at least --min-seconds of timed region exist (so that a small K still gives a measurable run);
+Timing: a timed block is EXACTLY K steps bracketed by barrier + synchronize on both sides (max over ranks).  By default one
+block is timed, so exactly K steps are; --min-seconds S repeats the block until S seconds of timed region exist.
 `ms_per_step` / `value` come from the MEDIAN block, HIP events record the same blocks on the compute stream.
+
+`--dump-outputs DIR`: rank 0 writes what the last timed step computed -- the (loss, scores) pair `train_step` returns, the
+flat gradient and the flat parameters after Adam -- as DIR/<name>.npy (float32, a few hundred KB).  Inputs are fixed by
+the arguments (seeded synthetic samples, `GCNN(seed=0)`), so two builds can be compared output for output
+(`--dump-outputs bench_outputs` is git-ignored).
 
 `roofline`: the standalone scatter-sum pass (K9, the pass BASELINE.json's 40%-of-HBM target names), timed live with HIP
 events in its own loop.  `roofline_step`: the kernels of the training step itself, launch by launch (HIP events inside the
@@ -48,12 +53,17 @@ def parse(argv=None):
     ap.add_argument("--problem", default="setcov", choices=["setcov", "combauc", "capfac", "indset"])
     ap.add_argument("--batch", type=int, default=32, help="samples per GPU (weak scaling) / in the global batch (strong scaling)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="repeat the K-step block until this much time is measured")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step block until this much time is measured "
+                    "(default 0: one block, exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="capture the step once and replay it as a hipGraph (measured: no faster than eager issue -- the GPU-side dependency chain is the limit, not the host)")
     ap.add_argument("--stub-worker", action="store_true", help=argparse.SUPPRESS)   # tests/test_host.py: ranks on CPU over gloo, no GPU work
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _import_heavy():
@@ -439,7 +449,7 @@ def main():
         step()
     blocks_wall, blocks_dev = [], []
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    loss = None
+    loss = last_scores = None
     while True:
         if group is not None:
             dist.barrier()
@@ -447,7 +457,7 @@ def main():
         t0 = time.perf_counter()
         ev0.record()
         for _ in range(args.steps):     # EXACTLY K steps per timed block
-            loss, _ = step()
+            loss, last_scores = step()
         ev1.record()
         torch.cuda.synchronize()
         if group is not None:
@@ -462,6 +472,11 @@ def main():
         blocks_dev.append(dev_ms)
         if sum(blocks_wall) >= args.min_seconds or len(blocks_wall) >= 1000:
             break
+    # what the last timed step computed, copied before anything below runs more steps on the same model
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = {"loss": loss.detach().float().cpu().numpy().reshape(-1), "scores": last_scores.detach().float().cpu().numpy(),
+                  "grads": ts.grads.detach().float().cpu().numpy(), "params": model.flat_parameters.detach().float().cpu().numpy()}
     from gcnn_cut_selector_amd import _lib
     with _lib.launch_profile() as prof:   # one more step on every rank, outside the timed region: how many launches a step is
         train_step(model, batch, targets, opt, ts, process_group=group)
@@ -520,6 +535,11 @@ def main():
     if not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.problem, args.batch, 0)
         out["config"]["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["best_value"], 1)   # against the fastest CPU point
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": {k: list(v.shape) for k, v in dumped.items()}}
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
     print(json.dumps(out), flush=True)

@@ -317,6 +317,19 @@ def test_bench_gpus_n_launches_n_ranks_itself():
     assert wrong.returncode != 0 and not wrong.stdout.strip()
 
 
+def test_bench_steps_sets_the_timed_steps_and_dump_outputs_parses():
+    """By default bench.py times ONE block of exactly --steps steps (--min-seconds 0); --dump-outputs takes a directory."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.steps == 7 and args.min_seconds == 0 and args.dump_outputs is None
+    assert bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
 def test_out_of_memory_skips_a_batch_single_gpu_and_propagates_data_parallel(monkeypatch, capsys):
     """The reference skips a batch that exhausts memory (model_trainer.py:308-311: `except ResourceExhaustedError: print(WARNING)`).
     Single GPU: the same.  Data parallel: the peers are already in this step's all-reduce, so a rank must not skip on its own --
