@@ -14,6 +14,9 @@
 // Wavefront = 64 lanes everywhere.  No atomics on floats anywhere: every sum has a fixed order => bitwise
 // reproducible results.
 
+#include <mutex>
+#include <unordered_map>
+
 #include "gcnn_common.hpp"
 #include "k_rows.hpp"
 #include "k_edge.hpp"
@@ -181,13 +184,16 @@ static int launch_edge_fwd(const EdgeArgs& a, int n_edges, int max_deg, bool cou
 }
 // backward, sender-ordered (owner = sender)
 // *n_parts = rows of a.dw_partial written (one per block of the launch(es)): what k_reduce has to sum into d w_edge
-static int launch_edge_bwd_send(EdgeArgs a, int n_edges, int max_deg, int* n_parts, hipStream_t st) {
+// (rows [0, *n_main) of the main blocks, then one per long-segment block; n_main = NULL: not wanted)
+static int launch_edge_bwd_send(EdgeArgs a, int n_edges, int max_deg, int* n_parts, hipStream_t st, int* n_main = nullptr) {
     *n_parts = 0;
+    if (n_main) *n_main = 0;
     if (a.n_own <= 0) return 0;
     const int slots = edge_slots(a.n_own, n_edges);
     const int grid = std::min(cdiv(cdiv(a.n_own, 4 / slots), 4), EDGE_MAX_GRID);
     const int lb = edge_needs_long_pass(slots, max_deg) ? edge_long_grid(a.n_own) : 0;
     *n_parts = grid + lb;
+    if (n_main) *n_main = grid;
     ProfScope prof(lb ? "k_edge_bwd_send + long segments" : "k_edge_bwd_send", st);
     if (slots == 4) hipLaunchKernelGGL((k_edge_bwd_send<4, false>), dim3(grid), dim3(256), 0, st, a, 0);
     else if (slots == 2 && lb) hipLaunchKernelGGL((k_edge_bwd_send<2, true>), dim3(grid + lb), dim3(256), 0, st, a, lb);
@@ -273,7 +279,7 @@ static void carve(const gcnn_dims* d, float* base, Work* w) {
 
 extern "C" {
 
-int gcnn_abi_version(void) { return 11; }
+int gcnn_abi_version(void) { return 12; }
 
 int gcnn_profile_begin(void) {
     int d = 0;
@@ -735,7 +741,7 @@ static int check_common(const gcnn_dims* d, const float* params, const gcnn_grap
 }
 
 // `targets` != nullptr: the last launch also evaluates the MSE head and the readout's Dense(64->1) gradient (CF_LOSS)
-static int forward_impl(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats,
+static int forward_enqueue(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats,
                         const float* cut_feats, const gcnn_graph* cg, const gcnn_graph* kg, float* workspace,
                         size_t workspace_floats, float* scores, int save_mode, const float* targets, float loss_scale,
                         hipStream_t st, IplanArgs* plan = nullptr) {
@@ -780,6 +786,33 @@ static int forward_impl(const gcnn_dims* d, const float* p, const float* cons_fe
         return conv_forward(p, cv[2], save, st, p + poff(P_OUT), p + poff(P_OUT + 1), nullptr, CF_LOSS, scores, &head);
     }
     return conv_forward(p, cv[2], save, st, p + poff(P_OUT), p + poff(P_OUT + 1), save ? A.O1 : nullptr, CF_READOUT, scores, nullptr, nullptr, keep_a);
+}
+// Which form the last forward on a workspace ran (its save mode; -1: it failed), keyed by the workspace pointer.  Only the
+// two-layer form (2) leaves the scatter-sum outputs A that gcnn_prenorm_stats reads for layers 6, 8 and 10: any other form
+// leaves whatever A an earlier forward wrote, so those layers refuse unless the last forward was that form.  Host-side only:
+// set when the forward is enqueued.  A table grown past FORM_TABLE_MAX entries (workspaces that came and went) starts over,
+// which can only make a later query refuse.
+#define FORM_TABLE_MAX 4096
+static std::mutex g_form_mu;
+static std::unordered_map<const float*, int> g_form;
+static void set_form(const float* ws, int mode) {
+    std::lock_guard<std::mutex> lk(g_form_mu);
+    if (g_form.size() >= FORM_TABLE_MAX && !g_form.count(ws)) g_form.clear();
+    g_form[ws] = mode;
+}
+static int last_form(const float* ws) {
+    std::lock_guard<std::mutex> lk(g_form_mu);
+    const auto it = g_form.find(ws);
+    return it == g_form.end() ? -1 : it->second;
+}
+static int forward_impl(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats,
+                        const float* cut_feats, const gcnn_graph* cg, const gcnn_graph* kg, float* workspace,
+                        size_t workspace_floats, float* scores, int save_mode, const float* targets, float loss_scale,
+                        hipStream_t st, IplanArgs* plan = nullptr) {
+    const int rc = forward_enqueue(d, p, cons_feats, var_feats, cut_feats, cg, kg, workspace, workspace_floats, scores, save_mode,
+                                   targets, loss_scale, st, plan);
+    set_form(workspace, rc ? -1 : save_mode);
+    return rc;
 }
 extern "C" int gcnn_forward(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats,
                  const float* cut_feats, const gcnn_graph* cg, const gcnn_graph* kg, float* workspace,
@@ -1018,13 +1051,17 @@ static int conv_backward_edges(const float* p, float* grads, const ConvIO& c, co
     // (the ReLU pattern is recomputed) and leaves d w_edge as one 64-float partial per block
     EdgeArgs e = conv_edge_args(p, c, !c.recv_left);
     e.d_s = c.gS; e.out = c.recv_left ? c.gPR : c.gPL; e.dw_partial = c.DWP;
-    int dw_parts = 0;
-    if ((rc = launch_edge_bwd_send(e, c.ne, c.recv_left ? c.g->v_max_deg : c.g->l_max_deg, &dw_parts, st))) return rc;
+    int dw_parts = 0, dw_main = 0;
+    if ((rc = launch_edge_bwd_send(e, c.ne, c.recv_left ? c.g->v_max_deg : c.g->l_max_deg, &dw_parts, st, &dw_main))) return rc;
     if (dw_parts > 0) {   // DW_CHUNK partial rows per block of the k_wgrad launch, then the usual fixed-order reduction
+        // the main blocks' rows and the long-segment blocks' rows are chunked apart and the latter added last, so that a pass
+        // that runs long-segment blocks without need (longest segment unknown) adds exactly 0 and the bits do not change
         const int k = jl.ndw++;
-        jl.dw.src[k] = c.DWP; jl.dw.dst[k] = c.DWP2; jl.dw.nparts[k] = dw_parts;
-        jl.dw.blk0[k + 1] = jl.dw.blk0[k] + cdiv(dw_parts, DW_CHUNK);
-        add_rd(jl, c.DWP2, grads + poff(c.pbase + C_WE), cdiv(dw_parts, DW_CHUNK), EMB, EMB);
+        const int nmc = dw_main_chunks(dw_main), nlc = cdiv(dw_parts - dw_main, DW_CHUNK);
+        jl.dw.src[k] = c.DWP; jl.dw.dst[k] = c.DWP2; jl.dw.nparts[k] = dw_parts; jl.dw.nmain[k] = dw_main;
+        jl.dw.blk0[k + 1] = jl.dw.blk0[k] + nmc + nlc;
+        if (nlc) { jl.rd.tail_job[k] = jl.rd.njobs; jl.rd.tail_n[k] = nlc; }
+        add_rd(jl, c.DWP2, grads + poff(c.pbase + C_WE), nmc, EMB, EMB);
     }
     const int* seg = c.recv_left ? c.g->l_ptr : c.g->v_ptr;
     add_wg(jl, c.Z1, nullptr, c.gOUT, nullptr, nr, grads + poff(c.pbase + C_W2), grads + poff(c.pbase + C_B2), nullptr, w.partial);
@@ -1188,6 +1225,8 @@ extern "C" int gcnn_prenorm_stats(const gcnn_dims* d, const float* p, const floa
         const int fs[5] = {4, 1, 14, 6, 1};
         a.src = ST_COLS; a.x = xs[layer]; a.n = ns[layer]; a.f = fs[layer]; units = a.f; count = (double)a.n;
     } else {
+        // the projections P every forward form writes (5, 7, 9) / A, which only the two-layer form writes (6, 8, 10)
+        if (last_form(workspace) < (((layer - 5) & 1) ? 2 : 0)) return GCNN_E_BADARG;
         ConvIO cv[3]; conv_setup(cv, d, w, cg, kg);
         const ConvIO& c = cv[(layer - 5) >> 1];
         if (((layer - 5) & 1) == 0) {   // feature_module_final's PreNorm: all E*64 joint pre-activations, one unit

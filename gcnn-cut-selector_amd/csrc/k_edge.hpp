@@ -398,10 +398,10 @@ __device__ __forceinline__ void edge_bwd_send_impl(const EdgeArgs& a, const floa
             }
         }
     }
-    edge_dw_block_store<SLOTS>(dwsum, s1, a.dw_partial + (size_t)blockIdx.x * EMB, L.ch);
+    edge_dw_block_store<SLOTS>(dwsum, s1, a.dw_partial + (size_t)bid * EMB, L.ch);
 }
 template <int SLOTS>
-__device__ __forceinline__ void edge_bwd_send_long_body(const EdgeArgs& a, int nb, int blk, int thresh) {
+__device__ __forceinline__ void edge_bwd_send_long_body(const EdgeArgs& a, int nb, int blk, int thresh, float* dw_row) {
     constexpr int G = 16 * SLOTS, NG = 256 / G;
     __shared__ float4 red[NG][16];
     const float s1 = *a.s1;
@@ -425,14 +425,21 @@ __device__ __forceinline__ void edge_bwd_send_long_body(const EdgeArgs& a, int n
         }
         __syncthreads();
     });
-    edge_dw_block_store<SLOTS>(dwsum, s1, a.dw_partial + (size_t)blockIdx.x * EMB, L.ch);
+    edge_dw_block_store<SLOTS>(dwsum, s1, dw_row, L.ch);
 }
-// every block (long-row blocks first, see k_edge_fwd) leaves one partial row of d w_edge at dw_partial[blockIdx.x]
+// Every block leaves one partial row of d w_edge.  The main blocks (the last nblk of the launch) own rows [0, nblk) whether or
+// not long-segment blocks ride in front of them; those write rows nblk + blockIdx.x behind.  So the rows of the main blocks, and
+// the order in which they are added up (DW_CHUNK groups, k_wgrad.hpp), do not depend on the long-segment launch: a pass that
+// runs it without need (longest segment unknown) adds its all-zero rows as a separate last term, +0 (gcnn_capi.hip).
 template <int SLOTS, bool LONG = false>
 __global__ __launch_bounds__(256) void k_edge_bwd_send(EdgeArgs a, int long_blocks) {
-    if (LONG && (int)blockIdx.x < long_blocks) { edge_bwd_send_long_body<SLOTS>(a, long_blocks, blockIdx.x, edge_long_threshold(SLOTS)); return; }
+    const int nblk = gridDim.x - (LONG ? long_blocks : 0);
+    if (LONG && (int)blockIdx.x < long_blocks) {
+        edge_bwd_send_long_body<SLOTS>(a, long_blocks, blockIdx.x, edge_long_threshold(SLOTS), a.dw_partial + (size_t)(nblk + blockIdx.x) * EMB);
+        return;
+    }
     const float s1 = *a.s1;
-    const int bid = blockIdx.x - (LONG ? long_blocks : 0), nblk = gridDim.x - (LONG ? long_blocks : 0);
+    const int bid = blockIdx.x - (LONG ? long_blocks : 0);
     if (s1 < 0.f) edge_bwd_send_impl<SLOTS, true>(a, s1, bid, nblk); else edge_bwd_send_impl<SLOTS, false>(a, s1, bid, nblk);
 }
 

@@ -186,14 +186,19 @@ __device__ __forceinline__ void wg_body(const WgJob& jb, float* slab, int rbeg, 
 
 // d w_edge: the edge-gradient passes leave one 64-float partial per thread block (up to thousands).  Third block type of
 // this launch: block j of convolution c adds DW_CHUNK consecutive partial rows in a fixed order, so that k_reduce is left
-// with a few dozen rows per convolution like for every other gradient.
+// with a few dozen rows per convolution like for every other gradient.  The rows of the main blocks [0, nmain) and those of
+// the long-segment blocks [nmain, nparts) are chunked apart (main chunks first): the main rows are grouped the same way whether
+// or not long-segment blocks ran, and k_reduce adds the long chunks' sum as one last term (RdArgs.tail_*).
 #define DW_CHUNK 128
-struct DwRedArgs { const float* src[3]; float* dst[3]; int nparts[3]; int blk0[4]; };
+struct DwRedArgs { const float* src[3]; float* dst[3]; int nparts[3]; int nmain[3]; int blk0[4]; };
+__host__ __device__ inline int dw_main_chunks(int nmain) { return (nmain + DW_CHUNK - 1) / DW_CHUNK; }
 __device__ __forceinline__ void dw_reduce_block(const DwRedArgs& d, int b, float* red) {
     int c = 0;
     while (c < 2 && b >= d.blk0[c + 1]) ++c;
     const int chunk = b - d.blk0[c], col = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int p0 = chunk * DW_CHUNK, p1 = min(d.nparts[c], p0 + DW_CHUNK);
+    const int nmc = dw_main_chunks(d.nmain[c]);
+    const int p0 = chunk < nmc ? chunk * DW_CHUNK : d.nmain[c] + (chunk - nmc) * DW_CHUNK;
+    const int p1 = min(chunk < nmc ? d.nmain[c] : d.nparts[c], p0 + DW_CHUNK);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     const float* src = d.src[c] + col;
     int p = p0 + part;
@@ -257,7 +262,9 @@ struct RdJob { const float* src; float* dst; int nparts; int stride; int len; in
 // optional fused optimizer step: every reduced element that lies inside the flat gradient buffer [gbase, gbase+gn) is a
 // finished gradient, so the Keras-form Adam update (see k_adam) of the same flat slot can follow in the same thread
 struct RdAdam { float* p; float* m; float* v; const float* gbase; int gn; float lr_t, b1, b2, eps; };
-struct RdArgs { int njobs; float* cdst; float cval; RdAdam adam; RdJob job[RD_MAX_JOBS]; };   // cdst (optional): a constant the launch also stores
+// cdst (optional): a constant the launch also stores.  tail_*: up to three jobs (the d w_edge ones) whose source continues with
+// tail_n[i] more rows after its nparts: they are summed on their own, in the same fixed order, and added to the job's sum last
+struct RdArgs { int njobs; float* cdst; float cval; RdAdam adam; int tail_job[3], tail_n[3]; RdJob job[RD_MAX_JOBS]; };
 
 // ---------------------------------------------------------------------------------------------------------------
 // Gradients of the folded layers (k_rows.hpp, Program 2): the forward uses M = s2*Wf*W1a and u = s2*bf*W1a, the weight-gradient
@@ -388,21 +395,25 @@ __global__ __launch_bounds__(256) void k_reduce(RdArgs a, FoldArgs f) {
     const int chunk = bid - jb.blk0;
     const int col = threadIdx.x & 63, part = threadIdx.x >> 6;
     const int e = chunk * EMB + col;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (e < jb.len) {
-        const float* src = jb.src + e;
+    int ntail = 0;
+    for (int t = 0; t < 3; ++t) if (a.tail_n[t] > 0 && a.tail_job[t] == ji) ntail = a.tail_n[t];
+    const auto rows_sum = [&](const float* src, int n) {
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
         int p = part;
-        for (; p + 12 < jb.nparts; p += 16) {  // 4 loads in flight per thread; the order of the adds is fixed
+        for (; p + 12 < n; p += 16) {  // 4 loads in flight per thread; the order of the adds is fixed
             const float v0 = src[(size_t)p * jb.stride], v1 = src[(size_t)(p + 4) * jb.stride];
             const float v2 = src[(size_t)(p + 8) * jb.stride], v3 = src[(size_t)(p + 12) * jb.stride];
             s0 += v0; s1 += v1; s2 += v2; s3 += v3;
         }
-        for (; p < jb.nparts; p += 4) s0 += src[(size_t)p * jb.stride];
-    }
-    red[part][col] = (s0 + s1) + (s2 + s3);
+        for (; p < n; p += 4) s0 += src[(size_t)p * jb.stride];
+        return (s0 + s1) + (s2 + s3);
+    };
+    red[part][col] = e < jb.len ? rows_sum(jb.src + e, jb.nparts) : 0.f;
+    if (ntail) red[4 + part][col] = e < jb.len ? rows_sum(jb.src + (size_t)jb.nparts * jb.stride + e, ntail) : 0.f;
     __syncthreads();
     if (part == 0 && e < jb.len) {
-        const float gi = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
+        float gi = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
+        if (ntail) gi += (red[4][col] + red[5][col]) + (red[6][col] + red[7][col]);
         jb.dst[e] = gi;
         const long long idx = (jb.dst + e) - a.adam.gbase;
         if (a.adam.p && idx >= 0 && idx < a.adam.gn) {

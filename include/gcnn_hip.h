@@ -129,7 +129,9 @@ int gcnn_linear_bwd(float* dy, const float* ymask, const float* wa, const float*
  *           t_e = [s1*J_e > 0] * d_s[r]:
  *           d_p_send[u] = s1*sum_{e in seg(u)} t_e ;  the gradient of feature_module_edge's kernel (model.py:490-492),
  *           s1*sum_e c_e*t_e, is left as *n_parts partial rows dw_partial[i][64] (one per thread block, fixed summation
- *           order; the caller adds the rows up).  dw_partial must hold GCNN_EDGE_DW_PARTS rows. */
+ *           order; the caller adds the rows up): the main blocks' rows first, then, when the pass ran them (max_degree
+ *           0 or beyond the long-segment threshold), one per long-segment block.  dw_partial must hold GCNN_EDGE_DW_PARTS
+ *           rows. */
 #define GCNN_EDGE_DW_PARTS 16384
 int gcnn_conv_edge_fwd(const int32_t* seg_ptr, const int32_t* oth, const float* coef, int32_t n_recv, int32_t n_edges,
                        const float* p_recv, const float* p_oth, const float* w_edge, const float* e_shift,
@@ -238,7 +240,12 @@ int gcnn_backward(const gcnn_dims* dims, const float* params, const float* cons_
  * 5+2k / 6+2k = feature_module_final / post_conv_module of convolution k) writes the population mean [units] followed by
  * the mean squared deviation [units] of that layer's input to out_mean_var (device doubles; units = 4,1,14,6,1 for the
  * input layers, 1 otherwise).  Layers >= 5 read activations of a preceding gcnn_forward(save_for_backward=2) on the same
- * workspace, inputs and parameters.  The streaming merge over batches (Chan et al.) is the caller's, as in the reference. */
+ * workspace, inputs and parameters.  The library records which form the last gcnn_forward / gcnn_forward_loss on a
+ * workspace (keyed by its pointer) ran, and returns GCNN_E_BADARG instead of reading stale memory: for layers 6, 8 and 10
+ * (the scatter-sum outputs A, which only save_for_backward = 2 stores) unless that forward was save_for_backward = 2, for
+ * layers 5, 7 and 9 (the projections, which every form stores) unless a forward on the workspace succeeded at all.  It cannot
+ * tell whether that forward had the same inputs and parameters: that stays the caller's part.
+ * The streaming merge over batches (Chan et al.) is the caller's, as in the reference. */
 int gcnn_prenorm_stats(const gcnn_dims* dims, const float* params, const float* cons_feats, const float* var_feats,
                        const float* cut_feats, const gcnn_graph* cons_graph, const gcnn_graph* cut_graph,
                        float* workspace, size_t workspace_floats, int32_t layer, double* out_mean_var, void* stream);

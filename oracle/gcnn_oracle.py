@@ -167,11 +167,61 @@ def prenorm(x, shift, scale, hook=None, key=None):
     return x
 
 
-def dense(x, w, b=None, relu=False):
+class ReluHook:
+    """Optional hook on every ReLU of forward() -- test infrastructure for telling a rounding-level branch flip from a defect.
+
+    Sites (names): `{cons,var,cut}_emb_1`, `{cons,var,cut}_emb_2` (the embeddings' Dense layers), `{conv}_joint` (the per-edge
+    relu(joint) of feature_module_final, rows = edges in input order), `{conv}_out_1`, `{conv}_out_2` (output_module) and `out_1`
+    (the head's hidden layer).  Units are (site, row, column).
+
+    record: keeps, per site, the pre-activation z and its magnitude m = the sum of the absolute values of the summands z is
+        made of (for a Dense layer |x| @ |W| + |b|; for the joint, those of the three projections it adds) -- a bound for the
+        rounding error of z in any evaluation order is a small multiple of u * m -- and, once a backward pass has run, the
+        gradient g of the loss w.r.t. the ReLU's output and the largest |input| of each row (`rows`: the row's |x| entries for
+        a Dense layer; for the joint, its scale times the largest entry of the two gathered rows and the edge feature).  A flip
+        of unit (r, c) moves the gradient of dz[r, c] by g[r, c], hence its layer's bias gradient by that much and its kernel
+        gradient by up to rows[r] times that.
+    force: {(site, row, col), ...} -- these units take the branch opposite to the one their own z selects (z > 0: dead; z <= 0:
+        passes z on), in value and in gradient.
+    Without a hook forward() runs torch.relu unchanged."""
+
+    def __init__(self, force=(), record=True):
+        self.force = {}
+        for site, row, col in force:
+            self.force.setdefault(site, []).append((int(row), int(col)))
+        self.record = record
+        self.sites = {}   # site -> (z, m), detached
+        self.grads = {}   # site -> g (after backward)
+        self.rows = {}    # site -> largest |input| per row
+
+    def __call__(self, site, z, magnitude, rows):
+        keep = z > 0
+        units = self.force.get(site)
+        if units:
+            keep = keep.clone()
+            rows_, cols = (torch.tensor(a) for a in zip(*units))
+            keep[rows_, cols] = ~keep[rows_, cols]
+        out = z * keep.to(z.dtype)
+        if self.record:
+            self.sites[site] = (z.detach().clone(), magnitude().detach())
+            self.rows[site] = rows().detach()
+            if out.requires_grad:
+                out.register_hook(lambda g: self.grads.__setitem__(site, g.detach().clone()))
+        return out
+
+
+def _relu(z, relu_hook, site, magnitude, rows):
+    return torch.relu(z) if relu_hook is None else relu_hook(site, z, magnitude, rows)
+
+
+def dense(x, w, b=None, relu=False, relu_hook=None, site=None):
     y = x @ w
     if b is not None:
         y = y + b
-    return torch.relu(y) if relu else y
+    if not relu:
+        return y
+    return _relu(y, relu_hook, site, lambda: x.abs() @ w.abs() + (b.abs() if b is not None else 0),
+                 lambda: x.abs().amax(1) if x.shape[1] else x.new_zeros(x.shape[0]))
 
 
 def scatter_nd_sum(updates, index, out_size):
@@ -181,24 +231,39 @@ def scatter_nd_sum(updates, index, out_size):
     return out
 
 
-def conv(p, name, left, ei, ef, var, out_size, from_v, hook=None):
+def conv(p, name, left, ei, ef, var, out_size, from_v, hook=None, relu_hook=None):
     """PartialGraphConvolution.call, model.py:533-575, materialising every [E,64] tensor like the reference."""
     recv_idx, recv = (ei[0], left) if from_v else (ei[1], var)  # model.py:553-560
-    joint = (dense(left, p[f"{name}_feat_left/kernel"], p[f"{name}_feat_left/bias"]).index_select(0, ei[0])
-             + dense(ef, p[f"{name}_feat_edge/kernel"])
-             + dense(var, p[f"{name}_feat_right/kernel"]).index_select(0, ei[1]))  # model.py:564-565
+    wl, bl, we, wr = (p[f"{name}_feat_left/kernel"], p[f"{name}_feat_left/bias"], p[f"{name}_feat_edge/kernel"],
+                      p[f"{name}_feat_right/kernel"])
+    joint = (dense(left, wl, bl).index_select(0, ei[0])
+             + dense(ef, we)
+             + dense(var, wr).index_select(0, ei[1]))  # model.py:564-565
     joint = prenorm(joint, None, p[f"{name}_final_prenorm/scale"], hook, f"{name}_final_prenorm/scale")
-    joint = dense(torch.relu(joint), p[f"{name}_feat_final/kernel"], p[f"{name}_feat_final/bias"])  # :498-500
+
+    def joint_magnitude():
+        s = p[f"{name}_final_prenorm/scale"].abs()
+        return s * ((left.abs() @ wl.abs() + bl.abs()).index_select(0, ei[0]) + ef.abs() @ we.abs()
+                    + (var.abs() @ wr.abs()).index_select(0, ei[1]))
+    def joint_rows():
+        s = p[f"{name}_final_prenorm/scale"].abs()
+        return s * torch.maximum(torch.maximum(left.abs().amax(1).index_select(0, ei[0]), ef.abs().amax(1)),
+                                 var.abs().amax(1).index_select(0, ei[1]))
+    joint = dense(_relu(joint, relu_hook, f"{name}_joint", joint_magnitude, joint_rows), p[f"{name}_feat_final/kernel"],
+                  p[f"{name}_feat_final/bias"])  # :498-500
     agg = scatter_nd_sum(joint, recv_idx, out_size)  # model.py:568-569
     agg = prenorm(agg, None, p[f"{name}_post_prenorm/scale"], hook, f"{name}_post_prenorm/scale")  # :570
-    h = dense(torch.cat([agg, recv], dim=1), p[f"{name}_out_1/kernel"], p[f"{name}_out_1/bias"], relu=True)
-    return dense(h, p[f"{name}_out_2/kernel"], p[f"{name}_out_2/bias"], relu=True)  # model.py:573
+    h = dense(torch.cat([agg, recv], dim=1), p[f"{name}_out_1/kernel"], p[f"{name}_out_1/bias"], relu=True,
+              relu_hook=relu_hook, site=f"{name}_out_1")
+    return dense(h, p[f"{name}_out_2/kernel"], p[f"{name}_out_2/bias"], relu=True, relu_hook=relu_hook,
+                 site=f"{name}_out_2")  # model.py:573
 
 
-def _embed(p, prefix, x, hook):
+def _embed(p, prefix, x, hook, relu_hook=None):
     x = prenorm(x, p[f"{prefix}_prenorm/shift"], p[f"{prefix}_prenorm/scale"], hook, f"{prefix}_prenorm/scale")
-    x = dense(x, p[f"{prefix}_emb_1/kernel"], p[f"{prefix}_emb_1/bias"], relu=True)
-    return dense(x, p[f"{prefix}_emb_2/kernel"], p[f"{prefix}_emb_2/bias"], relu=True)
+    x = dense(x, p[f"{prefix}_emb_1/kernel"], p[f"{prefix}_emb_1/bias"], relu=True, relu_hook=relu_hook, site=f"{prefix}_emb_1")
+    return dense(x, p[f"{prefix}_emb_2/kernel"], p[f"{prefix}_emb_2/bias"], relu=True, relu_hook=relu_hook,
+                 site=f"{prefix}_emb_2")
 
 
 def as_inputs(state, dtype=torch.float32):
@@ -209,25 +274,27 @@ def as_inputs(state, dtype=torch.float32):
     return f(c), i(cei), f(cef), f(v), f(k), i(kei), f(kef), int(nc), int(nv), int(nk)
 
 
-def forward(p, inputs, hook=None):
-    """GCNN.call, model.py:257-300.  `inputs` from as_inputs(); returns flat [n_cuts] scores (model.py:300)."""
+def forward(p, inputs, hook=None, relu_hook=None):
+    """GCNN.call, model.py:257-300.  `inputs` from as_inputs(); returns flat [n_cuts] scores (model.py:300).
+    `relu_hook`: an optional ReluHook on every ReLU."""
     c, cei, cef, v, k, kei, kef, n_cons, n_vars, n_cuts = inputs
-    c = _embed(p, "cons", c, hook)  # model.py:287
+    c = _embed(p, "cons", c, hook, relu_hook)  # model.py:287
     cef = prenorm(cef, p["cons_edge_prenorm/shift"], p["cons_edge_prenorm/scale"], hook, "cons_edge_prenorm/scale")
-    v = _embed(p, "var", v, hook)  # model.py:289
-    k = _embed(p, "cut", k, hook)  # model.py:290
+    v = _embed(p, "var", v, hook, relu_hook)  # model.py:289
+    k = _embed(p, "cut", k, hook, relu_hook)  # model.py:290
     kef = prenorm(kef, p["cut_edge_prenorm/shift"], p["cut_edge_prenorm/scale"], hook, "cut_edge_prenorm/scale")
-    c = conv(p, "cons_conv", c, cei, cef, v, n_cons, True, hook)  # model.py:294
-    v = conv(p, "var_conv", c, cei, cef, v, n_vars, False, hook)  # model.py:295
-    k = conv(p, "cut_conv", k, kei, kef, v, n_cuts, True, hook)  # model.py:296
-    out = dense(dense(k, p["out_1/kernel"], p["out_1/bias"], relu=True), p["out_2/kernel"], p["out_2/bias"])
+    c = conv(p, "cons_conv", c, cei, cef, v, n_cons, True, hook, relu_hook)  # model.py:294
+    v = conv(p, "var_conv", c, cei, cef, v, n_vars, False, hook, relu_hook)  # model.py:295
+    k = conv(p, "cut_conv", k, kei, kef, v, n_cuts, True, hook, relu_hook)  # model.py:296
+    out = dense(dense(k, p["out_1/kernel"], p["out_1/bias"], relu=True, relu_hook=relu_hook, site="out_1"),
+                p["out_2/kernel"], p["out_2/bias"])
     return out.reshape(-1)  # model.py:299-300
 
 
-def loss_and_grads(params: dict, state, targets, dtype=torch.float32):
+def loss_and_grads(params: dict, state, targets, dtype=torch.float32, relu_hook=None):
     """model_trainer.py:266-273: loss = mean((pred - y)^2) over ALL cuts; grads w.r.t. the 46 trainables."""
     p = to_torch(params, dtype, requires_grad=True)
-    pred = forward(p, as_inputs(state, dtype))
+    pred = forward(p, as_inputs(state, dtype), relu_hook=relu_hook)
     y = torch.as_tensor(np.asarray(targets), dtype=dtype)
     loss = ((pred - y) ** 2).mean()
     names = [n for n, _, t in PARAM_SPEC if t]
@@ -235,9 +302,9 @@ def loss_and_grads(params: dict, state, targets, dtype=torch.float32):
     return pred.detach().numpy(), float(loss.detach()), {n: g.numpy() for n, g in zip(names, grads)}
 
 
-def scores(params: dict, state, dtype=torch.float32):
+def scores(params: dict, state, dtype=torch.float32, relu_hook=None):
     with torch.no_grad():
-        return forward(to_torch(params, dtype), as_inputs(state, dtype)).numpy()
+        return forward(to_torch(params, dtype), as_inputs(state, dtype), relu_hook=relu_hook).numpy()
 
 
 def keras_adam_step(theta, grad, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-7):

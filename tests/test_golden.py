@@ -79,11 +79,16 @@ def test_hip_reproduces_golden_step(dev, golden_dir):
     y = torch.as_tensor(z["targets"], dtype=torch.float32).to(dev)
     loss, _ = train_step(m, batch, y, None, ts)       # gradients only
     assert abs(float(loss) - float(z["loss"])) <= 1e-4 * max(1.0, float(z["loss"]))
-    grads = [g.cpu().numpy() for g in m.gradients(ts.grads)]
+    # the rule of tests/test_gpu_model.py _grad_check: 1e-4 of each tensor's largest entry, or twice the distance of the fp32
+    # restatement from fp64 where that is larger; beyond it only a proven ReLU flip passes (tests/gradparity.py)
+    import gradparity
     names = [n for n, _, t in O.PARAM_SPEC if t]
-    for name, g in zip(names, grads):
-        ref = z["g_" + name.replace("/", "__")]
-        assert np.abs(g - ref).max() <= 5e-4 * max(np.abs(ref).max(), 1e-6) + 1e-7, name
+    got = dict(zip(names, (g.cpu().numpy() for g in m.gradients(ts.grads))))
+    want = {n: z["g_" + n.replace("/", "__")].astype(np.float64) for n in names}
+    flips = gradparity.check(got, _weights(z, np.float32), _state(z, "in_"), z["targets"],
+                             lambda ref, gap: max(1e-4 * ref, 2 * gap) + 1e-7, want64=want)
+    if flips:
+        print(f"\ngolden step: gradients match with ReLU units {flips} flipped")
     # two optimizer steps with the GOLDEN gradient (isolates the Adam kernel from gradient noise)
     flat_g = torch.zeros_like(m.flat_parameters.detach())
     for (off, rows, cols, tr), name in zip(m._layout, O.PARAM_NAMES):

@@ -146,7 +146,7 @@ def _grad_check(m, params, state, y, rtol=1e-4):
     # Tolerance: fp32 kernels vs the fp64 oracle, relative to the largest entry of each tensor: 1e-4 (measured on these cases:
     # 2e-7 .. 5e-6, as close as or closer than torch's own fp32 evaluation of the restatement).  The exception is inherent to
     # fp32: a ReLU pre-activation that lands within rounding of 0 can take the other branch than in fp64, and one such edge
-    # moves a gradient entry by that edge's whole share (capfac at scale 0.2: 5e-4 of the largest entry -- for the fp32
+    # moves a gradient entry by that edge's whole share (capfac at scale 0.2: 0.05 % of the largest entry -- for the fp32
     # restatement exactly as for the kernels).  So where the reference's arithmetic itself (fp32, restated) is farther than
     # 1e-4 from fp64, the bound is twice ITS distance.
     pred = m(state, True)

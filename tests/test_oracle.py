@@ -198,3 +198,83 @@ def test_ranking_fraction():
     assert O.ranking_fraction(np.array([3., 2, 1]), np.array([9., 5, 1])) == 1.0
     assert O.ranking_fraction(np.array([3., 1, 2]), np.array([9., 5, 1])) == pytest.approx(1 / 3)
     assert O.ranking_fraction(np.array([1., 2, 3]), np.array([9., 5, 1])) == 0.0
+
+
+def test_relu_hook_records_and_forces_one_unit():
+    """ReluHook: an empty hook changes nothing; the recorded pre-activations and magnitudes are those of the layer; forcing one
+    unit of the head's hidden layer changes the loss and the head's gradients exactly as the hand-computed flip predicts."""
+    p, st = _params(4), _tiny_state(2)
+    y = np.array([0.1, -0.2, 0.05])
+    pred0, loss0, g0 = O.loss_and_grads(p, st, y, torch.float64)
+    rec = O.ReluHook()
+    pred1, loss1, g1 = O.loss_and_grads(p, st, y, torch.float64, relu_hook=rec)
+    assert np.array_equal(pred0, pred1) and loss0 == loss1
+    assert all(np.array_equal(g0[n], g1[n]) for n in g0)
+    sites = {f"{e}_emb_{i}" for e in ("cons", "var", "cut") for i in (1, 2)}
+    sites |= {f"{c}_{s}" for c in ("cons_conv", "var_conv", "cut_conv") for s in ("joint", "out_1", "out_2")} | {"out_1"}
+    assert set(rec.sites) == sites
+    assert rec.sites["cons_conv_joint"][0].shape == (st[1].shape[1], 64)
+    for z, m in rec.sites.values():
+        assert bool((m >= z.abs() * (1 - 1e-12)).all())
+    # the head by hand from the recorded tensors: k = relu(z of cut_conv_out_2), z1 = k W1 + b1
+    k = torch.relu(rec.sites["cut_conv_out_2"][0]).numpy()
+    z1 = rec.sites["out_1"][0].numpy()
+    np.testing.assert_allclose(z1, k @ p["out_1/kernel"] + p["out_1/bias"], rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(rec.sites["out_1"][1].numpy(), np.abs(k) @ np.abs(p["out_1/kernel"]) + np.abs(p["out_1/bias"]),
+                               rtol=1e-12)
+    w2, b2 = p["out_2/kernel"], p["out_2/bias"]
+
+    def head(mask):
+        h = z1 * mask
+        pred = (h @ w2 + b2).reshape(-1)
+        d = 2 * (pred - y) / len(y)                       # d loss / d pred
+        dz = (d[:, None] * w2[:, 0][None, :]) * mask     # d loss / d z1
+        return pred, np.mean((pred - y) ** 2), {"out_2/kernel": h.T @ d[:, None], "out_2/bias": d.sum(keepdims=True),
+                                                 "out_1/bias": dz.sum(0), "out_1/kernel": k.T @ dz}
+    mask = (z1 > 0).astype(np.float64)
+    r, c = np.unravel_index(np.argmin(np.abs(z1)), z1.shape)   # the unit nearest its kink: the one rounding could flip
+    flipped = mask.copy()
+    flipped[r, c] = 1 - flipped[r, c]
+    for msk, (pr, ls, gs) in ((mask, (pred0, loss0, g0)), (flipped, O.loss_and_grads(
+            p, st, y, torch.float64, relu_hook=O.ReluHook(force=[("out_1", r, c)], record=False)))):
+        want_pred, want_loss, want = head(msk)
+        np.testing.assert_allclose(pr, want_pred, rtol=1e-12, atol=1e-13)
+        assert abs(ls - want_loss) <= 1e-12 * max(1.0, want_loss)
+        for name, w in want.items():
+            np.testing.assert_allclose(gs[name], w, rtol=1e-11, atol=1e-13, err_msg=name)
+    # the flip moves out_1/kernel in column c only, by the unit's own share k[r] * dz[r, c]
+    _, _, gf = O.loss_and_grads(p, st, y, torch.float64, relu_hook=O.ReluHook(force=[("out_1", r, c)], record=False))
+    moved = np.abs(gf["out_1/kernel"] - g0["out_1/kernel"]).max(0) > 0
+    if abs(z1[r, c]) > 0:
+        assert moved[c]
+    # forcing a unit elsewhere (a joint unit of the first convolution: edge 3, constraint 2 -> variable 2, which reaches the cuts)
+    # reaches the gradients before it
+    _, _, gj = O.loss_and_grads(p, st, y, torch.float64, relu_hook=O.ReluHook(force=[("cons_conv_joint", 3, 0)], record=False))
+    assert not np.array_equal(gj["cons_conv_feat_final/kernel"], g0["cons_conv_feat_final/kernel"])
+
+
+def test_flip_proof_accepts_a_proven_flip_and_rejects_a_defect():
+    """tests/gradparity.py on the CPU: gradients of the fp64 oracle with one ambiguous unit forced (what an fp32 evaluation that
+    rounds that unit the other way computes) pass only through that proof; the same gradients with one column of a weight
+    gradient moved by 2e-4 of its largest entry -- the size of a flip, but not a flip -- fail."""
+    import gradparity
+    from test_gpu_stress import CASES, _state
+    params = O.randomize_params(O.init_params(11, np.float32), 12)
+    p64 = {k: v.astype(np.float64) for k, v in params.items()}
+    rng = np.random.default_rng(1005)
+    state = _state(CASES[5], rng)
+    y = rng.uniform(0, 0.2, state[9])
+    units = gradparity.ambiguous_units(p64, state, y)
+    assert 1 <= len(units) <= gradparity.MAX_AMBIGUOUS, units
+    unit = units[0][:3]
+    _, _, flipped = O.loss_and_grads(p64, state, y, torch.float64, relu_hook=O.ReluHook(force=[unit], record=False))
+    got = {n: g.astype(np.float32) for n, g in flipped.items()}
+    rule = lambda ref, gap: max(1e-4 * ref, 3 * gap) + 1e-7 * ref
+    _, _, plain = O.loss_and_grads(p64, state, y, torch.float64)
+    assert any(np.abs(flipped[n] - plain[n]).max() > 1e-4 * np.abs(plain[n]).max() for n in plain)   # the flip is visible
+    assert gradparity.check(got, params, state, y, rule) == [unit]
+    bad = {n: g.astype(np.float32) for n, g in plain.items()}
+    w = bad["var_conv_out_1/kernel"]
+    w[:, 7] += 2e-4 * np.abs(plain["var_conv_out_1/kernel"]).max()
+    with pytest.raises(AssertionError):
+        gradparity.check(bad, params, state, y, rule)
