@@ -1,5 +1,11 @@
 #!/bin/sh
 # Build libgcnn_hip.so for MI355X (gfx950).  hipcc cross-compiles without a GPU.
+# `build.sh tuning`: the experiment build libgcnn_hip_tuning.so instead -- the same sources with -DGCNN_TUNING, which reads the
+# tuning knobs of tools/README.md from the environment (the variant tests force each dispatch variant through it).
 set -e
 cd "$(dirname "$0")"
+if [ "$1" = tuning ]; then
+  shift
+  exec /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -shared -fPIC -DGCNN_TUNING -o libgcnn_hip_tuning.so gcnn_capi.hip "$@"
+fi
 exec /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -shared -fPIC -o libgcnn_hip.so gcnn_capi.hip "$@"

@@ -34,8 +34,18 @@
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // Tuning knobs (tools/README.md): an experiment build (-DGCNN_TUNING, tools/mklib.sh) reads them from the environment once per
 // process; the product library is built without and every knob is its compile-time default -- no getenv on the launch path.
+// An experiment build says on stderr, once per call site, which value it took ("gcnn knob GCNN_SPLIT_MAX_TILES=0"): the tests
+// that force a variant read that line as proof the setting reached the library.
 #ifdef GCNN_TUNING
-#define GCNN_KNOB(name, dflt) ([] { static const int v_ = getenv(name) ? atoi(getenv(name)) : (dflt); return v_; }())
+#include <cstdio>
+#include <cstdlib>
+static int gcnn_knob_read(const char* name, int dflt) {
+    const char* s = getenv(name);
+    const int v = s ? atoi(s) : dflt;
+    fprintf(stderr, "gcnn knob %s=%d\n", name, v);
+    return v;
+}
+#define GCNN_KNOB(name, dflt) ([] { static const int v_ = gcnn_knob_read(name, (dflt)); return v_; }())
 #else
 #define GCNN_KNOB(name, dflt) (dflt)
 #endif

@@ -334,36 +334,52 @@ _BITS_SCRIPT = r"""
 import hashlib, sys
 import numpy as np, torch
 sys.path.insert(0, {root!r})
-from gcnn_cut_selector_amd import synthetic, utils
+from gcnn_cut_selector_amd import _lib, synthetic, utils
 from gcnn_cut_selector_amd.model import GCNN
 from gcnn_cut_selector_amd.trainer import TrainState, train_step
 from oracle import gcnn_oracle as O
+assert _lib.LIB_PATH == {lib!r}, _lib.LIB_PATH
 dev = torch.device("cuda", 0)
 params = O.randomize_params(O.init_params(31, np.float32), 32)
 m = GCNN(device=dev); m.set_weights([params[n] for n in O.PARAM_NAMES])
 state, y, _ = synthetic.make_batch("setcov", 6)
-batch = m.prepare(state); ts = TrainState(m)
-loss, scores = train_step(m, batch, torch.as_tensor(y).to(dev), None, ts)
+with _lib.launch_profile() as prof:
+    batch = m.prepare(state); ts = TrainState(m)
+    loss, scores = train_step(m, batch, torch.as_tensor(y).to(dev), None, ts)
+    s1, _ = synthetic.make_sample("combauc", 2)
+    single = utils.state_to_inputs(s1)
+    with torch.no_grad():
+        plain = m(single, False).numpy()
+    ranked = m.score_state(single, rank=True)
 h = hashlib.sha256()
 h.update(ts.grads.cpu().numpy().tobytes()); h.update(scores.cpu().numpy().tobytes()); h.update(np.float32(float(loss)).tobytes())
-s1, _ = synthetic.make_sample("combauc", 2)
-h.update(m.score_state(utils.state_to_inputs(s1), rank=True).numpy().tobytes())
+h.update(plain.tobytes()); h.update(ranked.numpy().tobytes()); h.update(np.asarray(ranked.rankings).tobytes())
+print("LAUNCHES", "|".join(n for n, _ in prof.launches))
 print("BITS", h.hexdigest())
 """
 
 
 def test_few_tile_programs_give_the_same_bits_as_the_one_wave_programs(dev):
     """k_rows_split.hpp (four waves per tile; launches of <= 256 tiles: the training turnaround, single-state inference) keeps
-    the MFMA order per output element, so gradients, scores and loss must not change by one bit when it is switched off
-    (GCNN_SPLIT_MAX_TILES=0, read once per process -> two child processes)."""
+    the MFMA order per output element, so gradients, scores, loss and inference scores must not change by one bit when it is
+    switched off (GCNN_SPLIT_MAX_TILES=0).  The product library has the knob compiled in, so both children load the experiment
+    build (libgcnn_hip_tuning.so, -DGCNN_TUNING), and each must prove the setting took: the library's knob line on stderr, and
+    the embedding launch of the small no-grad forward is k_embed_fwd_split with 256 and k_embed_fwd with 0."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = []
+    lib = os.path.join(root, "gcnn-cut-selector_amd", "csrc", "libgcnn_hip_tuning.so")
+    assert os.path.exists(lib), "build() makes libgcnn_hip_tuning.so"
+    out, launches = [], []
     for knob in ("256", "0"):
-        env = dict(os.environ, GCNN_SPLIT_MAX_TILES=knob)
-        r = subprocess.run([sys.executable, "-c", _BITS_SCRIPT.format(root=root)], env=env, capture_output=True, text=True, timeout=600)
+        env = dict(os.environ, GCNN_SPLIT_MAX_TILES=knob, GCNN_LIB=lib)
+        r = subprocess.run([sys.executable, "-c", _BITS_SCRIPT.format(root=root, lib=lib)], env=env, capture_output=True, text=True,
+                           timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
+        assert f"gcnn knob GCNN_SPLIT_MAX_TILES={knob}" in r.stderr.splitlines(), r.stderr[-2000:]
         out.append([l for l in r.stdout.splitlines() if l.startswith("BITS")][-1])
+        launches.append([l for l in r.stdout.splitlines() if l.startswith("LAUNCHES")][-1][len("LAUNCHES "):].split("|"))
+    assert "k_embed_fwd_split" in launches[0], launches[0]
+    assert "k_embed_fwd_split" not in launches[1] and "k_embed_fwd" in launches[1], launches[1]
     assert out[0] == out[1]
 
 
