@@ -16,7 +16,7 @@ import torch  # noqa: F401  -- MUST be imported before the CDLL below: torch shi
 #                              would register the kernels with a second HIP runtime (hipErrorNoDevice at first launch)
 
 LIB_PATH = os.environ.get("GCNN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libgcnn_hip.so")  # GCNN_LIB: A/B builds
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class GcnnError(RuntimeError):
@@ -44,12 +44,16 @@ class InferLayout(C.Structure):
                 ("arena_bytes", C.c_size_t), ("dev_off", C.c_size_t * 8)]
 
 
+class SelectLayout(C.Structure):
+    _fields_ = [("infer", InferLayout), ("forced_off", C.c_size_t * 3), ("n_kept_off", C.c_size_t), ("ws_off", C.c_size_t)]
+
+
 class CollateJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("unit_kind", C.c_int32), ("width", C.c_int32),
                 ("add_kind", C.c_int32), ("is_ptr", C.c_int32)]
 
 
-_P, _I, _F, _Z = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
+_P, _I, _F, _Z, _D = C.c_void_p, C.c_int32, C.c_float, C.c_size_t, C.c_double
 _DP, _GP = C.POINTER(Dims), C.POINTER(Graph)
 
 # name -> (restype, argtypes); every symbol include/gcnn_hip.h declares
@@ -84,6 +88,10 @@ SIGNATURES = {
     "gcnn_adam_step_dev": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P]),
     "gcnn_host_sort_edges_by_row": (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "gcnn_host_pack_edges": (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    "gcnn_select_workspace_bytes": (_Z, [_I, _I, _I]),
+    "gcnn_select_cuts": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _D, _P, _P, _P, _Z, _P]),
+    "gcnn_infer_select_layout_for": (C.c_int, [_DP, _I, _I, C.POINTER(SelectLayout)]),
+    "gcnn_infer_select": (C.c_int, [_DP, _I, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
 }
 
 _lib = None

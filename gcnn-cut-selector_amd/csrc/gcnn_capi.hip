@@ -289,7 +289,7 @@ static void carve(const gcnn_dims* d, float* base, Work* w) {
 
 extern "C" {
 
-int gcnn_abi_version(void) { return 12; }
+int gcnn_abi_version(void) { return 13; }
 
 int gcnn_profile_begin(void) {
     int d = 0;
@@ -833,7 +833,10 @@ extern "C" int gcnn_forward(const gcnn_dims* d, const float* p, const float* con
 }
 // ---- single-state inference: the SCIP cut selector's call (model_evaluator.py:82-111) as ONE entry point --------------------
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) {
+// extra_in / extra_out: a block behind the inputs (in the upload) / behind the flags (in the download), for callers that extend the
+// call (gcnn_infer_select); gcnn_infer's own layout is the one with both zero.  The extra input block starts at the in_bytes of the
+// plain layout, the extra output block at its out_bytes.
+static int infer_layout(const gcnn_dims* d, size_t extra_in, size_t extra_out, gcnn_infer_layout* L) {
     if (!d || !L || d->n_cons < 0 || d->n_vars < 0 || d->n_cuts < 0 || d->n_cons_edges < 0 || d->n_cut_edges < 0) return GCNN_E_BADARG;
     if (d->n_vars > IPLAN_MAX_VARS) return GCNN_E_UNSUPPORTED;
     const size_t C = d->n_cons, V = d->n_vars, K = d->n_cuts, E1 = d->n_cons_edges, E2 = d->n_cut_edges;
@@ -847,9 +850,10 @@ extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) {
     L->in_off[5] = take(24 * K);                     // cut_feats [K,6]
     L->in_off[6] = take(8 * E2);                     // cut_edge_inds [2,E2]
     L->in_off[7] = take(4 * E2);                     // cut_edge_feats [E2]
+    if (extra_in) take(extra_in);
     L->in_bytes = off;
     L->out_off[0] = 0; L->out_off[1] = al16(4 * K); L->out_off[2] = L->out_off[1] + al16(4 * K);
-    L->out_bytes = L->out_off[2] + 16;               // scores[K] | order[K] | flags[4]
+    L->out_bytes = L->out_off[2] + 16 + extra_out;   // scores[K] | order[K] | flags[4] | extra
     // device arena: the uploaded block, the plan, the output block, the forward workspace
     size_t a = off;
     auto dev = [&](size_t bytes) { const size_t o = a; a += (bytes + 255) & ~(size_t)255; return o; };
@@ -861,6 +865,32 @@ extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) {
     L->arena_bytes = a;
     return 0;
 }
+extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) { return infer_layout(d, 0, 0, L); }
+
+// The upload, the graph plan and the forward pass of the single-state call: scores land at A + L.dev_off[6]; *kg receives the cut
+// edge set as the arena holds it (by-left CSR = the uploaded list), *flags the plan's flag words.
+static int infer_forward(const gcnn_dims* d, const float* params, const void* host_in, char* A, const gcnn_infer_layout& L,
+                         hipStream_t st, gcnn_graph* kg, const int** flags) {
+    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));      // ONE upload: zero block + the seven arrays
+    const int C = d->n_cons, V = d->n_vars, K = d->n_cuts, E1 = d->n_cons_edges, E2 = d->n_cut_edges;
+    int* zero = (int*)(A + L.in_off[0]);
+    IplanArgs ia; memset(&ia, 0, sizeof(ia));
+    ia.s[0] = IplanSet{(int*)(A + L.in_off[2]), E1, C, (int*)(A + L.dev_off[0])};
+    ia.s[1] = IplanSet{(int*)(A + L.in_off[6]), E2, K, (int*)(A + L.dev_off[1])};
+    ia.n_vars = V; ia.vcount = zero; ia.cursor = zero + V; ia.flags = zero + 2 * V;
+    ia.v_ptr = (int*)(A + L.dev_off[2]); ia.v_pos = (int*)(A + L.dev_off[3]); ia.v_oth = (int*)(A + L.dev_off[4]);
+    ia.v_coef = (float*)(A + L.dev_off[5]); ia.cons_coef = (const float*)(A + L.in_off[3]);
+    gcnn_graph cg; memset(&cg, 0, sizeof(cg)); memset(kg, 0, sizeof(*kg));
+    cg.l_ptr = ia.s[0].l_ptr; cg.l_oth = ia.s[0].inds + E1; cg.l_coef = ia.cons_coef;       // by-left order = the input lists
+    cg.v_ptr = ia.v_ptr; cg.v_oth = ia.v_oth; cg.v_coef = ia.v_coef;
+    kg->l_ptr = ia.s[1].l_ptr; kg->l_oth = ia.s[1].inds + E2; kg->l_coef = (const float*)(A + L.in_off[7]);
+    kg->v_ptr = ia.v_ptr;   // never read: conv v->k gathers by cut only and nothing is differentiated
+    *flags = ia.flags;
+    float* out = (float*)(A + L.dev_off[6]);
+    // the plan's three steps ride in the forward pass's first three launches (k_infer.hpp)
+    return forward_impl(d, params, (const float*)(A + L.in_off[1]), (const float*)(A + L.in_off[4]), (const float*)(A + L.in_off[5]),
+                        &cg, kg, (float*)(A + L.dev_off[7]), gcnn_workspace_floats(d), out, 0, nullptr, 0.f, st, &ia);
+}
 
 extern "C" int gcnn_infer(const gcnn_dims* d, const float* params, const void* host_in, void* host_out, void* arena,
                           size_t arena_bytes, int32_t want_order, void* stream) {
@@ -871,31 +901,18 @@ extern "C" int gcnn_infer(const gcnn_dims* d, const float* params, const void* h
     if (want_order && d->n_cuts > 4096) return GCNN_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
-    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));      // ONE upload: zero block + the seven arrays
-    const int C = d->n_cons, V = d->n_vars, K = d->n_cuts, E1 = d->n_cons_edges, E2 = d->n_cut_edges;
-    int* zero = (int*)(A + L.in_off[0]);
-    IplanArgs ia; memset(&ia, 0, sizeof(ia));
-    ia.s[0] = IplanSet{(int*)(A + L.in_off[2]), E1, C, (int*)(A + L.dev_off[0])};
-    ia.s[1] = IplanSet{(int*)(A + L.in_off[6]), E2, K, (int*)(A + L.dev_off[1])};
-    ia.n_vars = V; ia.vcount = zero; ia.cursor = zero + V; ia.flags = zero + 2 * V;
-    ia.v_ptr = (int*)(A + L.dev_off[2]); ia.v_pos = (int*)(A + L.dev_off[3]); ia.v_oth = (int*)(A + L.dev_off[4]);
-    ia.v_coef = (float*)(A + L.dev_off[5]); ia.cons_coef = (const float*)(A + L.in_off[3]);
-    gcnn_graph cg, kg; memset(&cg, 0, sizeof(cg)); memset(&kg, 0, sizeof(kg));
-    cg.l_ptr = ia.s[0].l_ptr; cg.l_oth = ia.s[0].inds + E1; cg.l_coef = ia.cons_coef;       // by-left order = the input lists
-    cg.v_ptr = ia.v_ptr; cg.v_oth = ia.v_oth; cg.v_coef = ia.v_coef;
-    kg.l_ptr = ia.s[1].l_ptr; kg.l_oth = ia.s[1].inds + E2; kg.l_coef = (const float*)(A + L.in_off[7]);
-    kg.v_ptr = ia.v_ptr;   // never read: conv v->k gathers by cut only and nothing is differentiated
-    float* out = (float*)(A + L.dev_off[6]);
-    // the plan's three steps ride in the forward pass's first three launches (k_infer.hpp)
-    rc = forward_impl(d, params, (const float*)(A + L.in_off[1]), (const float*)(A + L.in_off[4]), (const float*)(A + L.in_off[5]),
-                      &cg, &kg, (float*)(A + L.dev_off[7]), gcnn_workspace_floats(d), out, 0, nullptr, 0.f, st, &ia);
+    gcnn_graph kg;
+    const int* flags = nullptr;
+    rc = infer_forward(d, params, host_in, A, L, st, &kg, &flags);
     if (rc) return rc;
+    const int K = d->n_cuts;
+    float* out = (float*)(A + L.dev_off[6]);
     if (want_order && K > 0) {
         ProfScope prof("k_rank_scores", st);
         hipLaunchKernelGGL(k_rank_scores, dim3(1), dim3(256), 0, st, out, K, (int*)((char*)out + L.out_off[1]));
         LAUNCHCHK();
     }
-    HIPCHK(hipMemcpyAsync((char*)out + L.out_off[2], ia.flags, 16, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync((char*)out + L.out_off[2], flags, 16, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));  // ONE download: scores | order | flags
     return 0;
 }
@@ -1304,3 +1321,6 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
     LAUNCHCHK();
     return 0;
 }
+
+// the cut selection (include/gcnn_hip.h: gcnn_select_cuts, gcnn_infer_select): its own launchers and launch names
+#include "gcnn_select.hpp"

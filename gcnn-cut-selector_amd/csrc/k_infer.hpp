@@ -151,20 +151,21 @@ __device__ __forceinline__ void iplan_order_body(const IplanArgs& a, const int b
 __global__ __launch_bounds__(256) void k_iplan_order(IplanArgs a) { iplan_order_body<256>(a, blockIdx.x, gridDim.x); }
 
 // Descending stable ranking of the scores (model_evaluator.py:110-111: sorted(range(n), key=quality, reverse=True) keeps equal
-// scores in index order): the same bitonic network and total order as the ranking metric.  One block, n <= RK_MAX.
-__global__ __launch_bounds__(256) void k_rank_scores(const float* __restrict__ scores, int n, int* __restrict__ order) {
-    __shared__ float v[4096];
-    __shared__ int ix[4096];
+// scores in index order): the same bitonic network and total order as the ranking metric.  Run by all NT threads of a block,
+// n <= RK_MAX; leaves the sorted keys (NaN as -inf) in v and the cut indices in ix, ix[0] = the best cut.  Shared by
+// k_rank_scores and the cut selection's filter (k_select.hpp).
+template <int NT>
+__device__ __forceinline__ void rank_desc_lds(const float* __restrict__ scores, int n, float* v, int* ix) {
     int m = 1;
     while (m < n) m <<= 1;
-    for (int i = threadIdx.x; i < m; i += 256) {
+    for (int i = threadIdx.x; i < m; i += NT) {
         const float x = i < n ? scores[i] : -INFINITY;
         v[i] = x != x ? -INFINITY : x; ix[i] = i < n ? i : 0x7fffffff;
     }
     __syncthreads();
     for (int k = 2; k <= m; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < m; i += 256) {
+            for (int i = threadIdx.x; i < m; i += NT) {
                 const int p = i ^ j;
                 if (p > i) {
                     const bool up = (i & k) == 0;
@@ -177,6 +178,12 @@ __global__ __launch_bounds__(256) void k_rank_scores(const float* __restrict__ s
             }
             __syncthreads();
         }
+}
+// One block, n <= RK_MAX.
+__global__ __launch_bounds__(256) void k_rank_scores(const float* __restrict__ scores, int n, int* __restrict__ order) {
+    __shared__ float v[4096];
+    __shared__ int ix[4096];
+    rank_desc_lds<256>(scores, n, v, ix);
     for (int i = threadIdx.x; i < n; i += 256) order[i] = ix[i];
 }
 

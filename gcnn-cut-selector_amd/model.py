@@ -79,6 +79,17 @@ class ScoreArray(np.ndarray):
         return np.asarray(self)
 
 
+class SelectResult:
+    """What `GCNN.select_cuts` returns: `order` (int32 cut indices in STATE order: the kept cuts first, best first, then the
+    removed ones), `n_selected` = min(n_kept, max_selected) -- the reference's 'nselectedcuts' --, `n_kept` and the `scores`."""
+
+    def __init__(self, order, n_kept, n_selected, scores):
+        self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
+
+    def __repr__(self):
+        return f"SelectResult(n_selected={self.n_selected}, n_kept={self.n_kept}, order={self.order!r})"
+
+
 class _UseGeneralPath(Exception):
     """The specialised single-state path declined (unsorted edge list, very long segment, too many variables)."""
 
@@ -108,10 +119,24 @@ class _InferenceSession:
             self.layouts[key] = lay
         return lay
 
-    def run(self, inputs, want_order, timings=None):
-        """`timings` (optional dict): filled with the host-side phases in seconds (tools/latency.py)."""
-        import time
-        t0 = time.perf_counter()
+    def _select_layout(self, key, n_forced, n_entries):
+        skey = key + (n_forced, n_entries)
+        lay = self.layouts.get(skey)
+        if lay is None:
+            dims, lay = _lib.Dims(*key), _lib.SelectLayout()
+            rc = _lib.lib().gcnn_infer_select_layout_for(C.byref(dims), n_forced, n_entries, C.byref(lay))
+            if rc == -4:
+                lay = False
+            else:
+                _lib.check(rc, "gcnn_infer_select_layout_for")
+                lay = (dims, lay.infer, list(lay.infer.in_off), list(lay.infer.out_off), lay)
+            if len(self.layouts) >= 256:
+                self.layouts.pop(next(iter(self.layouts)))
+            self.layouts[skey] = lay
+        return lay
+
+    @staticmethod
+    def _check_inputs(inputs):
         c, cei, cef, v, k, kei, kef, n_cons, n_vars, n_cuts = inputs
         c, v, k = np.asarray(c), np.asarray(v), np.asarray(k)
         cei, kei, cef, kef = np.asarray(cei), np.asarray(kei), np.asarray(cef), np.asarray(kef)
@@ -131,15 +156,10 @@ class _InferenceSession:
             # flags catch everything that is out of range but representable)
             if ei.dtype != np.int32 and ei.size and (int(ei.max()) > 2 ** 31 - 1 or int(ei.min()) < -2 ** 31):
                 raise ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
-        # The specialised plan wants lists sorted by row, which is what get_state emits (utils.py:102-104).  Packing is one native
-        # pass per list (gcnn_host_pack_edges): copy into the staging buffer, look at the order on the way, and only a list in
-        # another order goes through a stable counting sort on the host (tens of microseconds for a few 10^4 entries; NumPy's
-        # stable argsort alone would take longer than the whole general path).
         key = (c.shape[0], v.shape[0], k.shape[0], cei.shape[1], kei.shape[1])
-        lay = self._layout(key)
-        if lay is False or (want_order and key[2] > 4096):
-            raise _UseGeneralPath()
-        dims, L, in_off, out_off = lay
+        return (c, cei, cef, v, k, kei, kef), key
+
+    def _buffers(self, L):
         dev = self.model.device
         if self.pin_in is None or self.pin_in.numel() < L.in_bytes:
             self.pin_in = torch.empty(max(2 * L.in_bytes, 1 << 20), dtype=torch.uint8).pin_memory()
@@ -150,6 +170,9 @@ class _InferenceSession:
         if self.arena is None or self.arena.numel() < L.arena_bytes:
             self.arena = None
             self.arena = torch.empty(max(2 * L.arena_bytes, 1 << 24), dtype=torch.uint8, device=dev)
+
+    def _pack(self, arrays, key, in_off):
+        c, cei, cef, v, k, kei, kef = arrays
         buf = self.in_np
         buf[in_off[0]:in_off[1]] = 0      # the plan's counters and flags travel zeroed inside the upload
         base = self.pin_in.data_ptr()
@@ -167,6 +190,30 @@ class _InferenceSession:
                                                  ei32.shape[1], n_left, base + io, base + fo, self.sort_scratch.ctypes.data)
             if rc < 0:      # (0 / 1 / 2: packed -- as it was, sorted here, or as it was with a row id the device check reports)
                 _lib.check(rc, "gcnn_host_pack_edges")
+
+    def _flags(self, out_off):
+        flags = self.out_np[out_off[2]:out_off[2] + 16].view(np.int32)
+        if flags[0]:
+            raise ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
+        if flags[1] or flags[2] or flags[3]:
+            raise _UseGeneralPath()
+
+    def run(self, inputs, want_order, timings=None):
+        """`timings` (optional dict): filled with the host-side phases in seconds (tools/latency.py)."""
+        import time
+        t0 = time.perf_counter()
+        arrays, key = self._check_inputs(inputs)
+        # The specialised plan wants lists sorted by row, which is what get_state emits (utils.py:102-104).  Packing is one native
+        # pass per list (gcnn_host_pack_edges): copy into the staging buffer, look at the order on the way, and only a list in
+        # another order goes through a stable counting sort on the host (tens of microseconds for a few 10^4 entries; NumPy's
+        # stable argsort alone would take longer than the whole general path).
+        lay = self._layout(key)
+        if lay is False or (want_order and key[2] > 4096):
+            raise _UseGeneralPath()
+        dims, L, in_off, out_off = lay
+        dev = self.model.device
+        self._buffers(L)
+        self._pack(arrays, key, in_off)
         t1 = time.perf_counter()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
@@ -180,16 +227,42 @@ class _InferenceSession:
         if timings is not None:
             timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2)
         out = self.out_np
-        flags = out[out_off[2]:out_off[2] + 16].view(np.int32)
-        if flags[0]:
-            raise ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
-        if flags[1] or flags[2] or flags[3]:
-            raise _UseGeneralPath()
+        self._flags(out_off)
         n = key[2]
         scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
         if want_order:
             scores.rankings = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy()
         return scores
+
+    def run_select(self, inputs, forced, p_max, p_max_ub):
+        """gcnn_infer_select: scores, selection order and n_kept of ONE host state.  `forced`: (ptr, col, val) host arrays
+        (ops.pack_rows).  Raises _UseGeneralPath where gcnn_infer would."""
+        arrays, key = self._check_inputs(inputs)
+        fptr, fcol, fval = forced
+        n_forced, n_entries = fptr.size - 1, fcol.size
+        lay = self._select_layout(key, n_forced, n_entries)
+        if lay is False:
+            raise _UseGeneralPath()
+        dims, L, in_off, out_off, SL = lay
+        dev = self.model.device
+        self._buffers(L)
+        self._pack(arrays, key, in_off)
+        buf = self.in_np
+        for off, a in zip(SL.forced_off, (fptr, fcol, fval)):
+            buf[off:off + a.nbytes] = a.view(np.uint8)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib().gcnn_infer_select(C.byref(dims), n_forced, n_entries, C.c_void_p(self.model._flat.data_ptr()),
+                                                   C.c_void_p(self.pin_in.data_ptr()), C.c_void_p(self.pin_out.data_ptr()),
+                                                   C.c_void_p(self.arena.data_ptr()), self.arena.numel(), float(p_max),
+                                                   float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_select")
+            stream.synchronize()
+        self._flags(out_off)
+        out, n = self.out_np, key[2]
+        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
+        order = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy()
+        n_kept = int(out[SL.n_kept_off:SL.n_kept_off + 4].view(np.int32)[0])
+        return scores, order, n_kept
 
 
 class Batch:
@@ -589,6 +662,50 @@ class GCNN:
             if rank:
                 scores.rankings = np.argsort(-np.asarray(scores), kind="stable").astype(np.int32)
             return scores
+
+    def select_cuts(self, state, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        """Score ONE state and run the parallelism filter of the SCIP plugin's cutselselect (model_evaluator.py:109-154) on the
+        device.  `forced`: None or (edge_inds [2,E], values [E], n_forced) -- the forced cuts' rows built as get_state builds the
+        cut edges (coefficient / norm over LP column positions); (edge_inds, values) alone takes n_forced = max row id + 1.
+        Host arrays take the single call gcnn_infer_select (one upload, one download); states it declines, device tensors and
+        prepared `Batch`es take prepare + forward + gcnn_select_cuts.  Both give the same bits.  Returns a `SelectResult`."""
+        from . import ops
+        ops.check_thresholds(p_max, p_max_ub)
+        general = isinstance(state, Batch) or any(isinstance(x, torch.Tensor) for x in state[:7])
+        n_cuts = state.dims.n_cuts if isinstance(state, Batch) else int(state[4].shape[0])
+        n_vars = state.dims.n_vars if isinstance(state, Batch) else int(state[3].shape[0])
+        if n_cuts > ops.SELECT_MAX_CUTS:
+            raise _lib.GcnnError(f"select_cuts: the state has {n_cuts} cuts; the device selection handles at most "
+                                 f"{ops.SELECT_MAX_CUTS} and there is no CPU fallback")
+        if forced is None:
+            forced = (np.zeros((2, 0), np.int32), np.zeros(0, np.float32), 0)
+        if len(forced) == 2:
+            fi = np.asarray(forced[0])
+            forced = (forced[0], forced[1], int(fi[0].max()) + 1 if fi.size else 0)
+        fi, fv, n_forced = forced
+        if isinstance(fi, torch.Tensor):
+            fi, fv = fi.cpu().numpy(), fv.cpu().numpy()
+        packed = ops.pack_rows(fi, fv, int(n_forced), n_vars)
+        result = None
+        if not general:
+            if self._session is None:
+                self._session = _InferenceSession(self)
+            try:
+                scores, order, n_kept = self._session.run_select(state, packed, p_max, p_max_ub)
+                result = (scores, order, n_kept)
+            except _UseGeneralPath:
+                pass
+        if result is None:
+            with torch.no_grad():
+                batch = self.prepare(state)
+                scores_dev = self.call(batch, False).as_subclass(torch.Tensor)
+                forced_dev = tuple(torch.from_numpy(a).to(self.device) for a in packed)
+                order, n_kept = ops.select_cuts(scores_dev, batch.cut_graph, None, forced_dev, p_max=p_max,
+                                                p_max_ub=p_max_ub, max_cuts=n_cuts)
+                result = (scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0]))
+        scores, order, n_kept = result
+        n_selected = n_kept if max_selected is None else min(n_kept, int(max_selected))
+        return SelectResult(order, n_kept, n_selected, scores)
 
     def get_concrete_function(self):
         """Counterpart of `tf.function(model.call).get_concrete_function()` (model_evaluator.py:310-311): an inference

@@ -135,3 +135,85 @@ def scatter_sum(messages: torch.Tensor, index, out_size: int):
     if plan.n_edges != messages.shape[0]:
         raise ValueError("one index per message row expected")
     return _ScatterSum.apply(messages, plan)
+
+
+# ---- cut selection (gcnn_select_cuts): the parallelism filter of the SCIP plugin's cutselselect, model_evaluator.py:109-154 ----
+SELECT_MAX_CUTS = 4096
+
+
+def check_thresholds(p_max, p_max_ub):
+    import math
+    for name, x in (("p_max", p_max), ("p_max_ub", p_max_ub)):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(float(x)):
+            raise ValueError(f"{name} must be a finite number, got {x!r}")
+
+
+def pack_rows(edge_inds, edge_vals, n_rows, n_vars):
+    """Host edge list of rows (row 0 = row id, row 1 = variable id, as get_state builds the cut edges) -> host CSR
+    (ptr [n_rows+1], col, val): int32 / int32 / float32, entries of a row in their input order."""
+    import numpy as np
+    ei = np.asarray(edge_inds)
+    ev = np.asarray(edge_vals, dtype=np.float32).reshape(-1)
+    if ei.ndim != 2 or ei.shape[0] != 2 or ei.dtype.kind not in "iu" or ev.size != ei.shape[1]:
+        raise ValueError(f"forced rows: expected an integer [2,E] index array and E values, got {ei.dtype} {tuple(ei.shape)} and "
+                         f"{ev.size} values")
+    rows, cols = ei[0].astype(np.int64), ei[1].astype(np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= n_rows or cols.min() < 0 or cols.max() >= n_vars):
+        raise ValueError(f"forced rows: row ids must be in [0,{n_rows}), variable ids in [0,{n_vars})")
+    perm = np.argsort(rows, kind="stable")
+    ptr = np.zeros(n_rows + 1, np.int32)
+    np.cumsum(np.bincount(rows, minlength=n_rows), out=ptr[1:])
+    return ptr, cols[perm].astype(np.int32), np.ascontiguousarray(ev[perm])
+
+
+def select_cuts(quality, cut_graph: BipartiteGraph, cut_offsets=None, forced=None, forced_offsets=None, *, p_max=0.1,
+                p_max_ub=0.5, max_cuts=None):
+    """Parallelism filter of cutselselect on the device, one workgroup per sample (gcnn_select_cuts); nothing is synchronised.
+
+    quality: [total_cuts] fp32 device scores (state order); cut_graph: the cut edge set (its by-left CSR holds the rows);
+    cut_offsets: [n_samples+1] int32 device tensor, None = one sample; forced: None or (ptr, col, val) device CSR of the forced
+    rows (pack_rows), with forced_offsets [n_samples+1] for more than one sample; max_cuts: the largest sample, None = derived
+    (from the total without a host read when that is <= 4,096).  Returns (order [total_cuts] int32, n_kept [n_samples] int32)
+    device tensors: order holds sample-local cut indices at each sample's offset; n_kept[s] = -1 flags a sample above max_cuts."""
+    check_thresholds(p_max, p_max_ub)
+    if not quality.is_cuda or quality.dtype != torch.float32 or quality.dim() != 1:
+        raise ValueError("quality must be a 1-D fp32 device tensor")
+    quality = quality.contiguous()
+    total = quality.numel()
+    if cut_graph.n_left != total:
+        raise ValueError(f"quality has {total} entries, the cut graph {cut_graph.n_left} rows")
+    dev = quality.device
+    if cut_offsets is not None:
+        cut_offsets = cut_offsets.to(device=dev, dtype=torch.int32).contiguous()
+        n_samples = cut_offsets.numel() - 1
+        if n_samples < 1:
+            raise ValueError("cut_offsets needs n_samples + 1 >= 2 entries")
+    else:
+        n_samples = 1
+    if max_cuts is None:
+        max_cuts = total if (cut_offsets is None or total <= SELECT_MAX_CUTS) else \
+            int((cut_offsets[1:] - cut_offsets[:-1]).max())
+    if max_cuts > SELECT_MAX_CUTS:
+        raise _lib.GcnnError(f"select_cuts: a state with {max_cuts} cuts; the device selection handles at most "
+                             f"{SELECT_MAX_CUTS} per state and there is no CPU fallback")
+    f_ptr = f_col = f_val = None
+    n_forced = 0
+    if forced is not None:
+        f_ptr, f_col, f_val = (t.to(dev).contiguous() for t in forced)
+        n_forced = f_ptr.numel() - 1
+        if n_samples > 1 and n_forced > 0:
+            if forced_offsets is None:
+                raise ValueError("forced_offsets is required with forced rows and more than one sample")
+            forced_offsets = forced_offsets.to(device=dev, dtype=torch.int32).contiguous()
+    order = torch.empty(total, dtype=torch.int32, device=dev)
+    n_kept = torch.empty(n_samples, dtype=torch.int32, device=dev)
+    lib = _lib.lib()
+    ws_bytes = lib.gcnn_select_workspace_bytes(total, n_forced, max_cuts)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gcnn_select_cuts(_ptr(quality), _ptr(cut_graph.l_ptr), _ptr(cut_graph.l_oth), _ptr(cut_graph.l_coef),
+                                        _ptr(cut_offsets), n_samples, total, int(max_cuts), cut_graph.n_var, _ptr(f_ptr),
+                                        _ptr(f_col), _ptr(f_val), _ptr(forced_offsets) if n_forced else None, n_forced,
+                                        float(p_max), float(p_max_ub), _ptr(order), _ptr(n_kept), _ptr(ws), ws_bytes,
+                                        _stream(dev)), "gcnn_select_cuts")
+    return order, n_kept

@@ -276,6 +276,50 @@ int gcnn_ranking_metric(const float* pred, const float* truth, const int32_t* of
                         int32_t max_cuts, const float* fractions, int32_t n_fractions, float* acc, float* frac_out,
                         const float* loss_in, float loss_weight, float* loss_acc, void* stream);
 
+/* ---- cut selection: the parallelism filter of the SCIP plugin's cutselselect, model_evaluator.py:109-154 ----------------
+ * (the same loop: model_benchmarker.py:112-157, data_collector.py:150-195).  Per sample s (cuts cut_offsets[s] .. [s+1]-1 of the
+ * stacked vectors, forced rows forced_offsets[s] .. [s+1]-1), all in STATE order (cut k = row k of cut_feats / cut_edge_inds):
+ *   order   = the descending stable ranking of quality (NaN as -inf): what gcnn_infer's order holds;
+ *   low[p]  = quality[order[p]] < t in fp32, t = (float)(0.9 * (double)quality[order[0]]) -- fixed by POSITION p;
+ *   P(x,y)  = |sum_v x_v y_v| over the rows as dense vectors (duplicate entries add), accumulated in fp64; 0 for an empty row
+ *             (get_state stores each cut row divided by its norm, utils.py:214-236, so this is SCIP's row parallelism);
+ *   a cut at position p is removed by pivot row r when P > p_max and (low[p] or P > p_max_ub);
+ *   forced phase: for each forced row in order, the removed positions among [0, n) move behind all others (position order kept
+ *   on both sides) and n shrinks; main phase: for i = 0, 1, ... while i < n - 1, the same with pivot order[i] and the positions
+ *   (i, n).  Output: order[] (sample-local cut indices, at the sample's cut offset) and n_kept[s] = n (-1 when the sample has
+ *   more than max_cuts cuts).
+ * quality: [total_cuts] any score vector (device).  cut_ptr / cut_col / cut_val: the cut rows as by-left CSR (a gcnn_graph's
+ * l_ptr / l_oth / l_coef); forced_ptr / forced_col / forced_val: the forced rows in the same form and column space (row offsets
+ * over the stacked forced rows; NULL when total_forced = 0).  Entries whose column lies outside [0, n_vars) take no part.
+ * cut_offsets / forced_offsets: [n_samples+1] device int32, or NULL for n_samples = 1.  max_cuts: the largest sample (host value,
+ * <= 4096, else GCNN_E_UNSUPPORTED).  p_max, p_max_ub: finite, else GCNN_E_BADARG.  workspace: gcnn_select_workspace_bytes
+ * (the two parallelism bits of every pair the filter can consult).  Two launches; nothing is synchronised. */
+size_t gcnn_select_workspace_bytes(int32_t total_cuts, int32_t total_forced, int32_t max_cuts);
+int gcnn_select_cuts(const float* quality, const int32_t* cut_ptr, const int32_t* cut_col, const float* cut_val,
+                     const int32_t* cut_offsets, int32_t n_samples, int32_t total_cuts, int32_t max_cuts, int32_t n_vars,
+                     const int32_t* forced_ptr, const int32_t* forced_col, const float* forced_val,
+                     const int32_t* forced_offsets, int32_t total_forced, double p_max, double p_max_ub, int32_t* order,
+                     int32_t* n_kept /* [n_samples] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Single call: gcnn_infer (want_order) followed by gcnn_select_cuts on its scores and on the cut rows already in the arena, with
+ * ONE upload (the packed state of gcnn_infer, then the forced rows) and ONE download (scores | order | flags | n_kept).
+ * layout.infer: as gcnn_infer_layout_for, except that in_bytes / out_bytes / arena_bytes cover this call.  host_in additionally
+ * holds forced_off[0]: forced_ptr [n_forced+1] int32 (offsets from 0), forced_off[1]: forced_col [n_forced_entries] int32,
+ * forced_off[2]: forced_val [n_forced_entries] f32.  host_out additionally holds n_kept (int32) at n_kept_off.  The flags are those
+ * of gcnn_infer: any set => scores and selection are NOT valid; the caller takes the general path (gcnn_graph_build +
+ * gcnn_forward + gcnn_select_cuts).  Returns GCNN_E_UNSUPPORTED for more than 32,768 variables or 4,096 cuts. */
+typedef struct gcnn_select_layout {
+    gcnn_infer_layout infer;
+    size_t forced_off[3];
+    size_t n_kept_off;
+    size_t ws_off;            /* internal: the selection workspace inside the arena */
+} gcnn_select_layout;
+int gcnn_infer_select_layout_for(const gcnn_dims* dims, int32_t n_forced, int32_t n_forced_entries,
+                                 gcnn_select_layout* layout /* host */);
+int gcnn_infer_select(const gcnn_dims* dims, int32_t n_forced, int32_t n_forced_entries, const float* params,
+                      const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max, double p_max_ub,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
