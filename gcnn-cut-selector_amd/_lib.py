@@ -105,6 +105,7 @@ SIGNATURES = {
     "gcnn_group_table_bytes": (C.c_int, [_I, C.POINTER(C.c_size_t)]),
     "gcnn_group_train_step": (C.c_int, [_I, C.POINTER(GroupMember), _P, _P, _Z, _P]),
     "gcnn_group_forward": (C.c_int, [_I, C.POINTER(GroupMember), _P, _P, _Z, _P]),
+    "gcnn_rank_deviations": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 
 _lib = None

@@ -1328,3 +1328,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_select.hpp"
 // groups of models stepped together (include/gcnn_hip.h: gcnn_group_train_step, gcnn_group_forward): launch names k_group_*
 #include "gcnn_group.hpp"
+// the test stage's rankings of many candidates against one truth (include/gcnn_hip.h: gcnn_rank_deviations): launch name k_rank_multi
+#include "gcnn_rank.hpp"

@@ -153,14 +153,15 @@ __global__ __launch_bounds__(256) void k_iplan_order(IplanArgs a) { iplan_order_
 // Descending stable ranking of the scores (model_evaluator.py:110-111: sorted(range(n), key=quality, reverse=True) keeps equal
 // scores in index order): the same bitonic network and total order as the ranking metric.  Run by all NT threads of a block,
 // n <= RK_MAX; leaves the sorted keys (NaN as -inf) in v and the cut indices in ix, ix[0] = the best cut.  Shared by
-// k_rank_scores and the cut selection's filter (k_select.hpp).
-template <int NT>
-__device__ __forceinline__ void rank_desc_lds(const float* __restrict__ scores, int n, float* v, int* ix) {
+// k_rank_scores, the cut selection's filter (k_select.hpp) and the test-set ranking (k_rank.hpp, which also sorts fp64 keys: T is
+// the key type, compared as it is -- an fp64 key is never narrowed).
+template <int NT, typename T>
+__device__ __forceinline__ void rank_desc_lds(const T* __restrict__ scores, int n, T* v, int* ix) {
     int m = 1;
     while (m < n) m <<= 1;
     for (int i = threadIdx.x; i < m; i += NT) {
-        const float x = i < n ? scores[i] : -INFINITY;
-        v[i] = x != x ? -INFINITY : x; ix[i] = i < n ? i : 0x7fffffff;
+        const T x = i < n ? scores[i] : (T)-INFINITY;
+        v[i] = x != x ? (T)-INFINITY : x; ix[i] = i < n ? i : 0x7fffffff;
     }
     __syncthreads();
     for (int k = 2; k <= m; k <<= 1)
@@ -169,7 +170,7 @@ __device__ __forceinline__ void rank_desc_lds(const float* __restrict__ scores, 
                 const int p = i ^ j;
                 if (p > i) {
                     const bool up = (i & k) == 0;
-                    const float vi = v[i], vp = v[p];
+                    const T vi = v[i], vp = v[p];
                     const int ii = ix[i], ip = ix[p];
                     const bool before_pi = vp > vi || (vp == vi && ip < ii);   // p's element ranks before i's
                     const bool before_ip = vi > vp || (vi == vp && ii < ip);

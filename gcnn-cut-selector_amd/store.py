@@ -26,6 +26,20 @@ StoreBatch = namedtuple("StoreBatch", "batch n_cons n_vars n_cuts improvements")
 
 _K_CONS, _K_VAR, _K_CUT, _K_E1, _K_E2 = range(5)   # unit kinds: which offset table indexes an array
 _GRAPH_FIELDS = ("l_ptr", "l_oth", "l_coef", "v_ptr", "v_oth", "v_coef")
+HYBRID_FEATURES = ("efficacy", "int_support", "parallelism")   # the cut features of SCIP's hybrid rule (model_tester.py:113-120)
+
+
+def hybrid_quality(cut):
+    """SCIP's hybrid cut quality of one sample (model_tester.py:113-120): efficacy + 0.1 * int_support + 0.1 * parallelism, with the
+    columns looked up by name and computed by NumPy in the sample's own dtype; None when a column is missing."""
+    names = list(cut["features"])
+    if not all(f in names for f in HYBRID_FEATURES):
+        return None
+    feats = cut["values"]
+    int_support = feats[:, names.index("int_support")]
+    efficacy = feats[:, names.index("efficacy")]
+    parallelism = feats[:, names.index("parallelism")]
+    return efficacy + 0.1 * int_support + 0.1 * parallelism
 
 
 def _localise(graph: BipartiteGraph, n_left, n_var, n_edge, dev):
@@ -46,11 +60,19 @@ class SampleStore:
     """All samples of a data set resident on one GPU; `batch(ids)` collates a mini-batch on the device.
 
     Build with `from_files` (the reference's sample_*.pkl files, data_collector.py:135-140) or `from_samples`
-    ((state, improvements) pairs as `utils.load_sample` returns them).  Edge lists are validated once, at ingestion."""
+    ((state, improvements) pairs as `utils.load_sample` returns them).  Edge lists are validated once, at ingestion.
 
-    def __init__(self, device):
+    `baselines=True` also keeps what the test stage's baselines rank (model_tester.py:104-153), two fp64 vectors per cut:
+    `improvements64`, the file's improvements widened to fp64 (the fp32 `improvements` can tie where these do not), and `hybrid64`,
+    `hybrid_quality` widened to fp64 (which keeps its order and its ties).  A sample whose cuts lack a feature of the hybrid rule
+    is accepted (its `hybrid64` entries are zero) and flagged in `lacks_baselines`; `tester.test_group` refuses it."""
+
+    def __init__(self, device, baselines=False):
         self.device = torch.device(device)
+        self.baselines = bool(baselines)
         self._parts = {k: [] for k in ("cons_feats", "var_feats", "cut_feats", "improvements")}
+        if self.baselines:
+            self._parts.update(improvements64=[], hybrid64=[], lacks_baselines=[])
         self._gparts = [{f: [] for f in _GRAPH_FIELDS} for _ in range(2)]
         self._sizes = [[] for _ in range(5)]
         self._maxdeg = [[[], []] for _ in range(2)]    # per edge set: longest by-left / by-variable segment of every sample
@@ -60,16 +82,16 @@ class SampleStore:
 
     # ---- ingestion ---------------------------------------------------------------------------------------------
     @classmethod
-    def from_samples(cls, samples, device=None, chunk=64):
+    def from_samples(cls, samples, device=None, chunk=64, baselines=False):
         device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        store = cls(device)
+        store = cls(device, baselines)
         samples = list(samples)
         for i in range(0, len(samples), chunk):
             store._add_chunk(samples[i:i + chunk])
         return store._finalise()
 
     @classmethod
-    def from_files(cls, files, device=None, chunk=64, workers=8, process_group=None):
+    def from_files(cls, files, device=None, chunk=64, workers=8, process_group=None, baselines=False):
         """Decode every file once and move the samples to the device.  The gunzip work runs in `workers` child processes that are
         fresh, torch-free interpreters (`utils.decode_files`; `workers=0` decodes in-process); the calling script needs no
         `if __name__ == "__main__":` guard.
@@ -79,9 +101,11 @@ class SampleStore:
         host -- and the ranks then exchange their device arrays ONCE (one padded all-gather per array over RCCL / xGMI), so every
         rank ends up holding the whole store, array for array identical to a single-process ingestion: `batches(ids, b, rank,
         world)` keeps drawing any sample on any rank, as the reference's epoch sampling with replacement needs
-        (model_trainer.py:147), with shards balanced by edge count."""
+        (model_trainer.py:147), with shards balanced by edge count.  `baselines=True` (see the class) is single-process only."""
+        if baselines and process_group is not None:
+            raise ValueError("SampleStore.from_files: baselines=True with a process_group is not supported")
         device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        store = cls(device)
+        store = cls(device, baselines)
         files = list(files)
         rank, world = 0, 1
         if process_group is not None:
@@ -133,6 +157,12 @@ class SampleStore:
         g2 = BipartiteGraph(up(kei), up(kef), k.shape[0], v.shape[0], validate=True, sync_max_degree=True)
         for name, a in (("cons_feats", c), ("var_feats", v), ("cut_feats", k), ("improvements", imp)):
             self._parts[name].append(up(a))
+        if self.baselines:
+            hybrid = [hybrid_quality(s[0][3]) for s in samples]
+            self._parts["lacks_baselines"].append(np.asarray([h is None for h in hybrid], bool))
+            self._parts["improvements64"].append(up(np.concatenate([np.asarray(s[1]).astype(np.float64) for s in samples])))
+            self._parts["hybrid64"].append(up(np.concatenate([np.zeros(n, np.float64) if h is None else np.asarray(h).astype(np.float64)
+                                                              for h, n in zip(hybrid, n_cuts)])))
         for slot, (g, nl, ne) in enumerate(((g1, n_cons, n_e1), (g2, n_cuts, n_e2))):
             for f, t in _localise(g, nl, n_vars, ne, dev).items():
                 self._gparts[slot][f].append(t)
@@ -158,6 +188,12 @@ class SampleStore:
         self.sizes = np.stack([np.concatenate(s) if s else np.zeros(0, np.int64) for s in self._sizes])   # [5, n]
         self.offsets = np.concatenate([np.zeros((5, 1), np.int64), np.cumsum(self.sizes, axis=1)], axis=1)
         self.max_deg = [[np.concatenate(m) if m else np.zeros(0, np.int64) for m in per_set] for per_set in self._maxdeg]
+        if self.baselines:
+            f64 = torch.zeros(0, dtype=torch.float64, device=dev)
+            self.improvements64 = cat(self._parts["improvements64"], f64)
+            self.hybrid64 = cat(self._parts["hybrid64"], f64)
+            lacks = self._parts["lacks_baselines"]
+            self.lacks_baselines = np.concatenate(lacks) if lacks else np.zeros(0, bool)
         self._parts = self._gparts = self._sizes = self._maxdeg = None
         self._final = True
         return self
@@ -168,6 +204,8 @@ class SampleStore:
     @property
     def nbytes(self):
         ts = [self.cons_feats, self.var_feats, self.cut_feats, self.improvements] + [t for g in self.graphs for t in g.values()]
+        if self.baselines:
+            ts += [self.improvements64, self.hybrid64]
         return sum(t.numel() * t.element_size() for t in ts)
 
     # ---- collation ---------------------------------------------------------------------------------------------

@@ -294,26 +294,36 @@ def train_step_group(models, batches, targets, optimizers, states, process_group
     return out
 
 
-def forward_group(models, batches):
+def forward_group(models, batches, out=None):
     """Scores of every model on its batch (gcnn_group_forward): what `model(batch)` returns, bit for bit, for up to 8 models in
-    one set of launches.  Nothing is kept for a backward pass.  The batches may be the same object (validation)."""
+    one set of launches.  Nothing is kept for a backward pass.  The batches may be the same object (validation).
+    `out`: optional list of contiguous 1-D fp32 device tensors, one per model with one element per cut of its batch, that the
+    scores are written into (e.g. rows of one buffer); they must not overlap (the call refuses it).  Returns the score tensors."""
     dev = _check_group(models, batches)
-    members, out, taken, prepared = [], [], [], []
+    if out is not None and len(out) != len(models):
+        raise ValueError(f"{len(models)} models but {len(out)} output tensors")
+    members, result, taken, prepared = [], [], [], []
     try:
-        for model, batch in zip(models, batches):
+        for i, (model, batch) in enumerate(zip(models, batches)):
             if not isinstance(batch, Batch):
                 batch = model.prepare(batch)
             prepared.append(batch)   # alive until the call has enqueued its reads: the allocator would hand its memory on
+            if out is None:
+                scores = torch.empty(batch.dims.n_cuts, dtype=torch.float32, device=dev)
+            else:
+                scores = out[i]
+                if (scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous() or scores.device != dev
+                        or scores.numel() != batch.dims.n_cuts):
+                    raise ValueError(f"out[{i}] must be a contiguous 1-D float32 tensor of {batch.dims.n_cuts} elements on {dev}")
             ws = model._take_workspace(batch)
             taken.append((model, ws))
-            scores = torch.empty(batch.dims.n_cuts, dtype=torch.float32, device=dev)
             members.append(_group_member(model, batch, ws, scores))
-            out.append(scores)
+            result.append(scores)
         _tables(dev).call(_lib.lib().gcnn_group_forward, members, "gcnn_group_forward", dev)
     finally:
         for model, ws in taken:
             model._give_workspace(ws)
-    return out
+    return result
 
 
 def ranking_fraction(pred: np.ndarray, true: np.ndarray) -> float:

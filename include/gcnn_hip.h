@@ -355,6 +355,22 @@ int gcnn_group_train_step(int32_t n_members, const gcnn_group_member* members /*
 int gcnn_group_forward(int32_t n_members, const gcnn_group_member* members /* host */, void* host_staging, void* device_table,
                        size_t table_bytes, void* stream);
 
+/* ---- test stage: rankings of many candidates against one truth (model_tester.py:113-153, 205-224) --------------------------
+ * For every sample s (cuts offsets[s] .. offsets[s+1]-1; K_total = offsets[n_samples] is the row stride of scores and perms), the
+ * first position at which a candidate ranking deviates from the truth ranking.  Rankings are stable descending orders (Python's
+ * sorted(..., reverse=True): ties in index order), NaN ranked as -inf.  Output rows of deviations [rows][n_samples], int32:
+ *   0 .. n_scores-1       scores [n_scores][K_total] fp32 against truth32 [K_total] fp32
+ *   n_scores              hybrid [K_total] fp64, when not NULL, against truth64 [K_total] fp64
+ *   then n_perms rows     perms [n_perms][K_total] int32 (perm[r] = the sample-local cut at rank r) against truth64
+ * Each value: the first deviating position; the number of cuts when the rankings agree; 0 for a sample without cuts; -1 for a
+ * sample with more than 4,096 cuts (restate it on the host).  fp64 keys are compared in fp64.  All pointers are device memory.
+ * One launch.  GCNN_E_BADARG (nothing enqueued) for n_samples < 1, n_scores or n_perms outside 0..GCNN_GROUP_MAX, no candidate
+ * at all, or a missing pointer: offsets, deviations; truth32 and scores when n_scores > 0; perms when n_perms > 0; truth64 when
+ * hybrid or perms are given. */
+int gcnn_rank_deviations(const int32_t* offsets, int32_t n_samples, const float* truth32, const double* truth64,
+                         const float* scores, int32_t n_scores, const double* hybrid, const int32_t* perms, int32_t n_perms,
+                         int32_t* deviations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
