@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: bipartite-graph edges/sec (fwd+bwd) per training step, setcov-500 batch=32 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -22,6 +22,11 @@ block is timed, so exactly K steps are; --min-seconds S repeats the block until 
 flat gradient and the flat parameters after Adam -- as DIR/<name>.npy (float32, a few hundred KB).  Inputs are fixed by
 the arguments (seeded synthetic samples, `GCNN(seed=0)`), so two builds can be compared output for output
 (`--dump-outputs bench_outputs` is git-ignored).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+`--full` adds everything else, after the timed region and the copy of the dumped outputs: the launch count of one more step
+(`config.library_launches_per_step`), `roofline`, `roofline_step` and `cpu_baseline` (with --full, --no-roofline and
+--no-cpu-baseline drop a part of that).
 
 `roofline`: the standalone scatter-sum pass (K9, the pass BASELINE.json's 40%-of-HBM target names), timed live with HIP
 events in its own loop.  `roofline_step`: the kernels of the training step itself, launch by launch (HIP events inside the
@@ -56,8 +61,10 @@ def parse(argv=None):
     ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step block until this much time is measured "
                     "(default 0: one block, exactly --steps timed steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the launch count, the rooflines "
+                    "and the CPU baseline (a plain run reports the timed steps alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip roofline and roofline_step")
     ap.add_argument("--graph", action="store_true", help="capture the step once and replay it as a hipGraph (measured: no faster than eager issue -- the GPU-side dependency chain is the limit, not the host)")
     ap.add_argument("--stub-worker", action="store_true", help=argparse.SUPPRESS)   # tests/test_host.py: ranks on CPU over gloo, no GPU work
     args = ap.parse_args(argv)
@@ -477,10 +484,12 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped = {"loss": loss.detach().float().cpu().numpy().reshape(-1), "scores": last_scores.detach().float().cpu().numpy(),
                   "grads": ts.grads.detach().float().cpu().numpy(), "params": model.flat_parameters.detach().float().cpu().numpy()}
-    from gcnn_cut_selector_amd import _lib
-    with _lib.launch_profile() as prof:   # one more step on every rank, outside the timed region: how many launches a step is
-        train_step(model, batch, targets, opt, ts, process_group=group)
-    n_launches = len(prof.launches)
+    n_launches = None
+    if args.full:
+        from gcnn_cut_selector_amd import _lib
+        with _lib.launch_profile() as prof:   # one more step on every rank, outside the timed region: how many launches a step is
+            train_step(model, batch, targets, opt, ts, process_group=group)
+        n_launches = len(prof.launches)
     edges_total = float(edges_local)
     rank_info = [{"rank": rank, "device": torch.cuda.current_device(), "name": torch.cuda.get_device_name(dev),
                   "uuid": str(getattr(torch.cuda.get_device_properties(dev), "uuid", "")), "edges_per_step": edges_local,
@@ -528,11 +537,13 @@ def main():
                                        f"{ts.buf.numel()} elements per step") if group is not None else None,
                         "ranks": rank_info, "ms_per_step_local_min": min(local), "ms_per_step_local_max": max(local)},
     }
-    if not args.no_roofline:
+    if n_launches is None:   # a plain run does not count the launches
+        del out["config"]["library_launches_per_step"]
+    if args.full and not args.no_roofline:
         out["roofline"] = roofline_scatter_sum(batch, dev)
         if group is None:
             out["roofline_step"] = roofline_step(model, batch, targets, dev)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.problem, args.batch, 0)
         out["config"]["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["best_value"], 1)   # against the fastest CPU point
     if dumped is not None:

@@ -330,6 +330,19 @@ def test_bench_steps_sets_the_timed_steps_and_dump_outputs_parses():
         bench.parse(["--steps", "0"])
 
 
+def test_bench_full_is_off_by_default():
+    """A plain bench run times the steps alone; `--full` adds the launch count, the rooflines and the CPU baseline, and
+    --no-roofline / --no-cpu-baseline drop a part of that (tests/test_gpu_bench.py runs both on the GPU)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.no_roofline is False and plain.no_cpu_baseline is False
+    full = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--no-cpu-baseline"])
+    assert full.full is True and full.no_cpu_baseline is True and full.steps == 7 and full.warmup == 2
+
+
 def test_out_of_memory_skips_a_batch_single_gpu_and_propagates_data_parallel(monkeypatch, capsys):
     """The reference skips a batch that exhausts memory (model_trainer.py:308-311: `except ResourceExhaustedError: print(WARNING)`).
     Single GPU: the same.  Data parallel: the peers are already in this step's all-reduce, so a rank must not skip on its own --

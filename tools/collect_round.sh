@@ -10,7 +10,7 @@ O=${1:-gpurun_out/r03}; mkdir -p $O
 R=${2:-r03}
 python bench.py --steps 20 --warmup 5 --min-seconds 0 --no-cpu-baseline --no-roofline > $O/dims.json 2> $O/bench.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 bench.py --steps 10 --warmup 2 --min-seconds 0 --no-cpu-baseline > /dev/null 2> $O/pmc_$c.err
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 bench.py --full --steps 10 --warmup 2 --min-seconds 0 --no-cpu-baseline > /dev/null 2> $O/pmc_$c.err
 done
 F=$(find $O/pmc_FETCH_SIZE -name '*counter_collection.csv' | head -1); W=$(find $O/pmc_WRITE_SIZE -name '*counter_collection.csv' | head -1)
 python3 profiles/hbm_traffic.py $F $W > $O/step_hbm_traffic.txt
@@ -18,12 +18,12 @@ python3 profiles/hbm_traffic.py $F $W --json "k_seg_sum<4, false>" > $O/hbm_traf
 python3 profiles/hbm_traffic.py $F $W --step-json $(python3 -c "import json; c = json.load(open('$O/dims.json'))['config']; print(c['n_cons'], c['n_vars'], c['n_cuts'], c['n_cons_edges'], c['n_cut_edges'])") > $O/step_hbm_traffic.json
 cp $O/hbm_traffic.json profiles/${R}_hbm_traffic.json; cp $O/step_hbm_traffic.json profiles/${R}_step_hbm_traffic.json
 echo "pmc done"
-# 2. the default bench line (roofline, roofline_step, cpu_baseline)
-python bench.py > $O/bench.json 2>> $O/bench.err
+# 2. the full bench line (roofline, roofline_step, cpu_baseline)
+python bench.py --full > $O/bench.json 2>> $O/bench.err
 echo "bench done"
 # 3. kernel statistics + timeline of the same workload, INCLUDING the standalone scatter-sum loop of the roofline block, so that
 #    roofline.frac can be recomputed from the tracked summary (k_seg_sum row: 212,096,000 B / its average duration / 8.0e12)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 50 --warmup 10 --min-seconds 0 --no-cpu-baseline > $O/prof.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --steps 50 --warmup 10 --min-seconds 0 --no-cpu-baseline > $O/prof.json 2> $O/prof.err
 f=$(find $O/prof -name '*kernel_stats.csv' | head -1); cp $f $O/step_kernel_stats.csv
 python3 profiles/summarize.py $f 84 > $O/step_summary.txt        # 50 timed + 10 warm-up + 1 launch-count + 3 + 20 roofline_step steps
 python3 profiles/timeline.py $(find $O/prof -name '*kernel_trace.csv' | head -1) > $O/step_timeline.txt
