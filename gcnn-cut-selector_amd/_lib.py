@@ -56,6 +56,8 @@ class GroupMember(C.Structure):
 
 
 GROUP_MAX = 8   # GCNN_GROUP_MAX
+# gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
+PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
 
 class CollateJob(C.Structure):
@@ -105,6 +107,8 @@ SIGNATURES = {
     "gcnn_group_table_bytes": (C.c_int, [_I, C.POINTER(C.c_size_t)]),
     "gcnn_group_train_step": (C.c_int, [_I, C.POINTER(GroupMember), _P, _P, _Z, _P]),
     "gcnn_group_forward": (C.c_int, [_I, C.POINTER(GroupMember), _P, _P, _Z, _P]),
+    "gcnn_prenorm_merge": (C.c_int, [_DP, _P, _P, _P, _P, _GP, _GP, _P, _Z, _I, _P, _P]),
+    "gcnn_group_prenorm_merge": (C.c_int, [_I, C.POINTER(GroupMember), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), _P, _P, _Z, _P]),
     "gcnn_rank_deviations": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 

@@ -25,6 +25,7 @@
 #include "k_wgrad.hpp"
 #include "k_infer.hpp"
 #include "k_group.hpp"
+#include "k_prenorm.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
@@ -1235,16 +1236,20 @@ extern "C" int gcnn_backward(const gcnn_dims* d, const float* p, const float* co
 }
 
 // ---- PreNorm fitting statistics (model.py:394-423) ------------------------------------------------------------------
-extern "C" int gcnn_prenorm_stats(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats,
-                                  const float* cut_feats, const gcnn_graph* cg, const gcnn_graph* kg, float* workspace,
-                                  size_t workspace_floats, int32_t layer, double* out_mean_var, void* stream) {
+// What the statistics of one batch and one layer read: the k_stats arguments (without centre and partials), the element count,
+// the units, the grid, and for the edge layers the explicit left ids to expand first (x.n_seg > 0).  Shared by
+// gcnn_prenorm_stats and gcnn_prenorm_merge (gcnn_prenorm.hpp), so both sum in the same order.
+struct StatPlan { StatArgs a; double count; int units, grid; ExpandArgs x; };
+static int prenorm_plan(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats, const float* cut_feats,
+                        const gcnn_graph* cg, const gcnn_graph* kg, float* workspace, size_t workspace_floats, int32_t layer,
+                        StatPlan* s) {
     layout_init();
     int rc = check_common(d, p, cg, kg, workspace, workspace_floats);
     if (rc) return rc;
-    if (layer < 0 || layer > 10 || !out_mean_var) return GCNN_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
+    if (layer < 0 || layer > 10) return GCNN_E_BADARG;
     Work w; carve(d, workspace, &w);
-    StatArgs a; memset(&a, 0, sizeof(a));
+    StatArgs& a = s->a;
+    memset(s, 0, sizeof(*s));
     double count = 0.0;
     int units = 1;
     if (layer <= 4) {   // input layers: raw features, one unit per column (edge features: a single column)
@@ -1260,28 +1265,44 @@ extern "C" int gcnn_prenorm_stats(const gcnn_dims* d, const float* p, const floa
         if (((layer - 5) & 1) == 0) {   // feature_module_final's PreNorm: all E*64 joint pre-activations, one unit
             a.src = ST_EDGE; a.n = c.ne; a.right = c.g->l_oth; a.coef = c.g->l_coef; a.pl = c.PL; a.pr = c.PR;
             a.w_edge = p + poff(c.pbase + C_WE); a.e_shift = p + poff(c.pedge); a.e_scale = p + poff(c.pedge + 1);
-            if (c.ne > 0) {
-                hipLaunchKernelGGL(k_expand_ptr, dim3(std::min(cdiv(c.nl, 256), 1024)), dim3(256), 0, st, c.g->l_ptr, c.nl, w.stat_ids);
-                LAUNCHCHK();
-            }
+            if (c.ne > 0) s->x = ExpandArgs{c.g->l_ptr, c.nl, w.stat_ids};
             a.left = w.stat_ids; count = (double)c.ne * EMB;
         } else {                        // post_conv_module's PreNorm: all R*64 elements of the scatter-sum output, one unit
             a.src = ST_FLAT; a.x = c.A; a.n = c.recv_left ? c.nl : c.nv; count = (double)a.n * EMB;
         }
     }
-    if (count <= 0.0) {   // nothing to absorb: mean 0, variance 0 (the caller skips empty batches)
+    const int work = a.src == ST_EDGE ? cdiv(a.n, 16) : (a.src == ST_FLAT ? cdiv(a.n, 4) : cdiv(a.n, 256));
+    s->grid = std::max(1, std::min(work, ST_MAX_BLOCKS));
+    s->count = count;
+    s->units = units;
+    a.partial = w.stats;
+    return 0;
+}
+static inline int expand_grid(const ExpandArgs& x) { return std::min(cdiv(x.n_seg, 256), 1024); }
+extern "C" int gcnn_prenorm_stats(const gcnn_dims* d, const float* p, const float* cons_feats, const float* var_feats,
+                                  const float* cut_feats, const gcnn_graph* cg, const gcnn_graph* kg, float* workspace,
+                                  size_t workspace_floats, int32_t layer, double* out_mean_var, void* stream) {
+    StatPlan s;
+    int rc = prenorm_plan(d, p, cons_feats, var_feats, cut_feats, cg, kg, workspace, workspace_floats, layer, &s);
+    if (rc) return rc;
+    if (!out_mean_var) return GCNN_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (s.x.n_seg > 0) {
+        hipLaunchKernelGGL(k_expand_ptr, dim3(expand_grid(s.x)), dim3(256), 0, st, s.x);
+        LAUNCHCHK();
+    }
+    const int units = s.units, grid = s.grid;
+    if (s.count <= 0.0) {   // nothing to absorb: mean 0, variance 0 (the caller skips empty batches)
         HIPCHK(hipMemsetAsync(out_mean_var, 0, 2 * (size_t)units * sizeof(double), st));
         return 0;
     }
-    const int work = a.src == ST_EDGE ? cdiv(a.n, 16) : (a.src == ST_FLAT ? cdiv(a.n, 4) : cdiv(a.n, 256));
-    const int grid = std::max(1, std::min(work, ST_MAX_BLOCKS));
-    a.partial = w.stats;
+    StatArgs a = s.a;
     a.mean = nullptr;
     hipLaunchKernelGGL(k_stats, dim3(grid), dim3(256), 0, st, a); LAUNCHCHK();
-    hipLaunchKernelGGL(k_stats_final, dim3(1), dim3(64), 0, st, w.stats, grid, units, count, out_mean_var); LAUNCHCHK();
+    hipLaunchKernelGGL(k_stats_final, dim3(1), dim3(64), 0, st, a.partial, grid, units, s.count, out_mean_var); LAUNCHCHK();
     a.mean = out_mean_var;
     hipLaunchKernelGGL(k_stats, dim3(grid), dim3(256), 0, st, a); LAUNCHCHK();
-    hipLaunchKernelGGL(k_stats_final, dim3(1), dim3(64), 0, st, w.stats, grid, units, count, out_mean_var + units); LAUNCHCHK();
+    hipLaunchKernelGGL(k_stats_final, dim3(1), dim3(64), 0, st, a.partial, grid, units, s.count, out_mean_var + units); LAUNCHCHK();
     return 0;
 }
 
@@ -1328,5 +1349,8 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_select.hpp"
 // groups of models stepped together (include/gcnn_hip.h: gcnn_group_train_step, gcnn_group_forward): launch names k_group_*
 #include "gcnn_group.hpp"
+// PreNorm fitting with the merge on the device, solo and grouped (include/gcnn_hip.h: gcnn_prenorm_merge,
+// gcnn_group_prenorm_merge): launch names k_prenorm_* and k_group_*
+#include "gcnn_prenorm.hpp"
 // the test stage's rankings of many candidates against one truth (include/gcnn_hip.h: gcnn_rank_deviations): launch name k_rank_multi
 #include "gcnn_rank.hpp"

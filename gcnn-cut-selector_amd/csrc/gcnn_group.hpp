@@ -46,6 +46,16 @@ static GroupKernel g_group_kernels[] = {
     GK((k_edge_bwd_send<1, true>), (k_group_edge_bwd_send<1, true>), "k_group_edge_bwd_send + long segments"),
     GK(k_wgrad, k_group_wgrad, "k_group_wgrad"),
     GK(k_reduce, k_group_reduce, "k_group_reduce"),
+    // PreNorm fitting (gcnn_prenorm.hpp): the forward's keep-A row programs, then the statistics and the merge (k_prenorm.hpp)
+    GK((k_conv_fwd<8, CF_PROJ, true>), (k_pgroup_conv_fwd<8, CF_PROJ>), "k_group_conv_fwd<proj, keep A>"),
+    GK((k_conv_fwd<4, CF_PROJ, true>), (k_pgroup_conv_fwd<4, CF_PROJ>), "k_group_conv_fwd<proj, keep A>"),
+    GK((k_conv_fwd<8, CF_READOUT, true>), (k_pgroup_conv_fwd<8, CF_READOUT>), "k_group_conv_fwd<readout, keep A>"),
+    GK((k_conv_fwd<4, CF_READOUT, true>), (k_pgroup_conv_fwd<4, CF_READOUT>), "k_group_conv_fwd<readout, keep A>"),
+    GK((k_conv_fwd_split<CF_PROJ, true>), k_pgroup_conv_fwd_split<CF_PROJ>, "k_group_conv_fwd_split<proj, keep A>"),
+    GK((k_conv_fwd_split<CF_READOUT, true>), k_pgroup_conv_fwd_split<CF_READOUT>, "k_group_conv_fwd_split<readout, keep A>"),
+    GK(k_expand_ptr, k_pgroup_expand_ptr, "k_group_expand_ptr"),
+    GK(k_stats, k_pgroup_stats, "k_group_stats"),
+    GK(k_stats_fold, k_pgroup_stats_fold, "k_group_stats_fold"),
 };
 #undef GK
 static GroupKernel* group_kernel(const void* solo) {
@@ -68,8 +78,10 @@ extern "C" int gcnn_group_table_bytes(int32_t n_members, size_t* bytes) {
 static bool group_degenerate(const gcnn_dims& d) { return d.n_cons <= 0 || d.n_vars <= 0 || d.n_cuts <= 0; }
 
 // Everything a group call checks before it enqueues anything.  A member's writable buffers must not overlap any buffer of
-// another member, written or read: their launches run side by side.  Read-only inputs may be shared.
-static int group_check(int n, const gcnn_group_member* mem, const void* host, const void* dev, size_t table_bytes, bool train) {
+// another member, written or read: their launches run side by side.  Read-only inputs may be shared.  `states` (PreNorm
+// fitting, gcnn_group_prenorm_merge): one merge state per member, writable; the forward's scores then stay in the workspace.
+static int group_check(int n, const gcnn_group_member* mem, const void* host, const void* dev, size_t table_bytes, bool train,
+                       void* const* states = nullptr) {
     if (n < 1 || n > GCNN_GROUP_MAX || !mem || !host || !dev) return GCNN_E_BADARG;
     if (((uintptr_t)dev & 63) || ((uintptr_t)host & 15)) return GCNN_E_BADARG;
     if (table_bytes < group_table_bytes(n)) return GCNN_E_WORKSPACE;
@@ -81,8 +93,13 @@ static int group_check(int n, const gcnn_group_member* mem, const void* host, co
         const gcnn_group_member& m = mem[i];
         int rc = check_common(&m.dims, m.params, &m.cons_graph, &m.cut_graph, m.workspace, m.workspace_floats);
         if (rc) return rc;
-        if (m.dims.n_cuts > 0 && !m.scores) return GCNN_E_BADARG;
-        spans[i] = {{m.workspace, m.workspace_floats * sizeof(float)}, {m.scores, (size_t)m.dims.n_cuts * sizeof(float)}};
+        if (states) {
+            if (!states[i] || ((uintptr_t)states[i] & 7)) return GCNN_E_BADARG;
+            spans[i] = {{m.workspace, m.workspace_floats * sizeof(float)}, {states[i], (size_t)GCNN_PRENORM_STATE_BYTES}};
+        } else {
+            if (m.dims.n_cuts > 0 && !m.scores) return GCNN_E_BADARG;
+            spans[i] = {{m.workspace, m.workspace_floats * sizeof(float)}, {m.scores, (size_t)m.dims.n_cuts * sizeof(float)}};
+        }
         const size_t C = m.dims.n_cons, V = m.dims.n_vars, K = m.dims.n_cuts, E1 = m.dims.n_cons_edges, E2 = m.dims.n_cut_edges;
         const gcnn_graph &cg = m.cons_graph, &kg = m.cut_graph;
         reads[i] = {{m.params, P}, {m.cons_feats, 16 * C}, {m.var_feats, 56 * V}, {m.cut_feats, 24 * K},
@@ -131,9 +148,10 @@ struct GroupRecScope {   // installs a recorder on this thread for one member's 
     ~GroupRecScope() { g_group_rec = nullptr; }
 };
 
-static int group_step(int n, const gcnn_group_member* mem, void* host, void* dev, size_t table_bytes, bool train, hipStream_t st) {
-    int rc = group_check(n, mem, host, dev, table_bytes, train);
-    if (rc) return rc;
+// The group call proper, after group_check: member_step(i) enqueues member i's solo work (or records it)
+template <class Step>
+static int group_run(int n, const gcnn_group_member* mem, void* host, void* dev, Step member_step, hipStream_t st) {
+    int rc;
     // 1. record every regular member's step (nothing is enqueued)
     static thread_local std::vector<GroupRecord> recs;
     recs.resize((size_t)GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES);
@@ -145,7 +163,7 @@ static int group_step(int n, const gcnn_group_member* mem, void* host, void* dev
         q = GroupRecorder{recs.data() + (size_t)nreg * GCNN_GROUP_MAX_STAGES, 0, GCNN_GROUP_MAX_STAGES, false};
         {
             GroupRecScope scope(&q);
-            rc = group_member_step(mem[i], train, st);
+            rc = member_step(i);
         }
         if (rc) return rc;
         if (q.bad) return GCNN_E_UNSUPPORTED;
@@ -195,8 +213,14 @@ static int group_step(int n, const gcnn_group_member* mem, void* host, void* dev
         HIPCHK(hipLaunchKernel(L.k->group, dim3(L.grid), dim3(L.block), args, L.smem, st));
     }
     for (int i = 0; i < n; ++i)
-        if (group_degenerate(mem[i].dims) && (rc = group_member_step(mem[i], train, st))) return rc;
+        if (group_degenerate(mem[i].dims) && (rc = member_step(i))) return rc;
     return 0;
+}
+
+static int group_step(int n, const gcnn_group_member* mem, void* host, void* dev, size_t table_bytes, bool train, hipStream_t st) {
+    const int rc = group_check(n, mem, host, dev, table_bytes, train);
+    if (rc) return rc;
+    return group_run(n, mem, host, dev, [&](int i) { return group_member_step(mem[i], train, st); }, st);
 }
 
 extern "C" int gcnn_group_train_step(int32_t n_members, const gcnn_group_member* members, void* host_staging, void* device_table,

@@ -198,17 +198,18 @@ struct StatArgs {
     const int* left; const int* right; const float* coef; const float* pl; const float* pr; const float* w_edge;
     const float* e_shift; const float* e_scale;   // ST_EDGE (by-left order arrays: left id via seg search is avoided: `left` is explicit)
     const double* mean;                     // pass 2: centre (device, [units]); nullptr in pass 1
-    double* partial;                        // [gridDim.x][units]
+    double* partial;                        // [blocks][units]
 };
 
-__global__ __launch_bounds__(256) void k_stats(StatArgs a) {
-    __shared__ double red[256];
+// one block's share (block `bid` of `nblk`): the solo launch runs it with (blockIdx.x, gridDim.x), a group launch with the member's
+// own pair, so the partial rows -- and the fp64 sums -- are the solo launch's
+__device__ __forceinline__ void stats_body(const StatArgs& a, double* red, const int bid, const int nblk) {
     const int units = a.src == ST_COLS ? a.f : 1;
     double acc[ST_MAX_UNITS];
 #pragma unroll
     for (int u = 0; u < ST_MAX_UNITS; ++u) acc[u] = 0.0;
     if (a.src == ST_COLS) {
-        for (int r = blockIdx.x * 256 + threadIdx.x; r < a.n; r += gridDim.x * 256)
+        for (int r = bid * 256 + threadIdx.x; r < a.n; r += nblk * 256)
 #pragma unroll
             for (int u = 0; u < ST_MAX_UNITS; ++u)
                 if (u < a.f) {
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256) void k_stats(StatArgs a) {
     } else if (a.src == ST_FLAT) {
         const double mu = a.mean ? a.mean[0] : 0.0;
         const size_t total = (size_t)a.n * EMB;
-        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        for (size_t i = (size_t)bid * 256 + threadIdx.x; i < total; i += (size_t)nblk * 256) {
             const double v = (double)a.x[i];
             if (a.mean) { const double d = v - mu; acc[0] += d * d; } else acc[0] += v;
         }
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(256) void k_stats(StatArgs a) {
         const float esh = *a.e_shift, esc = *a.e_scale;
         const int ch = (threadIdx.x & 15) * 4;
         const float4 w = *(const float4*)(a.w_edge + ch);
-        for (int e = blockIdx.x * 16 + (threadIdx.x >> 4); e < a.n; e += gridDim.x * 16) {
+        for (int e = bid * 16 + (threadIdx.x >> 4); e < a.n; e += nblk * 16) {
             const float c = (a.coef[e] + esh) * esc;
             const float4 p = *(const float4*)(a.pl + (size_t)a.left[e] * EMB + ch);
             const float4 q = *(const float4*)(a.pr + (size_t)a.right[e] * EMB + ch);
@@ -250,9 +251,13 @@ __global__ __launch_bounds__(256) void k_stats(StatArgs a) {
             if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
             __syncthreads();
         }
-        if (threadIdx.x == 0) a.partial[(size_t)blockIdx.x * units + u] = red[0];
+        if (threadIdx.x == 0) a.partial[(size_t)bid * units + u] = red[0];
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(256) void k_stats(StatArgs a) {
+    __shared__ double red[256];
+    stats_body(a, red, blockIdx.x, gridDim.x);
 }
 // out[u] = (sum over blocks of partial[b][u]) / count      (one block, fixed order)
 __global__ __launch_bounds__(64) void k_stats_final(const double* __restrict__ partial, int nblocks, int units, double count,
@@ -263,11 +268,53 @@ __global__ __launch_bounds__(64) void k_stats_final(const double* __restrict__ p
     for (int b = 0; b < nblocks; ++b) s += partial[(size_t)b * units + u];
     out[u] = s / count;
 }
-// expand a by-left CSR pointer into explicit left ids (pretraining only)
-__global__ void k_expand_ptr(const int* __restrict__ ptr, int n_seg, int* __restrict__ ids) {
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n_seg; r += gridDim.x * blockDim.x)
-        for (int e = ptr[r]; e < ptr[r + 1]; ++e) ids[e] = r;
+// expand a by-left CSR pointer into explicit left ids (pretraining only; 256 threads per block)
+struct ExpandArgs { const int* ptr; int n_seg; int* ids; };
+__device__ __forceinline__ void expand_ptr_body(const ExpandArgs& a, const int bid, const int nblk) {
+    for (int r = bid * 256 + threadIdx.x; r < a.n_seg; r += nblk * 256)
+        for (int e = a.ptr[r]; e < a.ptr[r + 1]; ++e) a.ids[e] = r;
 }
+__global__ __launch_bounds__(256) void k_expand_ptr(ExpandArgs a) { expand_ptr_body(a, blockIdx.x, gridDim.x); }
+
+// ---- the streaming merge of the statistics on the device (gcnn_prenorm_merge, include/gcnn_hip.h) -------------------------
+// A member's merge state (GCNN_PRENORM_STATE_BYTES, layout in include/gcnn_hip.h): the running fp32 count, mean[units] and
+// var[units] of the layer being fitted, and the fp64 batch mean between the two statistics passes.
+struct PrenormState { float count; float pad[3]; float mean[ST_MAX_UNITS]; float var[ST_MAX_UNITS]; double mean64[ST_MAX_UNITS]; };
+static_assert(sizeof(PrenormState) == GCNN_PRENORM_STATE_BYTES && offsetof(PrenormState, mean) == GCNN_PRENORM_STATE_MEAN &&
+              offsetof(PrenormState, var) == GCNN_PRENORM_STATE_VAR, "include/gcnn_hip.h");
+// out[u] = (sum over blocks of partial[b][u]) / count, in k_stats_final's order; then, with `state`, the batch's mean (out, from
+// the first pass) and variance (this sum) merge into the state
+struct StatFoldArgs { const double* partial; int nblocks, units; double count; double* out; PrenormState* state; };
+// Chan et al. in fp32 as the reference evaluates it in NumPy (model.py:415-423, GCNN.pretrain): the fp64 batch statistics
+// and the integer sample count rounded to fp32, every operation rounded on its own, left to right.  Contraction is off here:
+// an FMA would round once where NumPy rounds twice.
+__device__ __forceinline__ void prenorm_chan(PrenormState* st, int u, float count, double mean64, double var64, double n) {
+#pragma clang fp contract(off)
+    const float sm = (float)mean64, sv = (float)var64, sc = (float)n;
+    const float mean = st->mean[u], var = st->var[u];
+    const float delta = sm - mean;
+    const float m2 = (var * count + sv * sc) + ((delta * delta) * count) * sc / (count + sc);
+    const float c1 = count + sc;
+    st->mean[u] = mean + delta * sc / c1;
+    st->var[u] = m2 / c1;
+}
+__device__ __forceinline__ void stats_fold_body(const StatFoldArgs& a) {
+    const int u = threadIdx.x;
+    const float count = a.state ? a.state->count : 0.f;   // read by every unit before unit 0 moves it
+    __syncthreads();
+    if (u < a.units) {
+        double s = 0.0;
+        for (int b = 0; b < a.nblocks; ++b) s += a.partial[(size_t)b * a.units + u];
+        const double v = s / a.count;
+        if (a.out) a.out[u] = v;
+        if (a.state) prenorm_chan(a.state, u, count, a.state->mean64[u], v, a.count);
+    }
+    if (a.state && u == 0) {
+#pragma clang fp contract(off)
+        a.state->count = count + (float)a.count;
+    }
+}
+__global__ __launch_bounds__(64) void k_stats_fold(StatFoldArgs a) { stats_fold_body(a); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // device-side batch collation: gather the samples of one mini-batch out of a device-resident sample store

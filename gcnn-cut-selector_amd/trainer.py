@@ -2,7 +2,7 @@
 
 Mirrors (file:line in /root/reference):
   process(model, dataloader, fractions, loss_fn, optimizer)  model_trainer.py:239-316  -> process() (same positional order)
-  pretrain(model, dataloader)                                 model_trainer.py:194-236  -> pretrain()
+  pretrain(model, dataloader)                                 model_trainer.py:194-236  -> pretrain() (pretrain_many: a group)
   MeanSquaredError / Adam(learning_rate=lambda: lr)           model_trainer.py:131-132  -> mse_loss() / Adam
   ranking-prefix accuracy                                     model_trainer.py:280-302  -> ranking_fraction()
 `train_step` is the fused fast path (no autograd graph): forward -> MSE head -> backward -> [RCCL all-reduce of ONE flat
@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from .graph import _ptr, _stream
-from .model import GCNN, Batch
+from .model import GCNN, Batch, EMB, PRENORM_LAYERS
 from .store import StoreBatch
 
 
@@ -460,6 +460,99 @@ def pretrain(model: GCNN, dataloader, process_group=None):
     return i
 
 
+def _prenorm_count(dims, layer):
+    """GCNN.pretrain's sample_count: the elements PreNorm layer `layer` absorbs from a batch of these dims."""
+    if layer <= 4:
+        return [dims.n_cons, dims.n_cons_edges, dims.n_vars, dims.n_cuts, dims.n_cut_edges][layer]
+    conv, post = (layer - 5) // 2, (layer - 5) % 2
+    n_recv = [dims.n_cons, dims.n_vars, dims.n_cuts][conv]
+    n_edge = [dims.n_cons_edges, dims.n_cons_edges, dims.n_cut_edges][conv]
+    return (n_recv if post else n_edge) * EMB
+
+
+def pretrain_many(models, loaders, process_group=None):
+    """`pretrain` for up to 8 models in lockstep (gcnn_group_prenorm_merge): model i fits its PreNorm layers on loaders[i]
+    (re-iterable, yielding `SampleStore` batches or `load_batch` 11-tuples), one layer per pass, and each step of a pass sends
+    the models' batches out as one group call.  The streaming merge of the statistics runs on the device, into a small state
+    per model that the host reads once, at the end of the pass: store batches need no host read in between (tuples still go
+    through `prepare`, which checks them on the host).  A model whose loader ends waits for the others.  Returns one
+    fitted-layer count per model; model i's parameters, PreNorm state and count are those of `pretrain(models[i], loaders[i])`."""
+    if process_group is not None:
+        raise ValueError("pretrain_many: data-parallel groups are not supported (process_group must be None)")
+    n = len(models)
+    if len(loaders) != n:
+        raise ValueError(f"pretrain_many: {n} models but {len(loaders)} loaders")
+    dev = _check_group(models, loaders)
+    lib = _lib.lib()
+    words = _lib.PRENORM_STATE_BYTES // 4
+    mean0, var0 = _lib.PRENORM_STATE_MEAN // 4, _lib.PRENORM_STATE_VAR // 4
+    states = torch.empty((n, words), dtype=torch.float32, device=dev)
+    for m in models:
+        m.pretrain_init()
+    fitted = [0] * n
+    live = list(range(n))
+    while True:
+        layer = {}   # the layer each model fits in this pass: its first waiting one (none left: that model is done)
+        for i in live:
+            waiting = [j for j, st in enumerate(models[i]._prenorm_state) if st["waiting"]]
+            if waiting:
+                layer[i] = waiting[0]
+        live = [i for i in live if i in layer]
+        if not live:
+            break
+        states.zero_()
+        received = dict.fromkeys(live, False)
+        iters = {i: iter(loaders[i]) for i in live}
+        going = list(live)
+        while going:
+            step = []
+            for i in list(going):
+                try:
+                    step.append((i, next(iters[i])))
+                except StopIteration:
+                    going.remove(i)
+            members, idx, taken, prepared = [], [], [], []
+            try:
+                for i, b in step:
+                    m = models[i]
+                    try:
+                        inputs = b.batch if isinstance(b, StoreBatch) else \
+                            tuple(b[:7]) + (int(np.sum(b[7])), int(np.sum(b[8])), int(np.sum(b[9])))
+                        batch = m.prepare(inputs)
+                        received[i] = True
+                        if _prenorm_count(batch.dims, layer[i]) == 0:
+                            continue
+                        ws = m._take_workspace(batch)
+                    except torch.OutOfMemoryError:   # as `pretrain`: the batch is skipped
+                        print("WARNING: batch skipped.")
+                        continue
+                    taken.append((m, ws))
+                    prepared.append(batch)   # alive until the call has enqueued its reads
+                    members.append(_group_member(m, batch, ws, None))
+                    idx.append(i)
+                if members:
+                    layers = (C.c_int32 * len(idx))(*[layer[i] for i in idx])
+                    ptrs = (C.c_void_p * len(idx))(*[states[i].data_ptr() for i in idx])
+                    _tables(dev).call(lambda k, arr, host, table, nbytes, stream: lib.gcnn_group_prenorm_merge(
+                        k, arr, layers, ptrs, host, table, nbytes, stream), members, "gcnn_group_prenorm_merge", dev)
+            finally:
+                for m, ws in taken:
+                    m._give_workspace(ws)
+        host = states.cpu().numpy()   # the pass's one read
+        for i in live:
+            units = PRENORM_LAYERS[layer[i]][2]
+            st = models[i]._prenorm_state[layer[i]]
+            st["count"] = np.float32(host[i, 0])
+            st["mean"], st["var"] = host[i, mean0:mean0 + units].copy(), host[i, var0:var0 + units].copy()
+            st["received"] = received[i]
+            if models[i].pretrain_next() is None:
+                layer.pop(i)
+            else:
+                fitted[i] += 1
+        live = [i for i in live if i in layer]
+    return fitted
+
+
 def process_many(models, loaders, fractions: np.ndarray, optimizers=None):
     """`process` for a group of models in lockstep: model i iterates loaders[i] (training with optimizers[i] when optimizers is
     given, else validation), and the models' steps go out as group calls (`train_step_group`, `forward_group`).  A model whose
@@ -538,7 +631,7 @@ def train_models(models, seeds, train_stores, valid_stores, best_paths, fraction
     """The reference's `train_model` (model_trainer.py:52-185) for up to 8 models at once, e.g. the five seeds of a problem.
     Model i trains on `train_stores[i]` and validates on `valid_stores[i]` (`SampleStore`s; the same store may serve several
     models), with its own `np.random.default_rng(seeds[i])`, learning rate, plateau counter and best checkpoint
-    (`best_paths[i]`, written by `save_state`).  Epoch 0 pretrains each model (solo) and validates; every later epoch draws
+    (`best_paths[i]`, written by `save_state`).  Epoch 0 pretrains the models together (`pretrain_many`) and validates; every later epoch draws
     `epoch_size * batch_size` training samples with replacement, trains and validates the models still running in lockstep
     groups.  A model leaves the group at its early stop.  At the end every model is restored to its best state and validated.
     A model's history and best parameters are those of a run with that model alone.  Returns one history dict per model."""
@@ -560,10 +653,12 @@ def train_models(models, seeds, train_stores, valid_stores, best_paths, fraction
         if not live:
             break
         if epoch == 0:
+            loaders = []
             for i in live:
                 ids = np.arange(len(train_stores[i]))
-                hist[i]["pretrained_layers"] = pretrain(models[i], _StoreBatches(train_stores[i], ids[ids % 10 == 0],
-                                                                                 pretrain_batch_size))
+                loaders.append(_StoreBatches(train_stores[i], ids[ids % 10 == 0], pretrain_batch_size))
+            for i, k in zip(live, pretrain_many([models[i] for i in live], loaders)):
+                hist[i]["pretrained_layers"] = k
         else:
             loaders = [train_stores[i].batches(rngs[i].choice(len(train_stores[i]), epoch_size * batch_size, replace=True),
                                                batch_size) for i in live]

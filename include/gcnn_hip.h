@@ -355,6 +355,31 @@ int gcnn_group_train_step(int32_t n_members, const gcnn_group_member* members /*
 int gcnn_group_forward(int32_t n_members, const gcnn_group_member* members /* host */, void* host_staging, void* device_table,
                        size_t table_bytes, void* stream);
 
+/* ---- PreNorm fitting with the streaming merge on the device: GCNN.pretrain without a host read per batch --------------------
+ * gcnn_prenorm_merge: for ONE batch and ONE PreNorm layer (numbered as in gcnn_prenorm_stats), everything GCNN.pretrain does with
+ * the batch -- for layers >= 5 the gcnn_forward(save_for_backward = 2) it reads (its scores land in the workspace), then
+ * gcnn_prenorm_stats' two statistics passes (the same grids, so the same fp64 sums), then the streaming merge (Chan et al.,
+ * model.py:415-423) of the batch's mean and variance into `state`, in fp32 and rounded as NumPy rounds it: bit for bit the
+ * host merge of GCNN.pretrain.  `state`: GCNN_PRENORM_STATE_BYTES of device memory, 8-B aligned, zeroed before the first batch
+ * of a layer and read after the last: the fp32 count at byte 0, mean [units] at GCNN_PRENORM_STATE_MEAN and var [units] at
+ * GCNN_PRENORM_STATE_VAR (the rest is scratch).  A batch with nothing to absorb (the layer's input is empty: known from the
+ * dims, so the caller may skip the call) enqueues nothing and leaves the state as it was.  Arguments are checked as
+ * gcnn_prenorm_stats checks them.
+ * gcnn_group_prenorm_merge: the same for up to GCNN_GROUP_MAX models in one set of launches, member i on layers[i] (host) into
+ * states[i] (host array of device pointers), recorded and launched as gcnn_group_forward is (the members' scores, targets,
+ * grads, loss_out and adam are not used).  Every state gets the bits gcnn_prenorm_merge gives it.  Staging, table and checks
+ * as gcnn_group_forward, and also GCNN_E_BADARG (nothing enqueued) for a layer outside 0..10, a missing or misaligned state, or
+ * a state that overlaps any buffer of another member. */
+#define GCNN_PRENORM_STATE_BYTES 272
+#define GCNN_PRENORM_STATE_MEAN 16
+#define GCNN_PRENORM_STATE_VAR 80
+int gcnn_prenorm_merge(const gcnn_dims* dims, const float* params, const float* cons_feats, const float* var_feats,
+                       const float* cut_feats, const gcnn_graph* cons_graph, const gcnn_graph* cut_graph,
+                       float* workspace, size_t workspace_floats, int32_t layer, void* state, void* stream);
+int gcnn_group_prenorm_merge(int32_t n_members, const gcnn_group_member* members /* host */, const int32_t* layers /* host */,
+                             void* const* states /* host */, void* host_staging, void* device_table, size_t table_bytes,
+                             void* stream);
+
 /* ---- test stage: rankings of many candidates against one truth (model_tester.py:113-153, 205-224) --------------------------
  * For every sample s (cuts offsets[s] .. offsets[s+1]-1; K_total = offsets[n_samples] is the row stride of scores and perms), the
  * first position at which a candidate ranking deviates from the truth ranking.  Rankings are stable descending orders (Python's
