@@ -48,6 +48,16 @@ class SelectLayout(C.Structure):
     _fields_ = [("infer", InferLayout), ("forced_off", C.c_size_t * 3), ("n_kept_off", C.c_size_t), ("ws_off", C.c_size_t)]
 
 
+IBATCH_MAX, IBATCH_TABLE_COLS, IBATCH_TABLE_STRIDE = 64, 7, 72   # GCNN_IBATCH_*
+IBATCH_SCORES, IBATCH_RANK, IBATCH_SELECT = 0, 1, 2
+
+
+class IbatchLayout(C.Structure):
+    _fields_ = [("total", Dims), ("n_forced", C.c_int32), ("n_forced_entries", C.c_int32), ("max_cuts", C.c_int32),
+                ("n_states", C.c_int32), ("in_bytes", C.c_size_t), ("in_off", C.c_size_t * 12), ("out_bytes", C.c_size_t),
+                ("out_off", C.c_size_t * 4), ("arena_bytes", C.c_size_t), ("dev_off", C.c_size_t * 16)]
+
+
 class GroupMember(C.Structure):
     _fields_ = [("dims", Dims), ("params", C.c_void_p), ("cons_feats", C.c_void_p), ("var_feats", C.c_void_p),
                 ("cut_feats", C.c_void_p), ("cons_graph", Graph), ("cut_graph", Graph), ("workspace", C.c_void_p),
@@ -110,6 +120,9 @@ SIGNATURES = {
     "gcnn_prenorm_merge": (C.c_int, [_DP, _P, _P, _P, _P, _GP, _GP, _P, _Z, _I, _P, _P]),
     "gcnn_group_prenorm_merge": (C.c_int, [_I, C.POINTER(GroupMember), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), _P, _P, _Z, _P]),
     "gcnn_rank_deviations": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "gcnn_infer_batch_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(IbatchLayout)]),
+    "gcnn_infer_batch_fill_table": (C.c_int, [_I, _P, _P, _P, _P]),
+    "gcnn_infer_batch": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
 }
 
 _lib = None

@@ -1354,3 +1354,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_prenorm.hpp"
 // the test stage's rankings of many candidates against one truth (include/gcnn_hip.h: gcnn_rank_deviations): launch name k_rank_multi
 #include "gcnn_rank.hpp"
+// many host states in one call (include/gcnn_hip.h: gcnn_infer_batch): launch names k_ib_*
+#include "gcnn_ibatch.hpp"

@@ -1,0 +1,190 @@
+// gcnn_ibatch.hpp -- host side of gcnn_infer_batch (include/gcnn_hip.h): 1..64 host states in one upload, one forward pass over their
+// disjoint union, one download.  Included at the end of gcnn_capi.hip (it shares that file's statics: ProfScope, forward_impl, the
+// selection's launcher), kept apart so that its launch names form their own inventory (tests/test_ibatch_build.py).
+//
+// By-variable order of the union: the by-variable stage of gcnn_graph_build -- the same stable rocprim radix sort of (variable id,
+// input position), k_seg_offsets and k_gather_edges -- on the shifted list, not a generalised k_iplan_*.  The single-state plan
+// scans its per-variable counts in one block's LDS (32,768 variables) and ranks each variable's segment quadratically (2,048
+// edges); a union of 64 states passes the first bound at BASELINE sizes, and lifting it needs a device-wide scan, i.e. what the
+// radix sort already is.  The sort is stable, so the plan equals what BipartiteGraph builds from the collated union, and it has
+// no degree limit.  The by-left stage of gcnn_graph_build is not used: k_ib_unpack finds those offsets state by state, which
+// keeps a state with bad or unsorted ids from moving a neighbour's segments (k_ibatch.hpp).
+#include "k_ibatch.hpp"
+
+static_assert(IB_MAX_STATES == GCNN_IBATCH_MAX && IB_TS == GCNN_IBATCH_TABLE_STRIDE && IB_COLS == GCNN_IBATCH_TABLE_COLS, "table shape");
+static_assert(IB_TS >= IB_MAX_STATES + 1 && IB_TS % 4 == 0, "one offset per state and the total, 16-byte columns");
+
+struct IbSums { long long c, v, k, e1, e2, f, fe; int max_cuts; };
+static int ibatch_sums(int n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
+                       IbSums* t, int32_t* table) {
+    if (n_states < 1 || n_states > GCNN_IBATCH_MAX || !dims) return GCNN_E_BADARG;
+    if (mode < GCNN_IBATCH_SCORES || mode > GCNN_IBATCH_SELECT) return GCNN_E_BADARG;
+    IbSums s = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i <= n_states; ++i) {
+        if (table) {
+            table[IB_C * IB_TS + i] = (int)s.c; table[IB_V * IB_TS + i] = (int)s.v; table[IB_K * IB_TS + i] = (int)s.k;
+            table[IB_E1 * IB_TS + i] = (int)s.e1; table[IB_E2 * IB_TS + i] = (int)s.e2;
+            table[IB_F * IB_TS + i] = (int)s.f; table[IB_FE * IB_TS + i] = (int)s.fe;
+        }
+        if (i == n_states) break;
+        const gcnn_dims& d = dims[i];
+        const int nf = (mode == GCNN_IBATCH_SELECT && n_forced) ? n_forced[i] : 0;
+        const int nfe = (mode == GCNN_IBATCH_SELECT && n_forced_entries) ? n_forced_entries[i] : 0;
+        if (d.n_cons < 0 || d.n_vars < 0 || d.n_cuts < 0 || d.n_cons_edges < 0 || d.n_cut_edges < 0 || nf < 0 || nfe < 0) return GCNN_E_BADARG;
+        if (nf == 0 && nfe > 0) return GCNN_E_BADARG;
+        // edges with nothing to point at: every id would be out of range and there is no node of the state's own to park them on
+        if ((d.n_cons_edges > 0 && (d.n_cons == 0 || d.n_vars == 0)) || (d.n_cut_edges > 0 && (d.n_cuts == 0 || d.n_vars == 0)))
+            return GCNN_E_UNSUPPORTED;
+        s.c += d.n_cons; s.v += d.n_vars; s.k += d.n_cuts; s.e1 += d.n_cons_edges; s.e2 += d.n_cut_edges; s.f += nf; s.fe += nfe;
+        if (d.n_cuts <= SEL_MAX_CUTS) s.max_cuts = std::max(s.max_cuts, d.n_cuts);
+        // (checked as the sums grow, so that the table's int32 entries cannot wrap)
+        if (s.c > (1 << 24) || s.v > (1 << 24) || s.k > (1 << 24) || s.e1 > (1 << 30) || s.e2 > (1 << 30) || s.f > (1 << 24) || s.fe > (1 << 30))
+            return GCNN_E_UNSUPPORTED;
+    }
+    if (t) *t = s;
+    return 0;
+}
+
+static int ibatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
+                         gcnn_ibatch_layout* L) {
+    if (!L) return GCNN_E_BADARG;
+    IbSums t;
+    const int rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, mode, &t, nullptr);
+    if (rc) return rc;
+    memset(L, 0, sizeof(*L));
+    L->total = gcnn_dims{(int)t.c, (int)t.v, (int)t.k, (int)t.e1, (int)t.e2};
+    L->n_forced = (int)t.f; L->n_forced_entries = (int)t.fe; L->max_cuts = t.max_cuts; L->n_states = n_states;
+    const size_t S = n_states, C = t.c, V = t.v, K = t.k, E1 = t.e1, E2 = t.e2, F = t.f, FE = t.fe;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al16(bytes); return o; };
+    L->in_off[0] = take(4 * (size_t)IB_COLS * IB_TS);
+    L->in_off[1] = take(al16(16 * S) + al16(4 * (C + 1)) + al16(4 * (K + 1)));   // zero block: flags | l_ptr cons | l_ptr cut
+    L->in_off[2] = take(16 * C);
+    L->in_off[3] = take(8 * E1);
+    L->in_off[4] = take(4 * E1);
+    L->in_off[5] = take(56 * V);
+    L->in_off[6] = take(24 * K);
+    L->in_off[7] = take(8 * E2);
+    L->in_off[8] = take(4 * E2);
+    L->in_off[9] = take(4 * (F + 1));
+    L->in_off[10] = take(4 * FE);
+    L->in_off[11] = take(4 * FE);
+    L->in_bytes = off;
+    L->out_off[0] = 0; L->out_off[1] = al16(4 * K); L->out_off[2] = L->out_off[1] + al16(4 * K);
+    L->out_off[3] = L->out_off[2] + al16(4 * S);
+    L->out_bytes = L->out_off[3] + 16 * S;
+    size_t a = (off + 255) & ~(size_t)255;
+    auto dev = [&](size_t bytes) { const size_t o = a; a += (bytes + 255) & ~(size_t)255; return o; };
+    L->dev_off[0] = dev(4 * E1);            // left: union row ids of the constraint edges
+    L->dev_off[1] = dev(4 * E1);            // var, constraint edges (= by-left oth)
+    L->dev_off[2] = dev(4 * E2);            // var, cut edges
+    L->dev_off[3] = dev(4 * E1);            // iota
+    L->dev_off[4] = dev(4 * E1);            // sorted keys
+    L->dev_off[5] = dev(4 * E1);            // permutation
+    L->dev_off[6] = dev(4 * (V + 1));       // v_ptr
+    L->dev_off[7] = dev(4 * E1);            // v_oth
+    L->dev_off[8] = dev(4 * E1);            // v_coef
+    L->dev_off[9] = dev(4 * FE);            // forced columns in the union's column space
+    L->dev_off[10] = dev(sort_temp_bytes((int)E1));
+    L->dev_off[11] = dev(L->out_bytes);
+    L->dev_off[12] = dev(sizeof(float) * gcnn_workspace_floats(&L->total));
+    L->dev_off[13] = dev(mode == GCNN_IBATCH_SELECT ? select_ws_bytes((int)K, (int)F, t.max_cuts) : 0);
+    L->arena_bytes = a;
+    return 0;
+}
+
+extern "C" int gcnn_infer_batch_layout_for(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
+                                           const int32_t* n_forced_entries, int32_t mode, gcnn_ibatch_layout* L) {
+    return ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, L);
+}
+
+extern "C" int gcnn_infer_batch_fill_table(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
+                                           const int32_t* n_forced_entries, int32_t* table) {
+    if (!table) return GCNN_E_BADARG;
+    // (forced rows are counted whenever they are given: a table filled for SELECT serves the other modes too)
+    return ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, table);
+}
+
+extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                                int32_t mode, const float* params, const void* host_in, void* host_out, void* arena,
+                                size_t arena_bytes, double p_max, double p_max_ub, void* stream) {
+    gcnn_ibatch_layout L;
+    int rc = ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, &L);
+    if (rc) return rc;
+    if (!params || !host_in || !host_out || !arena || arena_bytes < L.arena_bytes || ((uintptr_t)arena & 255)) return GCNN_E_BADARG;
+    if (mode == GCNN_IBATCH_SELECT && (!finite_threshold(p_max) || !finite_threshold(p_max_ub))) return GCNN_E_BADARG;
+    layout_init();
+    const gcnn_dims& T = L.total;
+    {   // what the forward pass itself would refuse, before anything is enqueued
+        gcnn_graph g; memset(&g, 0, sizeof(g));
+        if ((rc = check_common(&T, params, &g, &g, (float*)arena, gcnn_workspace_floats(&T)))) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char* A = (char*)arena;
+    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload
+    const size_t S = n_states;
+    const int E1 = T.n_cons_edges, E2 = T.n_cut_edges, V = T.n_vars, K = T.n_cuts, FE = L.n_forced_entries;
+    const int* table = (const int*)(A + L.in_off[0]);
+    IbArgs ia; memset(&ia, 0, sizeof(ia));
+    ia.table = table; ia.n_states = n_states;
+    ia.packed[0] = (const int*)(A + L.in_off[3]); ia.packed[1] = (const int*)(A + L.in_off[7]);
+    ia.left = (int*)(A + L.dev_off[0]); ia.var[0] = (int*)(A + L.dev_off[1]); ia.var[1] = (int*)(A + L.dev_off[2]);
+    ia.flags = (int*)(A + L.in_off[1]);
+    ia.l_ptr[0] = (int*)(A + L.in_off[1] + al16(16 * S));
+    ia.l_ptr[1] = (int*)(A + L.in_off[1] + al16(16 * S) + al16(4 * ((size_t)T.n_cons + 1)));
+    ia.iota = (int*)(A + L.dev_off[3]);
+    ia.f_col_in = (const int*)(A + L.in_off[10]); ia.f_col = (int*)(A + L.dev_off[9]);
+    {
+        const long long items = (long long)E1 + E2 + 2 * n_states + FE;
+        ProfScope prof("k_ib_unpack", st);
+        hipLaunchKernelGGL(k_ib_unpack, dim3((unsigned)std::min<long long>((items + 255) / 256, 1024)), dim3(256), 0, st, ia);
+        LAUNCHCHK();
+    }
+    gcnn_graph cg, kg; memset(&cg, 0, sizeof(cg)); memset(&kg, 0, sizeof(kg));
+    cg.l_ptr = ia.l_ptr[0]; cg.l_oth = ia.var[0]; cg.l_coef = (const float*)(A + L.in_off[4]);
+    cg.v_ptr = (int*)(A + L.dev_off[6]); cg.v_oth = (int*)(A + L.dev_off[7]); cg.v_coef = (float*)(A + L.dev_off[8]);
+    kg.l_ptr = ia.l_ptr[1]; kg.l_oth = ia.var[1]; kg.l_coef = (const float*)(A + L.in_off[8]);
+    kg.v_ptr = cg.v_ptr;   // never read: conv v->k gathers by cut only and nothing is differentiated
+    if (E1 > 0) {          // gcnn_graph_build's by-variable stage on the union's list
+        int* keys = (int*)(A + L.dev_off[4]);
+        int* perm = (int*)(A + L.dev_off[5]);
+        size_t sort_bytes = sort_temp_bytes(E1);
+        unsigned bits = 1;
+        while ((1ll << bits) < (long long)V + 1 && bits < 31) ++bits;
+        const int grid = std::min(cdiv(E1 + 1, 256), 4096);
+        ProfScope prof("k_ib_by_variable", st);
+        HIPCHK(rocprim::radix_sort_pairs((void*)(A + L.dev_off[10]), sort_bytes, (const int*)ia.var[0], keys, (const int*)ia.iota, perm,
+                                         (unsigned)E1, 0u, bits, st));
+        hipLaunchKernelGGL(k_seg_offsets, dim3(grid), dim3(256), 0, st, (const int*)keys, E1, V, (int*)cg.v_ptr);
+        LAUNCHCHK();
+        hipLaunchKernelGGL(k_gather_edges, dim3(grid), dim3(256), 0, st, (const int*)perm, (const int*)ia.left, cg.l_coef, E1,
+                           (int*)cg.v_oth, (float*)cg.v_coef);
+        LAUNCHCHK();
+    } else {
+        HIPCHK(hipMemsetAsync((void*)cg.v_ptr, 0, ((size_t)V + 1) * sizeof(int), st));
+    }
+    char* out = A + L.dev_off[11];
+    float* scores = (float*)(out + L.out_off[0]);
+    // ONE forward pass over the union (the longest segments are not known here: 0)
+    rc = forward_impl(&T, params, (const float*)(A + L.in_off[2]), (const float*)(A + L.in_off[5]), (const float*)(A + L.in_off[6]),
+                      &cg, &kg, (float*)(A + L.dev_off[12]), gcnn_workspace_floats(&T), scores, 0, nullptr, 0.f, st);
+    if (rc) return rc;
+    if (mode == GCNN_IBATCH_RANK && K > 0) {
+        ProfScope prof("k_ib_rank", st);
+        hipLaunchKernelGGL(k_ib_rank, dim3(n_states), dim3(256), 0, st, (const float*)scores, table, (int*)(out + L.out_off[1]));
+        LAUNCHCHK();
+    }
+    if (mode == GCNN_IBATCH_SELECT) {
+        SelArgs a;
+        a.q = scores; a.c_ptr = kg.l_ptr; a.c_col = kg.l_oth; a.c_val = kg.l_coef; a.c_off = table + IB_K * IB_TS;
+        a.f_ptr = (const int*)(A + L.in_off[9]); a.f_col = ia.f_col; a.f_val = (const float*)(A + L.in_off[11]);
+        a.f_off = L.n_forced > 0 ? table + IB_F * IB_TS : nullptr;
+        a.n_samples = n_states; a.total_cuts = K; a.total_forced = L.n_forced; a.max_cuts = L.max_cuts; a.n_vars = V;
+        a.words = (L.max_cuts + 63) / 64; a.p_max = p_max; a.p_max_ub = p_max_ub;
+        a.bits = (unsigned long long*)(A + L.dev_off[13]); a.order = (int*)(out + L.out_off[1]); a.n_kept = (int*)(out + L.out_off[2]);
+        if ((rc = launch_select(a, st))) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(out + L.out_off[3], ia.flags, 16 * S, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));   // ONE download: scores | order | n_kept | flags
+    return 0;
+}

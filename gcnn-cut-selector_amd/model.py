@@ -265,6 +265,108 @@ class _InferenceSession:
         return scores, order, n_kept
 
 
+class _BatchSession:
+    """Host side of gcnn_infer_batch (include/gcnn_hip.h): persistent pinned staging buffers and a device arena, one C call for up to
+    64 host states.  `run` answers per state: ("ok", scores, order, n_kept), ("bad_index",) or ("declined",)."""
+    MAX = _lib.IBATCH_MAX
+
+    def __init__(self, model):
+        self.model = model
+        self.pin_in = self.pin_out = self.arena = None
+        self.in_np = self.out_np = None
+        self.sort_scratch = None
+        self.layouts = {}
+        self.calls = 0            # C calls made (tools and tests read it)
+
+    _buffers = _InferenceSession._buffers
+
+    def _layout(self, keys, fshapes, mode):
+        lkey = (mode, keys, fshapes)
+        lay = self.layouts.get(lkey)
+        if lay is None:
+            n = len(keys)
+            dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
+            nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
+            nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+            L = _lib.IbatchLayout()
+            rc = _lib.lib().gcnn_infer_batch_layout_for(n, dims, nf, nfe, mode, C.byref(L))
+            if rc == -4:
+                lay = False
+            else:
+                _lib.check(rc, "gcnn_infer_batch_layout_for")
+                table = np.zeros(_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE, np.int32)
+                _lib.check(_lib.lib().gcnn_infer_batch_fill_table(n, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
+                lay = (dims, nf, nfe, L, list(L.in_off), list(L.out_off), table,
+                       table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :n + 1].tolist())
+            if len(self.layouts) >= 64:
+                self.layouts.pop(next(iter(self.layouts)))   # evict the oldest entry only
+            self.layouts[lkey] = lay
+        return lay
+
+    def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
+        """checked: [(arrays, key)] as `_InferenceSession._check_inputs` returns them; forced: None or [(ptr, col, val)] per state.
+        Returns None when the library declines the union as a whole (too large: the caller splits it)."""
+        keys = tuple(k for _, k in checked)
+        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        lay = self._layout(keys, fshapes, mode)
+        if lay is False:
+            return None
+        dims, nf, nfe, L, in_off, out_off, table, (c_off, v_off, k_off, e1_off, e2_off, f_off, fe_off) = lay
+        self._buffers(L)
+        buf, base = self.in_np, self.pin_in.data_ptr()
+        buf[in_off[0]:in_off[0] + table.nbytes] = table.view(np.uint8)
+        buf[in_off[1]:in_off[2]] = 0          # flags and by-left offsets travel zeroed inside the upload
+        pack = _lib.lib().gcnn_host_pack_edges
+        for s, ((c, cei, cef, v, k, kei, kef), key) in enumerate(checked):
+            for off, a in ((in_off[2] + 16 * c_off[s], c), (in_off[5] + 56 * v_off[s], v), (in_off[6] + 24 * k_off[s], k)):
+                if a.size:
+                    np.copyto(buf[off:off + 4 * a.size].view(np.float32).reshape(a.shape), a, casting="unsafe")
+            for io, fo, ei, ef, n_left in ((in_off[3] + 8 * e1_off[s], in_off[4] + 4 * e1_off[s], cei, cef, key[0]),
+                                           (in_off[7] + 8 * e2_off[s], in_off[8] + 4 * e2_off[s], kei, kef, key[2])):
+                if not ei.size:
+                    continue
+                ei32 = np.ascontiguousarray(ei, dtype=np.int32)
+                ef32 = np.ascontiguousarray(ef, dtype=np.float32).reshape(-1)
+                if self.sort_scratch is None or self.sort_scratch.size < n_left + 1:
+                    self.sort_scratch = np.empty(2 * (n_left + 1), np.int32)
+                rc = pack(ei32.ctypes.data, ei32.ctypes.data + 4 * ei32.shape[1], ef32.ctypes.data, ei32.shape[1], n_left,
+                          base + io, base + fo, self.sort_scratch.ctypes.data)
+                if rc < 0:
+                    _lib.check(rc, "gcnn_host_pack_edges")
+            if forced is not None:
+                fptr, fcol, fval = forced[s]
+                o = in_off[9] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next state's first
+                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
+                for off, a in ((in_off[10] + 4 * fe_off[s], fcol), (in_off[11] + 4 * fe_off[s], fval)):
+                    buf[off:off + a.nbytes] = a.view(np.uint8)
+        if forced is None:
+            buf[in_off[9]:in_off[9] + 4] = 0
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib().gcnn_infer_batch(len(checked), dims, nf, nfe, mode, C.c_void_p(self.model._flat.data_ptr()),
+                                                  C.c_void_p(self.pin_in.data_ptr()), C.c_void_p(self.pin_out.data_ptr()),
+                                                  C.c_void_p(self.arena.data_ptr()), self.arena.numel(), float(p_max),
+                                                  float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_batch")
+            stream.synchronize()
+        self.calls += 1
+        out, n = self.out_np, len(checked)
+        flags = out[out_off[3]:out_off[3] + 16 * n].view(np.int32).reshape(n, 4)
+        n_kept = out[out_off[2]:out_off[2] + 4 * n].view(np.int32)
+        res = []
+        for s in range(n):
+            if flags[s, 0]:
+                res.append(("bad_index",))
+            elif flags[s, 1] or flags[s, 2] or flags[s, 3]:
+                res.append(("declined",))
+            else:
+                lo, K = 4 * k_off[s], 4 * (k_off[s + 1] - k_off[s])
+                scores = out[out_off[0] + lo:out_off[0] + lo + K].view(np.float32).copy().view(ScoreArray)
+                order = out[out_off[1] + lo:out_off[1] + lo + K].view(np.int32).copy() if mode else None
+                res.append(("ok", scores, order, int(n_kept[s]) if mode == _lib.IBATCH_SELECT else None))
+        return res
+
+
 class Batch:
     """A stacked mini-batch resident on the GPU: features + both CSR orders of both edge sets (GCNN.prepare)."""
 
@@ -347,6 +449,7 @@ class GCNN:
                                  ("float32", (None, 1)), ("int32", ()), ("int32", ()), ("int32", ())), ("bool", ())]
         self._ws_pool = []
         self._session = None      # single-state inference (gcnn_infer): pinned staging + device arena, created on first use
+        self._batch_session = None   # many host states per call (gcnn_infer_batch), created on first use
         self._pin = None          # pinned host staging buffer for prepare()
         self._pin_event = None
         self._prenorm_state = None
@@ -706,6 +809,120 @@ class GCNN:
         scores, order, n_kept = result
         n_selected = n_kept if max_selected is None else min(n_kept, int(max_selected))
         return SelectResult(order, n_kept, n_selected, scores)
+
+    # ---- many host states in one call (gcnn_infer_batch): what a scoring server does with the requests that queued up ----------
+    def _many(self, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0):
+        """Common part of `score_states` / `select_cuts_many`: results per state -- ("ok", scores, order, n_kept), or an exception.
+        `solo(i)`: the existing single-state entry point for state i (a state the batch declines goes there and comes back in
+        place).  `forced`: None or per state a packed (ptr, col, val) / an exception raised while it was packed."""
+        n = len(states)
+        results, checked, batch_ids, solo_ids = [None] * n, {}, [], []
+        for i, st in enumerate(states):
+            try:
+                if forced is not None and isinstance(forced[i], Exception):
+                    raise forced[i]
+                if isinstance(st, Batch) or len(st) != 10 or any(isinstance(x, torch.Tensor) for x in st[:7]):
+                    solo_ids.append(i)          # device tensors, prepared batches, malformed tuples: the solo path answers (or raises)
+                    continue
+                arrays, key = _InferenceSession._check_inputs(st)
+            except Exception as exc:  # noqa: BLE001 -- the error belongs to this state's slot
+                results[i] = exc
+                continue
+            n_cons, n_vars, n_cuts, e1, e2 = key
+            declined = (n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096)
+                        or (e1 and (n_cons == 0 or n_vars == 0)) or (e2 and n_vars == 0))
+            if declined:
+                solo_ids.append(i)
+            else:
+                checked[i] = (arrays, key)
+                batch_ids.append(i)
+        if self._batch_session is None:
+            self._batch_session = _BatchSession(self)
+        todo = [batch_ids[j:j + _BatchSession.MAX] for j in range(0, len(batch_ids), _BatchSession.MAX)]
+        while todo:
+            ids = todo.pop(0)
+            got = self._batch_session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode,
+                                          p_max, p_max_ub)
+            if got is None:                     # the union is past the library's limits: halves, and a single state goes solo
+                if len(ids) == 1:
+                    solo_ids.append(ids[0])
+                else:
+                    todo[:0] = [ids[:len(ids) // 2], ids[len(ids) // 2:]]
+                continue
+            for i, r in zip(ids, got):
+                if r[0] == "ok":
+                    results[i] = r
+                elif r[0] == "bad_index":
+                    results[i] = ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
+                else:
+                    solo_ids.append(i)
+        for i in solo_ids:
+            try:
+                results[i] = solo(i)
+            except Exception as exc:  # noqa: BLE001
+                results[i] = exc
+        return results
+
+    @staticmethod
+    def _finish_many(results, return_exceptions):
+        if not return_exceptions:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
+
+    def score_states(self, states, rank=False, return_exceptions=False):
+        """`score_state` for many host states at once: one upload, ONE forward pass over their disjoint union, one download
+        (gcnn_infer_batch; up to 64 states per call, more are served in several calls).  Returns a list of `ScoreArray`, with
+        `.rankings` when `rank`.  Errors are per state: with `return_exceptions=True` a state's exception (e.g. the ValueError
+        of an out-of-range index) sits in its slot; otherwise the first one is raised after every state has been served.  States
+        the batch declines (no cuts, more than 4,096 cuts when ranking, ...) go through `score_state` and come back in place."""
+        states = list(states)
+        mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
+        results = self._many(states, mode, lambda i: self.score_state(states[i], rank))
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                scores = r[1]
+                if rank:
+                    scores.rankings = r[2]
+                results[i] = scores
+        return self._finish_many(results, return_exceptions)
+
+    def select_cuts_many(self, states, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
+        """`select_cuts` for many host states at once (gcnn_infer_batch in selection mode).  `forced`: None, or one entry per state
+        in the forms `select_cuts` accepts (None = no forced rows).  Returns a list of `SelectResult`; errors per state as in
+        `score_states` (a state with more than 4,096 cuts holds the `GcnnError` `select_cuts` raises for it)."""
+        from . import ops
+        ops.check_thresholds(p_max, p_max_ub)
+        states = list(states)
+        forced = [None] * len(states) if forced is None else list(forced)
+        if len(forced) != len(states):
+            raise ValueError(f"forced: one entry per state expected, got {len(forced)} for {len(states)} states")
+        packed = []
+        for st, f in zip(states, forced):
+            try:
+                if f is None:
+                    f = (np.zeros((2, 0), np.int32), np.zeros(0, np.float32), 0)
+                if len(f) == 2:
+                    fi = np.asarray(f[0])
+                    f = (f[0], f[1], int(fi[0].max()) + 1 if fi.size else 0)
+                fi, fv, n_forced = f
+                if isinstance(fi, torch.Tensor):
+                    fi, fv = fi.cpu().numpy(), fv.cpu().numpy()
+                n_vars = st.dims.n_vars if isinstance(st, Batch) else int(np.asarray(st[3]).shape[0])
+                packed.append(ops.pack_rows(fi, fv, int(n_forced), n_vars))
+            except Exception as exc:  # noqa: BLE001
+                packed.append(exc)
+
+        def solo(i):
+            return self.select_cuts(states[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
+
+        results = self._many(states, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub)
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                _, scores, order, n_kept = r
+                results[i] = SelectResult(order, n_kept, n_kept if max_selected is None else min(n_kept, int(max_selected)), scores)
+        return self._finish_many(results, return_exceptions)
 
     def get_concrete_function(self):
         """Counterpart of `tf.function(model.call).get_concrete_function()` (model_evaluator.py:310-311): an inference

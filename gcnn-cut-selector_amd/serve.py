@@ -1,0 +1,368 @@
+"""A scoring server: any number of CPU-only worker processes (the evaluators' task farms, model_evaluator.py:157-241: SCIP in every
+worker, one selector call per separation round) share ONE process that owns the GPU.
+
+    server = ScoringServer({"setcov": model}, "/tmp/gcnn.sock"); server.start()          # the GPU process
+    client = ScoringClient("/tmp/gcnn.sock", "setcov")                                    # a worker: NumPy only, no torch
+    CustomCutsel(function=client.get_concrete_function(), ...)                            # model_evaluator.py:310-314
+
+The server takes every request that is waiting, groups them by model and kind, answers each group with one
+`GCNN.score_states` / `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) and goes back
+for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.
+
+Wire format (AF_UNIX stream; little-endian; no pickle -- nothing a peer sends is ever executed): a message is a uint32 byte count
+followed by that many bytes: a fixed header, the model key, then arrays, each a 24-byte descriptor (dtype code, ndim, two
+dimensions, byte count) followed by its raw buffer.  This module imports no torch: workers stay light."""
+
+from __future__ import annotations
+
+import os
+import selectors
+import socket
+import struct
+import threading
+
+import numpy as np
+
+MAGIC = b"GCS1"
+KIND_SCORE, KIND_RANK, KIND_SELECT = 0, 1, 2
+MAX_MESSAGE = 1 << 30
+# request: magic, kind, n_arrays, key length, p_max, p_max_ub, max_selected (-1: none), n_forced (-1: no forced rows), n_cons, n_vars, n_cuts
+_REQ = struct.Struct("<4sBBHddiiiii")
+# reply: magic, status (0 ok, else an error class), n_arrays, pad, n_kept, n_selected
+_REP = struct.Struct("<4sBBHii")
+_ARR = struct.Struct("<BBHIIQ4x")      # dtype code, ndim, pad, dim0, dim1, bytes
+_DTYPES = ("<f4", "<f8", "<i4", "<i8", "|u1")
+_CODES = {np.dtype(d): i for i, d in enumerate(_DTYPES)}
+ERR_VALUE, ERR_GCNN, ERR_OTHER = 1, 2, 3
+
+
+class ServerError(RuntimeError):
+    """The server answered a request with an error that is not a ValueError of the request's own data."""
+
+
+class ProtocolError(ValueError):
+    pass
+
+
+def _wire_array(a):
+    a = np.asarray(a)
+    if a.dtype not in _CODES:
+        if a.dtype.kind in "iub":
+            a = a.astype(np.int64)
+        elif a.dtype.kind == "f":
+            a = a.astype(np.float64)
+        else:
+            raise ValueError(f"cannot send an array of dtype {a.dtype}")
+    if a.ndim > 2:
+        raise ValueError(f"cannot send an array of {a.ndim} dimensions")
+    return np.ascontiguousarray(a)
+
+
+def _put_arrays(parts, arrays):
+    for a in arrays:
+        a = _wire_array(a)
+        shape = tuple(a.shape) + (0,) * (2 - a.ndim)
+        parts.append(_ARR.pack(_CODES[a.dtype], a.ndim, 0, shape[0], shape[1], a.nbytes))
+        parts.append(a.tobytes())
+
+
+def _get_arrays(buf, at, count):
+    out = []
+    for _ in range(count):
+        if at + _ARR.size > len(buf):
+            raise ProtocolError("truncated array descriptor")
+        code, ndim, _, d0, d1, nbytes = _ARR.unpack_from(buf, at)
+        at += _ARR.size
+        if code >= len(_DTYPES) or ndim > 2:
+            raise ProtocolError("unknown dtype code or rank")
+        dt = np.dtype(_DTYPES[code])
+        shape = (d0, d1)[:ndim]
+        if int(np.prod(shape, dtype=np.int64)) * dt.itemsize != nbytes or at + nbytes > len(buf):
+            raise ProtocolError("array size does not match its descriptor")
+        out.append(np.frombuffer(buf, dt, int(nbytes // dt.itemsize), at).reshape(shape).copy())
+        at += nbytes
+    return out, at
+
+
+def encode_request(model_key, kind, state, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
+    """-> the message's bytes (without the length prefix).  `state`: the model's 10-tuple of host arrays; `forced`: None or
+    (edge_inds [2,E], values [E][, n_forced]) as `GCNN.select_cuts` takes it."""
+    if len(state) != 10:
+        raise ValueError(f"expected the 10-tuple state, got {len(state)} items")
+    key = model_key.encode("utf-8")
+    arrays = list(state[:7])
+    n_forced = -1
+    if forced is not None:
+        fi = np.asarray(forced[0])
+        n_forced = int(forced[2]) if len(forced) > 2 else (int(fi[0].max()) + 1 if fi.size else 0)
+        arrays += [fi, np.asarray(forced[1])]
+    parts = [_REQ.pack(MAGIC, kind, len(arrays), len(key), float(p_max), float(p_max_ub), -1 if max_selected is None else int(max_selected),
+                       n_forced, int(state[7]), int(state[8]), int(state[9])), key]
+    _put_arrays(parts, arrays)
+    return b"".join(parts)
+
+
+def decode_request(buf):
+    """-> dict(model_key, kind, state, forced, p_max, p_max_ub, max_selected); raises ProtocolError on anything malformed."""
+    if len(buf) < _REQ.size:
+        raise ProtocolError("truncated header")
+    magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, n_cons, n_vars, n_cuts = _REQ.unpack_from(buf, 0)
+    if magic != MAGIC or kind > KIND_SELECT or n_arrays != (9 if n_forced >= 0 else 7):
+        raise ProtocolError("not a request of this protocol")
+    at = _REQ.size + key_len
+    if at > len(buf):
+        raise ProtocolError("truncated model key")
+    key = bytes(buf[_REQ.size:at]).decode("utf-8", "replace")
+    arrays, at = _get_arrays(buf, at, n_arrays)
+    if at != len(buf):
+        raise ProtocolError("trailing bytes")
+    return dict(model_key=key, kind=kind, state=tuple(arrays[:7]) + (n_cons, n_vars, n_cuts),
+                forced=(arrays[7], arrays[8], n_forced) if n_forced >= 0 else None, p_max=p_max, p_max_ub=p_max_ub,
+                max_selected=None if max_selected < 0 else max_selected)
+
+
+def encode_reply(arrays=(), n_kept=-1, n_selected=-1, error=None):
+    if error is not None:
+        status = ERR_VALUE if isinstance(error, ValueError) else ERR_GCNN if type(error).__name__ == "GcnnError" else ERR_OTHER
+        arrays = [np.frombuffer(f"{type(error).__name__}: {error}".encode("utf-8", "replace"), np.uint8)]
+    else:
+        status = 0
+    parts = [_REP.pack(MAGIC, status, len(arrays), 0, n_kept, n_selected)]
+    _put_arrays(parts, arrays)
+    return b"".join(parts)
+
+
+def decode_reply(buf):
+    """-> (arrays, n_kept, n_selected); raises what the server reported."""
+    if len(buf) < _REP.size:
+        raise ProtocolError("truncated reply")
+    magic, status, n_arrays, _, n_kept, n_selected = _REP.unpack_from(buf, 0)
+    if magic != MAGIC:
+        raise ProtocolError("not a reply of this protocol")
+    arrays, _ = _get_arrays(buf, _REP.size, n_arrays)
+    if status:
+        text = arrays[0].tobytes().decode("utf-8", "replace") if arrays else "error"
+        raise (ValueError if status == ERR_VALUE else ServerError)(text)
+    return arrays, n_kept, n_selected
+
+
+def _recv_exact(sock, n):
+    chunks, got = [], 0
+    while got < n:
+        c = sock.recv(min(n - got, 1 << 20))
+        if not c:
+            raise ConnectionError("the scoring server closed the connection")
+        chunks.append(c)
+        got += len(c)
+    return b"".join(chunks)
+
+
+# ---- client: NumPy only ------------------------------------------------------------------------------------------------------------
+class Scores(np.ndarray):
+    """Scores as the plugins use them: an ndarray that answers `.numpy()` (model_evaluator.py:103); `rankings` when asked for."""
+    rankings = None
+
+    def numpy(self):
+        return np.asarray(self)
+
+
+class Selection:
+    """`order` (kept cuts first, best first, then the removed ones), `n_kept`, `n_selected` = min(n_kept, max_selected), `scores`."""
+
+    def __init__(self, order, n_kept, n_selected, scores):
+        self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
+
+
+class ScoringClient:
+    def __init__(self, address, model_key, timeout=None):
+        self.model_key = model_key
+        self.sock = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
+        self.sock.settimeout(timeout)
+        self.sock.connect(address)
+
+    def _call(self, message):
+        self.sock.sendall(struct.pack("<I", len(message)) + message)
+        (n,) = struct.unpack("<I", _recv_exact(self.sock, 4))
+        return decode_reply(_recv_exact(self.sock, n))
+
+    def score_state(self, state, rank=False):
+        arrays, _, _ = self._call(encode_request(self.model_key, KIND_RANK if rank else KIND_SCORE, state))
+        scores = arrays[0].view(Scores)
+        if rank:
+            scores.rankings = arrays[1]
+        return scores
+
+    def select_cuts(self, state, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        arrays, n_kept, n_selected = self._call(encode_request(self.model_key, KIND_SELECT, state, forced, p_max, p_max_ub, max_selected))
+        return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores))
+
+    def get_concrete_function(self):
+        """The `(state10, training) -> scores` callable `CustomCutsel(function=...)` stores (model_evaluator.py:310-314)."""
+        def get_improvements(state, training=False, rank=False):
+            return self.score_state(state, rank)
+        return get_improvements
+
+    def close(self):
+        self.sock.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+# ---- server ------------------------------------------------------------------------------------------------------------------------
+class ScoringServer:
+    """Owns the models (and with them the GPU).  `address`: path of the AF_UNIX socket, bound and listening from construction on, so
+    that requests sent before `start()` simply wait.  `start()` serves in a thread of this process; `serve_forever()` in the
+    calling thread.  `stats`: requests, calls (one per group served) and batched_calls (calls that served more than one request),
+    max_batch."""
+
+    def __init__(self, models, address, backlog=128):
+        self.models = dict(models)
+        self.address = address
+        self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0)
+        self._listen = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
+        self._listen.bind(address)
+        self._listen.listen(backlog)
+        self._wake_r, self._wake_w = socket.socketpair()
+        self._closing = False
+        self._thread = None
+        self._buffers = {}
+
+    def start(self):
+        self._thread = threading.Thread(target=self.serve_forever, name="gcnn-scoring-server", daemon=True)
+        self._thread.start()
+        return self
+
+    def close(self):
+        """Ends the loop (after the group being served), closes every connection and removes the socket file."""
+        self._closing = True
+        try:
+            self._wake_w.send(b"x")
+        except OSError:
+            pass
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+        else:
+            self._shutdown()
+
+    def _shutdown(self):
+        for s in list(self._buffers) + [self._listen, self._wake_r, self._wake_w]:
+            try:
+                s.close()
+            except OSError:
+                pass
+        self._buffers.clear()
+        try:
+            os.unlink(self.address)
+        except OSError:
+            pass
+
+    def _reply(self, conn, message):
+        try:
+            conn.sendall(struct.pack("<I", len(message)) + message)
+        except OSError:
+            self._drop(conn)
+
+    def _drop(self, conn):
+        if conn in self._buffers:
+            del self._buffers[conn]
+            try:
+                self._sel.unregister(conn)
+            except (KeyError, ValueError):
+                pass
+            conn.close()
+
+    def _read(self, conn, pending):
+        try:
+            data = conn.recv(1 << 20)
+        except OSError:
+            data = b""
+        if not data:
+            self._drop(conn)
+            return
+        buf = self._buffers[conn]
+        buf += data
+        while len(buf) >= 4:
+            (n,) = struct.unpack_from("<I", buf, 0)
+            if n > MAX_MESSAGE:            # the framing itself cannot be trusted any more: answer and hang up
+                self.stats["errors"] += 1
+                self._reply(conn, encode_reply(error=ProtocolError("message too large")))
+                self._drop(conn)
+                return
+            if len(buf) < 4 + n:
+                break
+            message = bytes(buf[4:4 + n])
+            del buf[:4 + n]
+            self.stats["requests"] += 1
+            try:
+                req = decode_request(message)
+                if req["model_key"] not in self.models:
+                    raise KeyError(f"no model {req['model_key']!r}")
+                pending.append((conn, req))
+            except Exception as exc:  # noqa: BLE001 -- a bad request gets its error; the server keeps serving
+                self.stats["errors"] += 1
+                self._reply(conn, encode_reply(error=exc))
+
+    def _serve(self, pending):
+        groups = {}
+        for conn, req in pending:
+            gkey = (req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if req["kind"] == KIND_SELECT else ())
+            groups.setdefault(gkey, []).append((conn, req))
+        for gkey, items in groups.items():
+            model, kind = self.models[gkey[0]], gkey[1]
+            states = [r["state"] for _, r in items]
+            self.stats["calls"] += 1
+            self.stats["batched_calls"] += len(items) > 1
+            self.stats["max_batch"] = max(self.stats["max_batch"], len(items))
+            try:
+                if kind == KIND_SELECT:
+                    results = model.select_cuts_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3],
+                                                     return_exceptions=True)
+                else:
+                    results = model.score_states(states, rank=kind == KIND_RANK, return_exceptions=True)
+            except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
+                results = [exc] * len(items)
+            for (conn, req), res in zip(items, results):
+                if conn not in self._buffers:
+                    continue
+                if isinstance(res, Exception):
+                    self.stats["errors"] += 1
+                    self._reply(conn, encode_reply(error=res))
+                elif kind == KIND_SELECT:
+                    ms = req["max_selected"]
+                    self._reply(conn, encode_reply([np.asarray(res.scores), np.asarray(res.order, np.int32)], res.n_kept,
+                                                   res.n_kept if ms is None else min(res.n_kept, ms)))
+                else:
+                    arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if kind == KIND_RANK else [])
+                    self._reply(conn, encode_reply(arrays))
+
+    def serve_forever(self):
+        self._sel = sel = selectors.DefaultSelector()
+        sel.register(self._listen, selectors.EVENT_READ)
+        sel.register(self._wake_r, selectors.EVENT_READ)
+        pending = []
+        try:
+            while not self._closing:
+                # block only when nothing is waiting; otherwise sweep up what has arrived and serve -- no timer, no fill target
+                events = sel.select(None if not pending else 0)
+                for key, _ in events:
+                    s = key.fileobj
+                    if s is self._listen:
+                        conn, _ = s.accept()
+                        self._buffers[conn] = bytearray()
+                        sel.register(conn, selectors.EVENT_READ)
+                    elif s is self._wake_r:
+                        s.recv(16)
+                    else:
+                        self._read(s, pending)
+                if pending and not events:
+                    batch, pending = pending, []
+                    self._serve(batch)
+        finally:
+            sel.close()
+            self._shutdown()

@@ -396,6 +396,55 @@ int gcnn_rank_deviations(const int32_t* offsets, int32_t n_samples, const float*
                          const float* scores, int32_t n_scores, const double* hybrid, const int32_t* perms, int32_t n_perms,
                          int32_t* deviations, void* stream);
 
+/* ---- many host states in one call: the evaluators' task farms (model_evaluator.py:157-241) behind one GPU process ---------------
+ * gcnn_infer's contract -- ONE host->device copy of a packed pinned buffer, ONE device->host copy, nothing synchronised, nothing
+ * allocated -- for 1..GCNN_IBATCH_MAX states at once, scored as their disjoint union (utils.py:389-426) in ONE forward pass.
+ * Every state comes with STATE-LOCAL indices; the device shifts them.  dims[s]: the sizes of state s; n_forced[s] /
+ * n_forced_entries[s]: its forced rows (may be NULL = none; only GCNN_IBATCH_SELECT reads forced rows).
+ *
+ * host_in (pinned), with O = in_off and c/v/k/e1/e2/f/fe_off[s] = the exclusive prefix sums of the states' sizes:
+ *   O[0]  the table: GCNN_IBATCH_TABLE_COLS columns of GCNN_IBATCH_TABLE_STRIDE int32 -- c_off, v_off, k_off, e1_off, e2_off,
+ *         f_off, fe_off, entries 0..n_states (the last = the total); gcnn_infer_batch_fill_table writes it
+ *   O[1]  a block the CALLER keeps zero up to O[2] (per-state flags and the by-left offsets of both edge sets)
+ *   O[2]  cons_feats [C,4]: state s at row c_off[s]            O[5]  var_feats [V,14]     O[6]  cut_feats [K,6]
+ *   O[3]  constraint edges: state s's own [2,E1_s] int32 block at int32 position 2*e1_off[s] (what gcnn_host_pack_edges writes)
+ *   O[4]  cons_edge_feats [E1]: state s at e1_off[s]           O[7], O[8]  the cut edges in the same two forms
+ *   O[9]  forced_ptr [F+1] int32: offsets over the STACKED forced entries (state s's own offsets + fe_off[s])
+ *   O[10] forced_col [FE] int32, state-local column ids        O[11] forced_val [FE] f32
+ * host_out (pinned): out_off[0] scores [K] (state s at k_off[s]), out_off[1] order [K] int32 (state-local cut indices at k_off[s];
+ *   RANK: the descending stable ranking, NaN as -inf; SELECT: as gcnn_select_cuts), out_off[2] n_kept [n_states] int32 (SELECT
+ *   only; -1 for a state with more than 4,096 cuts), out_off[3] flags [n_states][4] int32 with the meaning of gcnn_infer's flags
+ *   ([3] stays 0: the by-variable order is a stable radix sort of the union's list and knows no degree limit).
+ * A state with a flag set has no valid scores, order or n_kept; neither has, in RANK / SELECT, the order of a state with more than
+ * 4,096 cuts.  Such a state does not change any other state's results: its bad ids are replaced inside its own index ranges and a
+ * disjoint union shares no node between states.  The caller re-runs it alone (gcnn_infer, or gcnn_graph_build + gcnn_forward).
+ * Returned before anything is enqueued: GCNN_E_BADARG for n_states outside 1..GCNN_IBATCH_MAX, a negative size, an unknown mode or
+ * a threshold that is not finite; GCNN_E_UNSUPPORTED for a union of more than 2^24 rows of one kind or 2^30 edges of one set, and
+ * for a state that has edges but no row or no variable they could refer to (every id of it would be out of range). */
+#define GCNN_IBATCH_MAX 64
+#define GCNN_IBATCH_TABLE_COLS 7
+#define GCNN_IBATCH_TABLE_STRIDE 72
+#define GCNN_IBATCH_SCORES 0
+#define GCNN_IBATCH_RANK 1
+#define GCNN_IBATCH_SELECT 2
+typedef struct gcnn_ibatch_layout {
+    gcnn_dims total;                       /* the union's sizes */
+    int32_t n_forced, n_forced_entries;    /* totals */
+    int32_t max_cuts;                      /* the largest state that takes part in RANK / SELECT (<= 4,096) */
+    int32_t n_states;
+    size_t in_bytes, in_off[12];
+    size_t out_bytes, out_off[4];
+    size_t arena_bytes, dev_off[16];       /* dev_off: internal carving of the arena behind the uploaded block */
+} gcnn_ibatch_layout;
+int gcnn_infer_batch_layout_for(int32_t n_states, const gcnn_dims* dims /* host [n_states] */, const int32_t* n_forced,
+                                const int32_t* n_forced_entries, int32_t mode, gcnn_ibatch_layout* layout /* host */);
+/* table: host_in + in_off[0] (host).  No device work. */
+int gcnn_infer_batch_fill_table(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
+                                const int32_t* n_forced_entries, int32_t* table /* host */);
+int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                     int32_t mode, const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes,
+                     double p_max, double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
