@@ -1,0 +1,323 @@
+"""Host arrays in, one C call, host arrays out: the host side of gcnn_infer, gcnn_infer_select and gcnn_infer_batch
+(include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
+of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers."""
+
+from __future__ import annotations
+
+import ctypes as C
+import time
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+BAD_INDEX = "edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))"
+
+
+class ScoreArray(np.ndarray):
+    """Host-side scores of the single-state inference path: an ndarray that also answers `.numpy()` (the reference's call sites do
+    `get_improvements(state, False).numpy()`, model_evaluator.py:103).  `rankings` (optional): indices in descending score
+    order, equal scores in index order -- `sorted(range(n), key=lambda x: quality[x], reverse=True)` of model_evaluator.py:110."""
+    rankings = None
+
+    def numpy(self):
+        return np.asarray(self)
+
+
+class SelectResult:
+    """What `GCNN.select_cuts` returns: `order` (int32 cut indices in STATE order: the kept cuts first, best first, then the
+    removed ones), `n_selected` = min(n_kept, max_selected) -- the reference's 'nselectedcuts' --, `n_kept` and the `scores`."""
+
+    def __init__(self, order, n_kept, n_selected, scores):
+        self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
+
+    def __repr__(self):
+        return f"SelectResult(n_selected={self.n_selected}, n_kept={self.n_kept}, order={self.order!r})"
+
+
+class _UseGeneralPath(Exception):
+    """The specialised single-state path declined (unsorted edge list, very long segment, too many variables)."""
+
+
+def is_host_state(state):
+    """True for a tuple of host arrays; False for a prepared `Batch` (it has `dims`) and for a tuple that holds a torch tensor."""
+    return not (hasattr(state, "dims") or any(isinstance(x, torch.Tensor) for x in state[:7]))
+
+
+def n_selected(n_kept, max_selected):
+    return n_kept if max_selected is None else min(n_kept, int(max_selected))
+
+
+def stable_ranking(scores):
+    """Cut indices in descending score order, equal scores in index order."""
+    return np.argsort(-np.asarray(scores), kind="stable").astype(np.int32)
+
+
+def check_feature_shapes(c, v, k, n_cons, n_vars, n_cuts):
+    """Feature matrices (NumPy arrays or torch tensors) against their widths and the state's three counts."""
+    for name, t, f in (("cons_feats", c, 4), ("var_feats", v, 14), ("cut_feats", k, 6)):
+        if t.ndim != 2 or t.shape[1] != f:
+            raise ValueError(f"{name} must have shape [N,{f}], got {tuple(t.shape)}")
+    for name, total, t in (("n_cons", n_cons, c), ("n_vars", n_vars, v), ("n_cuts", n_cuts, k)):
+        if int(total) != t.shape[0]:
+            raise ValueError(f"{name}={int(total)} does not match the {t.shape[0]} feature rows")
+
+
+def check_state(inputs):
+    """The model's 10-tuple of host arrays -> (the seven arrays, key = (n_cons, n_vars, n_cuts, E1, E2))."""
+    c, cei, cef, v, k, kei, kef, n_cons, n_vars, n_cuts = inputs
+    c, v, k = np.asarray(c), np.asarray(v), np.asarray(k)
+    cei, kei, cef, kef = np.asarray(cei), np.asarray(kei), np.asarray(cef), np.asarray(kef)
+    check_feature_shapes(c, v, k, n_cons, n_vars, n_cuts)
+    for name, ei, ef in (("cons_edge_inds", cei, cef), ("cut_edge_inds", kei, kef)):
+        if ei.ndim != 2 or ei.shape[0] != 2 or ei.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be an integer array of shape [2,E], got {ei.dtype} {tuple(ei.shape)}")
+        if ef.size != ei.shape[1]:
+            raise ValueError("edge features must hold one value per edge")
+        # the upload packs indices as int32 with an unchecked cast: an int64 / uint index of 2**31 or more would wrap, possibly
+        # into range, and score another graph -- such lists are rejected here (int32 input cannot overflow; the device
+        # flags catch everything that is out of range but representable)
+        if ei.dtype != np.int32 and ei.size and (int(ei.max()) > 2 ** 31 - 1 or int(ei.min()) < -2 ** 31):
+            raise ValueError(BAD_INDEX)
+    key = (c.shape[0], v.shape[0], k.shape[0], cei.shape[1], kei.shape[1])
+    return (c, cei, cef, v, k, kei, kef), key
+
+
+def pack_state(buf, base, arrays, key, where, scratch):
+    """Write one checked state into a staging buffer.  `buf`: writable uint8 array, `base`: its address; `where`: the byte offset
+    of each of the seven arrays.  Features are cast to fp32; an edge set lands as [rows | cols] int32 and fp32 values, brought
+    into row order on the way when it is not (gcnn_host_pack_edges: one native pass per list, a stable counting sort only for a
+    list in another order -- NumPy's stable argsort alone would take longer than the whole general path).  `scratch`: the sort's
+    int32 scratch or None; returned, grown when a state needed more."""
+    c, cei, cef, v, k, kei, kef = arrays
+    oc, oci, ocf, ov, ok, oki, okf = where
+    pack = _lib.lib().gcnn_host_pack_edges
+    for off, a in ((oc, c), (ov, v), (ok, k)):
+        if a.size:
+            np.copyto(buf[off:off + 4 * a.size].view(np.float32).reshape(a.shape), a, casting="unsafe")
+    for io, fo, ei, ef, n_left in ((oci, ocf, cei, cef, key[0]), (oki, okf, kei, kef, key[2])):
+        if not ei.size:
+            continue
+        ei32 = np.ascontiguousarray(ei, dtype=np.int32)                  # no copies for what get_state hands over
+        ef32 = np.ascontiguousarray(ef, dtype=np.float32).reshape(-1)
+        if scratch is None or scratch.size < n_left + 1:
+            scratch = np.empty(2 * (n_left + 1), np.int32)
+        rc = pack(ei32.ctypes.data, ei32.ctypes.data + 4 * ei32.shape[1], ef32.ctypes.data, ei32.shape[1], n_left, base + io,
+                  base + fo, scratch.ctypes.data)
+        if rc < 0:      # (0 / 1 / 2: packed -- as it was, sorted here, or as it was with a row id the device check reports)
+            _lib.check(rc, "gcnn_host_pack_edges")
+    return scratch
+
+
+def normalize_forced(forced, n_vars):
+    """Forced rows as `GCNN.select_cuts` takes them -- None, (edge_inds [2,E], values [E]) or (edge_inds, values, n_forced), NumPy
+    or torch -- -> host CSR (ptr, col, val) of `ops.pack_rows`.  Two entries take n_forced = max row id + 1."""
+    if forced is None:
+        forced = (np.zeros((2, 0), np.int32), np.zeros(0, np.float32), 0)
+    if len(forced) == 2:
+        fi = np.asarray(forced[0])
+        forced = (forced[0], forced[1], int(fi[0].max()) + 1 if fi.size else 0)
+    fi, fv, n_forced = forced
+    if isinstance(fi, torch.Tensor):
+        fi, fv = fi.cpu().numpy(), fv.cpu().numpy()
+    return ops.pack_rows(fi, fv, int(n_forced), n_vars)
+
+
+def _unsupported(rc, what):
+    """True when a layout function declines the sizes (-4); any other failure raises."""
+    if rc != -4:
+        _lib.check(rc, what)
+    return rc == -4
+
+
+class _Staging:
+    """Persistent pinned staging buffers, a device arena, the packer's scratch and a bounded cache of layouts."""
+    CAP = 256
+
+    def __init__(self, model):
+        self.model = model
+        self.pin_in = self.pin_out = self.arena = None
+        self.in_np = self.out_np = None
+        self.scratch = None
+        self.layouts = {}
+
+    def cached(self, key, make, *args):
+        """The layout entry of `key`; `make(*args)` builds a missing one, or returns False where the library declines."""
+        lay = self.layouts.get(key)
+        if lay is None:
+            lay = make(*args)
+            if len(self.layouts) >= self.CAP:
+                self.layouts.pop(next(iter(self.layouts)))   # evict the oldest entry only
+            self.layouts[key] = lay
+        return lay
+
+    def _buffers(self, L):
+        if self.pin_in is None or self.pin_in.numel() < L.in_bytes:
+            self.pin_in = torch.empty(max(2 * L.in_bytes, 1 << 20), dtype=torch.uint8).pin_memory()
+            self.in_np = self.pin_in.numpy()
+        if self.pin_out is None or self.pin_out.numel() < L.out_bytes:
+            self.pin_out = torch.empty(max(2 * L.out_bytes, 1 << 16), dtype=torch.uint8).pin_memory()
+            self.out_np = self.pin_out.numpy()
+        if self.arena is None or self.arena.numel() < L.arena_bytes:
+            self.arena = None
+            self.arena = torch.empty(max(2 * L.arena_bytes, 1 << 24), dtype=torch.uint8, device=self.model.device)
+
+    def _pointers(self):
+        P = C.c_void_p
+        return (P(self.model._flat.data_ptr()), P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(self.arena.data_ptr()),
+                self.arena.numel())
+
+
+def _solo_layout(key, n_forced=None, n_entries=None):
+    """Layout entry of one state: gcnn_infer's, or with forced sizes gcnn_infer_select's (whose extra offsets come last).
+    in_off[0] .. in_off[1] is the block the caller zeroes, in_off[1..7] say `where` the seven arrays go."""
+    dims = _lib.Dims(*key)
+    if n_forced is None:
+        L, SL = _lib.InferLayout(), None
+        declined = _unsupported(_lib.lib().gcnn_infer_layout_for(C.byref(dims), C.byref(L)), "gcnn_infer_layout_for")
+    else:
+        SL = _lib.SelectLayout()
+        declined = _unsupported(_lib.lib().gcnn_infer_select_layout_for(C.byref(dims), n_forced, n_entries, C.byref(SL)),
+                                "gcnn_infer_select_layout_for")
+        L = SL.infer
+    in_off = tuple(L.in_off)
+    return False if declined else (dims, L, in_off[0], in_off[1], in_off[1:], list(L.out_off), SL)
+
+
+class _InferenceSession(_Staging):
+    """Host side of gcnn_infer and gcnn_infer_select: one C call per state."""
+
+    def _run(self, inputs, want_order, timings, forced=None, p_max=0.0, p_max_ub=0.0):
+        """pack -> call -> wait -> flags -> (scores, order | None, n_kept | None); with `forced` the call is gcnn_infer_select."""
+        t0 = time.perf_counter()
+        arrays, key = check_state(inputs)
+        # The specialised plan wants lists sorted by row, which is what get_state emits (utils.py:102-104); `pack_state` sees to it
+        if forced is None:
+            lay = self.cached(key, _solo_layout, key)
+        else:
+            n_forced, n_entries = forced[0].size - 1, forced[1].size
+            lay = self.cached(key + (n_forced, n_entries), _solo_layout, key, n_forced, n_entries)
+        if lay is False or (want_order and key[2] > 4096):
+            raise _UseGeneralPath()
+        dims, L, zero_from, zero_to, where, out_off, SL = lay
+        self._buffers(L)
+        buf = self.in_np
+        buf[zero_from:zero_to] = 0      # the plan's counters and flags travel zeroed inside the upload
+        self.scratch = pack_state(buf, self.pin_in.data_ptr(), arrays, key, where, self.scratch)
+        if forced is not None:
+            for off, a in zip(SL.forced_off, forced):
+                buf[off:off + a.nbytes] = a.view(np.uint8)
+        t1 = time.perf_counter()
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            if forced is None:
+                _lib.check(_lib.lib().gcnn_infer(C.byref(dims), *self._pointers(), int(want_order),
+                                                C.c_void_p(stream.cuda_stream)), "gcnn_infer")
+            else:
+                _lib.check(_lib.lib().gcnn_infer_select(C.byref(dims), n_forced, n_entries, *self._pointers(), float(p_max),
+                                                       float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_select")
+            t2 = time.perf_counter()
+            stream.synchronize()
+        t3 = time.perf_counter()
+        if timings is not None:
+            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2)
+        out, n = self.out_np, key[2]
+        flags = out[out_off[2]:out_off[2] + 16].view(np.int32)
+        if flags[0]:
+            raise ValueError(BAD_INDEX)
+        if flags[1] or flags[2] or flags[3]:
+            raise _UseGeneralPath()
+        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
+        order = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy() if want_order else None
+        n_kept = int(out[SL.n_kept_off:SL.n_kept_off + 4].view(np.int32)[0]) if forced is not None else None
+        return scores, order, n_kept
+
+    def run(self, inputs, want_order, timings=None):
+        """Scores of ONE host state (`.rankings` from the device when `want_order`).  `timings` (optional dict): filled with the
+        host-side phases in seconds (tools/latency.py)."""
+        scores, order, _ = self._run(inputs, want_order, timings)
+        if want_order:
+            scores.rankings = order
+        return scores
+
+    def run_select(self, inputs, forced, p_max, p_max_ub):
+        """gcnn_infer_select: scores, selection order and n_kept of ONE host state.  `forced`: (ptr, col, val) host arrays
+        (ops.pack_rows).  Raises _UseGeneralPath where gcnn_infer would."""
+        return self._run(inputs, True, None, forced, p_max, p_max_ub)
+
+
+class _BatchSession(_Staging):
+    """Host side of gcnn_infer_batch: one C call for up to 64 host states.  `run` answers per state: ("ok", scores, order, n_kept),
+    ("bad_index",) or ("declined",)."""
+    MAX = _lib.IBATCH_MAX
+    CAP = 64
+    # in_off[2..8] hold the seven arrays of every state: (table column of the state's offset, bytes per row or edge)
+    PLACES = ((0, 16), (3, 8), (3, 4), (1, 56), (2, 24), (4, 8), (4, 4))
+
+    def __init__(self, model):
+        super().__init__(model)
+        self.calls = 0            # C calls made (tools and tests read it)
+
+    def _layout(self, keys, fshapes, mode):
+        n = len(keys)
+        dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
+        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
+        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        L = _lib.IbatchLayout()
+        if _unsupported(_lib.lib().gcnn_infer_batch_layout_for(n, dims, nf, nfe, mode, C.byref(L)), "gcnn_infer_batch_layout_for"):
+            return False
+        table = np.zeros(_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE, np.int32)
+        _lib.check(_lib.lib().gcnn_infer_batch_fill_table(n, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
+        cols = table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :n + 1].tolist()
+        in_off = list(L.in_off)
+        where = [tuple(in_off[2 + j] + size * cols[col][s] for j, (col, size) in enumerate(self.PLACES)) for s in range(n)]
+        return dims, nf, nfe, L, in_off, list(L.out_off), table, cols, where
+
+    def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
+        """checked: [(arrays, key)] as `check_state` returns them; forced: None or [(ptr, col, val)] per state.
+        Returns None when the library declines the union as a whole (too large: the caller splits it)."""
+        keys = tuple(k for _, k in checked)
+        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        lay = self.cached((mode, keys, fshapes), self._layout, keys, fshapes, mode)
+        if lay is False:
+            return None
+        dims, nf, nfe, L, in_off, out_off, table, cols, where = lay
+        k_off, f_off, fe_off = cols[2], cols[5], cols[6]
+        self._buffers(L)
+        buf, base = self.in_np, self.pin_in.data_ptr()
+        buf[in_off[0]:in_off[0] + table.nbytes] = table.view(np.uint8)
+        buf[in_off[1]:in_off[2]] = 0          # flags and by-left offsets travel zeroed inside the upload
+        for s, (arrays, key) in enumerate(checked):
+            self.scratch = pack_state(buf, base, arrays, key, where[s], self.scratch)
+            if forced is not None:
+                fptr, fcol, fval = forced[s]
+                o = in_off[9] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next state's first
+                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
+                for off, a in ((in_off[10] + 4 * fe_off[s], fcol), (in_off[11] + 4 * fe_off[s], fval)):
+                    buf[off:off + a.nbytes] = a.view(np.uint8)
+        if forced is None:
+            buf[in_off[9]:in_off[9] + 4] = 0
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib().gcnn_infer_batch(len(checked), dims, nf, nfe, mode, *self._pointers(), float(p_max),
+                                                  float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_batch")
+            stream.synchronize()
+        self.calls += 1
+        out, n = self.out_np, len(checked)
+        flags = out[out_off[3]:out_off[3] + 16 * n].view(np.int32).reshape(n, 4)
+        n_kept = out[out_off[2]:out_off[2] + 4 * n].view(np.int32)
+        res = []
+        for s in range(n):
+            if flags[s, 0]:
+                res.append(("bad_index",))
+            elif flags[s, 1] or flags[s, 2] or flags[s, 3]:
+                res.append(("declined",))
+            else:
+                lo, K = 4 * k_off[s], 4 * (k_off[s + 1] - k_off[s])
+                scores = out[out_off[0] + lo:out_off[0] + lo + K].view(np.float32).copy().view(ScoreArray)
+                order = out[out_off[1] + lo:out_off[1] + lo + K].view(np.int32).copy() if mode else None
+                res.append(("ok", scores, order, int(n_kept[s]) if mode == _lib.IBATCH_SELECT else None))
+        return res

@@ -19,8 +19,10 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, _safe_pickle
+from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
+from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _UseGeneralPath, check_feature_shapes,
+                    check_state, is_host_state, n_selected, normalize_forced, stable_ranking)
 
 EMB = 64
 
@@ -69,302 +71,14 @@ class ScoreTensor(torch.Tensor):
         return torch.Tensor.numpy(self.detach().cpu().as_subclass(torch.Tensor), *args, **kwargs)
 
 
-class ScoreArray(np.ndarray):
-    """Host-side scores of the single-state inference path: an ndarray that also answers `.numpy()` (the reference's call sites do
-    `get_improvements(state, False).numpy()`, model_evaluator.py:103).  `rankings` (optional): indices in descending score
-    order, equal scores in index order -- `sorted(range(n), key=lambda x: quality[x], reverse=True)` of model_evaluator.py:110."""
-    rankings = None
-
-    def numpy(self):
-        return np.asarray(self)
-
-
-class SelectResult:
-    """What `GCNN.select_cuts` returns: `order` (int32 cut indices in STATE order: the kept cuts first, best first, then the
-    removed ones), `n_selected` = min(n_kept, max_selected) -- the reference's 'nselectedcuts' --, `n_kept` and the `scores`."""
-
-    def __init__(self, order, n_kept, n_selected, scores):
-        self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
-
-    def __repr__(self):
-        return f"SelectResult(n_selected={self.n_selected}, n_kept={self.n_kept}, order={self.order!r})"
-
-
-class _UseGeneralPath(Exception):
-    """The specialised single-state path declined (unsorted edge list, very long segment, too many variables)."""
-
-
-class _InferenceSession:
-    """Host side of gcnn_infer (include/gcnn_hip.h): persistent pinned staging buffers and a device arena, one C call per state."""
-
-    def __init__(self, model):
-        self.model = model
-        self.pin_in = self.pin_out = self.arena = None
-        self.in_np = self.out_np = None
-        self.sort_scratch = None
-        self.layouts = {}
-
-    def _layout(self, key):
-        lay = self.layouts.get(key)
-        if lay is None:
-            dims, lay = _lib.Dims(*key), _lib.InferLayout()
-            rc = _lib.lib().gcnn_infer_layout_for(C.byref(dims), C.byref(lay))
-            if rc == -4:
-                lay = False
-            else:
-                _lib.check(rc, "gcnn_infer_layout_for")
-                lay = (dims, lay, list(lay.in_off), list(lay.out_off))
-            if len(self.layouts) >= 256:
-                self.layouts.pop(next(iter(self.layouts)))   # evict the oldest entry only
-            self.layouts[key] = lay
-        return lay
-
-    def _select_layout(self, key, n_forced, n_entries):
-        skey = key + (n_forced, n_entries)
-        lay = self.layouts.get(skey)
-        if lay is None:
-            dims, lay = _lib.Dims(*key), _lib.SelectLayout()
-            rc = _lib.lib().gcnn_infer_select_layout_for(C.byref(dims), n_forced, n_entries, C.byref(lay))
-            if rc == -4:
-                lay = False
-            else:
-                _lib.check(rc, "gcnn_infer_select_layout_for")
-                lay = (dims, lay.infer, list(lay.infer.in_off), list(lay.infer.out_off), lay)
-            if len(self.layouts) >= 256:
-                self.layouts.pop(next(iter(self.layouts)))
-            self.layouts[skey] = lay
-        return lay
-
-    @staticmethod
-    def _check_inputs(inputs):
-        c, cei, cef, v, k, kei, kef, n_cons, n_vars, n_cuts = inputs
-        c, v, k = np.asarray(c), np.asarray(v), np.asarray(k)
-        cei, kei, cef, kef = np.asarray(cei), np.asarray(kei), np.asarray(cef), np.asarray(kef)
-        for name, t, f in (("cons_feats", c, 4), ("var_feats", v, 14), ("cut_feats", k, 6)):
-            if t.ndim != 2 or t.shape[1] != f:
-                raise ValueError(f"{name} must have shape [N,{f}], got {tuple(t.shape)}")
-        for name, total, t in (("n_cons", n_cons, c), ("n_vars", n_vars, v), ("n_cuts", n_cuts, k)):
-            if int(total) != t.shape[0]:
-                raise ValueError(f"{name}={int(total)} does not match the {t.shape[0]} feature rows")
-        for name, ei, ef in (("cons_edge_inds", cei, cef), ("cut_edge_inds", kei, kef)):
-            if ei.ndim != 2 or ei.shape[0] != 2 or ei.dtype.kind not in "iu":
-                raise ValueError(f"{name} must be an integer array of shape [2,E], got {ei.dtype} {tuple(ei.shape)}")
-            if ef.size != ei.shape[1]:
-                raise ValueError("edge features must hold one value per edge")
-            # the upload packs indices as int32 with an unchecked cast: an int64 / uint index of 2**31 or more would wrap, possibly
-            # into range, and score another graph -- such lists are rejected here (int32 input cannot overflow; the device
-            # flags catch everything that is out of range but representable)
-            if ei.dtype != np.int32 and ei.size and (int(ei.max()) > 2 ** 31 - 1 or int(ei.min()) < -2 ** 31):
-                raise ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
-        key = (c.shape[0], v.shape[0], k.shape[0], cei.shape[1], kei.shape[1])
-        return (c, cei, cef, v, k, kei, kef), key
-
-    def _buffers(self, L):
-        dev = self.model.device
-        if self.pin_in is None or self.pin_in.numel() < L.in_bytes:
-            self.pin_in = torch.empty(max(2 * L.in_bytes, 1 << 20), dtype=torch.uint8).pin_memory()
-            self.in_np = self.pin_in.numpy()
-        if self.pin_out is None or self.pin_out.numel() < L.out_bytes:
-            self.pin_out = torch.empty(max(2 * L.out_bytes, 1 << 16), dtype=torch.uint8).pin_memory()
-            self.out_np = self.pin_out.numpy()
-        if self.arena is None or self.arena.numel() < L.arena_bytes:
-            self.arena = None
-            self.arena = torch.empty(max(2 * L.arena_bytes, 1 << 24), dtype=torch.uint8, device=dev)
-
-    def _pack(self, arrays, key, in_off):
-        c, cei, cef, v, k, kei, kef = arrays
-        buf = self.in_np
-        buf[in_off[0]:in_off[1]] = 0      # the plan's counters and flags travel zeroed inside the upload
-        base = self.pin_in.data_ptr()
-        for off, a, dt in ((in_off[1], c, np.float32), (in_off[4], v, np.float32), (in_off[5], k, np.float32)):
-            if a.size:
-                np.copyto(buf[off:off + 4 * a.size].view(dt).reshape(a.shape), a, casting="unsafe")
-        for io, fo, ei, ef, n_left in ((in_off[2], in_off[3], cei, cef, key[0]), (in_off[6], in_off[7], kei, kef, key[2])):
-            if not ei.size:
-                continue
-            ei32 = np.ascontiguousarray(ei, dtype=np.int32)                  # no copies for what get_state hands over
-            ef32 = np.ascontiguousarray(ef, dtype=np.float32).reshape(-1)
-            if self.sort_scratch is None or self.sort_scratch.size < n_left + 1:
-                self.sort_scratch = np.empty(2 * (n_left + 1), np.int32)
-            rc = _lib.lib().gcnn_host_pack_edges(ei32.ctypes.data, ei32.ctypes.data + 4 * ei32.shape[1], ef32.ctypes.data,
-                                                 ei32.shape[1], n_left, base + io, base + fo, self.sort_scratch.ctypes.data)
-            if rc < 0:      # (0 / 1 / 2: packed -- as it was, sorted here, or as it was with a row id the device check reports)
-                _lib.check(rc, "gcnn_host_pack_edges")
-
-    def _flags(self, out_off):
-        flags = self.out_np[out_off[2]:out_off[2] + 16].view(np.int32)
-        if flags[0]:
-            raise ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
-        if flags[1] or flags[2] or flags[3]:
-            raise _UseGeneralPath()
-
-    def run(self, inputs, want_order, timings=None):
-        """`timings` (optional dict): filled with the host-side phases in seconds (tools/latency.py)."""
-        import time
-        t0 = time.perf_counter()
-        arrays, key = self._check_inputs(inputs)
-        # The specialised plan wants lists sorted by row, which is what get_state emits (utils.py:102-104).  Packing is one native
-        # pass per list (gcnn_host_pack_edges): copy into the staging buffer, look at the order on the way, and only a list in
-        # another order goes through a stable counting sort on the host (tens of microseconds for a few 10^4 entries; NumPy's
-        # stable argsort alone would take longer than the whole general path).
-        lay = self._layout(key)
-        if lay is False or (want_order and key[2] > 4096):
-            raise _UseGeneralPath()
-        dims, L, in_off, out_off = lay
-        dev = self.model.device
-        self._buffers(L)
-        self._pack(arrays, key, in_off)
-        t1 = time.perf_counter()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            _lib.check(_lib.lib().gcnn_infer(C.byref(dims), C.c_void_p(self.model._flat.data_ptr()),
-                                            C.c_void_p(self.pin_in.data_ptr()), C.c_void_p(self.pin_out.data_ptr()),
-                                            C.c_void_p(self.arena.data_ptr()), self.arena.numel(), int(want_order),
-                                            C.c_void_p(stream.cuda_stream)), "gcnn_infer")
-            t2 = time.perf_counter()
-            stream.synchronize()
-        t3 = time.perf_counter()
-        if timings is not None:
-            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2)
-        out = self.out_np
-        self._flags(out_off)
-        n = key[2]
-        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
-        if want_order:
-            scores.rankings = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy()
-        return scores
-
-    def run_select(self, inputs, forced, p_max, p_max_ub):
-        """gcnn_infer_select: scores, selection order and n_kept of ONE host state.  `forced`: (ptr, col, val) host arrays
-        (ops.pack_rows).  Raises _UseGeneralPath where gcnn_infer would."""
-        arrays, key = self._check_inputs(inputs)
-        fptr, fcol, fval = forced
-        n_forced, n_entries = fptr.size - 1, fcol.size
-        lay = self._select_layout(key, n_forced, n_entries)
-        if lay is False:
-            raise _UseGeneralPath()
-        dims, L, in_off, out_off, SL = lay
-        dev = self.model.device
-        self._buffers(L)
-        self._pack(arrays, key, in_off)
-        buf = self.in_np
-        for off, a in zip(SL.forced_off, (fptr, fcol, fval)):
-            buf[off:off + a.nbytes] = a.view(np.uint8)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            _lib.check(_lib.lib().gcnn_infer_select(C.byref(dims), n_forced, n_entries, C.c_void_p(self.model._flat.data_ptr()),
-                                                   C.c_void_p(self.pin_in.data_ptr()), C.c_void_p(self.pin_out.data_ptr()),
-                                                   C.c_void_p(self.arena.data_ptr()), self.arena.numel(), float(p_max),
-                                                   float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_select")
-            stream.synchronize()
-        self._flags(out_off)
-        out, n = self.out_np, key[2]
-        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
-        order = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy()
-        n_kept = int(out[SL.n_kept_off:SL.n_kept_off + 4].view(np.int32)[0])
-        return scores, order, n_kept
-
-
-class _BatchSession:
-    """Host side of gcnn_infer_batch (include/gcnn_hip.h): persistent pinned staging buffers and a device arena, one C call for up to
-    64 host states.  `run` answers per state: ("ok", scores, order, n_kept), ("bad_index",) or ("declined",)."""
-    MAX = _lib.IBATCH_MAX
-
-    def __init__(self, model):
-        self.model = model
-        self.pin_in = self.pin_out = self.arena = None
-        self.in_np = self.out_np = None
-        self.sort_scratch = None
-        self.layouts = {}
-        self.calls = 0            # C calls made (tools and tests read it)
-
-    _buffers = _InferenceSession._buffers
-
-    def _layout(self, keys, fshapes, mode):
-        lkey = (mode, keys, fshapes)
-        lay = self.layouts.get(lkey)
-        if lay is None:
-            n = len(keys)
-            dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
-            nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
-            nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
-            L = _lib.IbatchLayout()
-            rc = _lib.lib().gcnn_infer_batch_layout_for(n, dims, nf, nfe, mode, C.byref(L))
-            if rc == -4:
-                lay = False
-            else:
-                _lib.check(rc, "gcnn_infer_batch_layout_for")
-                table = np.zeros(_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE, np.int32)
-                _lib.check(_lib.lib().gcnn_infer_batch_fill_table(n, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
-                lay = (dims, nf, nfe, L, list(L.in_off), list(L.out_off), table,
-                       table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :n + 1].tolist())
-            if len(self.layouts) >= 64:
-                self.layouts.pop(next(iter(self.layouts)))   # evict the oldest entry only
-            self.layouts[lkey] = lay
-        return lay
-
-    def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
-        """checked: [(arrays, key)] as `_InferenceSession._check_inputs` returns them; forced: None or [(ptr, col, val)] per state.
-        Returns None when the library declines the union as a whole (too large: the caller splits it)."""
-        keys = tuple(k for _, k in checked)
-        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
-        lay = self._layout(keys, fshapes, mode)
-        if lay is False:
-            return None
-        dims, nf, nfe, L, in_off, out_off, table, (c_off, v_off, k_off, e1_off, e2_off, f_off, fe_off) = lay
-        self._buffers(L)
-        buf, base = self.in_np, self.pin_in.data_ptr()
-        buf[in_off[0]:in_off[0] + table.nbytes] = table.view(np.uint8)
-        buf[in_off[1]:in_off[2]] = 0          # flags and by-left offsets travel zeroed inside the upload
-        pack = _lib.lib().gcnn_host_pack_edges
-        for s, ((c, cei, cef, v, k, kei, kef), key) in enumerate(checked):
-            for off, a in ((in_off[2] + 16 * c_off[s], c), (in_off[5] + 56 * v_off[s], v), (in_off[6] + 24 * k_off[s], k)):
-                if a.size:
-                    np.copyto(buf[off:off + 4 * a.size].view(np.float32).reshape(a.shape), a, casting="unsafe")
-            for io, fo, ei, ef, n_left in ((in_off[3] + 8 * e1_off[s], in_off[4] + 4 * e1_off[s], cei, cef, key[0]),
-                                           (in_off[7] + 8 * e2_off[s], in_off[8] + 4 * e2_off[s], kei, kef, key[2])):
-                if not ei.size:
-                    continue
-                ei32 = np.ascontiguousarray(ei, dtype=np.int32)
-                ef32 = np.ascontiguousarray(ef, dtype=np.float32).reshape(-1)
-                if self.sort_scratch is None or self.sort_scratch.size < n_left + 1:
-                    self.sort_scratch = np.empty(2 * (n_left + 1), np.int32)
-                rc = pack(ei32.ctypes.data, ei32.ctypes.data + 4 * ei32.shape[1], ef32.ctypes.data, ei32.shape[1], n_left,
-                          base + io, base + fo, self.sort_scratch.ctypes.data)
-                if rc < 0:
-                    _lib.check(rc, "gcnn_host_pack_edges")
-            if forced is not None:
-                fptr, fcol, fval = forced[s]
-                o = in_off[9] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next state's first
-                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
-                for off, a in ((in_off[10] + 4 * fe_off[s], fcol), (in_off[11] + 4 * fe_off[s], fval)):
-                    buf[off:off + a.nbytes] = a.view(np.uint8)
-        if forced is None:
-            buf[in_off[9]:in_off[9] + 4] = 0
-        dev = self.model.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            _lib.check(_lib.lib().gcnn_infer_batch(len(checked), dims, nf, nfe, mode, C.c_void_p(self.model._flat.data_ptr()),
-                                                  C.c_void_p(self.pin_in.data_ptr()), C.c_void_p(self.pin_out.data_ptr()),
-                                                  C.c_void_p(self.arena.data_ptr()), self.arena.numel(), float(p_max),
-                                                  float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_batch")
-            stream.synchronize()
-        self.calls += 1
-        out, n = self.out_np, len(checked)
-        flags = out[out_off[3]:out_off[3] + 16 * n].view(np.int32).reshape(n, 4)
-        n_kept = out[out_off[2]:out_off[2] + 4 * n].view(np.int32)
-        res = []
-        for s in range(n):
-            if flags[s, 0]:
-                res.append(("bad_index",))
-            elif flags[s, 1] or flags[s, 2] or flags[s, 3]:
-                res.append(("declined",))
-            else:
-                lo, K = 4 * k_off[s], 4 * (k_off[s + 1] - k_off[s])
-                scores = out[out_off[0] + lo:out_off[0] + lo + K].view(np.float32).copy().view(ScoreArray)
-                order = out[out_off[1] + lo:out_off[1] + lo + K].view(np.int32).copy() if mode else None
-                res.append(("ok", scores, order, int(n_kept[s]) if mode == _lib.IBATCH_SELECT else None))
-        return res
+def prenorm_count(dims, layer):
+    """The elements PreNorm layer `layer` (call order) absorbs from a batch of these dims."""
+    if layer <= 4:
+        return [dims.n_cons, dims.n_cons_edges, dims.n_vars, dims.n_cuts, dims.n_cut_edges][layer]
+    conv, post = (layer - 5) // 2, (layer - 5) % 2
+    n_recv = [dims.n_cons, dims.n_vars, dims.n_cuts][conv]
+    n_edge = [dims.n_cons_edges, dims.n_cons_edges, dims.n_cut_edges][conv]
+    return (n_recv if post else n_edge) * EMB
 
 
 class Batch:
@@ -579,12 +293,7 @@ class GCNN:
             c, v, k = (_as_device(x, torch.float32, dev) for x in (c, v, k))
             cei, kei = _as_device(cei, torch.int32, dev), _as_device(kei, torch.int32, dev)
             cef, kef = _as_device(cef, torch.float32, dev), _as_device(kef, torch.float32, dev)
-        for name, t, f in (("cons_feats", c, 4), ("var_feats", v, 14), ("cut_feats", k, 6)):
-            if t.dim() != 2 or t.shape[1] != f:
-                raise ValueError(f"{name} must have shape [N,{f}], got {tuple(t.shape)}")
-        for name, total, t in (("n_cons", n_cons, c), ("n_vars", n_vars, v), ("n_cuts", n_cuts, k)):
-            if int(total) != t.shape[0]:
-                raise ValueError(f"{name}={int(total)} does not match the {t.shape[0]} feature rows")
+        check_feature_shapes(c, v, k, n_cons, n_vars, n_cuts)
         return Batch(c, v, k, BipartiteGraph(cei, cef, c.shape[0], v.shape[0], validate),
                      BipartiteGraph(kei, kef, k.shape[0], v.shape[0], validate))
 
@@ -662,27 +371,21 @@ class GCNN:
         self._prenorm_state = [dict(waiting=True, received=False, mean=np.zeros(u, np.float32), var=np.zeros(u, np.float32),
                                     count=np.float32(0)) for _, _, u in PRENORM_LAYERS]
 
+    def _waiting_layer(self):
+        """The PreNorm layer being fitted: the first one, in call order, that still waits for updates (None: none does)."""
+        return next((i for i, st in enumerate(self._prenorm_state or ()) if st["waiting"]), None)
+
     def pretrain(self, inputs, training=True) -> bool:
         """BaseModel.pretrain (model.py:119-133): run the model; the first PreNorm layer (in call order) that is still
         waiting absorbs this batch's statistics (PreNormLayer.update_params, model.py:394-423) and the call stops there
         (the reference raises PreNormException).  Returns True when a layer absorbed the batch."""
-        if self._prenorm_state is None:
+        layer = self._waiting_layer()
+        if layer is None:
             return False
-        waiting = [i for i, st in enumerate(self._prenorm_state) if st["waiting"]]
-        if not waiting:
-            return False
-        layer = waiting[0]
         st = self._prenorm_state[layer]
         units = PRENORM_LAYERS[layer][2]
         batch = self.prepare(inputs)
-        sizes = [batch.dims.n_cons, batch.dims.n_cons_edges, batch.dims.n_vars, batch.dims.n_cuts, batch.dims.n_cut_edges]
-        if layer <= 4:
-            sample_count = sizes[layer]
-        else:
-            conv, post = (layer - 5) // 2, (layer - 5) % 2
-            n_recv = [batch.dims.n_cons, batch.dims.n_vars, batch.dims.n_cuts][conv]
-            n_edge = [batch.dims.n_cons_edges, batch.dims.n_cons_edges, batch.dims.n_cut_edges][conv]
-            sample_count = (n_recv if post else n_edge) * EMB
+        sample_count = prenorm_count(batch.dims, layer)
         st["received"] = True
         if sample_count == 0:
             return True
@@ -712,13 +415,11 @@ class GCNN:
         """Data-parallel fitting: merge the statistics of the layer that is absorbing updates across the ranks of
         `process_group` (every rank saw only its shard of the pretraining batches).  Call once per pass, on every rank,
         before `pretrain_next`.  The merge is the same Chan update as between batches (model.py:415-423), in rank order."""
-        if self._prenorm_state is None or process_group is None:
-            return
-        waiting = [i for i, st in enumerate(self._prenorm_state) if st["waiting"]]
-        if not waiting:          # identical on every rank: the set of fitted layers only changes through this method's callers
+        layer = self._waiting_layer()
+        if layer is None or process_group is None:   # (identical on every rank: only this method's callers change the fitted set)
             return
         from .parallel import allgather_prenorm
-        st = self._prenorm_state[waiting[0]]
+        st = self._prenorm_state[layer]
         st["count"], st["mean"], st["var"], st["received"] = allgather_prenorm(st["count"], st["mean"], st["var"], st["received"],
                                                                               process_group, self.device)
 
@@ -752,19 +453,17 @@ class GCNN:
         32,768 variables, ...) run through `prepare` + the general forward pass instead; results are identical."""
         if self._session is None:
             self._session = _InferenceSession(self)
+        n_cuts = int(np.asarray(inputs[4]).shape[0])
+        on_device = bool(rank) and (rank == "device" or n_cuts > self.HOST_RANK_MAX)
         try:
-            n_cuts = int(np.asarray(inputs[4]).shape[0])
-            on_device = bool(rank) and (rank == "device" or n_cuts > self.HOST_RANK_MAX)
             scores = self._session.run(inputs, on_device)
-            if rank and not on_device:
-                scores.rankings = np.argsort(-np.asarray(scores), kind="stable").astype(np.int32)
-            return scores
         except _UseGeneralPath:
+            on_device = False
             with torch.no_grad():
                 scores = self.call(inputs, False).numpy().view(ScoreArray)
-            if rank:
-                scores.rankings = np.argsort(-np.asarray(scores), kind="stable").astype(np.int32)
-            return scores
+        if rank and not on_device:
+            scores.rankings = stable_ranking(scores)
+        return scores
 
     def select_cuts(self, state, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
         """Score ONE state and run the parallelism filter of the SCIP plugin's cutselselect (model_evaluator.py:109-154) on the
@@ -772,30 +471,20 @@ class GCNN:
         cut edges (coefficient / norm over LP column positions); (edge_inds, values) alone takes n_forced = max row id + 1.
         Host arrays take the single call gcnn_infer_select (one upload, one download); states it declines, device tensors and
         prepared `Batch`es take prepare + forward + gcnn_select_cuts.  Both give the same bits.  Returns a `SelectResult`."""
-        from . import ops
         ops.check_thresholds(p_max, p_max_ub)
-        general = isinstance(state, Batch) or any(isinstance(x, torch.Tensor) for x in state[:7])
+        host = is_host_state(state)
         n_cuts = state.dims.n_cuts if isinstance(state, Batch) else int(state[4].shape[0])
         n_vars = state.dims.n_vars if isinstance(state, Batch) else int(state[3].shape[0])
         if n_cuts > ops.SELECT_MAX_CUTS:
             raise _lib.GcnnError(f"select_cuts: the state has {n_cuts} cuts; the device selection handles at most "
                                  f"{ops.SELECT_MAX_CUTS} and there is no CPU fallback")
-        if forced is None:
-            forced = (np.zeros((2, 0), np.int32), np.zeros(0, np.float32), 0)
-        if len(forced) == 2:
-            fi = np.asarray(forced[0])
-            forced = (forced[0], forced[1], int(fi[0].max()) + 1 if fi.size else 0)
-        fi, fv, n_forced = forced
-        if isinstance(fi, torch.Tensor):
-            fi, fv = fi.cpu().numpy(), fv.cpu().numpy()
-        packed = ops.pack_rows(fi, fv, int(n_forced), n_vars)
+        packed = normalize_forced(forced, n_vars)
         result = None
-        if not general:
+        if host:
             if self._session is None:
                 self._session = _InferenceSession(self)
             try:
-                scores, order, n_kept = self._session.run_select(state, packed, p_max, p_max_ub)
-                result = (scores, order, n_kept)
+                result = self._session.run_select(state, packed, p_max, p_max_ub)
             except _UseGeneralPath:
                 pass
         if result is None:
@@ -807,8 +496,7 @@ class GCNN:
                                                 p_max_ub=p_max_ub, max_cuts=n_cuts)
                 result = (scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0]))
         scores, order, n_kept = result
-        n_selected = n_kept if max_selected is None else min(n_kept, int(max_selected))
-        return SelectResult(order, n_kept, n_selected, scores)
+        return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
 
     # ---- many host states in one call (gcnn_infer_batch): what a scoring server does with the requests that queued up ----------
     def _many(self, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0):
@@ -821,10 +509,10 @@ class GCNN:
             try:
                 if forced is not None and isinstance(forced[i], Exception):
                     raise forced[i]
-                if isinstance(st, Batch) or len(st) != 10 or any(isinstance(x, torch.Tensor) for x in st[:7]):
+                if not is_host_state(st) or len(st) != 10:
                     solo_ids.append(i)          # device tensors, prepared batches, malformed tuples: the solo path answers (or raises)
                     continue
-                arrays, key = _InferenceSession._check_inputs(st)
+                arrays, key = check_state(st)
             except Exception as exc:  # noqa: BLE001 -- the error belongs to this state's slot
                 results[i] = exc
                 continue
@@ -853,7 +541,7 @@ class GCNN:
                 if r[0] == "ok":
                     results[i] = r
                 elif r[0] == "bad_index":
-                    results[i] = ValueError("edge index out of range (left ids must be in [0,n_left), variable ids in [0,n_vars))")
+                    results[i] = ValueError(BAD_INDEX)
                 else:
                     solo_ids.append(i)
         for i in solo_ids:
@@ -892,7 +580,6 @@ class GCNN:
         """`select_cuts` for many host states at once (gcnn_infer_batch in selection mode).  `forced`: None, or one entry per state
         in the forms `select_cuts` accepts (None = no forced rows).  Returns a list of `SelectResult`; errors per state as in
         `score_states` (a state with more than 4,096 cuts holds the `GcnnError` `select_cuts` raises for it)."""
-        from . import ops
         ops.check_thresholds(p_max, p_max_ub)
         states = list(states)
         forced = [None] * len(states) if forced is None else list(forced)
@@ -901,16 +588,7 @@ class GCNN:
         packed = []
         for st, f in zip(states, forced):
             try:
-                if f is None:
-                    f = (np.zeros((2, 0), np.int32), np.zeros(0, np.float32), 0)
-                if len(f) == 2:
-                    fi = np.asarray(f[0])
-                    f = (f[0], f[1], int(fi[0].max()) + 1 if fi.size else 0)
-                fi, fv, n_forced = f
-                if isinstance(fi, torch.Tensor):
-                    fi, fv = fi.cpu().numpy(), fv.cpu().numpy()
-                n_vars = st.dims.n_vars if isinstance(st, Batch) else int(np.asarray(st[3]).shape[0])
-                packed.append(ops.pack_rows(fi, fv, int(n_forced), n_vars))
+                packed.append(normalize_forced(f, st.dims.n_vars if isinstance(st, Batch) else int(np.asarray(st[3]).shape[0])))
             except Exception as exc:  # noqa: BLE001
                 packed.append(exc)
 
@@ -921,7 +599,7 @@ class GCNN:
         for i, r in enumerate(results):
             if isinstance(r, tuple):
                 _, scores, order, n_kept = r
-                results[i] = SelectResult(order, n_kept, n_kept if max_selected is None else min(n_kept, int(max_selected)), scores)
+                results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
         return self._finish_many(results, return_exceptions)
 
     def get_concrete_function(self):
@@ -929,8 +607,8 @@ class GCNN:
         callable `(state10, training) -> scores` with `.numpy()`.  Host arrays (what `get_state` produces) take the
         single-call path `score_state`; device tensors / prepared batches the general forward pass."""
         def get_improvements(state, training=False, rank=False):
-            if isinstance(state, Batch) or any(isinstance(x, torch.Tensor) for x in state[:7]):
-                with torch.no_grad():
-                    return self.call(state, training)
-            return self.score_state(state, rank)
+            if is_host_state(state):
+                return self.score_state(state, rank)
+            with torch.no_grad():
+                return self.call(state, training)
         return get_improvements

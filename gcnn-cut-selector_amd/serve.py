@@ -146,6 +146,10 @@ def decode_reply(buf):
     return arrays, n_kept, n_selected
 
 
+def _n_selected(n_kept, max_selected):   # `infer.n_selected`, restated: this module imports nothing that imports torch
+    return n_kept if max_selected is None else min(n_kept, max_selected)
+
+
 def _recv_exact(sock, n):
     chunks, got = [], 0
     while got < n:
@@ -334,9 +338,8 @@ class ScoringServer:
                     self.stats["errors"] += 1
                     self._reply(conn, encode_reply(error=res))
                 elif kind == KIND_SELECT:
-                    ms = req["max_selected"]
                     self._reply(conn, encode_reply([np.asarray(res.scores), np.asarray(res.order, np.int32)], res.n_kept,
-                                                   res.n_kept if ms is None else min(res.n_kept, ms)))
+                                                   _n_selected(res.n_kept, req["max_selected"])))
                 else:
                     arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if kind == KIND_RANK else [])
                     self._reply(conn, encode_reply(arrays))

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from .graph import _ptr, _stream
-from .model import GCNN, Batch, EMB, PRENORM_LAYERS
+from .model import GCNN, Batch, PRENORM_LAYERS, prenorm_count
 from .store import StoreBatch
 
 
@@ -49,14 +49,21 @@ class Adam:
     def _lr(self):
         return float(self.learning_rate() if callable(self.learning_rate) else self.learning_rate)
 
+    def _moments(self, flat):
+        if self.m is None:
+            self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
+
+    def _tick(self):
+        """Advance the step counter; returns this step's lr_t."""
+        self.iterations += 1
+        t = self.iterations
+        return self._lr() * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+
     def apply_flat(self, model: GCNN, flat_grad: torch.Tensor, grad_scale: torch.Tensor | None = None, divide=False):
         """grad_scale: optional device scalar multiplying (divide=False) or dividing (divide=True) every gradient."""
         flat = model.flat_parameters.detach()
-        if self.m is None:
-            self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.iterations += 1
-        t = self.iterations
-        lr_t = self._lr() * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        self._moments(flat)
+        lr_t = self._tick()
         with torch.cuda.device(flat.device):
             _lib.check(_lib.lib().gcnn_adam_step(_ptr(flat), _ptr(flat_grad), _ptr(self.m), _ptr(self.v), flat.numel(),
                                                  lr_t, self.beta_1, self.beta_2, self.epsilon, _ptr(grad_scale),
@@ -66,19 +73,14 @@ class Adam:
         """Advance the step counter and return the `gcnn_adam_args` for `GCNN._backward_into(adam=...)`: the same update as
         `apply_flat`, executed by the backward pass's last launch instead of a launch of its own."""
         flat = model.flat_parameters.detach()
-        if self.m is None:
-            self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.iterations += 1
-        t = self.iterations
-        lr_t = self._lr() * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
-        return _lib.AdamArgs(flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), lr_t, self.beta_1, self.beta_2, self.epsilon)
+        self._moments(flat)
+        return _lib.AdamArgs(flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._tick(), self.beta_1, self.beta_2, self.epsilon)
 
     def apply_flat_dev(self, model: GCNN, flat_grad: torch.Tensor, grad_scale: torch.Tensor | None = None, divide=False):
         """The same update with hyper-parameters and step counter resident on the device (gcnn_adam_step_dev): nothing
         step-dependent crosses the host, so the call can sit inside a captured hipGraph and be replayed."""
         flat = model.flat_parameters.detach()
-        if self.m is None:
-            self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
+        self._moments(flat)
         if self._dev is None:
             self._dev = torch.tensor([self._lr(), self.beta_1, self.beta_2, self.epsilon, float(self.iterations), 0.0],
                                      dtype=torch.float32, device=flat.device)
@@ -102,6 +104,15 @@ class Adam:
         self.apply_flat(model, g)
 
 
+def _check_targets(y: torch.Tensor, n_cuts: int) -> torch.Tensor:
+    """Targets as the kernels read them: contiguous fp32, one per cut."""
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        y = y.to(torch.float32).contiguous()
+    if y.numel() != n_cuts:
+        raise ValueError(f"expected {n_cuts} targets, got {y.numel()}")
+    return y
+
+
 class TrainState:
     """Buffers reused across steps by `train_step` (flat gradient + the data-parallel count slot)."""
 
@@ -123,10 +134,7 @@ def train_step(model: GCNN, batch: Batch, targets: torch.Tensor, optimizer: Adam
     flat = model.flat_parameters.detach()
     ws = model._take_workspace(batch)
     n_cuts = batch.dims.n_cuts
-    if targets.dtype != torch.float32 or not targets.is_contiguous():
-        targets = targets.to(torch.float32).contiguous()
-    if targets.numel() != n_cuts:
-        raise ValueError(f"expected {n_cuts} targets, got {targets.numel()}")
+    targets = _check_targets(targets, n_cuts)
     loss = torch.empty(1, dtype=torch.float32, device=model.device)
     # The MSE head rides in the forward's last launch (gcnn_forward_loss), so the backward starts at the readout's hidden layer
     if process_group is None:
@@ -257,13 +265,8 @@ def train_step_group(models, batches, targets, optimizers, states, process_group
     dev = _check_group(models, batches)
     if not len(targets) == len(optimizers) == len(states) == len(models):
         raise ValueError("train_step_group: one target vector, optimizer and state per model")
-    ys = []
-    for batch, y in zip(batches, targets):   # every member is checked before any optimizer's step counter moves
-        if y.dtype != torch.float32 or not y.is_contiguous():
-            y = y.to(torch.float32).contiguous()
-        if y.numel() != batch.dims.n_cuts:
-            raise ValueError(f"expected {batch.dims.n_cuts} targets, got {y.numel()}")
-        ys.append(y)
+    # every member is checked before any optimizer's step counter moves
+    ys = [_check_targets(y, batch.dims.n_cuts) for batch, y in zip(batches, targets)]
     members, keep, out, taken, steps = [], [], [], [], []
     try:
         for model, batch, y, opt, state in zip(models, batches, ys, optimizers, states):
@@ -353,15 +356,61 @@ def ranking_metric(pred: torch.Tensor, true: torch.Tensor, n_cuts, fractions_dev
     return frac
 
 
+class _EpochTotals:
+    """One model's loss and ranking accuracy over an epoch.  They accumulate ON THE DEVICE and the host reads them once, in
+    `result`; only a batch with a sample too large for the device metric (more than 4,096 cuts) is ranked on the host."""
+
+    def __init__(self, fractions: np.ndarray, device):
+        self.fractions, self.device = fractions, device
+        self.frac_dev = torch.from_numpy(fractions).to(device)
+        self.acc = torch.zeros(len(fractions), dtype=torch.float32, device=device)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=device)
+        self.host_acc, self.host_loss = np.zeros(len(fractions)), 0.0
+        self.n_samples = self.cut_count = 0
+
+    def add(self, pred: torch.Tensor, y: torch.Tensor, n_cuts: np.ndarray, loss: torch.Tensor, weight: float):
+        """One batch: predictions and targets of its cuts, per-sample cut counts, its loss and the weight the loss enters with."""
+        if len(n_cuts) == 0:
+            pass
+        elif n_cuts.max() <= 4096:
+            ranking_metric(pred, y, n_cuts, self.frac_dev, self.acc, loss, self.loss, weight)
+        else:
+            p, t = pred.cpu().numpy(), y.cpu().numpy()
+            start = 0
+            for nk in n_cuts:
+                self.host_acc += ranking_fraction(p[start:start + nk], t[start:start + nk]) >= self.fractions
+                start += nk
+            self.host_loss += float(loss) * weight
+        self.n_samples += len(n_cuts)
+        self.cut_count += int(n_cuts.sum())
+
+    def result(self, process_group=None):
+        """(cut-weighted mean loss, accuracy per fraction), over all ranks of `process_group` when one is given."""
+        dev = self.device
+        totals = torch.cat([self.loss.double() + self.host_loss, self.acc.double() + torch.from_numpy(self.host_acc).to(dev),
+                            torch.tensor([float(self.n_samples), float(self.cut_count)], dtype=torch.float64, device=dev)])
+        if process_group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(totals, op=dist.ReduceOp.SUM, group=process_group)
+        totals = totals.cpu().numpy()
+        return float(totals[0]) / max(totals[-1], 1.0), totals[1:-2] / max(totals[-2], 1.0)
+
+
+def _model_inputs(item):
+    """A loader item -- `utils.load_batch` 11-tuple or `SampleStore` batch -- as the model takes it: the prepared `Batch`, or the
+    10-tuple with the per-sample counts summed."""
+    if isinstance(item, StoreBatch):     # collated on the device by a SampleStore: nothing left to move
+        return item.batch
+    return tuple(item[:7]) + (int(np.sum(item[7])), int(np.sum(item[8])), int(np.sum(item[9])))
+
+
 def _unpack_batch(model: GCNN, batch):
-    """`utils.load_batch` 11-tuple or `SampleStore` batch -> (prepared Batch, per-sample n_cuts, device targets)."""
-    if isinstance(batch, StoreBatch):     # collated on the device by a SampleStore: nothing left to move
-        return batch.batch, np.asarray(batch.n_cuts).reshape(-1), batch.improvements
-    (c, cei, cef, v, k, kei, kef, n_cons, n_vars, n_cuts, improvements) = batch
-    n_cuts = np.asarray(n_cuts).reshape(-1)
-    prepared = model.prepare((c, cei, cef, v, k, kei, kef, int(np.sum(n_cons)), int(np.sum(n_vars)), int(n_cuts.sum())))
-    y = torch.as_tensor(np.asarray(improvements), dtype=torch.float32).to(model.device, non_blocking=True)
-    return prepared, n_cuts, y
+    """A loader item -> (prepared Batch, per-sample n_cuts, device targets)."""
+    prepared = model.prepare(_model_inputs(batch))
+    if isinstance(batch, StoreBatch):
+        return prepared, np.asarray(batch.n_cuts).reshape(-1), batch.improvements
+    y = torch.as_tensor(np.asarray(batch[10]), dtype=torch.float32).to(model.device, non_blocking=True)
+    return prepared, np.asarray(batch[9]).reshape(-1), y
 
 
 def process(model: GCNN, dataloader, fractions: np.ndarray, loss_fn=None, optimizer: Adam | None = None, *,
@@ -382,13 +431,7 @@ def process(model: GCNN, dataloader, fractions: np.ndarray, loss_fn=None, optimi
                         "reference's loss_fn slot; pass the optimizer fifth (or optimizer=...)")
     if loss_fn is not None and not callable(loss_fn):
         raise TypeError("loss_fn must be None or a callable (it is accepted for call compatibility and not called)")
-    dev = model.device
-    fractions = np.asarray(fractions, dtype=np.float32)
-    frac_dev = torch.from_numpy(fractions).to(dev)
-    acc_dev = torch.zeros(len(fractions), dtype=torch.float32, device=dev)
-    loss_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-    host_acc, host_loss = np.zeros(len(fractions)), 0.0   # samples too large for the device metric (> 4096 cuts)
-    n_samples = cut_count = 0
+    totals = _EpochTotals(np.asarray(fractions, dtype=np.float32), model.device)
     state = TrainState(model) if optimizer is not None else None
     for batch in dataloader:
         try:
@@ -403,19 +446,7 @@ def process(model: GCNN, dataloader, fractions: np.ndarray, loss_fn=None, optimi
                     predictions = model(prepared, False)
                 loss, _ = mse_loss(predictions, y, want_grad=False)
                 weight = float(total)
-            if len(n_cuts) == 0:
-                pass
-            elif n_cuts.max() <= 4096:
-                ranking_metric(predictions.detach().as_subclass(torch.Tensor), y, n_cuts, frac_dev, acc_dev, loss, loss_dev, weight)
-            else:
-                pred, true = predictions.detach().cpu().numpy(), y.cpu().numpy()
-                start = 0
-                for nk in n_cuts:
-                    host_acc += ranking_fraction(pred[start:start + nk], true[start:start + nk]) >= fractions
-                    start += nk
-                host_loss += float(loss) * weight
-            n_samples += len(n_cuts)
-            cut_count += total
+            totals.add(predictions.detach().as_subclass(torch.Tensor), y, n_cuts, loss, weight)
         except torch.OutOfMemoryError:  # the reference skips batches that exhaust memory (model_trainer.py:308-311)
             if process_group is not None:
                 # Data parallel: the peers are in (or heading for) this step's all-reduce; a rank that skipped on its own
@@ -423,15 +454,7 @@ def process(model: GCNN, dataloader, fractions: np.ndarray, loss_fn=None, optimi
                 # so the error propagates instead (with the store resident in HBM a batch that does not fit is a sizing bug).
                 raise
             print("WARNING: batch skipped.")
-    totals = torch.cat([loss_dev.double() + host_loss, acc_dev.double() + torch.from_numpy(host_acc).to(dev),
-                        torch.tensor([float(n_samples), float(cut_count)], dtype=torch.float64, device=dev)])
-    if process_group is not None:
-        import torch.distributed as dist
-        dist.all_reduce(totals, op=dist.ReduceOp.SUM, group=process_group)
-    totals = totals.cpu().numpy()
-    mean_loss = float(totals[0]) / max(totals[-1], 1.0)
-    mean_acc = totals[1:-2] / max(totals[-2], 1.0)
-    return mean_loss, mean_acc
+    return totals.result(process_group)
 
 
 def pretrain(model: GCNN, dataloader, process_group=None):
@@ -444,12 +467,8 @@ def pretrain(model: GCNN, dataloader, process_group=None):
     i = 0
     while True:
         for batch in dataloader:
-            if isinstance(batch, StoreBatch):
-                inputs = batch.batch
-            else:
-                inputs = tuple(batch[:7]) + (int(np.sum(batch[7])), int(np.sum(batch[8])), int(np.sum(batch[9])))
             try:
-                if not model.pretrain(inputs, True):
+                if not model.pretrain(_model_inputs(batch), True):
                     break
             except torch.OutOfMemoryError:
                 print("WARNING: batch skipped.")
@@ -458,16 +477,6 @@ def pretrain(model: GCNN, dataloader, process_group=None):
             break
         i += 1
     return i
-
-
-def _prenorm_count(dims, layer):
-    """GCNN.pretrain's sample_count: the elements PreNorm layer `layer` absorbs from a batch of these dims."""
-    if layer <= 4:
-        return [dims.n_cons, dims.n_cons_edges, dims.n_vars, dims.n_cuts, dims.n_cut_edges][layer]
-    conv, post = (layer - 5) // 2, (layer - 5) % 2
-    n_recv = [dims.n_cons, dims.n_vars, dims.n_cuts][conv]
-    n_edge = [dims.n_cons_edges, dims.n_cons_edges, dims.n_cut_edges][conv]
-    return (n_recv if post else n_edge) * EMB
 
 
 def pretrain_many(models, loaders, process_group=None):
@@ -494,9 +503,9 @@ def pretrain_many(models, loaders, process_group=None):
     while True:
         layer = {}   # the layer each model fits in this pass: its first waiting one (none left: that model is done)
         for i in live:
-            waiting = [j for j, st in enumerate(models[i]._prenorm_state) if st["waiting"]]
-            if waiting:
-                layer[i] = waiting[0]
+            waiting = models[i]._waiting_layer()
+            if waiting is not None:
+                layer[i] = waiting
         live = [i for i in live if i in layer]
         if not live:
             break
@@ -516,11 +525,9 @@ def pretrain_many(models, loaders, process_group=None):
                 for i, b in step:
                     m = models[i]
                     try:
-                        inputs = b.batch if isinstance(b, StoreBatch) else \
-                            tuple(b[:7]) + (int(np.sum(b[7])), int(np.sum(b[8])), int(np.sum(b[9])))
-                        batch = m.prepare(inputs)
+                        batch = m.prepare(_model_inputs(b))
                         received[i] = True
-                        if _prenorm_count(batch.dims, layer[i]) == 0:
+                        if prenorm_count(batch.dims, layer[i]) == 0:
                             continue
                         ws = m._take_workspace(batch)
                     except torch.OutOfMemoryError:   # as `pretrain`: the batch is skipped
@@ -563,13 +570,8 @@ def process_many(models, loaders, fractions: np.ndarray, optimizers=None):
         raise ValueError("process_many: one loader (and optimizer) per model")
     if not 1 <= n <= _lib.GROUP_MAX or len({id(m) for m in models}) != n:
         raise ValueError(f"process_many: 1..{_lib.GROUP_MAX} distinct models")
-    dev = models[0].device
     fractions = np.asarray(fractions, dtype=np.float32)
-    frac_dev = torch.from_numpy(fractions).to(dev)
-    acc = [torch.zeros(len(fractions), dtype=torch.float32, device=dev) for _ in models]
-    loss_acc = [torch.zeros(1, dtype=torch.float32, device=dev) for _ in models]
-    host_acc, host_loss = [np.zeros(len(fractions)) for _ in models], [0.0] * n
-    n_samples, cut_count = [0] * n, [0] * n
+    totals = [_EpochTotals(fractions, models[0].device) for _ in models]
     states = [TrainState(m) for m in models] if optimizers is not None else None
     iters = [iter(ld) for ld in loaders]
     live = list(range(n))
@@ -592,27 +594,8 @@ def process_many(models, loaders, fractions: np.ndarray, optimizers=None):
             preds = forward_group([models[i] for i in idx], [u[0] for u in unpacked])
             losses = [mse_loss(p, u[2], want_grad=False)[0] for p, u in zip(preds, unpacked)]
         for i, (_, n_cuts, y), loss, pred in zip(idx, unpacked, losses, preds):
-            total = int(n_cuts.sum())
-            if len(n_cuts) == 0:
-                pass
-            elif n_cuts.max() <= 4096:
-                ranking_metric(pred, y, n_cuts, frac_dev, acc[i], loss, loss_acc[i], float(total))
-            else:
-                p, t = pred.cpu().numpy(), y.cpu().numpy()
-                start = 0
-                for nk in n_cuts:
-                    host_acc[i] += ranking_fraction(p[start:start + nk], t[start:start + nk]) >= fractions
-                    start += nk
-                host_loss[i] += float(loss) * float(total)
-            n_samples[i] += len(n_cuts)
-            cut_count[i] += total
-    result = []
-    for i in range(n):
-        totals = torch.cat([loss_acc[i].double() + host_loss[i], acc[i].double() + torch.from_numpy(host_acc[i]).to(dev),
-                            torch.tensor([float(n_samples[i]), float(cut_count[i])], dtype=torch.float64, device=dev)])
-        totals = totals.cpu().numpy()
-        result.append((float(totals[0]) / max(totals[-1], 1.0), totals[1:-2] / max(totals[-2], 1.0)))
-    return result
+            totals[i].add(pred, y, n_cuts, loss, float(n_cuts.sum()))
+    return [t.result() for t in totals]
 
 
 class _StoreBatches:
