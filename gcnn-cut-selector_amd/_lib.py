@@ -65,6 +65,23 @@ class GroupMember(C.Structure):
                 ("grads", C.c_void_p), ("loss_out", C.c_void_p), ("adam", C.POINTER(AdamArgs))]
 
 
+class LpDims(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("n_cuts", C.c_int32), ("row_nnz", C.c_int32), ("cut_nnz", C.c_int32),
+                ("has_incumbent", C.c_int32), ("n_model_vars", C.c_int32), ("n_state_rows", C.c_int32),
+                ("n_state_edges", C.c_int32), ("reserved", C.c_int32), ("infinity", C.c_double), ("sum_epsilon", C.c_double),
+                ("obj_norm", C.c_double)]
+
+
+LP_ARRAYS = 22   # GCNN_LP_ARRAYS
+
+
+class LpLayout(C.Structure):
+    _fields_ = [("snap_bytes", C.c_size_t), ("snap_off", C.c_size_t * LP_ARRAYS), ("scratch_bytes", C.c_size_t),
+                ("call_supported", C.c_int32), ("reserved", C.c_int32), ("in_bytes", C.c_size_t), ("forced_off", C.c_size_t * 3),
+                ("out_bytes", C.c_size_t), ("out_off", C.c_size_t * 6), ("arena_bytes", C.c_size_t), ("ws_off", C.c_size_t),
+                ("lp_off", C.c_size_t), ("scratch_off", C.c_size_t), ("state", InferLayout)]
+
+
 GROUP_MAX = 8   # GCNN_GROUP_MAX
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
@@ -123,6 +140,10 @@ SIGNATURES = {
     "gcnn_infer_batch_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(IbatchLayout)]),
     "gcnn_infer_batch_fill_table": (C.c_int, [_I, _P, _P, _P, _P]),
     "gcnn_infer_batch": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
+    "gcnn_lp_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, C.POINTER(LpLayout)]),
+    "gcnn_lp_state": (C.c_int, [C.POINTER(LpDims), _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gcnn_lp_infer": (C.c_int, [C.POINTER(LpDims), _P, _P, _P, _P, _Z, _I, _P]),
+    "gcnn_lp_infer_select": (C.c_int, [C.POINTER(LpDims), _I, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
 }
 
 _lib = None

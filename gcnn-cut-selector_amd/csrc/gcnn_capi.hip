@@ -869,11 +869,11 @@ static int infer_layout(const gcnn_dims* d, size_t extra_in, size_t extra_out, g
 }
 extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) { return infer_layout(d, 0, 0, L); }
 
-// The upload, the graph plan and the forward pass of the single-state call: scores land at A + L.dev_off[6]; *kg receives the cut
-// edge set as the arena holds it (by-left CSR = the uploaded list), *flags the plan's flag words.
-static int infer_forward(const gcnn_dims* d, const float* params, const void* host_in, char* A, const gcnn_infer_layout& L,
-                         hipStream_t st, gcnn_graph* kg, const int** flags) {
-    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));      // ONE upload: zero block + the seven arrays
+// The single-state call in two halves.  infer_run: the graph plan and the forward pass on a state that already lies in the arena
+// (zero block + the seven arrays at L.in_off, however they got there): scores land at A + L.dev_off[6]; *kg receives the cut edge
+// set as the arena holds it (by-left CSR = the list itself), *flags the plan's flag words.  infer_forward: the upload, then that.
+static int infer_run(const gcnn_dims* d, const float* params, char* A, const gcnn_infer_layout& L, hipStream_t st, gcnn_graph* kg,
+                     const int** flags) {
     const int C = d->n_cons, V = d->n_vars, K = d->n_cuts, E1 = d->n_cons_edges, E2 = d->n_cut_edges;
     int* zero = (int*)(A + L.in_off[0]);
     IplanArgs ia; memset(&ia, 0, sizeof(ia));
@@ -893,6 +893,21 @@ static int infer_forward(const gcnn_dims* d, const float* params, const void* ho
     return forward_impl(d, params, (const float*)(A + L.in_off[1]), (const float*)(A + L.in_off[4]), (const float*)(A + L.in_off[5]),
                         &cg, kg, (float*)(A + L.dev_off[7]), gcnn_workspace_floats(d), out, 0, nullptr, 0.f, st, &ia);
 }
+static int infer_forward(const gcnn_dims* d, const float* params, const void* host_in, char* A, const gcnn_infer_layout& L,
+                         hipStream_t st, gcnn_graph* kg, const int** flags) {
+    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));      // ONE upload: zero block + the seven arrays
+    return infer_run(d, params, A, L, st, kg, flags);
+}
+// the ranking on request, behind either half
+static int infer_rank(const gcnn_dims* d, char* A, const gcnn_infer_layout& L, hipStream_t st) {
+    float* out = (float*)(A + L.dev_off[6]);
+    if (d->n_cuts > 0) {
+        ProfScope prof("k_rank_scores", st);
+        hipLaunchKernelGGL(k_rank_scores, dim3(1), dim3(256), 0, st, out, d->n_cuts, (int*)((char*)out + L.out_off[1]));
+        LAUNCHCHK();
+    }
+    return 0;
+}
 
 extern "C" int gcnn_infer(const gcnn_dims* d, const float* params, const void* host_in, void* host_out, void* arena,
                           size_t arena_bytes, int32_t want_order, void* stream) {
@@ -907,13 +922,8 @@ extern "C" int gcnn_infer(const gcnn_dims* d, const float* params, const void* h
     const int* flags = nullptr;
     rc = infer_forward(d, params, host_in, A, L, st, &kg, &flags);
     if (rc) return rc;
-    const int K = d->n_cuts;
     float* out = (float*)(A + L.dev_off[6]);
-    if (want_order && K > 0) {
-        ProfScope prof("k_rank_scores", st);
-        hipLaunchKernelGGL(k_rank_scores, dim3(1), dim3(256), 0, st, out, K, (int*)((char*)out + L.out_off[1]));
-        LAUNCHCHK();
-    }
+    if (want_order && (rc = infer_rank(d, A, L, st))) return rc;
     HIPCHK(hipMemcpyAsync((char*)out + L.out_off[2], flags, 16, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));  // ONE download: scores | order | flags
     return 0;
@@ -1347,6 +1357,8 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 
 // the cut selection (include/gcnn_hip.h: gcnn_select_cuts, gcnn_infer_select): its own launchers and launch names
 #include "gcnn_select.hpp"
+// the state from a raw LP snapshot (include/gcnn_hip.h: gcnn_lp_state, gcnn_lp_infer, gcnn_lp_infer_select): launch names k_lp_*
+#include "gcnn_lpstate.hpp"
 // groups of models stepped together (include/gcnn_hip.h: gcnn_group_train_step, gcnn_group_forward): launch names k_group_*
 #include "gcnn_group.hpp"
 // PreNorm fitting with the merge on the device, solo and grouped (include/gcnn_hip.h: gcnn_prenorm_merge,

@@ -71,6 +71,20 @@ extern "C" int gcnn_infer_select_layout_for(const gcnn_dims* d, int32_t n_forced
     return select_layout(d, n_forced, n_forced_entries, L);
 }
 
+// The selection on scores and cut rows that lie in the arena of a single-state call (out: its output block); the forced rows
+// wherever the caller's upload put them.
+static int select_in_arena(const gcnn_dims* d, int32_t n_forced, const gcnn_graph& kg, const void* f_ptr, const void* f_col,
+                           const void* f_val, char* out, size_t order_off, size_t n_kept_off, void* ws, double p_max,
+                           double p_max_ub, hipStream_t st) {
+    SelArgs a;
+    a.q = (const float*)out; a.c_ptr = kg.l_ptr; a.c_col = kg.l_oth; a.c_val = kg.l_coef; a.c_off = nullptr;
+    a.f_ptr = (const int*)f_ptr; a.f_col = (const int*)f_col; a.f_val = (const float*)f_val; a.f_off = nullptr;
+    a.n_samples = 1; a.total_cuts = d->n_cuts; a.total_forced = n_forced; a.max_cuts = d->n_cuts; a.n_vars = d->n_vars;
+    a.words = (d->n_cuts + 63) / 64; a.p_max = p_max; a.p_max_ub = p_max_ub;
+    a.bits = (unsigned long long*)ws; a.order = (int*)(out + order_off); a.n_kept = (int*)(out + n_kept_off);
+    return launch_select(a, st);
+}
+
 extern "C" int gcnn_infer_select(const gcnn_dims* d, int32_t n_forced, int32_t n_forced_entries, const float* params,
                                  const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
                                  double p_max_ub, void* stream) {
@@ -87,14 +101,8 @@ extern "C" int gcnn_infer_select(const gcnn_dims* d, int32_t n_forced, int32_t n
     rc = infer_forward(d, params, host_in, A, L, st, &kg, &flags);   // the upload carries the forced rows too
     if (rc) return rc;
     char* out = A + L.dev_off[6];
-    SelArgs a;
-    a.q = (const float*)out; a.c_ptr = kg.l_ptr; a.c_col = kg.l_oth; a.c_val = kg.l_coef; a.c_off = nullptr;
-    a.f_ptr = (const int*)(A + SL.forced_off[0]); a.f_col = (const int*)(A + SL.forced_off[1]);
-    a.f_val = (const float*)(A + SL.forced_off[2]); a.f_off = nullptr;
-    a.n_samples = 1; a.total_cuts = d->n_cuts; a.total_forced = n_forced; a.max_cuts = d->n_cuts; a.n_vars = d->n_vars;
-    a.words = (d->n_cuts + 63) / 64; a.p_max = p_max; a.p_max_ub = p_max_ub;
-    a.bits = (unsigned long long*)(A + SL.ws_off); a.order = (int*)(out + L.out_off[1]); a.n_kept = (int*)(out + SL.n_kept_off);
-    rc = launch_select(a, st);
+    rc = select_in_arena(d, n_forced, kg, A + SL.forced_off[0], A + SL.forced_off[1], A + SL.forced_off[2], out, L.out_off[1],
+                         SL.n_kept_off, A + SL.ws_off, p_max, p_max_ub, st);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out + L.out_off[2], flags, 16, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));  // ONE download: scores | order | flags | n_kept

@@ -20,6 +20,7 @@ class ScoreArray(np.ndarray):
     `get_improvements(state, False).numpy()`, model_evaluator.py:103).  `rankings` (optional): indices in descending score
     order, equal scores in index order -- `sorted(range(n), key=lambda x: quality[x], reverse=True)` of model_evaluator.py:110."""
     rankings = None
+    cut_index = None      # calls that start from an LP snapshot: state position -> input cut (scores are in STATE order)
 
     def numpy(self):
         return np.asarray(self)
@@ -29,8 +30,9 @@ class SelectResult:
     """What `GCNN.select_cuts` returns: `order` (int32 cut indices in STATE order: the kept cuts first, best first, then the
     removed ones), `n_selected` = min(n_kept, max_selected) -- the reference's 'nselectedcuts' --, `n_kept` and the `scores`."""
 
-    def __init__(self, order, n_kept, n_selected, scores):
+    def __init__(self, order, n_kept, n_selected, scores, cut_index=None):
         self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
+        self.cut_index = cut_index     # `select_cuts_lp`: state position -> input cut, so cut_index[order[:n_selected]] are the inputs
 
     def __repr__(self):
         return f"SelectResult(n_selected={self.n_selected}, n_kept={self.n_kept}, order={self.order!r})"
@@ -321,3 +323,107 @@ class _BatchSession(_Staging):
                 order = out[out_off[1] + lo:out_off[1] + lo + K].view(np.int32).copy() if mode else None
                 res.append(("ok", scores, order, int(n_kept[s]) if mode == _lib.IBATCH_SELECT else None))
         return res
+
+
+class _LPSession(_Staging):
+    """Host side of the calls that start from a raw LP snapshot (lpstate.py): gcnn_lp_infer / gcnn_lp_infer_select -- one upload of
+    the packed snapshot, the state built in the arena, one download -- and gcnn_lp_state, which leaves the state in device tensors."""
+    def __init__(self, model):
+        super().__init__(model)
+        self.deep_check = False   # True: the O(nnz) facts are checked on the host as well (lpstate.check_snapshot)
+        self.last = None          # (layout, state key) of the last single call
+
+    @staticmethod
+    def _layout(dims, n_forced, n_entries):
+        from . import lpstate
+        _, L = lpstate.lp_layout(dims, n_forced, n_entries)
+        return L, list(L.snap_off), list(L.forced_off), list(L.out_off)
+
+    def _checked(self, snap, n_forced=-1, n_entries=0):
+        from . import lpstate
+        arrays, dims = lpstate.check_snapshot(snap, self.deep_check)
+        key = tuple(v for k, v in dims.items() if isinstance(v, int)) + (n_forced, n_entries)
+        return arrays, dims, self.cached(key, self._layout, dims, n_forced, n_entries)
+
+    def run(self, snap, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0):
+        """pack -> one call -> wait -> flags -> (scores, order | None, n_kept | None, cut_index), all in STATE order."""
+        from . import lpstate
+        t0 = time.perf_counter()
+        n_forced, n_entries = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        arrays, dims, (L, snap_off, forced_off, out_off) = self._checked(snap, n_forced, n_entries)
+        n = dims["n_cuts"]
+        if not L.call_supported or (want_order and n > 4096):
+            raise _UseGeneralPath()
+        d = _lib.LpDims(**dims)
+        self._buffers(L)
+        buf = self.in_np
+        lpstate.pack_snapshot(buf, snap_off, arrays)
+        if forced is not None:
+            for off, a in zip(forced_off, forced):
+                buf[off:off + a.nbytes] = a.view(np.uint8)
+        t1 = time.perf_counter()
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            if forced is None:
+                _lib.check(_lib.lib().gcnn_lp_infer(C.byref(d), *self._pointers(), int(want_order), C.c_void_p(stream.cuda_stream)),
+                           "gcnn_lp_infer")
+            else:
+                _lib.check(_lib.lib().gcnn_lp_infer_select(C.byref(d), n_forced, n_entries, *self._pointers(), float(p_max),
+                                                          float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_lp_infer_select")
+            t2 = time.perf_counter()
+            stream.synchronize()
+        t3 = time.perf_counter()
+        if timings is not None:
+            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2, upload_bytes=int(L.in_bytes))
+        self.last = (L, lpstate.state_key(dims))
+        out = self.out_np
+        lpstate.raise_for_flags(out[out_off[4]:out_off[4] + 16].view(np.int32))
+        flags = out[out_off[2]:out_off[2] + 16].view(np.int32)
+        if flags[0]:
+            raise ValueError(BAD_INDEX)
+        if flags[1] or flags[2] or flags[3]:
+            raise _UseGeneralPath()
+        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
+        order = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy() if want_order else None
+        n_kept = int(out[out_off[3]:out_off[3] + 4].view(np.int32)[0]) if forced is not None else None
+        return scores, order, n_kept, out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
+
+    def last_state(self):
+        """The seven arrays the last single call built in the arena, as host arrays (tests compare them with gcnn_lp_state's)."""
+        L, (c, v, k, e1, e2) = self.last
+        off = list(L.state.in_off)
+        shapes = ((c, 4), (2, e1), (e1, 1), (v, 14), (k, 6), (2, e2), (e2, 1))
+        kinds = (torch.float32, torch.int32, torch.float32, torch.float32, torch.float32, torch.int32, torch.float32)
+        out = []
+        for o, shape, dt in zip(off[1:], shapes, kinds):
+            out.append(self.arena[o:o + 4 * shape[0] * shape[1]].view(dt).view(shape).cpu().numpy())
+        return tuple(out)
+
+    def build_state(self, snap):
+        """gcnn_lp_state: the snapshot goes up once, the state stays on the device.  Returns (the model's 10-tuple with device
+        tensors, cut_index as a device tensor).  Raises ValueError for what the device flags."""
+        from . import lpstate
+        arrays, dims, (L, snap_off, _, _) = self._checked(snap)
+        d = _lib.LpDims(**dims)
+        if self.pin_in is None or self.pin_in.numel() < L.snap_bytes:
+            self.pin_in = torch.empty(max(2 * L.snap_bytes, 1 << 20), dtype=torch.uint8).pin_memory()
+            self.in_np = self.pin_in.numpy()
+        lpstate.pack_snapshot(self.in_np, snap_off, arrays)
+        dev = self.model.device
+        c, v, k, e1, e2 = lpstate.state_key(dims)
+        f32, i32 = torch.float32, torch.int32
+        with torch.cuda.device(dev):
+            snap_dev = torch.empty(max(L.snap_bytes, 16), dtype=torch.uint8, device=dev)
+            snap_dev.copy_(self.pin_in[:snap_dev.numel()], non_blocking=True)
+            scratch = torch.empty(max(L.scratch_bytes, 16), dtype=torch.uint8, device=dev)
+            outs = [torch.empty(s, dtype=t, device=dev) for s, t in (((c, 4), f32), ((2, e1), i32), ((e1, 1), f32), ((v, 14), f32),
+                                                                     ((k, 6), f32), ((2, e2), i32), ((e2, 1), f32), ((k,), i32),
+                                                                     ((4,), i32))]
+            P = C.c_void_p
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib().gcnn_lp_state(C.byref(d), P(snap_dev.data_ptr()), P(scratch.data_ptr()), scratch.numel(),
+                                                *(P(t.data_ptr()) for t in outs), P(stream.cuda_stream)), "gcnn_lp_state")
+            flags = outs[8].cpu().numpy()      # waits for the stream: the staging buffer is free again
+        lpstate.raise_for_flags(flags)
+        return tuple(outs[:7]) + (c, v, k), outs[7]

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _UseGeneralPath, check_feature_shapes,
+from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPSession, _UseGeneralPath, check_feature_shapes,
                     check_state, is_host_state, n_selected, normalize_forced, stable_ranking)
 
 EMB = 64
@@ -164,6 +164,7 @@ class GCNN:
         self._ws_pool = []
         self._session = None      # single-state inference (gcnn_infer): pinned staging + device arena, created on first use
         self._batch_session = None   # many host states per call (gcnn_infer_batch), created on first use
+        self._lp_session = None   # calls that start from a raw LP snapshot (gcnn_lp_*), created on first use
         self._pin = None          # pinned host staging buffer for prepare()
         self._pin_event = None
         self._prenorm_state = None
@@ -497,6 +498,63 @@ class GCNN:
                 result = (scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0]))
         scores, order, n_kept = result
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
+
+    # ---- from a raw LP snapshot (lpstate.LPSnapshot): get_state's arithmetic on the device, in front of the same calls ---------
+    def _lp(self):
+        if self._lp_session is None:
+            self._lp_session = _LPSession(self)
+        return self._lp_session
+
+    def state_from_lp(self, snapshot):
+        """The model's 10-tuple as host arrays, built on the device from an `LPSnapshot` (gcnn_lp_state: utils.get_state's
+        arithmetic, utils.py:35-238), and `cut_index` (int32: state position -> input cut).  What a sample writer stores
+        (`utils.inputs_to_state` + `utils.save_sample`).  Raises ValueError for a snapshot that breaks its contract."""
+        state, cut_index = self._lp().build_state(snapshot)
+        return tuple(t.cpu().numpy() for t in state[:7]) + state[7:], cut_index.cpu().numpy()
+
+    def score_lp(self, snapshot, rank=False):
+        """`score_state` from an `LPSnapshot`: ONE upload of the packed snapshot, two launches build the state where gcnn_infer
+        keeps its uploaded arrays, then the same plan and forward pass, one download (gcnn_lp_infer).  Scores are in STATE order;
+        `.cut_index[p]` is the input cut at state position p, `.rankings` (with `rank`) as `score_state` gives them.  A snapshot
+        past gcnn_infer's limits, or one whose state the specialised plan declines, is built with gcnn_lp_state and goes through
+        `prepare` + the general forward pass as device tensors; the bits are the same."""
+        n_cuts = int(np.asarray(snapshot.cut_lhs).shape[0])
+        on_device = bool(rank) and (rank == "device" or n_cuts > self.HOST_RANK_MAX)
+        try:
+            scores, order, _, cut_index = self._lp().run(snapshot, on_device)
+        except _UseGeneralPath:
+            on_device = False
+            state, cut_index = self._lp().build_state(snapshot)
+            with torch.no_grad():
+                scores = self.call(state, False).numpy().view(ScoreArray)
+            cut_index = cut_index.cpu().numpy()
+        scores.cut_index = cut_index
+        if rank:
+            scores.rankings = order if on_device else stable_ranking(scores)
+        return scores
+
+    def select_cuts_lp(self, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        """`select_cuts` from an `LPSnapshot` (gcnn_lp_infer_select).  `forced` as `select_cuts` takes it.  The `SelectResult`'s
+        `order` is in STATE order and it carries `cut_index`: `cut_index[order[:n_selected]]` are the selected input cuts."""
+        ops.check_thresholds(p_max, p_max_ub)
+        n_cuts, n_vars = int(np.asarray(snapshot.cut_lhs).shape[0]), int(np.asarray(snapshot.col_type).shape[0])
+        if n_cuts > ops.SELECT_MAX_CUTS:
+            raise _lib.GcnnError(f"select_cuts_lp: the snapshot has {n_cuts} cuts; the device selection handles at most "
+                                 f"{ops.SELECT_MAX_CUTS} and there is no CPU fallback")
+        packed = normalize_forced(forced, n_vars)
+        try:
+            scores, order, n_kept, cut_index = self._lp().run(snapshot, True, None, packed, p_max, p_max_ub)
+        except _UseGeneralPath:
+            state, cut_index = self._lp().build_state(snapshot)
+            with torch.no_grad():
+                batch = self.prepare(state)
+                scores_dev = self.call(batch, False).as_subclass(torch.Tensor)
+                forced_dev = tuple(torch.from_numpy(a).to(self.device) for a in packed)
+                order, n_kept = ops.select_cuts(scores_dev, batch.cut_graph, None, forced_dev, p_max=p_max, p_max_ub=p_max_ub,
+                                                max_cuts=n_cuts)
+            scores, order, n_kept = scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0])
+            cut_index = cut_index.cpu().numpy()
+        return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
     # ---- many host states in one call (gcnn_infer_batch): what a scoring server does with the requests that queued up ----------
     def _many(self, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0):

@@ -185,3 +185,83 @@ def make_batch(problem: str, batch_size: int, first_sample: int = 0, scale: floa
     b = stack_samples([make_sample(problem, first_sample + i, scale=scale) for i in range(batch_size)])
     state = b[:7] + (int(b[7].sum()), int(b[8].sum()), int(b[9].sum()))
     return state, b[10], b[9]
+
+
+def _scaled_rows(problem, rng, scale):
+    """The constraint rows of `make_sample` at `scale` (1.0: the BASELINE size), for `make_lp_snapshot`."""
+    if problem == "setcov" and scale != 1.0:
+        nr, ncol = max(4, int(500 * scale)), max(8, int(1000 * scale))
+        lo = max(2, int(25 * scale))
+        return _setcov_rows(rng, nr, ncol, nnz=max(nr * lo, int(nr * ncol * 0.05)), lo=lo, hi=max(lo + 2, int(77 * scale) + 2))
+    if problem == "indset" and scale != 1.0:
+        return _indset_rows(rng, max(12, int(750 * scale)))
+    if problem == "capfac" and scale != 1.0:
+        n = max(3, int(100 * scale))
+        return _capfac_rows(rng, n, n)
+    return _BUILDERS[problem](rng)
+
+
+def make_lp_snapshot(problem: str, sample_index: int, scale: float = 1.0, incumbent: bool = True, row_sides: str = "mixed",
+                     cut_sides: str = "mixed", n_cuts: int | None = None, extra_cols: int = 0, infinity: float = 1e20):
+    """One synthetic raw LP snapshot (`lpstate.LPSnapshot`) on the constraint structure of `make_sample`: what a solver binding
+    would hand to `GCNN.score_lp`.  Rows carry random coefficients and a mix of <=, >=, equality and ranged sides (`row_sides`:
+    "mixed", "rhs_only" -- no row has a finite lhs --, or "ranged" -- every row has both); cuts are violated on their rhs, on their
+    lhs, or ranged with one side clearly the more violated (`cut_sides`: "mixed" or "lhs"), so that no side choice sits near its
+    tie.  `incumbent` switches the primal columns on and off; `extra_cols` appends columns no row touches (sizes past the
+    single call's variable limit); `n_cuts` fixes K.  Generator contract: numpy.random.default_rng(7000 + 1000 * config + index)."""
+    from .lpstate import LPSnapshot
+    rng = np.random.default_rng(7000 + 1000 * CONFIG_INDEX[problem] + sample_index)
+    rows, n_vars, _ = _scaled_rows(problem, rng, scale)
+    n_struct = n_vars
+    n_vars += int(extra_cols)
+    R = len(rows)
+    lens = np.fromiter((len(r) for r in rows), np.int64, R)
+    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    row_col = (np.concatenate(rows) if R else np.zeros(0, np.int64)).astype(np.int32)
+    row_val = np.round(rng.uniform(0.5, 3.0, row_col.size), 3) * rng.choice([-1.0, 1.0], row_col.size)
+
+    col_type = np.zeros(n_vars, np.int8)
+    if problem == "capfac":
+        col_type[: n_struct - int(round(np.sqrt(n_struct)))] = 3           # x_ij continuous, y_j binary
+    col_type[n_struct:] = rng.integers(0, 4, n_vars - n_struct)
+    col_obj = rng.standard_normal(n_vars)
+    col_lb = np.where(rng.random(n_vars) < 0.1, -infinity, 0.0)
+    col_ub = np.where(rng.random(n_vars) < 0.2, infinity, 1.0)
+    col_basis = rng.integers(0, 4, n_vars).astype(np.int8)
+    col_lp = np.where(rng.random(n_vars) < 0.5, rng.integers(0, 2, n_vars).astype(np.float64), rng.random(n_vars))
+    col_redcost = rng.standard_normal(n_vars) * (col_basis != 1)
+
+    activity = np.bincount(np.repeat(np.arange(R), lens), weights=row_val * col_lp[row_col], minlength=R)
+    kind = {"mixed": rng.choice(4, R, p=[0.45, 0.25, 0.15, 0.15]), "rhs_only": np.zeros(R, np.int64),
+            "ranged": np.full(R, 3)}[row_sides]                              # 0: <=, 1: >=, 2: equality, 3: ranged
+    slack = rng.uniform(0.0, 2.0, R) * (rng.random(R) < 0.7)
+    row_rhs = np.where(kind == 1, infinity, activity + slack)
+    row_lhs = np.where(kind == 0, -infinity, np.where(kind == 2, row_rhs, activity - rng.uniform(0.0, 2.0, R)))
+    row_lhs = np.where(kind == 1, activity - slack, row_lhs)
+    row_basis = np.where(slack == 0, np.where(kind == 1, 0, 2), 1).astype(np.int8)
+    row_dual = rng.standard_normal(R) * (row_basis != 1)
+
+    K = int(rng.integers(10, 101)) if n_cuts is None else int(n_cuts)
+    cut_cols, cut_vals = [], []
+    for _ in range(K):
+        nnz = int(rng.integers(10, min(201, n_vars + 1))) if n_vars >= 10 else int(rng.integers(1, n_vars + 1))
+        cut_cols.append(np.sort(rng.choice(n_vars, size=nnz, replace=False)))
+        cut_vals.append(np.round(rng.standard_normal(nnz), 3) + 0.0005)      # (never exactly zero)
+    klens = np.fromiter((len(c) for c in cut_cols), np.int64, K)
+    cut_ptr = np.concatenate([[0], np.cumsum(klens)]).astype(np.int32)
+    cut_col = np.concatenate(cut_cols).astype(np.int32)
+    cut_val = np.concatenate(cut_vals)
+    kact = np.bincount(np.repeat(np.arange(K), klens), weights=cut_val * col_lp[cut_col], minlength=K)
+    viol = rng.uniform(0.1, 1.0, K)
+    ckind = rng.integers(0, 4, K) if cut_sides == "mixed" else rng.choice([1, 3], K)   # 0: rhs, 1: lhs, 2: ranged -> rhs, 3: ranged -> lhs
+    cut_rhs = np.where(ckind == 0, kact - viol, np.where(ckind == 1, infinity, np.where(ckind == 2, kact - viol, kact + 1.0 + viol)))
+    cut_lhs = np.where(ckind == 0, -infinity, np.where(ckind == 1, kact + viol, np.where(ckind == 2, kact - 1.0 - viol, kact + viol)))
+
+    primal = avg = None
+    if incumbent:
+        primal = np.where(col_type == 3, rng.random(n_vars), rng.integers(0, 2, n_vars).astype(np.float64))
+        avg = 0.5 * (primal + rng.random(n_vars))
+    return LPSnapshot(row_ptr=row_ptr, row_col=row_col, row_val=row_val, row_lhs=row_lhs, row_rhs=row_rhs, row_dual=row_dual,
+                      row_basis=row_basis, col_type=col_type, col_obj=col_obj, col_lb=col_lb, col_ub=col_ub, col_basis=col_basis,
+                      col_lp=col_lp, col_redcost=col_redcost, cut_ptr=cut_ptr, cut_col=cut_col, cut_val=cut_val, cut_lhs=cut_lhs,
+                      cut_rhs=cut_rhs, col_primal=primal, col_primal_avg=avg, infinity=infinity, n_model_vars=n_struct)

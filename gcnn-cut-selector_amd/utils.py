@@ -137,3 +137,15 @@ def state_to_inputs(state):
     return (np.asarray(cons["values"], f32), np.asarray(cons_edge["indices"], i32), np.asarray(cons_edge["values"], f32),
             np.asarray(var["values"], f32), np.asarray(cut["values"], f32), np.asarray(cut_edge["indices"], i32),
             np.asarray(cut_edge["values"], f32), cons["values"].shape[0], var["values"].shape[0], cut["values"].shape[0])
+
+
+def inputs_to_state(inputs):
+    """The inverse of `state_to_inputs`: the model's 10-tuple (e.g. what `GCNN.state_from_lp` builds from an LP snapshot) -> the
+    5-tuple of dicts `get_state` returns (utils.py:35-238), which is what `save_sample` writes."""
+    from .synthetic import FEATURE_NAMES as names
+    c, cei, cef, v, k, kei, kef = (np.asarray(x) for x in inputs[:7])
+    return ({"features": names["cons"], "values": c},
+            {"features": names["edge"], "indices": cei, "values": cef.reshape(-1, 1)},
+            {"features": names["var"], "values": v},
+            {"features": names["cut"], "values": k},
+            {"features": names["edge"], "indices": kei, "values": kef.reshape(-1, 1)})

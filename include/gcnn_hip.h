@@ -445,6 +445,81 @@ int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_f
                      int32_t mode, const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes,
                      double p_max, double p_max_ub, void* stream);
 
+/* ---- the state from a raw LP snapshot: the arithmetic of get_state (utils.py:35-238) on the device ---------------------------------
+ * get_state walks solver objects AND turns what it finds into the model's inputs.  Only the walk is solver-bound; these entry
+ * points do the rest.  The caller hands over the LP as the solver holds it -- float64 values, int32 indices, int8 codes --
+ *   rows  (R):  CSR row_ptr [R+1], row_col [nnz] (LP column positions), row_val [nnz]; row_lhs, row_rhs, row_dual [R];
+ *               row_basis [R]: 0 lower, 1 basic, 2 upper, 3 zero
+ *   cols  (V):  col_type [V]: 0 binary, 1 integer, 2 implicit integer, 3 continuous; col_obj, col_lb, col_ub [V]; col_basis [V];
+ *               col_lp, col_redcost [V]; with an incumbent also col_primal and col_primal_avg [V]
+ *   cuts  (K):  CSR cut_ptr [K+1], cut_col, cut_val; cut_lhs, cut_rhs [K]
+ * packed into ONE buffer at gcnn_lp_layout.snap_off, in the order of GCNN_LP_* below; snap_off[GCNN_LP_HEADER] is a reserved 16-byte block
+ * (not read).  The snapshot is read only: violations are noted in the scratch, so one device snapshot may serve several calls.
+ * Contract: within a row or cut the columns are strictly increasing (scipy's sum_duplicates(), utils.py:102,226),
+ * every cut has an entry, constants are already moved into lhs / rhs.  "finite" below means not |x| >= infinity.
+ * The device writes the reference's input tuple (model.py:263-275), in get_state's layout and order:
+ *   constraints: every row with a finite lhs, in LP order, negated: [-lhs/norm, basis == lower, -cosine, -dual], then every row with a
+ *     finite rhs: [rhs/norm, basis == upper, cosine, dual]; norm = sqrt(sum a^2) (0 -> 1), cosine = a.obj/(norm*obj_norm), dual =
+ *     row_dual/(norm*obj_norm).  C = #lhs + #rhs (equality and ranged rows appear twice); edges -a/norm | a/norm, (row, col)-sorted.
+ *   variables:   one-hot type, obj/obj_norm, has_lb, has_ub, basis == lower, basis == upper, 0.5 - |x - floor(x) - 0.5| (0 when
+ *     continuous), redcost/obj_norm, lp, primal, primal_avg (zeros without an incumbent)            (utils.py:118-159)
+ *   cuts:        activity = a.col_lp; a cut takes its lhs side iff lhs is finite and lhs - activity > activity - rhs; lhs-side cuts
+ *     first, then rhs-side cuts, each group in input order (utils.py:180-185): [-lhs/norm | rhs/norm, nnz/n_model_vars,
+ *     #non-continuous columns/nnz, efficacy, cutoff, parallelism]; edges as for rows.  With feasibility = min(rhs - activity,
+ *     activity - lhs): efficacy = -feasibility/norm; cutoff = 0 without an incumbent, else with d = a.(col_primal - col_lp) /
+ *     |col_primal - col_lp| (0 when that norm is 0), |d| <= sum_epsilon replaced by copysign(sum_epsilon, d): min(-feasibility/|d|,
+ *     infinity); parallelism = |a.col_obj|/(|a|*|col_obj|), 0 when the product is 0.  (This project's reading of SCIP's
+ *     getCutEfficacy, getCutLPSolCutoffDistance and getRowObjParallelism at default settings: DESIGN.md section 7.)
+ *   cut_index [K] int32: state position -> input cut.
+ * Sums, divisions and square roots are fp64, each output is rounded to fp32 once; no float atomics: the same bits from run to run.
+ * n_state_rows (C) and n_state_edges (E1) are the caller's: count the rows with a finite lhs / rhs and their entries (O(R)); the
+ * device recomputes both and reports a difference.  flags [4] int32 (device): [0] a column outside [0, n_cols), [1] columns of a row
+ * or cut not strictly increasing, [2] offsets not monotone inside [0, nnz], [3] C or E1 differ from the device's count.  Any flag
+ * set => the state is NOT valid.  Whatever the snapshot holds, no kernel reads or writes outside the arrays as sized by the dims. */
+typedef struct gcnn_lp_dims {
+    int32_t n_rows, n_cols, n_cuts, row_nnz, cut_nnz;
+    int32_t has_incumbent;
+    int32_t n_model_vars;                  /* getNVars() of utils.py:188; >= 1 */
+    int32_t n_state_rows, n_state_edges;   /* C, E1 */
+    int32_t reserved;
+    double infinity, sum_epsilon;          /* SCIP defaults: 1e20, 1e-6 */
+    double obj_norm;                       /* > 0: the objective's norm, a value <= 0 already replaced by 1 (utils.py:50-51) */
+} gcnn_lp_dims;
+#define GCNN_LP_ARRAYS 22
+enum { GCNN_LP_HEADER = 0, GCNN_LP_ROW_PTR, GCNN_LP_ROW_COL, GCNN_LP_ROW_VAL, GCNN_LP_ROW_LHS, GCNN_LP_ROW_RHS, GCNN_LP_ROW_DUAL,
+       GCNN_LP_ROW_BASIS, GCNN_LP_COL_TYPE, GCNN_LP_COL_OBJ, GCNN_LP_COL_LB, GCNN_LP_COL_UB, GCNN_LP_COL_BASIS, GCNN_LP_COL_LP,
+       GCNN_LP_COL_REDCOST, GCNN_LP_COL_PRIMAL, GCNN_LP_COL_PRIMAL_AVG, GCNN_LP_CUT_PTR, GCNN_LP_CUT_COL, GCNN_LP_CUT_VAL,
+       GCNN_LP_CUT_LHS, GCNN_LP_CUT_RHS };
+/* gcnn_lp_layout_for fills snap_* and scratch_bytes for every valid dims (what gcnn_lp_state needs), and the single call's part
+ * when the sizes are inside gcnn_infer's limits (call_supported = 1).  n_forced < 0: the layout of gcnn_lp_infer; >= 0: that of
+ * gcnn_lp_infer_select with so many forced rows / entries. */
+typedef struct gcnn_lp_layout {
+    size_t snap_bytes, snap_off[GCNN_LP_ARRAYS];
+    size_t scratch_bytes;
+    int32_t call_supported, reserved;
+    size_t in_bytes, forced_off[3];        /* host_in: the packed snapshot, then forced_ptr | forced_col | forced_val as in gcnn_infer_select */
+    size_t out_bytes, out_off[6];          /* host_out: scores [K] f32 | order [K] i32 | gcnn_infer's 4 flags | n_kept | the 4 LP flags | cut_index [K] */
+    size_t arena_bytes, ws_off, lp_off, scratch_off;   /* internal carving of the arena */
+    gcnn_infer_layout state;               /* internal: where the state, the plan and the forward workspace live in the arena */
+} gcnn_lp_layout;
+int gcnn_lp_layout_for(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries, gcnn_lp_layout* layout /* host */);
+/* snapshot (device, 16-byte aligned, packed at snap_off) -> the seven arrays and cut_index in device memory (cons_feats 16-byte
+ * aligned), on `stream`; two launches, nothing synchronised.  scratch: scratch_bytes of device memory, 16-byte aligned. */
+int gcnn_lp_state(const gcnn_lp_dims* dims, const void* snapshot, void* scratch, size_t scratch_bytes, float* cons_feats,
+                  int32_t* cons_edge_inds /* [2,E1] */, float* cons_edge_feats, float* var_feats, float* cut_feats,
+                  int32_t* cut_edge_inds /* [2,E2] */, float* cut_edge_feats, int32_t* cut_index, int32_t* flags /* [4] */,
+                  void* stream);
+/* gcnn_infer / gcnn_infer_select on a snapshot: ONE upload of host_in (pinned, in_bytes), the two state-building launches write the
+ * seven arrays where gcnn_infer's upload would have put them, then the same plan, forward pass and ranking / selection, ONE
+ * download of host_out (pinned, out_bytes).  Scores and order are in STATE order: map them through cut_index.  Any of the eight
+ * flags set => nothing else in host_out is valid (an LP flag, or gcnn_infer's [0]: bad input; gcnn_infer's [1..3]: build the state
+ * with gcnn_lp_state and take gcnn_graph_build + gcnn_forward).  GCNN_E_UNSUPPORTED where gcnn_infer / gcnn_infer_select return it. */
+int gcnn_lp_infer(const gcnn_lp_dims* dims, const float* params, const void* host_in, void* host_out, void* arena,
+                  size_t arena_bytes, int32_t want_order, void* stream);
+int gcnn_lp_infer_select(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries, const float* params,
+                         const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max, double p_max_ub,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
