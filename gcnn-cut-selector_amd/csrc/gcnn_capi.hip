@@ -347,6 +347,21 @@ size_t gcnn_graph_temp_bytes(int32_t n_edges) {
     const size_t e = ((size_t)(n_edges > 0 ? n_edges : 1) * sizeof(int) + 255) & ~(size_t)255;
     return sort_temp_bytes(n_edges) + 3 * e;  // radix-sort temp + iota + sorted keys + one permutation
 }
+// One receiver order of an edge list (n_edges > 0) by its key: a stable LSD radix sort of (node id, input position) -- ties keep the
+// input order => every sum has a fixed order --, the segment offsets, then the other side's ids and the values gathered into
+// that order.  It records nothing: a caller that wants the stage on the launch record wraps the call in its own ProfScope.
+static int by_key_stage(void* sort_tmp, size_t sort_bytes, const int* key_in, const int* iota, int* keys, int* perm, int nseg,
+                        int n_edges, const int* oth_in, const float* val_in, int* ptr, int* oth, float* coef, hipStream_t st) {
+    const int grid = std::min(cdiv(n_edges + 1, 256), 4096);
+    unsigned bits = 1;
+    while ((1ll << bits) < (long long)nseg + 1 && bits < 31) ++bits;
+    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, key_in, keys, iota, perm, (unsigned)n_edges, 0u, bits, st));
+    hipLaunchKernelGGL(k_seg_offsets, dim3(grid), dim3(256), 0, st, (const int*)keys, n_edges, nseg, ptr);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(k_gather_edges, dim3(grid), dim3(256), 0, st, (const int*)perm, oth_in, val_in, n_edges, oth, coef);
+    LAUNCHCHK();
+    return 0;
+}
 
 // One launch gathers every array of a mini-batch out of a device-resident sample store (see k_collate)
 int gcnn_collate(const gcnn_collate_job* jobs, int32_t n_jobs, const int64_t* src_off, const int64_t* dst_off,
@@ -417,15 +432,9 @@ int gcnn_graph_build(const int32_t* edge_inds, const float* edge_feats, int32_t 
             if (l_perm) HIPCHK(hipMemcpyAsync(l_perm, iota, (size_t)n_edges * sizeof(int), hipMemcpyDeviceToDevice, st));
             continue;
         }
-        unsigned bits = 1;
-        while ((1ll << bits) < (long long)nseg + 1 && bits < 31) ++bits;
-        // stable LSD radix sort of (node id, input position): ties keep the input order => every sum has a fixed order
-        HIPCHK(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, key_in, keys, (const int*)iota, perm, (unsigned)n_edges, 0u, bits, st));
-        hipLaunchKernelGGL(k_seg_offsets, dim3(grid), dim3(256), 0, st, keys, n_edges, nseg, side == 0 ? l_ptr : v_ptr);
-        LAUNCHCHK();
-        hipLaunchKernelGGL(k_gather_edges, dim3(grid), dim3(256), 0, st, perm, side == 0 ? var : left, edge_feats,
-                           n_edges, side == 0 ? l_oth : v_oth, side == 0 ? l_coef : v_coef);
-        LAUNCHCHK();
+        const int rc = by_key_stage(sort_tmp, sort_bytes, key_in, iota, keys, perm, nseg, n_edges, side == 0 ? var : left, edge_feats,
+                                    side == 0 ? l_ptr : v_ptr, side == 0 ? l_oth : v_oth, side == 0 ? l_coef : v_coef, st);
+        if (rc) return rc;
         if (side == 0 && l_perm) HIPCHK(hipMemcpyAsync(l_perm, perm, (size_t)n_edges * sizeof(int), hipMemcpyDeviceToDevice, st));
     }
     return 0;
@@ -835,6 +844,16 @@ extern "C" int gcnn_forward(const gcnn_dims* d, const float* p, const float* con
 }
 // ---- single-state inference: the SCIP cut selector's call (model_evaluator.py:82-111) as ONE entry point --------------------
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+// Byte carver of the call layouts (this one, gcnn_select.hpp, gcnn_lpstate.hpp, gcnn_ibatch.hpp): take() hands out the running offset
+// and moves it on by `bytes` rounded up to `align` -- 16 inside an upload or a scratch block, 256 for a block of the device arena.
+struct Carver {
+    size_t off;
+    size_t take(size_t bytes, size_t align) { const size_t o = off; off += (bytes + align - 1) & ~(align - 1); return o; }
+};
+// the forced rows as every selecting call uploads them: forced_ptr [F+1] int32 | forced_col [EF] int32 | forced_val [EF] f32
+static void forced_block(Carver& c, size_t F, size_t EF, size_t out[3]) {
+    out[0] = c.take(4 * (F + 1), 16); out[1] = c.take(4 * EF, 16); out[2] = c.take(4 * EF, 16);
+}
 // extra_in / extra_out: a block behind the inputs (in the upload) / behind the flags (in the download), for callers that extend the
 // call (gcnn_infer_select); gcnn_infer's own layout is the one with both zero.  The extra input block starts at the in_bytes of the
 // plain layout, the extra output block at its out_bytes.
@@ -842,36 +861,31 @@ static int infer_layout(const gcnn_dims* d, size_t extra_in, size_t extra_out, g
     if (!d || !L || d->n_cons < 0 || d->n_vars < 0 || d->n_cuts < 0 || d->n_cons_edges < 0 || d->n_cut_edges < 0) return GCNN_E_BADARG;
     if (d->n_vars > IPLAN_MAX_VARS) return GCNN_E_UNSUPPORTED;
     const size_t C = d->n_cons, V = d->n_vars, K = d->n_cuts, E1 = d->n_cons_edges, E2 = d->n_cut_edges;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al16(bytes); return o; };
-    L->in_off[0] = take(4 * (2 * V + 8 + (C + 1) + (K + 1)));   // zero block: vcount[V] | cursor[V] | flags[8] | l_ptr cons | l_ptr cut
-    L->in_off[1] = take(16 * C);                     // cons_feats [C,4]
-    L->in_off[2] = take(8 * E1);                     // cons_edge_inds [2,E1]
-    L->in_off[3] = take(4 * E1);                     // cons_edge_feats [E1]
-    L->in_off[4] = take(56 * V);                     // var_feats [V,14]
-    L->in_off[5] = take(24 * K);                     // cut_feats [K,6]
-    L->in_off[6] = take(8 * E2);                     // cut_edge_inds [2,E2]
-    L->in_off[7] = take(4 * E2);                     // cut_edge_feats [E2]
-    if (extra_in) take(extra_in);
-    L->in_bytes = off;
+    // zero block: vcount[V] | cursor[V] | flags[8] | l_ptr cons | l_ptr cut; then cons_feats [C,4], cons_edge_inds [2,E1], cons_edge_feats
+    // [E1], var_feats [V,14], cut_feats [K,6], cut_edge_inds [2,E2], cut_edge_feats [E2]
+    const size_t sizes[8] = {4 * (2 * V + 8 + (C + 1) + (K + 1)), 16 * C, 8 * E1, 4 * E1, 56 * V, 24 * K, 8 * E2, 4 * E2};
+    Carver in{0};
+    for (int i = 0; i < 8; ++i) L->in_off[i] = in.take(sizes[i], 16);
+    if (extra_in) in.take(extra_in, 16);
+    L->in_bytes = in.off;
     L->out_off[0] = 0; L->out_off[1] = al16(4 * K); L->out_off[2] = L->out_off[1] + al16(4 * K);
     L->out_bytes = L->out_off[2] + 16 + extra_out;   // scores[K] | order[K] | flags[4] | extra
     // device arena: the uploaded block, the plan, the output block, the forward workspace
-    size_t a = off;
-    auto dev = [&](size_t bytes) { const size_t o = a; a += (bytes + 255) & ~(size_t)255; return o; };
+    Carver dev{in.off};
     L->dev_off[0] = L->in_off[0] + 4 * (2 * V + 8); L->dev_off[1] = L->dev_off[0] + 4 * (C + 1);            // l_ptr cons, l_ptr cut: inside the zero block
-    L->dev_off[2] = dev(4 * (V + 1));                                                                          // v_ptr
-    L->dev_off[3] = dev(4 * E1); L->dev_off[4] = dev(4 * E1); L->dev_off[5] = dev(4 * E1);                    // v_pos, v_oth, v_coef
-    L->dev_off[6] = dev(L->out_bytes);
-    L->dev_off[7] = dev(sizeof(float) * gcnn_workspace_floats(d));
-    L->arena_bytes = a;
+    L->dev_off[2] = dev.take(4 * (V + 1), 256);                                                                // v_ptr
+    for (int i = 3; i < 6; ++i) L->dev_off[i] = dev.take(4 * E1, 256);                                         // v_pos, v_oth, v_coef
+    L->dev_off[6] = dev.take(L->out_bytes, 256);
+    L->dev_off[7] = dev.take(sizeof(float) * gcnn_workspace_floats(d), 256);
+    L->arena_bytes = dev.off;
     return 0;
 }
 extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) { return infer_layout(d, 0, 0, L); }
 
-// The single-state call in two halves.  infer_run: the graph plan and the forward pass on a state that already lies in the arena
-// (zero block + the seven arrays at L.in_off, however they got there): scores land at A + L.dev_off[6]; *kg receives the cut edge
-// set as the arena holds it (by-left CSR = the list itself), *flags the plan's flag words.  infer_forward: the upload, then that.
+// infer_run: the graph plan and the forward pass on a state that already lies in the arena (zero block + the seven arrays at
+// L.in_off, however they got there: gcnn_infer and gcnn_infer_select upload them, gcnn_select.hpp; the LP calls build them there,
+// gcnn_lpstate.hpp): scores land at A + L.dev_off[6]; *kg receives the cut edge set as the arena holds it (by-left CSR = the list
+// itself), *flags the plan's flag words.  What follows it -- selection or ranking, flags, download -- is infer_tail (gcnn_select.hpp).
 static int infer_run(const gcnn_dims* d, const float* params, char* A, const gcnn_infer_layout& L, hipStream_t st, gcnn_graph* kg,
                      const int** flags) {
     const int C = d->n_cons, V = d->n_vars, K = d->n_cuts, E1 = d->n_cons_edges, E2 = d->n_cut_edges;
@@ -893,12 +907,7 @@ static int infer_run(const gcnn_dims* d, const float* params, char* A, const gcn
     return forward_impl(d, params, (const float*)(A + L.in_off[1]), (const float*)(A + L.in_off[4]), (const float*)(A + L.in_off[5]),
                         &cg, kg, (float*)(A + L.dev_off[7]), gcnn_workspace_floats(d), out, 0, nullptr, 0.f, st, &ia);
 }
-static int infer_forward(const gcnn_dims* d, const float* params, const void* host_in, char* A, const gcnn_infer_layout& L,
-                         hipStream_t st, gcnn_graph* kg, const int** flags) {
-    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));      // ONE upload: zero block + the seven arrays
-    return infer_run(d, params, A, L, st, kg, flags);
-}
-// the ranking on request, behind either half
+// the ranking on request, behind it
 static int infer_rank(const gcnn_dims* d, char* A, const gcnn_infer_layout& L, hipStream_t st) {
     float* out = (float*)(A + L.dev_off[6]);
     if (d->n_cuts > 0) {
@@ -906,26 +915,6 @@ static int infer_rank(const gcnn_dims* d, char* A, const gcnn_infer_layout& L, h
         hipLaunchKernelGGL(k_rank_scores, dim3(1), dim3(256), 0, st, out, d->n_cuts, (int*)((char*)out + L.out_off[1]));
         LAUNCHCHK();
     }
-    return 0;
-}
-
-extern "C" int gcnn_infer(const gcnn_dims* d, const float* params, const void* host_in, void* host_out, void* arena,
-                          size_t arena_bytes, int32_t want_order, void* stream) {
-    gcnn_infer_layout L;
-    int rc = gcnn_infer_layout_for(d, &L);
-    if (rc) return rc;
-    if (!params || !host_in || !host_out || !arena || arena_bytes < L.arena_bytes || ((uintptr_t)arena & 255)) return GCNN_E_BADARG;
-    if (want_order && d->n_cuts > 4096) return GCNN_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    char* A = (char*)arena;
-    gcnn_graph kg;
-    const int* flags = nullptr;
-    rc = infer_forward(d, params, host_in, A, L, st, &kg, &flags);
-    if (rc) return rc;
-    float* out = (float*)(A + L.dev_off[6]);
-    if (want_order && (rc = infer_rank(d, A, L, st))) return rc;
-    HIPCHK(hipMemcpyAsync((char*)out + L.out_off[2], flags, 16, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));  // ONE download: scores | order | flags
     return 0;
 }
 

@@ -1,9 +1,10 @@
 // gcnn_ibatch.hpp -- host side of gcnn_infer_batch (include/gcnn_hip.h): 1..64 host states in one upload, one forward pass over their
-// disjoint union, one download.  Included at the end of gcnn_capi.hip (it shares that file's statics: ProfScope, forward_impl, the
-// selection's launcher), kept apart so that its launch names form their own inventory (tests/test_ibatch_build.py).
+// disjoint union, one download.  Included at the end of gcnn_capi.hip (it shares that file's statics: ProfScope, the carver,
+// by_key_stage, forward_impl; and gcnn_select.hpp's call_check, sel_args and launcher), kept apart so that its launch names form
+// their own inventory (tests/test_ibatch_build.py).
 //
-// By-variable order of the union: the by-variable stage of gcnn_graph_build -- the same stable rocprim radix sort of (variable id,
-// input position), k_seg_offsets and k_gather_edges -- on the shifted list, not a generalised k_iplan_*.  The single-state plan
+// By-variable order of the union: the by-variable stage of gcnn_graph_build (by_key_stage: a stable rocprim radix sort of (variable
+// id, input position), k_seg_offsets and k_gather_edges) on the shifted list, not a generalised k_iplan_*.  The single-state plan
 // scans its per-variable counts in one block's LDS (32,768 variables) and ranks each variable's segment quadratically (2,048
 // edges); a union of 64 states passes the first bound at BASELINE sizes, and lifting it needs a device-wide scan, i.e. what the
 // radix sort already is.  The sort is stable, so the plan equals what BipartiteGraph builds from the collated union, and it has
@@ -55,41 +56,25 @@ static int ibatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_f
     L->total = gcnn_dims{(int)t.c, (int)t.v, (int)t.k, (int)t.e1, (int)t.e2};
     L->n_forced = (int)t.f; L->n_forced_entries = (int)t.fe; L->max_cuts = t.max_cuts; L->n_states = n_states;
     const size_t S = n_states, C = t.c, V = t.v, K = t.k, E1 = t.e1, E2 = t.e2, F = t.f, FE = t.fe;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al16(bytes); return o; };
-    L->in_off[0] = take(4 * (size_t)IB_COLS * IB_TS);
-    L->in_off[1] = take(al16(16 * S) + al16(4 * (C + 1)) + al16(4 * (K + 1)));   // zero block: flags | l_ptr cons | l_ptr cut
-    L->in_off[2] = take(16 * C);
-    L->in_off[3] = take(8 * E1);
-    L->in_off[4] = take(4 * E1);
-    L->in_off[5] = take(56 * V);
-    L->in_off[6] = take(24 * K);
-    L->in_off[7] = take(8 * E2);
-    L->in_off[8] = take(4 * E2);
-    L->in_off[9] = take(4 * (F + 1));
-    L->in_off[10] = take(4 * FE);
-    L->in_off[11] = take(4 * FE);
-    L->in_bytes = off;
+    // the table; the zero block: flags | l_ptr cons | l_ptr cut; the seven arrays of gcnn_infer's upload, stacked; the forced rows
+    const size_t sizes[9] = {4 * (size_t)IB_COLS * IB_TS, al16(16 * S) + al16(4 * (C + 1)) + al16(4 * (K + 1)),
+                             16 * C, 8 * E1, 4 * E1, 56 * V, 24 * K, 8 * E2, 4 * E2};
+    Carver in{0};
+    for (int i = 0; i < 9; ++i) L->in_off[i] = in.take(sizes[i], 16);
+    forced_block(in, F, FE, &L->in_off[9]);
+    L->in_bytes = in.off;
     L->out_off[0] = 0; L->out_off[1] = al16(4 * K); L->out_off[2] = L->out_off[1] + al16(4 * K);
     L->out_off[3] = L->out_off[2] + al16(4 * S);
     L->out_bytes = L->out_off[3] + 16 * S;
-    size_t a = (off + 255) & ~(size_t)255;
-    auto dev = [&](size_t bytes) { const size_t o = a; a += (bytes + 255) & ~(size_t)255; return o; };
-    L->dev_off[0] = dev(4 * E1);            // left: union row ids of the constraint edges
-    L->dev_off[1] = dev(4 * E1);            // var, constraint edges (= by-left oth)
-    L->dev_off[2] = dev(4 * E2);            // var, cut edges
-    L->dev_off[3] = dev(4 * E1);            // iota
-    L->dev_off[4] = dev(4 * E1);            // sorted keys
-    L->dev_off[5] = dev(4 * E1);            // permutation
-    L->dev_off[6] = dev(4 * (V + 1));       // v_ptr
-    L->dev_off[7] = dev(4 * E1);            // v_oth
-    L->dev_off[8] = dev(4 * E1);            // v_coef
-    L->dev_off[9] = dev(4 * FE);            // forced columns in the union's column space
-    L->dev_off[10] = dev(sort_temp_bytes((int)E1));
-    L->dev_off[11] = dev(L->out_bytes);
-    L->dev_off[12] = dev(sizeof(float) * gcnn_workspace_floats(&L->total));
-    L->dev_off[13] = dev(mode == GCNN_IBATCH_SELECT ? select_ws_bytes((int)K, (int)F, t.max_cuts) : 0);
-    L->arena_bytes = a;
+    // left: union row ids of the constraint edges | var, constraint edges (= by-left oth) | var, cut edges | iota | sorted keys |
+    // permutation | v_ptr | v_oth | v_coef | forced columns in the union's column space | sort temp | outputs | forward workspace |
+    // selection workspace
+    const size_t blocks[14] = {4 * E1, 4 * E1, 4 * E2, 4 * E1, 4 * E1, 4 * E1, 4 * (V + 1), 4 * E1, 4 * E1, 4 * FE,
+                               sort_temp_bytes((int)E1), L->out_bytes, sizeof(float) * gcnn_workspace_floats(&L->total),
+                               mode == GCNN_IBATCH_SELECT ? select_ws_bytes((int)K, (int)F, t.max_cuts) : 0};
+    Carver dev{(in.off + 255) & ~(size_t)255};
+    for (int i = 0; i < 14; ++i) L->dev_off[i] = dev.take(blocks[i], 256);
+    L->arena_bytes = dev.off;
     return 0;
 }
 
@@ -111,8 +96,7 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
     gcnn_ibatch_layout L;
     int rc = ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, &L);
     if (rc) return rc;
-    if (!params || !host_in || !host_out || !arena || arena_bytes < L.arena_bytes || ((uintptr_t)arena & 255)) return GCNN_E_BADARG;
-    if (mode == GCNN_IBATCH_SELECT && (!finite_threshold(p_max) || !finite_threshold(p_max_ub))) return GCNN_E_BADARG;
+    if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L.arena_bytes, mode == GCNN_IBATCH_SELECT, p_max, p_max_ub))) return rc;
     layout_init();
     const gcnn_dims& T = L.total;
     {   // what the forward pass itself would refuse, before anything is enqueued
@@ -146,20 +130,9 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
     kg.l_ptr = ia.l_ptr[1]; kg.l_oth = ia.var[1]; kg.l_coef = (const float*)(A + L.in_off[8]);
     kg.v_ptr = cg.v_ptr;   // never read: conv v->k gathers by cut only and nothing is differentiated
     if (E1 > 0) {          // gcnn_graph_build's by-variable stage on the union's list
-        int* keys = (int*)(A + L.dev_off[4]);
-        int* perm = (int*)(A + L.dev_off[5]);
-        size_t sort_bytes = sort_temp_bytes(E1);
-        unsigned bits = 1;
-        while ((1ll << bits) < (long long)V + 1 && bits < 31) ++bits;
-        const int grid = std::min(cdiv(E1 + 1, 256), 4096);
         ProfScope prof("k_ib_by_variable", st);
-        HIPCHK(rocprim::radix_sort_pairs((void*)(A + L.dev_off[10]), sort_bytes, (const int*)ia.var[0], keys, (const int*)ia.iota, perm,
-                                         (unsigned)E1, 0u, bits, st));
-        hipLaunchKernelGGL(k_seg_offsets, dim3(grid), dim3(256), 0, st, (const int*)keys, E1, V, (int*)cg.v_ptr);
-        LAUNCHCHK();
-        hipLaunchKernelGGL(k_gather_edges, dim3(grid), dim3(256), 0, st, (const int*)perm, (const int*)ia.left, cg.l_coef, E1,
-                           (int*)cg.v_oth, (float*)cg.v_coef);
-        LAUNCHCHK();
+        if ((rc = by_key_stage(A + L.dev_off[10], sort_temp_bytes(E1), ia.var[0], ia.iota, (int*)(A + L.dev_off[4]), (int*)(A + L.dev_off[5]),
+                               V, E1, ia.left, cg.l_coef, (int*)cg.v_ptr, (int*)cg.v_oth, (float*)cg.v_coef, st))) return rc;
     } else {
         HIPCHK(hipMemsetAsync((void*)cg.v_ptr, 0, ((size_t)V + 1) * sizeof(int), st));
     }
@@ -175,13 +148,11 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
         LAUNCHCHK();
     }
     if (mode == GCNN_IBATCH_SELECT) {
-        SelArgs a;
-        a.q = scores; a.c_ptr = kg.l_ptr; a.c_col = kg.l_oth; a.c_val = kg.l_coef; a.c_off = table + IB_K * IB_TS;
-        a.f_ptr = (const int*)(A + L.in_off[9]); a.f_col = ia.f_col; a.f_val = (const float*)(A + L.in_off[11]);
-        a.f_off = L.n_forced > 0 ? table + IB_F * IB_TS : nullptr;
-        a.n_samples = n_states; a.total_cuts = K; a.total_forced = L.n_forced; a.max_cuts = L.max_cuts; a.n_vars = V;
-        a.words = (L.max_cuts + 63) / 64; a.p_max = p_max; a.p_max_ub = p_max_ub;
-        a.bits = (unsigned long long*)(A + L.dev_off[13]); a.order = (int*)(out + L.out_off[1]); a.n_kept = (int*)(out + L.out_off[2]);
+        SelArgs a = sel_args(scores, SelRows{kg.l_ptr, kg.l_oth, kg.l_coef, table + IB_K * IB_TS},
+                             SelRows{(const int*)(A + L.in_off[9]), ia.f_col, (const float*)(A + L.in_off[11]),
+                                     L.n_forced > 0 ? table + IB_F * IB_TS : nullptr},
+                             n_states, K, L.n_forced, L.max_cuts, V, p_max, p_max_ub, A + L.dev_off[13], (int*)(out + L.out_off[1]),
+                             (int*)(out + L.out_off[2]));
         if ((rc = launch_select(a, st))) return rc;
     }
     HIPCHK(hipMemcpyAsync(out + L.out_off[3], ia.flags, 16 * S, hipMemcpyDeviceToDevice, st));

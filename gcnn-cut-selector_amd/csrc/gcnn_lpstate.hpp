@@ -1,7 +1,7 @@
 // gcnn_lpstate.hpp -- host side of the state built from a raw LP snapshot (k_lpstate.hpp): gcnn_lp_state and the single calls
-// gcnn_lp_infer / gcnn_lp_infer_select.  Included at the end of gcnn_capi.hip (it shares that file's statics: ProfScope, the
-// single-state call's layout and its run-from-the-arena half, the selection), kept apart so that its launch names form their own
-// inventory (tests/test_lpstate_build.py).
+// gcnn_lp_infer / gcnn_lp_infer_select.  Included at the end of gcnn_capi.hip (it shares that file's statics: ProfScope, the carver,
+// the single-state call's layout and its run-from-the-arena half; and gcnn_select.hpp's call_check and infer_tail), kept apart so
+// that its launch names form their own inventory (tests/test_lpstate_build.py).
 #include "k_lpstate.hpp"
 
 static bool lp_dims_ok(const gcnn_lp_dims* d) {
@@ -20,16 +20,15 @@ static gcnn_dims lp_state_dims(const gcnn_lp_dims* d) {
 // scratch carving: row_stat | cut_stat | col_part | row_part | cut_part | cut_aux | blk_flags
 struct LpScratch { size_t row_stat, cut_stat, col_part, row_part, cut_part, cut_aux, blk_flags, bytes; };
 static LpScratch lp_scratch(const gcnn_lp_dims* d) {
-    LpScratch s; size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al16(bytes); return o; };
-    s.row_stat = take(16 * (size_t)d->n_rows);
-    s.cut_stat = take(32 * (size_t)d->n_cuts);
-    s.col_part = take(16 * (size_t)(lp_chunks(d->n_cols) + 1));
-    s.row_part = take(16 * (size_t)(lp_chunks(d->n_rows) + 1));
-    s.cut_part = take(16 * (size_t)(lp_chunks(d->n_cuts) + 1));
-    s.cut_aux = take(8 * (size_t)d->n_cuts);
-    s.blk_flags = take(4 * (size_t)(lp_chunks(d->n_cols) + lp_chunks(d->n_rows) + lp_chunks(d->n_cuts) + 1));
-    s.bytes = off;
+    LpScratch s; Carver c{0};
+    s.row_stat = c.take(16 * (size_t)d->n_rows, 16);
+    s.cut_stat = c.take(32 * (size_t)d->n_cuts, 16);
+    s.col_part = c.take(16 * (size_t)(lp_chunks(d->n_cols) + 1), 16);
+    s.row_part = c.take(16 * (size_t)(lp_chunks(d->n_rows) + 1), 16);
+    s.cut_part = c.take(16 * (size_t)(lp_chunks(d->n_cuts) + 1), 16);
+    s.cut_aux = c.take(8 * (size_t)d->n_cuts, 16);
+    s.blk_flags = c.take(4 * (size_t)(lp_chunks(d->n_cols) + lp_chunks(d->n_rows) + lp_chunks(d->n_cuts) + 1), 16);
+    s.bytes = c.off;
     return s;
 }
 
@@ -37,19 +36,17 @@ static int lp_layout(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_e
     if (!L || !lp_dims_ok(d) || (n_forced >= 0 && n_forced_entries < 0)) return GCNN_E_BADARG;
     memset(L, 0, sizeof(*L));
     const size_t R = d->n_rows, V = d->n_cols, K = d->n_cuts, NR = d->row_nnz, NK = d->cut_nnz, P = d->has_incumbent ? V : 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al16(bytes); return o; };
+    Carver in{0};
     const size_t sizes[GCNN_LP_ARRAYS] = {16, 4 * (R + 1), 4 * NR, 8 * NR, 8 * R, 8 * R, 8 * R, R,          // header, rows
                                           V, 8 * V, 8 * V, 8 * V, V, 8 * V, 8 * V, 8 * P, 8 * P,           // columns
                                           4 * (K + 1), 4 * NK, 8 * NK, 8 * K, 8 * K};                      // cuts
-    for (int i = 0; i < GCNN_LP_ARRAYS; ++i) L->snap_off[i] = take(sizes[i]);
-    L->snap_bytes = off;
+    for (int i = 0; i < GCNN_LP_ARRAYS; ++i) L->snap_off[i] = in.take(sizes[i], 16);
+    L->snap_bytes = in.off;
     L->scratch_bytes = lp_scratch(d).bytes;
     // the single call: the snapshot, then the forced rows, in ONE upload
     const bool select = n_forced >= 0;
-    const size_t F = select ? n_forced : 0, EF = select ? n_forced_entries : 0;
-    L->forced_off[0] = take(4 * (F + 1)); L->forced_off[1] = take(4 * EF); L->forced_off[2] = take(4 * EF);
-    L->in_bytes = off;
+    forced_block(in, select ? n_forced : 0, select ? n_forced_entries : 0, L->forced_off);
+    L->in_bytes = in.off;
     const gcnn_dims sd = lp_state_dims(d);
     if (sd.n_vars > IPLAN_MAX_VARS || (select && sd.n_cuts > SEL_MAX_CUTS)) return 0;      // call_supported stays 0
     int rc = infer_layout(&sd, 0, 32 + al16(4 * K), &L->state);     // behind the flags: n_kept | lp flags | cut_index
@@ -57,12 +54,11 @@ static int lp_layout(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_e
     L->out_bytes = L->state.out_bytes;
     for (int i = 0; i < 3; ++i) L->out_off[i] = L->state.out_off[i];
     L->out_off[3] = L->out_off[2] + 16; L->out_off[4] = L->out_off[2] + 32; L->out_off[5] = L->out_off[2] + 48;
-    size_t a = (L->state.arena_bytes + 255) & ~(size_t)255;
-    auto dev = [&](size_t bytes) { const size_t o = a; a += (bytes + 255) & ~(size_t)255; return o; };
-    L->ws_off = dev(select ? select_ws_bytes(sd.n_cuts, n_forced, sd.n_cuts) : 0);
-    L->lp_off = dev(L->in_bytes);
-    L->scratch_off = dev(L->scratch_bytes);
-    L->arena_bytes = a;
+    Carver dev{(L->state.arena_bytes + 255) & ~(size_t)255};
+    L->ws_off = dev.take(select ? select_ws_bytes(sd.n_cuts, n_forced, sd.n_cuts) : 0, 256);
+    L->lp_off = dev.take(L->in_bytes, 256);
+    L->scratch_off = dev.take(L->scratch_bytes, 256);
+    L->arena_bytes = dev.off;
     L->call_supported = 1;
     return 0;
 }
@@ -129,10 +125,8 @@ static int lp_call(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_ent
     gcnn_lp_layout LL;
     int rc = lp_layout(d, n_forced, n_forced_entries, &LL);
     if (rc) return rc;
-    const bool select = n_forced >= 0;
     if (!LL.call_supported || (want_order && d->n_cuts > 4096)) return GCNN_E_UNSUPPORTED;
-    if (!params || !host_in || !host_out || !arena || arena_bytes < LL.arena_bytes || ((uintptr_t)arena & 255)) return GCNN_E_BADARG;
-    if (select && (!finite_threshold(p_max) || !finite_threshold(p_max_ub))) return GCNN_E_BADARG;
+    if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, LL.arena_bytes, n_forced >= 0, p_max, p_max_ub))) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
     const gcnn_infer_layout& L = LL.state;
@@ -151,14 +145,8 @@ static int lp_call(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_ent
     gcnn_graph kg;
     const int* flags = nullptr;
     if ((rc = infer_run(&sd, params, A, L, st, &kg, &flags))) return rc;
-    if (select)
-        rc = select_in_arena(&sd, n_forced, kg, snap + LL.forced_off[0], snap + LL.forced_off[1], snap + LL.forced_off[2], out,
-                             LL.out_off[1], LL.out_off[3], A + LL.ws_off, p_max, p_max_ub, st);
-    else if (want_order) rc = infer_rank(&sd, A, L, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out + L.out_off[2], flags, 16, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(host_out, out, LL.out_bytes, hipMemcpyDeviceToHost, st));   // ONE download
-    return 0;
+    return infer_tail(&sd, L, A, kg, flags, n_forced, forced_rows(snap, LL.forced_off), A + LL.ws_off, LL.out_off[3], want_order, p_max,
+                      p_max_ub, host_out, st);   // ONE download: LL.out_bytes = L.out_bytes
 }
 
 extern "C" int gcnn_lp_infer(const gcnn_lp_dims* d, const float* params, const void* host_in, void* host_out, void* arena,

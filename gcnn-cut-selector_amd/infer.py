@@ -154,13 +154,17 @@ class _Staging:
             self.layouts[key] = lay
         return lay
 
+    @staticmethod
+    def _pin(pin, view, nbytes, floor):
+        """A pinned staging buffer and its NumPy view that hold `nbytes`: one too small is replaced by one twice that size."""
+        if pin is None or pin.numel() < nbytes:
+            pin = torch.empty(max(2 * nbytes, floor), dtype=torch.uint8).pin_memory()
+            view = pin.numpy()
+        return pin, view
+
     def _buffers(self, L):
-        if self.pin_in is None or self.pin_in.numel() < L.in_bytes:
-            self.pin_in = torch.empty(max(2 * L.in_bytes, 1 << 20), dtype=torch.uint8).pin_memory()
-            self.in_np = self.pin_in.numpy()
-        if self.pin_out is None or self.pin_out.numel() < L.out_bytes:
-            self.pin_out = torch.empty(max(2 * L.out_bytes, 1 << 16), dtype=torch.uint8).pin_memory()
-            self.out_np = self.pin_out.numpy()
+        self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, L.in_bytes, 1 << 20)
+        self.pin_out, self.out_np = self._pin(self.pin_out, self.out_np, L.out_bytes, 1 << 16)
         if self.arena is None or self.arena.numel() < L.arena_bytes:
             self.arena = None
             self.arena = torch.empty(max(2 * L.arena_bytes, 1 << 24), dtype=torch.uint8, device=self.model.device)
@@ -169,6 +173,51 @@ class _Staging:
         P = C.c_void_p
         return (P(self.model._flat.data_ptr()), P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(self.arena.data_ptr()),
                 self.arena.numel())
+
+    def _put_forced(self, offsets, arrays):
+        """Forced-row arrays (host, packed) into the upload at their byte offsets."""
+        for off, a in zip(offsets, arrays):
+            self.in_np[off:off + a.nbytes] = a.view(np.uint8)
+
+    def _enqueue_wait(self, name, head, tail, timings=None, t0=0.0, **extra):
+        """The C call `name`(*head, params and the three buffers, *tail, stream) on the model's device and its current stream, then
+        the wait for the download.  `timings` (optional dict): filled with the host-side phases in seconds -- `pack` (since `t0`),
+        `enqueue`, `wait` -- and with `extra`."""
+        t1 = time.perf_counter()
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(getattr(_lib.lib(), name)(*head, *self._pointers(), *tail, C.c_void_p(stream.cuda_stream)), name)
+            t2 = time.perf_counter()
+            stream.synchronize()
+        t3 = time.perf_counter()
+        if timings is not None:
+            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2, **extra)
+
+    def _verdict(self, flags_off):
+        """The flag policy on one state's four plan flags in the download: "bad_index" (an index out of range), "declined"
+        (anything else the specialised plan does not take) or None: the answer stands."""
+        flags = self.out_np[flags_off:flags_off + 16].view(np.int32)
+        if flags[0]:
+            return "bad_index"
+        return "declined" if flags[1] or flags[2] or flags[3] else None
+
+    def _read(self, scores_off, order_off, n_kept_off, n):
+        """(scores, order | None, n_kept | None) of a state's `n` cuts, read at the given byte offsets (None: not asked for)."""
+        out = self.out_np
+        scores = out[scores_off:scores_off + 4 * n].view(np.float32).copy().view(ScoreArray)
+        order = None if order_off is None else out[order_off:order_off + 4 * n].view(np.int32).copy()
+        n_kept = None if n_kept_off is None else int(out[n_kept_off:n_kept_off + 4].view(np.int32)[0])
+        return scores, order, n_kept
+
+    def _answer(self, flags_off, *where):
+        """One state's answer of a single call: the flag policy as exceptions (ValueError, _UseGeneralPath), then `_read(*where)`."""
+        verdict = self._verdict(flags_off)
+        if verdict == "bad_index":
+            raise ValueError(BAD_INDEX)
+        if verdict:
+            raise _UseGeneralPath()
+        return self._read(*where)
 
 
 def _solo_layout(key, n_forced=None, n_entries=None):
@@ -191,50 +240,25 @@ class _InferenceSession(_Staging):
     """Host side of gcnn_infer and gcnn_infer_select: one C call per state."""
 
     def _run(self, inputs, want_order, timings, forced=None, p_max=0.0, p_max_ub=0.0):
-        """pack -> call -> wait -> flags -> (scores, order | None, n_kept | None); with `forced` the call is gcnn_infer_select."""
+        """check -> layout -> pack -> call -> (scores, order | None, n_kept | None); with `forced` the call is gcnn_infer_select."""
         t0 = time.perf_counter()
         arrays, key = check_state(inputs)
-        # The specialised plan wants lists sorted by row, which is what get_state emits (utils.py:102-104); `pack_state` sees to it
-        if forced is None:
-            lay = self.cached(key, _solo_layout, key)
-        else:
-            n_forced, n_entries = forced[0].size - 1, forced[1].size
-            lay = self.cached(key + (n_forced, n_entries), _solo_layout, key, n_forced, n_entries)
+        fshape = () if forced is None else (forced[0].size - 1, forced[1].size)
+        lay = self.cached(key + fshape, _solo_layout, key, *fshape)
         if lay is False or (want_order and key[2] > 4096):
             raise _UseGeneralPath()
         dims, L, zero_from, zero_to, where, out_off, SL = lay
         self._buffers(L)
-        buf = self.in_np
-        buf[zero_from:zero_to] = 0      # the plan's counters and flags travel zeroed inside the upload
-        self.scratch = pack_state(buf, self.pin_in.data_ptr(), arrays, key, where, self.scratch)
-        if forced is not None:
-            for off, a in zip(SL.forced_off, forced):
-                buf[off:off + a.nbytes] = a.view(np.uint8)
-        t1 = time.perf_counter()
-        dev = self.model.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            if forced is None:
-                _lib.check(_lib.lib().gcnn_infer(C.byref(dims), *self._pointers(), int(want_order),
-                                                C.c_void_p(stream.cuda_stream)), "gcnn_infer")
-            else:
-                _lib.check(_lib.lib().gcnn_infer_select(C.byref(dims), n_forced, n_entries, *self._pointers(), float(p_max),
-                                                       float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_select")
-            t2 = time.perf_counter()
-            stream.synchronize()
-        t3 = time.perf_counter()
-        if timings is not None:
-            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2)
-        out, n = self.out_np, key[2]
-        flags = out[out_off[2]:out_off[2] + 16].view(np.int32)
-        if flags[0]:
-            raise ValueError(BAD_INDEX)
-        if flags[1] or flags[2] or flags[3]:
-            raise _UseGeneralPath()
-        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
-        order = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy() if want_order else None
-        n_kept = int(out[SL.n_kept_off:SL.n_kept_off + 4].view(np.int32)[0]) if forced is not None else None
-        return scores, order, n_kept
+        self.in_np[zero_from:zero_to] = 0      # the plan's counters and flags travel zeroed inside the upload
+        # The specialised plan wants lists sorted by row, which is what get_state emits (utils.py:102-104); `pack_state` sees to it
+        self.scratch = pack_state(self.in_np, self.pin_in.data_ptr(), arrays, key, where, self.scratch)
+        if forced is None:
+            self._enqueue_wait("gcnn_infer", (C.byref(dims),), (int(want_order),), timings, t0)
+        else:
+            self._put_forced(SL.forced_off, forced)
+            self._enqueue_wait("gcnn_infer_select", (C.byref(dims), *fshape), (float(p_max), float(p_max_ub)), timings, t0)
+        return self._answer(out_off[2], out_off[0], out_off[1] if want_order else None, SL.n_kept_off if forced is not None else None,
+                            key[2])
 
     def run(self, inputs, want_order, timings=None):
         """Scores of ONE host state (`.rankings` from the device when `want_order`).  `timings` (optional dict): filled with the
@@ -297,31 +321,17 @@ class _BatchSession(_Staging):
                 fptr, fcol, fval = forced[s]
                 o = in_off[9] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next state's first
                 buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
-                for off, a in ((in_off[10] + 4 * fe_off[s], fcol), (in_off[11] + 4 * fe_off[s], fval)):
-                    buf[off:off + a.nbytes] = a.view(np.uint8)
+                self._put_forced((in_off[10] + 4 * fe_off[s], in_off[11] + 4 * fe_off[s]), (fcol, fval))
         if forced is None:
             buf[in_off[9]:in_off[9] + 4] = 0
-        dev = self.model.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            _lib.check(_lib.lib().gcnn_infer_batch(len(checked), dims, nf, nfe, mode, *self._pointers(), float(p_max),
-                                                  float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_infer_batch")
-            stream.synchronize()
+        self._enqueue_wait("gcnn_infer_batch", (len(checked), dims, nf, nfe, mode), (float(p_max), float(p_max_ub)))
         self.calls += 1
-        out, n = self.out_np, len(checked)
-        flags = out[out_off[3]:out_off[3] + 16 * n].view(np.int32).reshape(n, 4)
-        n_kept = out[out_off[2]:out_off[2] + 4 * n].view(np.int32)
         res = []
-        for s in range(n):
-            if flags[s, 0]:
-                res.append(("bad_index",))
-            elif flags[s, 1] or flags[s, 2] or flags[s, 3]:
-                res.append(("declined",))
-            else:
-                lo, K = 4 * k_off[s], 4 * (k_off[s + 1] - k_off[s])
-                scores = out[out_off[0] + lo:out_off[0] + lo + K].view(np.float32).copy().view(ScoreArray)
-                order = out[out_off[1] + lo:out_off[1] + lo + K].view(np.int32).copy() if mode else None
-                res.append(("ok", scores, order, int(n_kept[s]) if mode == _lib.IBATCH_SELECT else None))
+        for s in range(len(checked)):
+            lo, n = 4 * k_off[s], k_off[s + 1] - k_off[s]
+            verdict = self._verdict(out_off[3] + 16 * s)
+            res.append((verdict,) if verdict else ("ok",) + self._read(
+                out_off[0] + lo, out_off[1] + lo if mode else None, out_off[2] + 4 * s if mode == _lib.IBATCH_SELECT else None, n))
         return res
 
 
@@ -346,48 +356,28 @@ class _LPSession(_Staging):
         return arrays, dims, self.cached(key, self._layout, dims, n_forced, n_entries)
 
     def run(self, snap, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0):
-        """pack -> one call -> wait -> flags -> (scores, order | None, n_kept | None, cut_index), all in STATE order."""
+        """check -> layout -> pack -> one call -> (scores, order | None, n_kept | None, cut_index), all in STATE order."""
         from . import lpstate
         t0 = time.perf_counter()
-        n_forced, n_entries = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
-        arrays, dims, (L, snap_off, forced_off, out_off) = self._checked(snap, n_forced, n_entries)
+        fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        arrays, dims, (L, snap_off, forced_off, out_off) = self._checked(snap, *fshape)
         n = dims["n_cuts"]
         if not L.call_supported or (want_order and n > 4096):
             raise _UseGeneralPath()
         d = _lib.LpDims(**dims)
         self._buffers(L)
-        buf = self.in_np
-        lpstate.pack_snapshot(buf, snap_off, arrays)
-        if forced is not None:
-            for off, a in zip(forced_off, forced):
-                buf[off:off + a.nbytes] = a.view(np.uint8)
-        t1 = time.perf_counter()
-        dev = self.model.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            if forced is None:
-                _lib.check(_lib.lib().gcnn_lp_infer(C.byref(d), *self._pointers(), int(want_order), C.c_void_p(stream.cuda_stream)),
-                           "gcnn_lp_infer")
-            else:
-                _lib.check(_lib.lib().gcnn_lp_infer_select(C.byref(d), n_forced, n_entries, *self._pointers(), float(p_max),
-                                                          float(p_max_ub), C.c_void_p(stream.cuda_stream)), "gcnn_lp_infer_select")
-            t2 = time.perf_counter()
-            stream.synchronize()
-        t3 = time.perf_counter()
-        if timings is not None:
-            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2, upload_bytes=int(L.in_bytes))
+        lpstate.pack_snapshot(self.in_np, snap_off, arrays)
+        if forced is None:
+            self._enqueue_wait("gcnn_lp_infer", (C.byref(d),), (int(want_order),), timings, t0, upload_bytes=int(L.in_bytes))
+        else:
+            self._put_forced(forced_off, forced)
+            self._enqueue_wait("gcnn_lp_infer_select", (C.byref(d), *fshape), (float(p_max), float(p_max_ub)), timings, t0,
+                               upload_bytes=int(L.in_bytes))
         self.last = (L, lpstate.state_key(dims))
         out = self.out_np
         lpstate.raise_for_flags(out[out_off[4]:out_off[4] + 16].view(np.int32))
-        flags = out[out_off[2]:out_off[2] + 16].view(np.int32)
-        if flags[0]:
-            raise ValueError(BAD_INDEX)
-        if flags[1] or flags[2] or flags[3]:
-            raise _UseGeneralPath()
-        scores = out[out_off[0]:out_off[0] + 4 * n].view(np.float32).copy().view(ScoreArray)
-        order = out[out_off[1]:out_off[1] + 4 * n].view(np.int32).copy() if want_order else None
-        n_kept = int(out[out_off[3]:out_off[3] + 4].view(np.int32)[0]) if forced is not None else None
-        return scores, order, n_kept, out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
+        answer = self._answer(out_off[2], out_off[0], out_off[1] if want_order else None, out_off[3] if forced is not None else None, n)
+        return answer + (out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy(),)
 
     def last_state(self):
         """The seven arrays the last single call built in the arena, as host arrays (tests compare them with gcnn_lp_state's)."""
@@ -406,9 +396,7 @@ class _LPSession(_Staging):
         from . import lpstate
         arrays, dims, (L, snap_off, _, _) = self._checked(snap)
         d = _lib.LpDims(**dims)
-        if self.pin_in is None or self.pin_in.numel() < L.snap_bytes:
-            self.pin_in = torch.empty(max(2 * L.snap_bytes, 1 << 20), dtype=torch.uint8).pin_memory()
-            self.in_np = self.pin_in.numpy()
+        self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, L.snap_bytes, 1 << 20)
         lpstate.pack_snapshot(self.in_np, snap_off, arrays)
         dev = self.model.device
         c, v, k, e1, e2 = lpstate.state_key(dims)

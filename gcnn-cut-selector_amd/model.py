@@ -445,6 +445,32 @@ class GCNN:
     # ~2 us; the device ranking kernel costs a launch plus a dependent kernel in the chain: ~10 us end to end, tools/latency.py)
     HOST_RANK_MAX = 1024
 
+    def _sess(self, attr, cls):
+        """The session kept in attribute `attr` (pinned staging + device arena), created on first use."""
+        if getattr(self, attr) is None:
+            setattr(self, attr, cls(self))
+        return getattr(self, attr)
+
+    def _rank_on_device(self, rank, n_cuts):
+        return bool(rank) and (rank == "device" or n_cuts > self.HOST_RANK_MAX)
+
+    @staticmethod
+    def _check_select_size(entry, noun, n_cuts):
+        if n_cuts > ops.SELECT_MAX_CUTS:
+            raise _lib.GcnnError(f"{entry}: the {noun} has {n_cuts} cuts; the device selection handles at most "
+                                 f"{ops.SELECT_MAX_CUTS} and there is no CPU fallback")
+
+    def _select_general(self, state, packed, p_max, p_max_ub, n_cuts):
+        """The selection on the general path -- prepare + forward + gcnn_select_cuts -- for a state the single calls decline, device
+        tensors and prepared `Batch`es: (scores, order, n_kept) as host values.  `packed`: the forced rows (normalize_forced)."""
+        with torch.no_grad():
+            batch = self.prepare(state)
+            scores_dev = self.call(batch, False).as_subclass(torch.Tensor)
+            forced_dev = tuple(torch.from_numpy(a).to(self.device) for a in packed)
+            order, n_kept = ops.select_cuts(scores_dev, batch.cut_graph, None, forced_dev, p_max=p_max, p_max_ub=p_max_ub,
+                                            max_cuts=n_cuts)
+            return scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0])
+
     def score_state(self, inputs, rank=False):
         """Scores of ONE sampled state given as host arrays (the SCIP plugins' call, model_evaluator.py:84-111), through the
         single-call path gcnn_infer: one upload, a three-launch graph plan, the inference forward pass, one download.
@@ -452,12 +478,9 @@ class GCNN:
         score order (ties in index order): computed by the device ranking kernel for more than HOST_RANK_MAX cuts or with
         `rank="device"`, else by a stable argsort on the host (faster for a few dozen cuts).  States the specialised plan declines (edge lists not sorted by row, more than
         32,768 variables, ...) run through `prepare` + the general forward pass instead; results are identical."""
-        if self._session is None:
-            self._session = _InferenceSession(self)
-        n_cuts = int(np.asarray(inputs[4]).shape[0])
-        on_device = bool(rank) and (rank == "device" or n_cuts > self.HOST_RANK_MAX)
+        on_device = self._rank_on_device(rank, int(np.asarray(inputs[4]).shape[0]))
         try:
-            scores = self._session.run(inputs, on_device)
+            scores = self._sess("_session", _InferenceSession).run(inputs, on_device)
         except _UseGeneralPath:
             on_device = False
             with torch.no_grad():
@@ -473,37 +496,22 @@ class GCNN:
         Host arrays take the single call gcnn_infer_select (one upload, one download); states it declines, device tensors and
         prepared `Batch`es take prepare + forward + gcnn_select_cuts.  Both give the same bits.  Returns a `SelectResult`."""
         ops.check_thresholds(p_max, p_max_ub)
-        host = is_host_state(state)
         n_cuts = state.dims.n_cuts if isinstance(state, Batch) else int(state[4].shape[0])
         n_vars = state.dims.n_vars if isinstance(state, Batch) else int(state[3].shape[0])
-        if n_cuts > ops.SELECT_MAX_CUTS:
-            raise _lib.GcnnError(f"select_cuts: the state has {n_cuts} cuts; the device selection handles at most "
-                                 f"{ops.SELECT_MAX_CUTS} and there is no CPU fallback")
+        self._check_select_size("select_cuts", "state", n_cuts)
         packed = normalize_forced(forced, n_vars)
         result = None
-        if host:
-            if self._session is None:
-                self._session = _InferenceSession(self)
+        if is_host_state(state):
             try:
-                result = self._session.run_select(state, packed, p_max, p_max_ub)
+                result = self._sess("_session", _InferenceSession).run_select(state, packed, p_max, p_max_ub)
             except _UseGeneralPath:
                 pass
-        if result is None:
-            with torch.no_grad():
-                batch = self.prepare(state)
-                scores_dev = self.call(batch, False).as_subclass(torch.Tensor)
-                forced_dev = tuple(torch.from_numpy(a).to(self.device) for a in packed)
-                order, n_kept = ops.select_cuts(scores_dev, batch.cut_graph, None, forced_dev, p_max=p_max,
-                                                p_max_ub=p_max_ub, max_cuts=n_cuts)
-                result = (scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0]))
-        scores, order, n_kept = result
+        scores, order, n_kept = result or self._select_general(state, packed, p_max, p_max_ub, n_cuts)
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
 
     # ---- from a raw LP snapshot (lpstate.LPSnapshot): get_state's arithmetic on the device, in front of the same calls ---------
     def _lp(self):
-        if self._lp_session is None:
-            self._lp_session = _LPSession(self)
-        return self._lp_session
+        return self._sess("_lp_session", _LPSession)
 
     def state_from_lp(self, snapshot):
         """The model's 10-tuple as host arrays, built on the device from an `LPSnapshot` (gcnn_lp_state: utils.get_state's
@@ -518,8 +526,7 @@ class GCNN:
         `.cut_index[p]` is the input cut at state position p, `.rankings` (with `rank`) as `score_state` gives them.  A snapshot
         past gcnn_infer's limits, or one whose state the specialised plan declines, is built with gcnn_lp_state and goes through
         `prepare` + the general forward pass as device tensors; the bits are the same."""
-        n_cuts = int(np.asarray(snapshot.cut_lhs).shape[0])
-        on_device = bool(rank) and (rank == "device" or n_cuts > self.HOST_RANK_MAX)
+        on_device = self._rank_on_device(rank, int(np.asarray(snapshot.cut_lhs).shape[0]))
         try:
             scores, order, _, cut_index = self._lp().run(snapshot, on_device)
         except _UseGeneralPath:
@@ -538,21 +545,13 @@ class GCNN:
         `order` is in STATE order and it carries `cut_index`: `cut_index[order[:n_selected]]` are the selected input cuts."""
         ops.check_thresholds(p_max, p_max_ub)
         n_cuts, n_vars = int(np.asarray(snapshot.cut_lhs).shape[0]), int(np.asarray(snapshot.col_type).shape[0])
-        if n_cuts > ops.SELECT_MAX_CUTS:
-            raise _lib.GcnnError(f"select_cuts_lp: the snapshot has {n_cuts} cuts; the device selection handles at most "
-                                 f"{ops.SELECT_MAX_CUTS} and there is no CPU fallback")
+        self._check_select_size("select_cuts_lp", "snapshot", n_cuts)
         packed = normalize_forced(forced, n_vars)
         try:
             scores, order, n_kept, cut_index = self._lp().run(snapshot, True, None, packed, p_max, p_max_ub)
         except _UseGeneralPath:
             state, cut_index = self._lp().build_state(snapshot)
-            with torch.no_grad():
-                batch = self.prepare(state)
-                scores_dev = self.call(batch, False).as_subclass(torch.Tensor)
-                forced_dev = tuple(torch.from_numpy(a).to(self.device) for a in packed)
-                order, n_kept = ops.select_cuts(scores_dev, batch.cut_graph, None, forced_dev, p_max=p_max, p_max_ub=p_max_ub,
-                                                max_cuts=n_cuts)
-            scores, order, n_kept = scores_dev.cpu().numpy().view(ScoreArray), order.cpu().numpy(), int(n_kept.cpu()[0])
+            scores, order, n_kept = self._select_general(state, packed, p_max, p_max_ub, n_cuts)
             cut_index = cut_index.cpu().numpy()
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
@@ -582,13 +581,11 @@ class GCNN:
             else:
                 checked[i] = (arrays, key)
                 batch_ids.append(i)
-        if self._batch_session is None:
-            self._batch_session = _BatchSession(self)
+        session = self._sess("_batch_session", _BatchSession)
         todo = [batch_ids[j:j + _BatchSession.MAX] for j in range(0, len(batch_ids), _BatchSession.MAX)]
         while todo:
             ids = todo.pop(0)
-            got = self._batch_session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode,
-                                          p_max, p_max_ub)
+            got = session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode, p_max, p_max_ub)
             if got is None:                     # the union is past the library's limits: halves, and a single state goes solo
                 if len(ids) == 1:
                     solo_ids.append(ids[0])
