@@ -1,0 +1,99 @@
+"""The library's device code, cross-compiled once (helper for the *_build tests and test_kernel_resources.py): hipcc compiles
+gcnn_capi.hip to gfx950 assembly and reports registers, occupancy, LDS and scratch per function with
+-Rpass-analysis=kernel-resource-usage.  `device_build()` runs that compile once per Python process -- pytest imports this module
+once per session, so every module that asks shares it -- and remembers a failure as well as a success.  Also the check that a
+set of entry points is declared in the header, bound, exported and at ABI 13."""
+from __future__ import annotations
+
+import atexit
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc")
+HEADER = os.path.join(ROOT, "include", "gcnn_hip.h")
+HIPCC = "/opt/rocm/bin/hipcc"
+
+_PATTERNS = (("vgpr", r" VGPRs: (\d+)"), ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
+             ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"))   # " VGPRs" with its space: "AGPRs: " must not match
+
+
+def parse_resource_usage(stderr_text: str) -> dict[str, dict[str, int]]:
+    """Mangled function name -> {vgpr, occ, lds, scratch} from the compiler's kernel-resource-usage remarks."""
+    rows, cur = {}, None
+    for line in stderr_text.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = rows.setdefault(m.group(1), {})
+        for key, pat in _PATTERNS:
+            m = re.search(pat, line)
+            if m and cur is not None:
+                cur[key] = int(m.group(1))
+    return rows
+
+
+class DeviceBuild:
+    def __init__(self, rows: dict[str, dict[str, int]], asm: str):
+        self.rows, self.asm = rows, asm
+
+    def demangled(self) -> dict[str, dict[str, int]]:
+        """`rows` of the kernels (k_*), keyed by their demangled names where c++filt is there to give them."""
+        rows = self.rows
+        filt = shutil.which("c++filt")
+        names = list(rows)
+        if filt:
+            dem = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+            rows = {d: rows[n] for n, d in zip(names, dem)}
+        return {k: v for k, v in rows.items() if re.search(r"\bk_[a-z_0-9]+", k)}
+
+    def body(self, symbol: str) -> str:
+        """The function's instructions: from its label to the first end of program after it."""
+        body = self.asm[self.asm.index(f"{symbol}:"):]
+        return body[:body.index("s_endpgm")]
+
+    def wavefront_size(self, symbol: str) -> int:
+        meta = self.asm[self.asm.index(f".name:           {symbol}\n"):]
+        return int(re.search(r"\.wavefront_size:\s+(\d+)", meta).group(1))
+
+
+def _run_hipcc(out: str) -> subprocess.CompletedProcess:
+    return subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", out,
+                           os.path.join(CSRC, "gcnn_capi.hip"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True,
+                          text=True, timeout=600)
+
+
+_result = None   # a DeviceBuild, or the text every caller of a failed compile fails with
+
+
+def device_build() -> DeviceBuild:
+    global _result
+    if not os.path.exists(HIPCC):
+        pytest.skip(f"the cross-compiler {HIPCC} is not installed: the gfx950 resource check cannot run here")
+    if _result is None:
+        tmp = tempfile.mkdtemp(prefix="gcnn_device_build_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        out = os.path.join(tmp, "k.s")
+        try:
+            p = _run_hipcc(out)
+            _result = DeviceBuild(parse_resource_usage(p.stderr), open(out).read()) if p.returncode == 0 else p.stderr[-2000:]
+        except subprocess.TimeoutExpired as e:
+            _result = f"{e}"
+    assert isinstance(_result, DeviceBuild), _result
+    return _result
+
+
+def declared_everywhere(symbols) -> str:
+    """Every symbol is declared in the header, has a signature in the binding and is exported by the built library, and both
+    sides are at ABI 13.  Returns the header's text for the caller's own checks of it."""
+    from gcnn_cut_selector_amd import _lib
+    header = open(HEADER).read()
+    lib = _lib.lib()
+    for sym in symbols:
+        assert re.search(rf"\b{sym}\s*\(", header) and sym in _lib.SIGNATURES and hasattr(lib, sym)
+    assert _lib.ABI_VERSION == 13 and lib.gcnn_abi_version() == 13
+    return header

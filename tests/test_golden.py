@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpucommon import dev
 from oracle import gcnn_oracle as O
 
 STATE_KEYS = ["cons_feats", "cons_edge_inds", "cons_edge_feats", "var_feats", "cut_feats", "cut_edge_inds", "cut_edge_feats"]
@@ -59,12 +60,6 @@ def test_oracle_reproduces_golden_pretrain(golden_dir):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
 @pytest.mark.gpu
 def test_hip_reproduces_golden_step(dev, golden_dir):
     """Scores within 1e-4 (BASELINE.json north star); loss, all 46 gradients and two fused Keras-Adam steps."""

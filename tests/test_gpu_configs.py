@@ -17,27 +17,17 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
-from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
 
-from test_gpu_model import _grad_check, _model  # noqa: E402
+from test_gpu_model import _grad_check  # noqa: E402
+from gpucommon import dev, make_model, oracle_scores as _oracle_scores  # noqa: E402
 
 FULL = [("setcov", 32), ("combauc", 32), ("capfac", 32), ("indset", 64)]   # BASELINE.json configs[1..4]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _oracle_scores(params, state):
-    return O.scores({k: v.astype(np.float64) for k, v in params.items()}, state, torch.float64)
 
 
 @pytest.mark.parametrize("problem,batch", [("setcov", 4), ("combauc", 8), ("capfac", 2), ("indset", 4)])
 def test_inference_kernels_match_oracle(dev, problem, batch):
     """The no-grad path (what the SCIP plugin and validation run) vs the oracle -- not only vs the saving path."""
-    m, params = _model(50, dev)
+    m, params = make_model(50, dev)
     state, _, _ = synthetic.make_batch(problem, batch)
     with torch.no_grad():
         got = m(state, False).numpy()
@@ -51,7 +41,7 @@ def test_inference_kernels_match_oracle(dev, problem, batch):
 
 @pytest.mark.parametrize("problem,batch", FULL)
 def test_full_batch_forward_matches_oracle(dev, problem, batch):
-    m, params = _model(51, dev)
+    m, params = make_model(51, dev)
     state, _, _ = synthetic.make_batch(problem, batch)
     with torch.no_grad():
         got = m(state, False).numpy()
@@ -61,7 +51,7 @@ def test_full_batch_forward_matches_oracle(dev, problem, batch):
 @pytest.mark.parametrize("batch", [2, 8])
 def test_capfac_real_size_forward_backward(dev, batch):
     """capfac 100x100 instances (BASELINE configs[3]); batch 8 = 81,608 + 80,800 rows: rows_per_wave = 256 in k_wgrad."""
-    m, params = _model(52, dev)
+    m, params = make_model(52, dev)
     state, y, _ = synthetic.make_batch("capfac", batch)
     assert state[0].shape[0] == 10201 * batch and state[1].shape[1] == 40200 * batch
     got = m(state, True).numpy()
@@ -71,7 +61,7 @@ def test_capfac_real_size_forward_backward(dev, batch):
 
 @pytest.mark.parametrize("problem,batch", [("indset", 8), ("combauc", 32)])
 def test_backward_parity_larger_batches(dev, problem, batch):
-    m, params = _model(53, dev)
+    m, params = make_model(53, dev)
     state, y, _ = synthetic.make_batch(problem, batch)
     _grad_check(m, params, state, y)
 
@@ -80,7 +70,7 @@ def test_backward_parity_larger_batches(dev, problem, batch):
 def test_full_batch_backward_matches_oracle(dev, problem, batch):
     """Loss and all 46 gradients at the BASELINE batch sizes against the fp64 autograd oracle (10-20 GB of host memory for
     the [E,64] tensors the reference dataflow materialises; seconds on the GPU box's host cores)."""
-    m, params = _model(55, dev)
+    m, params = make_model(55, dev)
     state, y, _ = synthetic.make_batch(problem, batch)
     _grad_check(m, params, state, y)
 
@@ -101,7 +91,7 @@ def _sum_loss_grads(m, batch, y):
 @pytest.mark.parametrize("problem,batch", FULL[1:])     # setcov x 32: tests/test_gpu_train.py
 def test_full_batch_properties(dev, problem, batch):
     from gcnn_cut_selector_amd.trainer import TrainState, train_step
-    m, _ = _model(54, dev)
+    m, _ = make_model(54, dev)
     samples = [synthetic.make_sample(problem, i) for i in range(batch)]
     full = synthetic.stack_samples(samples)
     totals = lambda b: (int(b[7].sum()), int(b[8].sum()), int(b[9].sum()))

@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
 import gradparity  # noqa: E402
 import launchnames  # noqa: E402
+from gpucommon import make_model  # noqa: E402
 
 LONG = "k_edge_fwd<count> + long segments"
 
@@ -113,10 +114,9 @@ def results():
     launch names (PreNorm statistics with the two-layer forward, the stand-alone MSE and Adam, a fused Adam step)."""
     from gcnn_cut_selector_amd import _lib
     from gcnn_cut_selector_amd.trainer import Adam, TrainState, mse_loss, train_step
-    from test_gpu_model import _model
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     dev = torch.device("cuda", 0)
-    m, params = _model(11, dev)
+    m, params = make_model(11, dev)
     out, seen = {}, set()
     for cid in CASES:
         state, y = make_state(cid)
@@ -156,7 +156,7 @@ def results():
             seen.update(r[k])
         out[cid] = (state, y, r)
     # the rest of the library's launches, on the smallest case of the list above
-    m2, _ = _model(12, dev)
+    m2, _ = make_model(12, dev)
     state, y = make_state("vdeg/256")
     yt = torch.as_tensor(y, dtype=torch.float32).to(dev)
     with _lib.launch_profile() as p:

@@ -9,21 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
-from oracle import gcnn_oracle as O  # noqa: E402  (initial weights only)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _model(seed, dev):
-    from gcnn_cut_selector_amd.model import GCNN
-    params = O.randomize_params(O.init_params(seed, np.float32), seed + 1)
-    m = GCNN(device=dev)
-    m.set_weights([params[n] for n in O.PARAM_NAMES])
-    return m
+from gpucommon import dev, make_model  # noqa: E402
 
 
 def _strip_cuts(state):
@@ -43,7 +29,7 @@ def _member(spec, i, dev):
     else:
         prob, bs, first, scale, lr = spec
         state, y, _ = synthetic.make_batch(prob, bs, first, scale)
-    solo, grp = _model(40 + i, dev), _model(40 + i, dev)
+    solo, grp = make_model(40 + i, dev)[0], make_model(40 + i, dev)[0]
     batch = solo.prepare(state)
     return solo, grp, batch, torch.as_tensor(np.asarray(y, np.float32)).to(dev), lr
 
@@ -100,7 +86,7 @@ def test_degenerate_members_beside_regular_ones(dev):
 def test_forward_group_equals_model_call_on_a_shared_batch(dev):
     from gcnn_cut_selector_amd.trainer import forward_group
     state, _, _ = synthetic.make_batch("capfac", 4, 0)
-    models = [_model(60 + i, dev) for i in range(5)]
+    models = [make_model(60 + i, dev)[0] for i in range(5)]
     batch = models[0].prepare(state)
     with torch.no_grad():
         want = [m(batch) for m in models]
@@ -159,7 +145,7 @@ def test_refusals(dev):
     from gcnn_cut_selector_amd import _lib
     from gcnn_cut_selector_amd.trainer import Adam, TrainState, forward_group, train_step_group
     state, y, _ = synthetic.make_batch("setcov", 2, 0, 0.2)
-    models = [_model(80 + i, dev) for i in range(9)]
+    models = [make_model(80 + i, dev)[0] for i in range(9)]
     batch = models[0].prepare(state)
     yt = torch.as_tensor(y).to(dev)
     with pytest.raises(ValueError):
@@ -215,8 +201,8 @@ def test_process_many_equals_process_per_model(dev):
     stores = [_store("setcov", 9, 0, dev), _store("indset", 7, 0, dev), _store("setcov", 5, 20, dev)]
     ids = [np.arange(len(s))[::-1] for s in stores]
     for train in (True, False):
-        solo = [_model(90 + i, dev) for i in range(3)]
-        grp = [_model(90 + i, dev) for i in range(3)]
+        solo = [make_model(90 + i, dev)[0] for i in range(3)]
+        grp = [make_model(90 + i, dev)[0] for i in range(3)]
         opts_s = [Adam(1e-3 * (i + 1)) for i in range(3)] if train else [None] * 3
         opts_g = [Adam(1e-3 * (i + 1)) for i in range(3)] if train else None
         want = [process(m, s.batches(i, 2), fractions, None, o) for m, s, i, o in zip(solo, stores, ids, opts_s)]
@@ -233,13 +219,13 @@ def test_train_models_members_match_solo_runs(dev, tmp_path):
     valid = _store("setcov", 4, 50, dev, 0.2)
     kw = dict(max_epochs=8, epoch_size=2, batch_size=2, pretrain_batch_size=2, valid_batch_size=2, lr=0.02, patience=1,
               early_stopping=2)
-    models = [_model(100 + i, dev) for i in range(3)]
+    models = [make_model(100 + i, dev)[0] for i in range(3)]
     paths = [str(tmp_path / f"group{i}.pkl") for i in range(3)]
     hist = train_models(models, seeds, [train] * 3, [valid] * 3, paths, **kw)
     stopped = [h["stopped_epoch"] for h in hist]
     assert any(s is not None and s < kw["max_epochs"] for s in stopped), stopped
     for i, seed in enumerate(seeds):
-        solo = _model(100 + i, dev)
+        solo = make_model(100 + i, dev)[0]
         path = str(tmp_path / f"solo{i}.pkl")
         (h,) = train_models([solo], [seed], [train], [valid], [path], **kw)
         for key in ("train_loss", "valid_loss", "lr_changes", "best_epoch", "stopped_epoch", "pretrained_layers",

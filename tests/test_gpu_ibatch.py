@@ -13,23 +13,12 @@ import cutsel_restate as R  # noqa: E402
 from gcnn_cut_selector_amd import _lib, ops, synthetic, utils  # noqa: E402
 from gcnn_cut_selector_amd.graph import BipartiteGraph  # noqa: E402
 from gcnn_cut_selector_amd.model import SelectResult  # noqa: E402
-from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
 
-from test_gpu_model import _model  # noqa: E402
+from gpucommon import dev, make_model, oracle_scores as _oracle  # noqa: E402
 
 PROBLEMS = ("setcov", "combauc", "capfac", "indset")
 SCALES = (0.2, 1.0, 0.5)
 f32, i32 = np.float32, np.int32
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _oracle(params, inp):
-    return O.scores({k: v.astype(np.float64) for k, v in params.items()}, inp, torch.float64)
 
 
 def _mixed(S, first=0):
@@ -107,7 +96,7 @@ def _dense(inp):
 
 @pytest.mark.parametrize("S", [1, 2, 3, 8, 17, 64])
 def test_same_bits_as_the_general_path_and_fp64(dev, S):
-    m, params = _model(90 + S, dev)
+    m, params = make_model(90 + S, dev)
     inputs = _mixed(S, first=S)
     with _Spy(m) as spy:
         scored = m.score_states(inputs, rank=True)
@@ -138,7 +127,7 @@ def test_same_bits_as_the_general_path_and_fp64(dev, S):
 
 
 def test_it_really_took_the_new_path(dev):
-    m, _ = _model(95, dev)
+    m, _ = make_model(95, dev)
     inputs = _mixed(5, first=40)
     m.score_states(inputs)                                                 # buffers and layouts exist
     for call, extra in ((lambda: m.score_states(inputs), set()), (lambda: m.score_states(inputs, rank=True), {"k_ib_rank"}),
@@ -177,7 +166,7 @@ def _bad_states(rng):
 
 
 def test_isolation(dev):
-    m, params = _model(96, dev)
+    m, params = make_model(96, dev)
     rng = np.random.default_rng(7)
     bad_index, unsorted, huge, hub = _bad_states(rng)
     clean = _mixed(3, first=50)
@@ -229,7 +218,7 @@ def _forced_like_cuts(rng, inp, F):
 
 @pytest.mark.parametrize("p_max,p_max_ub", [(0.1, 0.5), (0.0, 0.0), (2.0, 2.0)])
 def test_forced_rows_per_state(dev, p_max, p_max_ub):
-    m, _ = _model(97, dev)
+    m, _ = make_model(97, dev)
     rng = np.random.default_rng(11)
     inputs = _mixed(6, first=60)
     counts = (0, 1, 40, 0, 3, 40)

@@ -8,24 +8,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic, utils  # noqa: E402
-from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
 
-from test_gpu_model import _model  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _oracle(params, inp):
-    return O.scores({k: v.astype(np.float64) for k, v in params.items()}, inp, torch.float64)
+from gpucommon import dev, make_model, oracle_scores as _oracle  # noqa: E402
 
 
 @pytest.mark.parametrize("problem", ["setcov", "combauc", "capfac", "indset"])
 def test_concrete_function_matches_oracle_and_general_path(dev, problem):
-    m, params = _model(80, dev)
+    m, params = make_model(80, dev)
     f = m.get_concrete_function()
     for i in (3, 4):
         state, _ = synthetic.make_sample(problem, i)
@@ -50,7 +39,7 @@ def test_concrete_function_matches_oracle_and_general_path(dev, problem):
 def test_concrete_function_on_unsorted_coo(dev, problem):
     """Edge lists in arbitrary order: sorted by row on the host while packing (stable), then the specialised plan -- same scores as
     the sorted state up to the order of the by-variable sums, and no detour through the general path."""
-    m, params = _model(81, dev)
+    m, params = make_model(81, dev)
     f = m.get_concrete_function()
     state, _ = synthetic.make_sample(problem, 5)
     inp = utils.state_to_inputs(state)
@@ -68,7 +57,7 @@ def test_concrete_function_on_unsorted_coo(dev, problem):
 
 
 def test_score_state_edge_cases(dev):
-    m, params = _model(82, dev)
+    m, params = make_model(82, dev)
     rng = np.random.default_rng(2)
     f32, i32 = np.float32, np.int32
     z2 = np.zeros((2, 0), i32)

@@ -13,7 +13,7 @@ import lpstate_restate as R  # noqa: E402
 from gcnn_cut_selector_amd import _lib, lpstate, synthetic  # noqa: E402
 from gcnn_cut_selector_amd.infer import _LPSession, _UseGeneralPath  # noqa: E402
 
-from test_gpu_model import _model  # noqa: E402
+from gpucommon import dev, make_model  # noqa: E402
 from test_lpstate_build import LP_NAMES  # noqa: E402
 
 CASES = [(p, dict()) for p in synthetic.PROBLEMS] + [
@@ -27,14 +27,8 @@ CASES = [(p, dict()) for p in synthetic.PROBLEMS] + [
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
 def model(dev):
-    return _model(91, dev)[0]
+    return make_model(91, dev)[0]
 
 
 def _same(a, b):

@@ -10,20 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _model(seed, dev):
-    from gcnn_cut_selector_amd.model import GCNN
-    params = O.randomize_params(O.init_params(seed, np.float32), seed + 1)
-    m = GCNN(device=dev)
-    m.set_weights([params[n] for n in O.PARAM_NAMES])
-    return m, params
+from gpucommon import dev, make_model  # noqa: E402
 
 
 def _check_scores(m, params, state, atol=1e-4):
@@ -42,7 +29,7 @@ def test_variable_spec_matches_oracle():
 @pytest.mark.parametrize("problem,batch,scale", [("setcov", 2, 0.1), ("setcov", 4, 1.0), ("combauc", 8, 1.0),
                                                  ("capfac", 2, 0.2), ("indset", 4, 1.0)])
 def test_forward_parity(dev, problem, batch, scale):
-    m, params = _model(1, dev)
+    m, params = make_model(1, dev)
     state, _, _ = synthetic.make_batch(problem, batch, scale=scale)
     _check_scores(m, params, state)
 
@@ -75,7 +62,7 @@ def test_forward_known_answer_single_edge(dev):
 
 
 def test_isolated_nodes_and_unsorted_edges(dev):
-    m, params = _model(2, dev)
+    m, params = make_model(2, dev)
     rng = np.random.default_rng(0)
     C, V, K = 37, 45, 9
     cei = np.stack([rng.integers(0, C - 5, 300), rng.integers(0, V - 7, 300)])   # last rows/cols isolated
@@ -86,7 +73,7 @@ def test_isolated_nodes_and_unsorted_edges(dev):
 
 
 def test_empty_cases(dev):
-    m, params = _model(3, dev)
+    m, params = make_model(3, dev)
     rng = np.random.default_rng(1)
     z2 = np.zeros((2, 0), np.int32)
     # no cuts at all -> empty score vector
@@ -100,7 +87,7 @@ def test_empty_cases(dev):
 
 
 def test_input_validation(dev):
-    m, _ = _model(3, dev)
+    m, _ = make_model(3, dev)
     state, _, _ = synthetic.make_batch("setcov", 1, scale=0.1)
     bad = list(state); bad[0] = bad[0][:, :3]
     with pytest.raises(ValueError):
@@ -115,7 +102,7 @@ def test_input_validation(dev):
 
 def test_batching_invariance(dev):
     """SURVEY section 4 invariant 1 on the HIP path."""
-    m, _ = _model(4, dev)
+    m, _ = make_model(4, dev)
     samples = [synthetic.make_sample("setcov", i, scale=0.2) for i in range(3)]
     full = synthetic.stack_samples(samples)
     batched = m(full[:7] + (int(full[7].sum()), int(full[8].sum()), int(full[9].sum())), False).numpy()
@@ -127,7 +114,7 @@ def test_batching_invariance(dev):
 
 
 def test_edge_order_invariance(dev):
-    m, _ = _model(5, dev)
+    m, _ = make_model(5, dev)
     state, _, _ = synthetic.make_batch("combauc", 2)
     rng = np.random.default_rng(0)
     p1, p2 = rng.permutation(state[1].shape[1]), rng.permutation(state[5].shape[1])
@@ -136,7 +123,7 @@ def test_edge_order_invariance(dev):
 
 
 def test_forward_is_deterministic_and_training_flag_inert(dev):
-    m, _ = _model(6, dev)
+    m, _ = make_model(6, dev)
     state, _, _ = synthetic.make_batch("indset", 2)
     a, b = m(state, False).numpy(), m(state, True).numpy()
     assert np.array_equal(a, b)
@@ -174,13 +161,13 @@ def _grad_check(m, params, state, y, rtol=1e-4):
 @pytest.mark.parametrize("problem,batch,scale", [("setcov", 2, 0.1), ("setcov", 3, 1.0), ("combauc", 4, 1.0),
                                                  ("capfac", 2, 0.2), ("indset", 3, 1.0)])
 def test_backward_parity(dev, problem, batch, scale):
-    m, params = _model(7, dev)
+    m, params = make_model(7, dev)
     state, y, _ = synthetic.make_batch(problem, batch, scale=scale)
     _grad_check(m, params, state, y)
 
 
 def test_backward_isolated_and_unsorted(dev):
-    m, params = _model(8, dev)
+    m, params = make_model(8, dev)
     rng = np.random.default_rng(3)
     C, V, K = 37, 45, 9
     cei = np.stack([rng.integers(0, C - 5, 300), rng.integers(0, V - 7, 300)])
@@ -196,7 +183,7 @@ def test_two_layer_form_for_prenorm_fitting_agrees_with_the_folded_form(dev):
     Same function: scores agree to rounding, and A equals S Wf + deg bf of the oracle."""
     import ctypes as C
     from gcnn_cut_selector_amd import _lib
-    m, params = _model(13, dev)
+    m, params = make_model(13, dev)
     state, _, _ = synthetic.make_batch("combauc", 3)
     batch = m.prepare(state)
     flat = m.flat_parameters.detach()
@@ -211,7 +198,7 @@ def test_two_layer_form_for_prenorm_fitting_agrees_with_the_folded_form(dev):
 
 def test_save_restore_roundtrip(dev, tmp_path):
     from gcnn_cut_selector_amd.model import GCNN
-    m, _ = _model(9, dev)
+    m, _ = make_model(9, dev)
     path = str(tmp_path / "best_params.pkl")
     m.save_state(path)
     m2 = GCNN(device=dev)

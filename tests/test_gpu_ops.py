@@ -6,13 +6,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from gpucommon import dev  # noqa: E402
+
 RTOL, ATOL = 3e-5, 3e-5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _close(a, b, rtol=RTOL, atol=ATOL, what=""):

@@ -12,22 +12,9 @@ pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
 from oracle import gcnn_oracle as O  # noqa: E402  (initial weights only)
+from gpucommon import dev, make_model  # noqa: E402
 
 STATE_KEYS = ["cons_feats", "cons_edge_inds", "cons_edge_feats", "var_feats", "cut_feats", "cut_edge_inds", "cut_edge_feats"]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _model(seed, dev):
-    from gcnn_cut_selector_amd.model import GCNN
-    params = O.randomize_params(O.init_params(seed, np.float32), seed + 1)
-    m = GCNN(device=dev)
-    m.set_weights([params[n] for n in O.PARAM_NAMES])
-    return m
 
 
 def _tuple(state10, y):
@@ -110,8 +97,8 @@ def loaders(dev):
 @pytest.mark.parametrize("size", [2, 5, 8])
 def test_members_match_solo_pretrain(dev, loaders, size):
     from gcnn_cut_selector_amd.trainer import pretrain, pretrain_many
-    solo = [_model(60 + i, dev) for i in range(size)]
-    grp = [_model(60 + i, dev) for i in range(size)]
+    solo = [make_model(60 + i, dev)[0] for i in range(size)]
+    grp = [make_model(60 + i, dev)[0] for i in range(size)]
     k_solo = [pretrain(m, ld) for m, ld in zip(solo, loaders)]
     k_grp = pretrain_many(grp, loaders[:size])
     torch.cuda.synchronize()
@@ -133,7 +120,7 @@ def test_same_shaped_members_share_launches(dev):
     from gcnn_cut_selector_amd.trainer import pretrain_many
     counts = {}
     for n in (1, 4):
-        models, lds = [_model(80 + i, dev) for i in range(n)], _same_shape(dev, n)
+        models, lds = [make_model(80 + i, dev)[0] for i in range(n)], _same_shape(dev, n)
         pretrain_many(models, lds)   # first use: launch attributes, tables
         with _lib.launch_profile() as prof:
             assert pretrain_many(models, lds) == [11] * n
@@ -147,7 +134,7 @@ def test_no_host_read_inside_a_pass(dev, monkeypatch):
     from gcnn_cut_selector_amd.model import GCNN
     from gcnn_cut_selector_amd.trainer import pretrain_many
     n = 3
-    models, lds = [_model(90 + i, dev) for i in range(n)], _same_shape(dev, n)
+    models, lds = [make_model(90 + i, dev)[0] for i in range(n)], _same_shape(dev, n)
     for ld in lds:
         ld.append(ld[0])   # two batches per pass
     events = []
@@ -177,13 +164,13 @@ def test_no_host_read_inside_a_pass(dev, monkeypatch):
 def test_refusals(dev):
     from gcnn_cut_selector_amd import _lib
     from gcnn_cut_selector_amd.trainer import _group_member, _tables, pretrain_many
-    models, lds = [_model(100 + i, dev) for i in range(2)], _same_shape(dev, 2)
+    models, lds = [make_model(100 + i, dev)[0] for i in range(2)], _same_shape(dev, 2)
     with pytest.raises(ValueError):
         pretrain_many(models, lds, process_group=object())
     with pytest.raises(ValueError):
         pretrain_many([models[0]] * 2, lds)
     with pytest.raises(ValueError):
-        pretrain_many([_model(0, dev) for _ in range(9)], [lds[0]] * 9)
+        pretrain_many([make_model(0, dev)[0] for _ in range(9)], [lds[0]] * 9)
     # overlapping merge states: refused, nothing enqueued
     batch = lds[0][0].batch
     wss = [m._take_workspace(batch) for m in models]

@@ -13,20 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _model(dev):
-    from gcnn_cut_selector_amd.model import GCNN
-    params = O.randomize_params(O.init_params(41, np.float32), 42)
-    m = GCNN(device=dev)
-    m.set_weights([params[n] for n in O.PARAM_NAMES])
-    return m, params
+from gpucommon import dev, make_model  # noqa: E402
 
 
 def _stats(m, batch, ws, layer):
@@ -64,7 +51,7 @@ def _other_batch(state, seed):
 
 
 def test_stats_of_all_layers_after_two_layer_forward_match_oracle(dev):
-    m, params = _model(dev)
+    m, params = make_model(41, dev, 42)
     state, _, _ = synthetic.make_batch("combauc", 3)
     batch = m.prepare(state)
     ws = m._take_workspace(batch)
@@ -81,7 +68,7 @@ def test_stats_of_all_layers_after_two_layer_forward_match_oracle(dev):
 @pytest.mark.parametrize("save", [0, 1])
 def test_post_conv_stats_refuse_after_other_forward_forms(dev, save):
     from gcnn_cut_selector_amd._lib import GcnnError
-    m, params = _model(dev)
+    m, params = make_model(41, dev, 42)
     state, _, _ = synthetic.make_batch("combauc", 2)
     batch = m.prepare(state)
     ws = m._take_workspace(batch)
@@ -100,7 +87,7 @@ def test_post_conv_stats_refuse_after_other_forward_forms(dev, save):
 def test_stale_activations_of_another_batch_are_refused(dev):
     """save=2 on X, then save=1 on Y with the same dims on the same workspace: layer 6 must refuse, not return X's statistics."""
     from gcnn_cut_selector_amd._lib import GcnnError
-    m, params = _model(dev)
+    m, params = make_model(41, dev, 42)
     x, _, _ = synthetic.make_batch("combauc", 2)
     y = _other_batch(x, 9)
     bx, by = m.prepare(x), m.prepare(y)

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
+from gpucommon import dev  # noqa: E402
 
 # mirror of the host rules in gcnn_capi.hip (edge_slots, edge_long_threshold, the send pass's grid): used only to prove that
 # each state exercises what it is here for
@@ -59,12 +60,6 @@ def _states():
 
 
 STATES = dict(_states())
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _three_batches(m, state):

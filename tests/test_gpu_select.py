@@ -13,21 +13,15 @@ import launchnames  # noqa: E402
 from gcnn_cut_selector_amd import _lib, ops, synthetic, utils  # noqa: E402
 from gcnn_cut_selector_amd.graph import BipartiteGraph  # noqa: E402
 
-from test_gpu_model import _model  # noqa: E402
+from gpucommon import dev, make_model  # noqa: E402
 from test_select_build import SELECT, SELECT_NAMES  # noqa: E402
 
 THRESHOLDS = [(0.1, 0.5), (0.0, 0.0), (0.9, 0.95)]
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
 def model(dev):
-    return _model(90, dev)[0]
+    return make_model(90, dev)[0]
 
 
 def plant_rows(rng, K, V, extras=True):

@@ -15,7 +15,7 @@ import cutsel_restate as R  # noqa: E402
 from gcnn_cut_selector_amd import serve  # noqa: E402
 
 import serve_worker_requests as W  # noqa: E402
-from test_gpu_model import _model  # noqa: E402
+from gpucommon import make_model  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_WORKERS = 8
@@ -24,7 +24,7 @@ N_WORKERS = 8
 def test_server_with_eight_workers(tmp_path):
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     dev = torch.device("cuda", 0)
-    models = {"a": _model(98, dev)[0], "b": _model(99, dev)[0]}
+    models = {"a": make_model(98, dev)[0], "b": make_model(99, dev)[0]}
     address = str(tmp_path / "gcnn.sock")
     server = serve.ScoringServer(models, address)
     assert os.path.exists(address)

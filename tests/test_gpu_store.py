@@ -8,15 +8,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic, utils  # noqa: E402
-from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
+from gpucommon import dev, make_model  # noqa: E402
 
 GRAPH_FIELDS = ("l_ptr", "l_oth", "l_coef", "v_ptr", "v_oth", "v_coef")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _samples():
@@ -31,14 +25,6 @@ def _samples():
     no_edge = dict(cons_edge, indices=cons_edge["indices"][:, :0], values=cons_edge["values"][:0])
     out.insert(8, ((cons, no_edge, var, no_cut, no_cut_edge), imp[:0]))
     return out
-
-
-def _model(seed, dev):
-    from gcnn_cut_selector_amd.model import GCNN
-    params = O.randomize_params(O.init_params(seed, np.float32), seed + 1)
-    m = GCNN(device=dev)
-    m.set_weights([params[n] for n in O.PARAM_NAMES])
-    return m
 
 
 def _assert_same_batch(got, want):
@@ -56,7 +42,7 @@ def _assert_same_batch(got, want):
 def test_store_batch_equals_host_collate_plus_prepare(dev, ids):
     from gcnn_cut_selector_amd.store import SampleStore
     samples = _samples()
-    m = _model(3, dev)
+    m = make_model(3, dev)[0]
     store = SampleStore.from_samples(samples, dev, chunk=4)       # several ingestion chunks
     assert len(store) == len(samples) and store.nbytes > 0
     sb = store.batch(ids)
@@ -86,7 +72,7 @@ def test_store_from_files_and_process_match_the_host_loader(dev, tmp_path):
     fractions = np.array([0.25, 0.5, 0.75, 1.0])
     results = []
     for use_store in (False, True):
-        m = _model(5, dev)
+        m = make_model(5, dev)[0]
         if use_store:
             loader = lambda idx, bs: list(store.batches(idx, bs))
         else:
@@ -125,7 +111,7 @@ def test_full_size_store_epoch_runs_and_matches_prepared_batch(dev):
     from gcnn_cut_selector_amd.trainer import TrainState, train_step
     samples = [synthetic.make_sample("setcov", i) for i in range(32)]
     store = SampleStore.from_samples(samples, dev, chunk=16)
-    m = _model(9, dev)
+    m = make_model(9, dev)[0]
     sb = store.batch(np.arange(32))
     state, y, _ = synthetic.make_batch("setcov", 32)
     want = m.prepare(state)

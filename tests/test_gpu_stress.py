@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
 import gradparity  # noqa: E402
+from gpucommon import dev, make_model  # noqa: E402
 
 # (C, V, K, max edges per node for E1, for E2, hubs, duplicates allowed, sorted like get_state)
 CASES = [
@@ -55,15 +56,8 @@ CASES = [
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
 def model(dev):
-    from test_gpu_model import _model
-    return _model(11, dev)
+    return make_model(11, dev)
 
 
 def _state(case, rng):

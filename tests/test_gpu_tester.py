@@ -24,6 +24,7 @@ from gcnn_cut_selector_amd import _lib, synthetic, tester, utils  # noqa: E402
 from gcnn_cut_selector_amd.model import GCNN  # noqa: E402
 from gcnn_cut_selector_amd.store import SampleStore, hybrid_quality  # noqa: E402
 from gcnn_cut_selector_amd.trainer import forward_group, mse_loss, ranking_metric  # noqa: E402
+from gpucommon import dev  # noqa: E402
 
 BS = 4
 PLANTED = (1, 255, 256, 257, 4096, 4097)
@@ -33,12 +34,6 @@ SPECS = [("syn", 0), ("one",), ("syn", 1), ("score", 200, 0), ("hybrid", 200, Fa
          ("random", 256, 9), ("syn", 3), ("score", 256, 8), ("hybrid", 257, True), ("syn", 4), ("score", 257, 9, True),
          ("syn", 5), ("score", 4096, 10), ("syn", 6), ("score", 4097, 5), ("hybrid", 4097, False), ("syn", 7), ("score", 40, 1),
          ("random", 4100, 2), ("syn", 8), ("score", 100, 7), ("syn", 9)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _planted(n, idx, dtype=np.float64, efficacy=None):

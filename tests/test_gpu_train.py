@@ -8,25 +8,12 @@ pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic, utils  # noqa: E402
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
-def _model(seed, dev):
-    from gcnn_cut_selector_amd.model import GCNN
-    params = O.randomize_params(O.init_params(seed, np.float32), seed + 1)
-    m = GCNN(device=dev)
-    m.set_weights([params[n] for n in O.PARAM_NAMES])
-    return m, params
+from gpucommon import dev, make_model  # noqa: E402
 
 
 def test_train_step_matches_oracle_and_autograd_path(dev):
     from gcnn_cut_selector_amd.trainer import Adam, TrainState, train_step
-    m, params = _model(20, dev)
+    m, params = make_model(20, dev)
     state, y, _ = synthetic.make_batch("combauc", 3)
     batch = m.prepare(state)
     yt = torch.as_tensor(y).to(dev)
@@ -58,7 +45,7 @@ def test_train_step_matches_oracle_and_autograd_path(dev):
 def test_data_parallel_loss_scaling_semantics(dev):
     """train_step's DP branch back-propagates the local SUM; scaled by 1/count it must equal the single-GPU gradient."""
     from gcnn_cut_selector_amd.trainer import TrainState, mse_loss
-    m, _ = _model(21, dev)
+    m, _ = make_model(21, dev)
     state, y, _ = synthetic.make_batch("indset", 2)
     batch = m.prepare(state)
     yt = torch.as_tensor(y).to(dev)
@@ -103,7 +90,7 @@ def test_process_and_pretrain_mirror_reference_flow(dev, tmp_path):
 
 
 def test_concrete_function_and_inference_mode(dev):
-    m, params = _model(22, dev)
+    m, params = make_model(22, dev)
     state, _, _ = synthetic.make_batch("setcov", 1, scale=0.3)
     f = m.get_concrete_function()
     q = f(state, False).numpy()                     # the SCIP plugin's call shape (model_evaluator.py:103)
@@ -118,7 +105,7 @@ def test_concrete_function_and_inference_mode(dev):
 # ---- BASELINE-size properties (setcov-500 x 32: ~1M edges) -----------------------------------------------------------
 def test_full_size_batching_invariance_determinism_and_finite_grads(dev):
     from gcnn_cut_selector_amd.trainer import TrainState, train_step
-    m, _ = _model(23, dev)
+    m, _ = make_model(23, dev)
     samples = [synthetic.make_sample("setcov", i) for i in range(32)]
     full = synthetic.stack_samples(samples)
     state = full[:7] + (int(full[7].sum()), int(full[8].sum()), int(full[9].sum()))
@@ -156,7 +143,7 @@ def test_graphed_step_matches_eager_steps(dev):
     state, y, _ = synthetic.make_batch("combauc", 4)
     finals = []
     for graphed in (False, True):
-        m, _ = _model(30, dev)
+        m, _ = make_model(30, dev)
         batch = m.prepare(state)
         yt = torch.as_tensor(y).to(dev)
         opt, ts = Adam(1e-3), TrainState(m)
@@ -177,8 +164,8 @@ def test_graphed_step_matches_eager_steps(dev):
 
 def test_device_resident_adam_matches_host_parameterised_adam(dev):
     from gcnn_cut_selector_amd.trainer import Adam
-    m1, _ = _model(31, dev)
-    m2, _ = _model(31, dev)
+    m1, _ = make_model(31, dev)
+    m2, _ = make_model(31, dev)
     g = torch.randn_like(m1.flat_parameters.detach()) * m1._trainable_mask
     o1, o2 = Adam(3e-4), Adam(3e-4)
     for _ in range(4):
@@ -216,7 +203,7 @@ def test_dp_step_world1_equals_single_gpu_step(dev):
     state, y, _ = synthetic.make_batch("indset", 2)
     outs = []
     for dp in (False, True):
-        m, _ = _model(40, dev)
+        m, _ = make_model(40, dev)
         batch = m.prepare(state)
         yt = torch.as_tensor(y).to(dev)
         opt, ts = Adam(1e-3), TrainState(m)
@@ -260,7 +247,7 @@ def test_train_step_on_degenerate_batches(dev):
         y = torch.as_tensor(rng.uniform(0, 0.1, state[9]).astype(f32)).to(dev)
         outs = []
         for fused in (True, False):
-            m, _ = _model(60, dev)
+            m, _ = make_model(60, dev)
             batch = m.prepare(state)
             opt, ts = Adam(1e-3), TrainState(m)
             for _ in range(2):   # second step: the moments are non-zero
@@ -286,7 +273,7 @@ def test_tester_process_matches_reference_semantics(dev, tmp_path):
     """tester.process vs model_tester.py:173-237 restated with the oracle: cut-weighted MSE and the MEAN ranking fraction."""
     from gcnn_cut_selector_amd import tester
     from gcnn_cut_selector_amd.store import SampleStore
-    m, params = _model(70, dev)
+    m, params = make_model(70, dev)
     samples = [synthetic.make_sample("combauc", 300 + i) for i in range(5)] + [synthetic.make_sample("setcov", 300, scale=0.2)]
     files = []
     for i, (state, imp) in enumerate(samples):
@@ -313,7 +300,7 @@ def test_adam_with_zero_global_cut_count_is_no_step(dev):
     """Data parallel: Adam divides by the all-reduced cut count; a global batch without cuts must leave weights, moments and
     the device-side step counter untouched (not 0 * inf = NaN)."""
     from gcnn_cut_selector_amd.trainer import Adam
-    m, _ = _model(71, dev)
+    m, _ = make_model(71, dev)
     before = m.flat_parameters.detach().clone()
     g = torch.zeros_like(before)
     zero = torch.zeros(1, device=dev)
@@ -391,7 +378,7 @@ def test_fused_adam_steps_are_bitwise_reproducible_and_equal_the_unfused_update(
     state, y, _ = synthetic.make_batch("setcov", 8)
     outs = []
     for rep in range(3):
-        m, _ = _model(31, dev)
+        m, _ = make_model(31, dev)
         batch = m.prepare(state)
         yt = torch.as_tensor(y).to(dev)
         opt, ts = Adam(learning_rate=lambda: 1e-3), TrainState(m)
@@ -400,7 +387,7 @@ def test_fused_adam_steps_are_bitwise_reproducible_and_equal_the_unfused_update(
                 train_step(m, batch, yt, opt, ts)
             outs.append(m.flat_parameters.detach().cpu().numpy().copy())
         else:   # one step: fused against gradients-then-Adam on a second copy of the model
-            m2, _ = _model(31, dev)
+            m2, _ = make_model(31, dev)
             opt2, ts2 = Adam(learning_rate=lambda: 1e-3), TrainState(m2)
             train_step(m, batch, yt, opt, ts)
             train_step(m2, m2.prepare(state), yt, None, ts2)

@@ -32,6 +32,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
 import gradparity  # noqa: E402
+from gpucommon import make_model  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TUNING_LIB = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc", "libgcnn_hip_tuning.so")
@@ -99,8 +100,7 @@ print("CHILD OK")
 
 
 def model(dev):
-    from test_gpu_model import _model
-    return _model(11, dev)
+    return make_model(11, dev)
 
 
 def _hub_state():
@@ -168,7 +168,7 @@ def runs(tmp_path_factory):
 @pytest.fixture(scope="module")
 def oracle():
     """fp64 scores and gradients of every input, and the fp32 weights they ran with."""
-    params = O.randomize_params(O.init_params(11, np.float32), 12)   # test_gpu_model._model(11)'s weights
+    params = O.randomize_params(O.init_params(11, np.float32), 12)   # gpucommon.make_model(11)'s weights
     p64 = {k: v.astype(np.float64) for k, v in params.items()}
     res = {}
     for name in INPUTS:

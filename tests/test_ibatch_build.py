@@ -10,21 +10,17 @@ import sys
 import numpy as np
 import pytest
 
+import buildsupport
 import launchnames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("gcnn_infer_batch_layout_for", "gcnn_infer_batch_fill_table", "gcnn_infer_batch")
 
 
 def test_symbols_in_header_library_and_binding():
     from gcnn_cut_selector_amd import _lib
-    header = open(os.path.join(ROOT, "include", "gcnn_hip.h")).read()
-    lib = _lib.lib()
-    for sym in SYMBOLS:
-        assert re.search(rf"\b{sym}\s*\(", header) and sym in _lib.SIGNATURES and hasattr(lib, sym)
-    assert _lib.ABI_VERSION == 13 and lib.gcnn_abi_version() == 13
+    header = buildsupport.declared_everywhere(SYMBOLS)
     for name, value in (("MAX", _lib.IBATCH_MAX), ("TABLE_COLS", _lib.IBATCH_TABLE_COLS), ("TABLE_STRIDE", _lib.IBATCH_TABLE_STRIDE),
                         ("SCORES", _lib.IBATCH_SCORES), ("RANK", _lib.IBATCH_RANK), ("SELECT", _lib.IBATCH_SELECT)):
         assert f"#define GCNN_IBATCH_{name} {value}\n" in header
@@ -96,38 +92,20 @@ def test_layout_and_limits_need_no_device():
 
 
 @pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("ib") / "k.s"
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(out),
-                        os.path.join(CSRC, "gcnn_capi.hip"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True,
-                       text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = rows.setdefault(m.group(1), {})
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m2 = re.search(pat, line)
-            if m2 and cur is not None:
-                cur[key] = int(m2.group(1))
-    return rows, out.read_text()
+def device_asm():
+    return buildsupport.device_build()
 
 
 def test_kernels_compile_without_scratch(device_asm):
-    rows, asm = device_asm
+    rows = device_asm.rows
     new = {k: v for k, v in rows.items() if "k_ib_" in k}
     assert len(new) == 2 and any("k_ib_unpack" in k for k in new) and any("k_ib_rank" in k for k in new), sorted(new)
     for name, v in new.items():
         assert v["scratch"] == 0 and v["lds"] <= 64 * 1024, (name, v)
     for name in new:   # wave64 code objects, and no float atomics in the new kernels
-        body = asm[asm.index(f"{name}:"):]
-        body = body[:body.index("s_endpgm")]
+        body = device_asm.body(name)
         assert not re.search(r"atomic_(add|pk_add)_f(16|32|64)", body), name
-        meta = asm[asm.index(f".name:           {name}\n"):]
-        assert re.search(r"\.wavefront_size:\s+(\d+)", meta).group(1) == "64", name
+        assert device_asm.wavefront_size(name) == 64, name
 
 
 def test_client_half_imports_no_torch():

@@ -6,42 +6,14 @@ resident waves -- k_embed_fwd<8> went from four waves per SIMD to three that way
   * k_wgrad: two waves per SIMD (ONE resident round of two blocks per CU, place_wg);
   * k_reduce: at least six waves per SIMD and at most 26 KB of LDS (six blocks per CU: one round for ~1,200 blocks);
   * the edge passes without the long-segment body: at least six waves per SIMD."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import buildsupport
 
 
 @pytest.fixture(scope="module")
-def usage(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("res") / "k.s"
-    src = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc", "gcnn_capi.hip")
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(out), src,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = rows.setdefault(m.group(1), {})
-        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
-                         ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    filt = shutil.which("c++filt")
-    names = list(rows)
-    if filt:
-        dem = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
-        rows = {d: rows[n] for n, d in zip(names, dem)}
-    return {k: v for k, v in rows.items() if re.search(r"\bk_[a-z_0-9]+", k)}
+def usage():
+    return buildsupport.device_build().demangled()
 
 
 def _one(usage, prefix):

@@ -4,16 +4,13 @@ cross-compile for gfx950 without scratch, and the layout queries are self-consis
 import ctypes as C
 import os
 import re
-import subprocess
 
-import pytest
-
+import buildsupport
 import launchnames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc")
 LPSTATE = os.path.join(CSRC, "gcnn_lpstate.hpp")
-HIPCC = "/opt/rocm/bin/hipcc"
 LP_NAMES = {"k_lp_stats", "k_lp_emit"}
 SYMBOLS = ("gcnn_lp_layout_for", "gcnn_lp_state", "gcnn_lp_infer", "gcnn_lp_infer_select")
 
@@ -38,22 +35,8 @@ def test_lp_launch_names_are_its_own():
         assert not names & launchnames.launch_names(os.path.join(CSRC, other))
 
 
-def test_lp_kernels_compile_without_scratch(tmp_path):
-    if not os.path.exists(HIPCC):
-        pytest.skip(f"the cross-compiler {HIPCC} is not installed: the gfx950 resource check cannot run here")
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(tmp_path / "k.s"),
-                        os.path.join(CSRC, "gcnn_capi.hip"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True,
-                       text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: \S*?(k_lp_[a-z]+)\d*LpArgs", line) or re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = rows.setdefault(m.group(1), {})
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m2 = re.search(pat, line)
-            if m2 and cur is not None:
-                cur[key] = int(m2.group(1))
+def test_lp_kernels_compile_without_scratch():
+    rows = {re.sub(r"^\S*?(k_lp_[a-z]+)\d*LpArgs.*", r"\1", k): v for k, v in buildsupport.device_build().rows.items()}
     lp = {k: v for k, v in rows.items() if k.startswith("k_lp_")}
     assert set(lp) == LP_NAMES, sorted(rows)
     for name, v in lp.items():

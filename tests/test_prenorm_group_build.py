@@ -4,29 +4,24 @@ scratch -- the merge with every fp32 operation rounded on its own."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+import buildsupport
 import launchnames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("gcnn_prenorm_merge", "gcnn_group_prenorm_merge")
 
 
 def test_symbols_in_header_library_and_binding():
     from gcnn_cut_selector_amd import _lib
-    header = open(os.path.join(ROOT, "include", "gcnn_hip.h")).read()
-    lib = _lib.lib()
-    for sym in SYMBOLS:
-        assert re.search(rf"\b{sym}\s*\(", header) and sym in _lib.SIGNATURES and hasattr(lib, sym)
+    header = buildsupport.declared_everywhere(SYMBOLS)
     for name, value in (("BYTES", _lib.PRENORM_STATE_BYTES), ("MEAN", _lib.PRENORM_STATE_MEAN), ("VAR", _lib.PRENORM_STATE_VAR)):
         assert f"#define GCNN_PRENORM_STATE_{name} {value}\n" in header
     # room for the 14 units of the widest input layer, each array 16-B aligned
     assert _lib.PRENORM_STATE_VAR - _lib.PRENORM_STATE_MEAN >= 4 * 14 and _lib.PRENORM_STATE_BYTES - _lib.PRENORM_STATE_VAR >= 4 * 14
-    assert _lib.ABI_VERSION == 13 and lib.gcnn_abi_version() == 13
     assert "#define GCNN_GROUP_MAX 8" in header
 
 
@@ -50,28 +45,12 @@ def test_launch_names_are_their_own():
 
 
 @pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("pn") / "k.s"
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(out),
-                        os.path.join(CSRC, "gcnn_capi.hip"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True,
-                       text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = rows.setdefault(m.group(1), {})
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("occ", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m2 = re.search(pat, line)
-            if m2 and cur is not None:
-                cur[key] = int(m2.group(1))
-    return rows, out.read_text()
+def device_asm():
+    return buildsupport.device_build()
 
 
 def test_kernels_compile_without_scratch(device_asm):
-    rows, _ = device_asm
+    rows = device_asm.rows
     new = {k: v for k, v in rows.items() if "k_pgroup_" in k or "k_stats_fold" in k or "k_expand_ptr" in k}
     # twins: 4 + 2 keep-A row programs, expand, stats, fold; solo: fold, expand
     assert len([k for k in new if "k_pgroup_" in k]) == 9 and len(new) == 11, sorted(new)
@@ -84,10 +63,8 @@ def test_kernels_compile_without_scratch(device_asm):
 def test_merge_rounds_every_operation(device_asm):
     """The Chan merge must round as NumPy does: no fused multiply-add outside the correctly rounded fp32 divisions (each
     v_div_scale / v_rcp / 3 v_fma + 2 v_fmac / v_div_fmas / v_div_fixup), and the three divisions of the merge are there."""
-    _, asm = device_asm
     for sym in ("_Z12k_stats_fold12StatFoldArgs", "_Z19k_pgroup_stats_foldPK9GroupHead"):
-        body = asm[asm.index(f"{sym}:"):]
-        body = body[:body.index("s_endpgm")]
+        body = device_asm.body(sym)
         fixup = len(re.findall(r"\bv_div_fixup_f32\b", body))
         fma = len(re.findall(r"\bv_fma_f32\b", body))
         fmac = len(re.findall(r"\bv_fmac_f32", body))

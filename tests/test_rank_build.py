@@ -3,15 +3,12 @@ launch name of its own file (gcnn_rank.hpp) apart from the 28 of gcnn_capi.hip, 
 scratch and within 80 KiB of LDS, and bad arguments refused on the host."""
 import os
 import re
-import subprocess
 
-import pytest
-
+import buildsupport
 import launchnames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def test_symbol_in_header_library_and_binding_at_abi_13():
@@ -31,22 +28,8 @@ def test_launch_name_is_its_own():
     assert len(launchnames.launch_names()) == 28
 
 
-def test_kernel_compiles_without_scratch_within_80k_lds(tmp_path):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(tmp_path / "k.s"),
-                        os.path.join(CSRC, "gcnn_capi.hip"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True,
-                       text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = rows.setdefault(m.group(1), {})
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m2 = re.search(pat, line)
-            if m2 and cur is not None:
-                cur[key] = int(m2.group(1))
+def test_kernel_compiles_without_scratch_within_80k_lds():
+    rows = buildsupport.device_build().rows
     hits = {k: v for k, v in rows.items() if "k_rank_multi" in k}
     assert len(hits) == 1, sorted(rows)
     (v,) = hits.values()

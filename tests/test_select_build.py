@@ -2,17 +2,16 @@
 the 28 of gcnn_capi.hip, its kernels cross-compile for gfx950 without scratch, and header, library and binding agree on ABI 13."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import buildsupport
 import launchnames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcnn-cut-selector_amd", "csrc")
 SELECT = os.path.join(CSRC, "gcnn_select.hpp")
-HIPCC = "/opt/rocm/bin/hipcc"
 SELECT_NAMES = {"k_sel_pairs", "k_sel_filter"}
 
 
@@ -23,22 +22,8 @@ def test_selection_launch_names_are_its_own():
     assert len(launchnames.launch_names()) == 28
 
 
-def test_selection_kernels_compile_without_scratch(tmp_path):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", str(tmp_path / "k.s"),
-                        os.path.join(CSRC, "gcnn_capi.hip"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True,
-                       text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: \S*(k_sel_\w+?)\d*SelArgs", line) or re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = rows.setdefault(m.group(1), {})
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m2 = re.search(pat, line)
-            if m2 and cur is not None:
-                cur[key] = int(m2.group(1))
+def test_selection_kernels_compile_without_scratch():
+    rows = {re.sub(r"^\S*(k_sel_\w+?)\d*SelArgs.*", r"\1", k): v for k, v in buildsupport.device_build().rows.items()}
     sel = {k: v for k, v in rows.items() if k.startswith("k_sel_")}
     assert set(sel) == SELECT_NAMES, sorted(rows)
     for name, v in sel.items():

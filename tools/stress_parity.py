@@ -13,7 +13,7 @@ import torch
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
 from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
-from test_gpu_model import _model  # noqa: E402
+from gpucommon import make_model as _model  # noqa: E402
 import gradparity  # noqa: E402
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
