@@ -2,7 +2,13 @@
 float64 restatement tests/lpstate_restate.py.  Integer and flag outputs must be equal; continuous outputs must lie within one float32
 ulp of the restatement's float32 value plus the element's summation bound (one final rounding plus fp64 reassociation: derived in
 the restatement, not measured).  Every case asserts that each cut's side choice is further from its tie than the activity's
-summation bound; no case is left out."""
+summation bound; no case is left out.
+
+These ten cases come from `synthetic.make_lp_snapshot`: at most one chunk of cuts, no degenerate value, no free or empty row.
+tests/test_gpu_lpstate_edges.py covers, under the same rule, several chunks of cuts / rows / columns with both sides in each, more
+than 256 chunks of a kind, lengths around the 16 lanes of a row, free and empty rows, K = 4,097, and the hand-made degenerate cases
+(side tie, zero norms, d = 0, incumbent = LP solution, capped cutoff, zero objective, sides at +-infinity).  Neither file checks the
+three interpreted cut features against SCIP: both compare with this project's own restatement."""
 import numpy as np
 import pytest
 import torch
