@@ -91,8 +91,8 @@ def forced_rows(rng, F, V, cut_edges):
             np.concatenate(out[2]).astype(np.float32))
 
 
-def state_with_cuts(problem, index, rng, K, shuffle=False, extras=True):
-    state, _ = synthetic.make_sample(problem, index, scale=0.3)
+def state_with_cuts(problem, index, rng, K, shuffle=False, extras=True, scale=0.3):
+    state, _ = synthetic.make_sample(problem, index, scale=scale)
     inp = list(utils.state_to_inputs(state))
     V = inp[8]
     rows, cols, vals = plant_rows(rng, K, V, extras)
