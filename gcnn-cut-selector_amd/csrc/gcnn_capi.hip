@@ -583,6 +583,17 @@ static bool rows_split(const int* n, int ngroups, int* blk0) {
         LAUNCHCHK();                                                                                                    \
     } while (0)
 
+// The write-through form of a training launch (k_*_wt, k_rows.hpp): while the launch's largest row set is one resident round of
+// about a tile per wave (GCNN_WT_MAX_ROWS, gcnn_common.hpp).  A group step records the plain kernels (k_group.hpp runs those bodies).
+static bool rows_write_through(const int* n, int ngroups) {
+#ifdef GCNN_STORE_PLAIN
+    return false;
+#else
+    int rows = 0;
+    for (int i = 0; i < ngroups; ++i) rows = std::max(rows, n[i]);
+    return !g_group_rec && rows <= GCNN_WT_MAX_ROWS;
+#endif
+}
 // `plan` (single-state inference, gcnn_infer): the plan's count step rides in this launch as extra blocks
 static int launch_embed_fwd(EmbGroupArgs& m, IplanArgs* plan, hipStream_t st) {
     const int n[3] = {m.v.n, m.c.n, m.k.n}, ns[3] = {4, 3, 3};
@@ -612,7 +623,8 @@ static int launch_embed_fwd(EmbGroupArgs& m, IplanArgs* plan, hipStream_t st) {
     if (m.blk0[3] == 0) return 0;
     // + 3 blocks: fuse_weights, the folded matrices of the three convolutions (two blocks of this launch fit a CU, so they do not
     // queue behind the embedding blocks)
-    ROWS_LAUNCH("k_embed_fwd", k_embed_fwd<8>, k_embed_fwd<4>, nwaves, m.blk0[3] + 3, EMB_LDS_FLOATS * sizeof(float), st, m);
+    if (rows_write_through(n, 3)) ROWS_LAUNCH("k_embed_fwd", k_embed_fwd_wt<8>, k_embed_fwd_wt<4>, nwaves, m.blk0[3] + 3, EMB_LDS_FLOATS * sizeof(float), st, m);
+    else ROWS_LAUNCH("k_embed_fwd", k_embed_fwd<8>, k_embed_fwd<4>, nwaves, m.blk0[3] + 3, EMB_LDS_FLOATS * sizeof(float), st, m);
     return 0;
 }
 // keep_a: the two-layer form that materialises A (PreNorm fitting); never together with a plan
@@ -656,6 +668,9 @@ static int launch_conv_fwd(const ConvFArgs& a, int tail, const IplanArgs* plan, 
     if (keep_a) {
         if (tail == CF_READOUT) ROWS_LAUNCH("k_conv_fwd<readout, keep A>", (k_conv_fwd<8, CF_READOUT, true>), (k_conv_fwd<4, CF_READOUT, true>), nwaves, blk0[1], smem, st, a);
         else ROWS_LAUNCH("k_conv_fwd<proj, keep A>", (k_conv_fwd<8, CF_PROJ, true>), (k_conv_fwd<4, CF_PROJ, true>), nwaves, blk0[1], smem, st, a);
+    } else if (rows_write_through(&a.n, 1)) {
+        if (tail == CF_READOUT) ROWS_LAUNCH("k_conv_fwd<readout>", (k_conv_fwd_wt<8, CF_READOUT>), (k_conv_fwd_wt<4, CF_READOUT>), nwaves, blk0[1], smem, st, a);
+        else ROWS_LAUNCH("k_conv_fwd<proj>", (k_conv_fwd_wt<8, CF_PROJ>), (k_conv_fwd_wt<4, CF_PROJ>), nwaves, blk0[1], smem, st, a);
     } else if (tail == CF_READOUT) ROWS_LAUNCH("k_conv_fwd<readout>", (k_conv_fwd<8, CF_READOUT>), (k_conv_fwd<4, CF_READOUT>), nwaves, blk0[1], smem, st, a);
     else ROWS_LAUNCH("k_conv_fwd<proj>", (k_conv_fwd<8, CF_PROJ>), (k_conv_fwd<4, CF_PROJ>), nwaves, blk0[1], smem, st, a);
     return 0;
@@ -679,14 +694,16 @@ static int launch_conv_bwd(ConvBGroupArgs& m, hipStream_t st) {
     const int n[2] = {m.cb.n, m.tail.n}, ns[2] = {5, 2};
     const int nwaves = rows_blocks(n, ns, 2, m.blk0);
     if (m.blk0[2] == 0) return 0;
-    ROWS_LAUNCH("k_conv_bwd", k_conv_bwd<8>, k_conv_bwd<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(5, 1) * sizeof(float), st, m);
+    if (rows_write_through(n, 2)) ROWS_LAUNCH("k_conv_bwd", k_conv_bwd_wt<8>, k_conv_bwd_wt<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(5, 1) * sizeof(float), st, m);
+    else ROWS_LAUNCH("k_conv_bwd", k_conv_bwd<8>, k_conv_bwd<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(5, 1) * sizeof(float), st, m);
     return 0;
 }
 static int launch_tail_bwd(TailGroupArgs& m, hipStream_t st) {
     const int n[2] = {m.a.n, m.b.n}, ns[2] = {3, 2};
     const int nwaves = rows_blocks(n, ns, 2, m.blk0);
     if (m.blk0[2] == 0) return 0;
-    ROWS_LAUNCH("k_tail_bwd", k_tail_bwd<8>, k_tail_bwd<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(3, 1) * sizeof(float), st, m);
+    if (rows_write_through(n, 2)) ROWS_LAUNCH("k_tail_bwd", k_tail_bwd_wt<8>, k_tail_bwd_wt<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(3, 1) * sizeof(float), st, m);
+    else ROWS_LAUNCH("k_tail_bwd", k_tail_bwd<8>, k_tail_bwd<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(3, 1) * sizeof(float), st, m);
     return 0;
 }
 

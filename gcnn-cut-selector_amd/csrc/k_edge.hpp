@@ -148,8 +148,8 @@ __device__ __forceinline__ void edge_fwd_segment(const EdgeArgs& a, const float 
                                                  const float esh, const float esc, const int r, const int beg, const int end) {
     const EdgeSum t = edge_fwd_partial<SLOTS, COUNT, NEG>(a, L, w, esh, esc, r, beg, end);
     if (L.slot == 0) {
-        *(float4*)(a.out + (size_t)r * EMB + L.ch) = make_float4(s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
-        if (COUNT) *(float4*)(a.cnt_rows + (size_t)r * EMB + L.ch) = t.cnt;
+        store16<GCNN_ST_EDGE>(a.out + (size_t)r * EMB + L.ch, s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
+        if (COUNT) store16<GCNN_ST_EDGE>(a.cnt_rows + (size_t)r * EMB + L.ch, t.cnt.x, t.cnt.y, t.cnt.z, t.cnt.w);
     }
 }
 
@@ -360,7 +360,7 @@ template <int SLOTS, bool NEG>
 __device__ __forceinline__ float4 edge_bwd_send_segment(const EdgeArgs& a, const float s1, const EdgeLane<SLOTS>& L, const float4 w,
                                                         const float esh, const float esc, const int u, const int beg, const int end) {
     const BwdSum t = edge_bwd_send_partial<SLOTS, NEG>(a, L, w, esh, esc, u, beg, end);
-    if (L.slot == 0) *(float4*)(a.out + (size_t)u * EMB + L.ch) = make_float4(s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
+    if (L.slot == 0) store16<GCNN_ST_EDGE>(a.out + (size_t)u * EMB + L.ch, s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
     return t.dw;
 }
 // d w_edge = s1 * sum over ALL edges of c_e * t_e.  Every lane group adds up the shares of the segments it serves (a fixed

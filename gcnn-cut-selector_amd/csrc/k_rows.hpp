@@ -19,7 +19,6 @@
 // So a whole program runs without any LDS round trip for activations; global rows are read/written as float4 pieces
 // X[row][16*m + 4*g .. +3] straight from/to that layout.
 // ---------------------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -48,13 +47,13 @@ __device__ __forceinline__ void rt_load(RTile& t, const float* x, int row, bool 
         t.v[m][0] = f.x; t.v[m][1] = f.y; t.v[m][2] = f.z; t.v[m][3] = f.w;
     }
 }
+// ST: the store policy of the calling program (store16, gcnn_common.hpp)
+template <int ST = ST_PLAIN>
 __device__ __forceinline__ void rt_store(const RTile& t, float* x, int row, bool ok, int g) {
     if (!ok || !x) return;
 #pragma unroll
-    for (int m = 0; m < 4; ++m)
-        *(float4*)(x + (size_t)row * EMB + 16 * m + 4 * g) = make_float4(t.v[m][0], t.v[m][1], t.v[m][2], t.v[m][3]);
+    for (int m = 0; m < 4; ++m) store16<ST>(x + (size_t)row * EMB + 16 * m + 4 * g, t.v[m][0], t.v[m][1], t.v[m][2], t.v[m][3]);
 }
-
 // acc[mo] += Wop[16*mo + (lane&15)][kf] * (scale * T[kf]), kf = 16*mt + 4*g + i;
 // forward (x @ W): Wop[o][k] = W[k][o];  backward (x @ W^T): Wop[o][k] = W[o][k].  wl: the matrix in LDS.
 // MODE (a bool converts): GEMM_FWD  = forward, matrix staged k-interleaved (stage_lds<..., true>): one float4 per four MFMAs
@@ -233,7 +232,7 @@ struct EmbArgs {
     const float* wp[2]; const float* bp[2]; float* po[2];
     int n;
 };
-template <int F, int NPROJ, int NT>
+template <int F, int NPROJ, int NT, int ST = ST_PLAIN>
 __device__ __forceinline__ void emb_program(const EmbArgs& a, float* smem, int bid, int nblk) {
     constexpr int NWAVES = NT / 64, NM = 1 + NPROJ, NV = 2 + NPROJ;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
@@ -292,13 +291,13 @@ __device__ __forceinline__ void emb_program(const EmbArgs& a, float* smem, int b
         rt_mm<false>(t, o, 1.f, smem, lane);
         rt_bias<true>(t, vecs + 64, g);
         rt_clear_unless(t, ok);
-        rt_store(t, a.xo, row, ok, g);
+        rt_store<ST>(t, a.xo, row, ok, g);
         rt_mask_store(t, a.m_x, row, ok, g);
 #pragma unroll
         for (int k = 0; k < NPROJ; ++k) {
             rt_mm<false>(o, t, 1.f, smem + (1 + k) * 64 * LDW, lane);
             rt_bias<false>(o, vecs + (2 + k) * 64, g);
-            rt_store(o, a.po[k], row, ok, g);
+            rt_store<ST>(o, a.po[k], row, ok, g);
         }
 #pragma unroll
         for (int f = 0; f < F; ++f) xv[f] = xn_[f];
@@ -357,17 +356,24 @@ static_assert(EMB_LDS_FLOATS >= 2 * 64 * LDW, "fuse_weights stages two matrices 
 // Two blocks of this launch share a CU when the row sets are large (launch_embed_fwd: 52 KB of LDS each, four waves per SIMD with
 // 8-wave blocks), which takes at most 128 registers per lane: pinned, since two registers more silently halve the residency.
 // (the bodies of the launches take their block index: a grouped launch, k_group.hpp, runs them for several models at once)
-template <int NWAVES>
+template <int NWAVES, int ST = ST_PLAIN>
 __device__ __forceinline__ void embed_fwd_body(const EmbGroupArgs& m, float* smem, const int b) {
-    if (b < m.blk0[1]) emb_program<14, 2, NWAVES * 64>(m.v, smem, b, m.blk0[1]);
-    else if (b < m.blk0[2]) emb_program<4, 1, NWAVES * 64>(m.c, smem, b - m.blk0[1], m.blk0[2] - m.blk0[1]);
-    else if (b < m.blk0[3]) emb_program<6, 1, NWAVES * 64>(m.k, smem, b - m.blk0[2], m.blk0[3] - m.blk0[2]);
+    if (b < m.blk0[1]) emb_program<14, 2, NWAVES * 64, ST>(m.v, smem, b, m.blk0[1]);
+    else if (b < m.blk0[2]) emb_program<4, 1, NWAVES * 64, ST>(m.c, smem, b - m.blk0[1], m.blk0[2] - m.blk0[1]);
+    else if (b < m.blk0[3]) emb_program<6, 1, NWAVES * 64, ST>(m.k, smem, b - m.blk0[2], m.blk0[3] - m.blk0[2]);
     else fuse_weights(m.fz, b - m.blk0[3], smem);
 }
 template <int NWAVES>
 __global__ __launch_bounds__(NWAVES * 64) __attribute__((amdgpu_waves_per_eu(NWAVES / 2, NWAVES / 2))) void k_embed_fwd(EmbGroupArgs m) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     embed_fwd_body<NWAVES>(m, smem, blockIdx.x);
+}
+// The write-through forms of the training launches (store16<ST_WT>, gcnn_common.hpp; chosen per launch by rows_write_through,
+// gcnn_capi.hip): the same bodies, their result tensors stored with sc1.  Same launch bounds and attributes as their plain twins.
+template <int NWAVES>
+__global__ __launch_bounds__(NWAVES * 64) __attribute__((amdgpu_waves_per_eu(NWAVES / 2, NWAVES / 2))) void k_embed_fwd_wt(EmbGroupArgs m) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    embed_fwd_body<NWAVES, ST_WT>(m, smem, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -443,7 +449,7 @@ __device__ __forceinline__ void loss_head_tile(RTile& go, const RTile& o1, float
     const float dbs = row_sum16(ds), ls = row_sum16(a.loss_scale * dlt * dlt);
     if (lane == 0) { slab[EMB] = dbs; slab[EMB + 1] = ls; }
 }
-template <int TAIL, int NT, bool KEEP_A = false>
+template <int TAIL, int NT, bool KEEP_A = false, int ST = ST_PLAIN>
 __device__ __forceinline__ void convf_program(const ConvFArgs& a, float* smem, int bid, int nblk) {
     constexpr int NWAVES = NT / 64, NM = KEEP_A ? 5 : 4, NV = 5;   // [Wf W1a | M] W1b W2 Wt | [bf | u] b1 b2 bt ws
     constexpr int iW1B = NM - 3, iW2 = NM - 2, iWT = NM - 1;
@@ -492,7 +498,7 @@ __device__ __forceinline__ void convf_program(const ConvFArgs& a, float* smem, i
             rt_mm<false>(t0, s_in, 1.f, smem, lane);
             add_deg(t0);
             rt_clear_unless(t0, ok);
-            rt_store(t0, a.a_out, row, ok, g);
+            rt_store<ST>(t0, a.a_out, row, ok, g);
             rt_mm2<false>(t1, t0, s2, smem + 64 * LDW, xr, smem + 2 * 64 * LDW, lane);
         } else {
             rt_mm2<false>(t1, s_in, 1.f, smem, xr, smem + iW1B * 64 * LDW, lane);
@@ -500,27 +506,27 @@ __device__ __forceinline__ void convf_program(const ConvFArgs& a, float* smem, i
         }
         rt_bias<true>(t1, vecs + 64, g);
         rt_clear_unless(t1, ok);
-        rt_store(t1, a.z1, row, ok, g);
+        rt_store<ST>(t1, a.z1, row, ok, g);
         rt_mask_store(t1, a.m_z1, row, ok, g);
         rt_mm<false>(t0, t1, 1.f, smem + iW2 * 64 * LDW, lane);
         rt_bias<true>(t0, vecs + 2 * 64, g);
         rt_clear_unless(t0, ok);
-        rt_store(t0, a.out, row, ok, g);
+        rt_store<ST>(t0, a.out, row, ok, g);
         rt_mask_store(t0, a.m_out, row, ok, g);
         rt_mm<false>(t1, t0, 1.f, smem + iWT * 64 * LDW, lane);
         if (TAIL == CF_PROJ) {
             rt_bias<false>(t1, vecs + 3 * 64, g);
-            rt_store(t1, a.t_out, row, ok, g);
+            rt_store<ST>(t1, a.t_out, row, ok, g);
         } else {
             rt_bias<true>(t1, vecs + 3 * 64, g);
             rt_clear_unless(t1, ok);
-            rt_store(t1, a.t_out, row, ok, g);
+            rt_store<ST>(t1, a.t_out, row, ok, g);
             const float score = readout_score(t1, vecs + 4 * 64, bs, g);
             if (g == 0 && ok) a.scores[row] = score;
             if (TAIL == CF_LOSS) {
                 RTile go;
                 loss_head_tile(go, t1, score, a, vecs + 4 * 64, tile, row, ok, lane);
-                rt_store(go, a.g_o1, row, ok, g);
+                rt_store<ST>(go, a.g_o1, row, ok, g);
             }
         }
         cur = nxt;
@@ -530,6 +536,11 @@ template <int NWAVES, int TAIL, bool KEEP_A = false>
 __global__ __launch_bounds__(NWAVES * 64) void k_conv_fwd(ConvFArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     convf_program<TAIL, NWAVES * 64, KEEP_A>(a, smem, blockIdx.x, gridDim.x);
+}
+template <int NWAVES, int TAIL>
+__global__ __launch_bounds__(NWAVES * 64) void k_conv_fwd_wt(ConvFArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    convf_program<TAIL, NWAVES * 64, false, ST_WT>(a, smem, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -549,7 +560,7 @@ struct ConvBArgs {
     const float *s1, *nrows; float* g_precv;
     int n;
 };
-template <int NT>
+template <int NT, int ST = ST_PLAIN>
 __device__ __forceinline__ void convb_program(const ConvBArgs& a, float* smem, int bid, int nblk) {
     constexpr int NWAVES = NT / 64;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
@@ -580,19 +591,19 @@ __device__ __forceinline__ void convb_program(const ConvBArgs& a, float* smem, i
         RTile t0, t1;
         rt_mm<true>(t0, in, 1.f, smem, lane);
         rt_mask_apply(t0, cur.m0);
-        rt_store(t0, a.g_out, row, ok, g);
+        rt_store<ST>(t0, a.g_out, row, ok, g);
         rt_mm<true>(t1, t0, 1.f, smem + 64 * LDW, lane);
         rt_mask_apply(t1, cur.m1);
-        rt_store(t1, a.g_z1, row, ok, g);
+        rt_store<ST>(t1, a.g_z1, row, ok, g);
         rt_mm<true>(t0, t1, 1.f, smem + 2 * 64 * LDW, lane);
-        rt_store(t0, a.g_xrecv, row, ok, g);
+        rt_store<ST>(t0, a.g_xrecv, row, ok, g);
         rt_mm<true>(t0, t1, 1.f, smem + 3 * 64 * LDW, lane);
-        rt_store(t0, a.g_s, row, ok, g);
+        rt_store<ST>(t0, a.g_s, row, ok, g);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int i = 0; i < 4; ++i) t0.v[m][i] = s1 * t0.v[m][i] * nr.v[m][i];
-        rt_store(t0, a.g_precv, row, ok, g);
+        rt_store<ST>(t0, a.g_precv, row, ok, g);
         cur = nxt;
     }
 }
@@ -701,7 +712,7 @@ struct TailBArgs {
     const float* w2; float* g_e1;
     int n;
 };
-template <bool HAS_INB, int NT>
+template <bool HAS_INB, int NT, int ST = ST_PLAIN>
 __device__ __forceinline__ void tailb_program(const TailBArgs& a, float* smem, int bid, int nblk) {
     constexpr int NWAVES = NT / 64;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
@@ -734,34 +745,44 @@ __device__ __forceinline__ void tailb_program(const TailBArgs& a, float* smem, i
 #pragma unroll
             for (int i = 0; i < 4; ++i) t0.v[m][i] += ad.v[m][i];
         rt_mask_apply(t0, cur.mk);
-        rt_store(t0, a.g_x, row, ok, g);
+        rt_store<ST>(t0, a.g_x, row, ok, g);
         rt_mm<true>(t1, t0, 1.f, smem + 64 * LDW, lane);
-        rt_store(t1, a.g_e1, row, ok, g);
+        rt_store<ST>(t1, a.g_e1, row, ok, g);
         cur = nxt;
     }
 }
 
 // backward launches: a receiver-gradient program, optionally with a tail program over another row set beside it ...
 struct ConvBGroupArgs { int blk0[3]; ConvBArgs cb; TailBArgs tail; };
-template <int NWAVES>
+template <int NWAVES, int ST = ST_PLAIN>
 __device__ __forceinline__ void conv_bwd_body(const ConvBGroupArgs& m, float* smem, const int b) {
-    if (b < m.blk0[1]) convb_program<NWAVES * 64>(m.cb, smem, b, m.blk0[1]);
-    else tailb_program<false, NWAVES * 64>(m.tail, smem, b - m.blk0[1], m.blk0[2] - m.blk0[1]);
+    if (b < m.blk0[1]) convb_program<NWAVES * 64, ST>(m.cb, smem, b, m.blk0[1]);
+    else tailb_program<false, NWAVES * 64, ST>(m.tail, smem, b - m.blk0[1], m.blk0[2] - m.blk0[1]);
 }
 template <int NWAVES>
 __global__ __launch_bounds__(NWAVES * 64) void k_conv_bwd(ConvBGroupArgs m) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     conv_bwd_body<NWAVES>(m, smem, blockIdx.x);
 }
+template <int NWAVES>
+__global__ __launch_bounds__(NWAVES * 64) void k_conv_bwd_wt(ConvBGroupArgs m) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    conv_bwd_body<NWAVES, ST_WT>(m, smem, blockIdx.x);
+}
 // ... and the two last tails together: `a` sums two projections (the raw variable embedding fed two convolutions)
 struct TailGroupArgs { int blk0[3]; TailBArgs a, b; };
-template <int NWAVES>
+template <int NWAVES, int ST = ST_PLAIN>
 __device__ __forceinline__ void tail_bwd_body(const TailGroupArgs& m, float* smem, const int b) {
-    if (b < m.blk0[1]) tailb_program<true, NWAVES * 64>(m.a, smem, b, m.blk0[1]);
-    else tailb_program<false, NWAVES * 64>(m.b, smem, b - m.blk0[1], m.blk0[2] - m.blk0[1]);
+    if (b < m.blk0[1]) tailb_program<true, NWAVES * 64, ST>(m.a, smem, b, m.blk0[1]);
+    else tailb_program<false, NWAVES * 64, ST>(m.b, smem, b - m.blk0[1], m.blk0[2] - m.blk0[1]);
 }
 template <int NWAVES>
 __global__ __launch_bounds__(NWAVES * 64) void k_tail_bwd(TailGroupArgs m) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     tail_bwd_body<NWAVES>(m, smem, blockIdx.x);
+}
+template <int NWAVES>
+__global__ __launch_bounds__(NWAVES * 64) void k_tail_bwd_wt(TailGroupArgs m) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    tail_bwd_body<NWAVES, ST_WT>(m, smem, blockIdx.x);
 }

@@ -250,8 +250,8 @@ __device__ __forceinline__ void wgrad_body(const WgArgs& a, const DwRedArgs& dw,
         const int q = i < head ? i : EMB * EMB / 4 + (i - head);
         const float4 p0 = ((const float4*)wg_red)[q], p1 = ((const float4*)(wg_red + WG_SLAB))[q];
         const float4 p2 = ((const float4*)(wg_red + 2 * WG_SLAB))[q], p3 = ((const float4*)(wg_red + 3 * WG_SLAB))[q];
-        slab[q] = make_float4((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y), (p0.z + p1.z) + (p2.z + p3.z),
-                              (p0.w + p1.w) + (p2.w + p3.w));
+        store16<GCNN_ST_WGRAD>((float*)(slab + q), (p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y), (p0.z + p1.z) + (p2.z + p3.z),
+                               (p0.w + p1.w) + (p2.w + p3.w));
     }
 }
 __global__ __launch_bounds__(64 * WG_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_wgrad(WgArgs a, DwRedArgs dw) {
