@@ -82,6 +82,13 @@ class LpLayout(C.Structure):
                 ("lp_off", C.c_size_t), ("scratch_off", C.c_size_t), ("state", InferLayout)]
 
 
+class LpBatchLayout(C.Structure):
+    _fields_ = [("state", IbatchLayout), ("n_snapshots", C.c_int32), ("reserved", C.c_int32), ("table_bytes", C.c_size_t),
+                ("in_bytes", C.c_size_t), ("snap_base", C.c_size_t * IBATCH_MAX), ("forced_off", C.c_size_t * 3),
+                ("out_bytes", C.c_size_t), ("out_off", C.c_size_t * 6), ("arena_bytes", C.c_size_t), ("up_off", C.c_size_t),
+                ("out_dev_off", C.c_size_t), ("scratch_off", C.c_size_t), ("scratch_base", C.c_size_t * IBATCH_MAX)]
+
+
 GROUP_MAX = 8   # GCNN_GROUP_MAX
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
@@ -144,6 +151,9 @@ SIGNATURES = {
     "gcnn_lp_state": (C.c_int, [C.POINTER(LpDims), _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcnn_lp_infer": (C.c_int, [C.POINTER(LpDims), _P, _P, _P, _P, _Z, _I, _P]),
     "gcnn_lp_infer_select": (C.c_int, [C.POINTER(LpDims), _I, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
+    "gcnn_lp_batch_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(LpBatchLayout)]),
+    "gcnn_lp_batch_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P]),
+    "gcnn_lp_batch": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
 }
 
 _lib = None

@@ -90,34 +90,40 @@ extern "C" int gcnn_infer_batch_fill_table(int32_t n_states, const gcnn_dims* di
     return ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, table);
 }
 
-extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
-                                int32_t mode, const float* params, const void* host_in, void* host_out, void* arena,
-                                size_t arena_bytes, double p_max, double p_max_ub, void* stream) {
-    gcnn_ibatch_layout L;
-    int rc = ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, &L);
-    if (rc) return rc;
-    if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L.arena_bytes, mode == GCNN_IBATCH_SELECT, p_max, p_max_ub))) return rc;
+// Where a union lies in device memory: the table, the zero block, the seven stacked arrays, the forced rows and the output block.
+// gcnn_infer_batch uploads all of them as one block at the arena's start; gcnn_lp_batch (gcnn_lpbatch.hpp) uploads the table and the
+// forced rows with its snapshots and builds the seven arrays in place.  The plan and the workspaces are at L.dev_off in either case.
+struct IbAt {
+    const int* table; char* zero; const char* arr[7];   // arr: gcnn_ibatch_layout.in_off[2..8]
+    const char* forced[3];                               // in_off[9..11]
+    char* out;                                           // scores | order | n_kept | flags, at L.out_off
+};
+
+// what the forward pass itself would refuse, before anything is enqueued
+static int ibatch_precheck(const gcnn_ibatch_layout& L, const float* params, void* arena) {
     layout_init();
+    gcnn_graph g; memset(&g, 0, sizeof(g));
+    return check_common(&L.total, params, &g, &g, (float*)arena, gcnn_workspace_floats(&L.total));
+}
+
+// ibatch_run: everything of gcnn_infer_batch between its upload and its download, on a union that lies at `at` (infer_run's
+// counterpart): the index pass, the by-variable stage, ONE forward pass, ranking or selection, the flags into the output block.
+static int ibatch_run(int n_states, int mode, const gcnn_ibatch_layout& L, const float* params, char* A, const IbAt& at, double p_max,
+                      double p_max_ub, hipStream_t st) {
+    int rc;
     const gcnn_dims& T = L.total;
-    {   // what the forward pass itself would refuse, before anything is enqueued
-        gcnn_graph g; memset(&g, 0, sizeof(g));
-        if ((rc = check_common(&T, params, &g, &g, (float*)arena, gcnn_workspace_floats(&T)))) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    char* A = (char*)arena;
-    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload
     const size_t S = n_states;
     const int E1 = T.n_cons_edges, E2 = T.n_cut_edges, V = T.n_vars, K = T.n_cuts, FE = L.n_forced_entries;
-    const int* table = (const int*)(A + L.in_off[0]);
+    const int* table = at.table;
     IbArgs ia; memset(&ia, 0, sizeof(ia));
     ia.table = table; ia.n_states = n_states;
-    ia.packed[0] = (const int*)(A + L.in_off[3]); ia.packed[1] = (const int*)(A + L.in_off[7]);
+    ia.packed[0] = (const int*)at.arr[1]; ia.packed[1] = (const int*)at.arr[5];
     ia.left = (int*)(A + L.dev_off[0]); ia.var[0] = (int*)(A + L.dev_off[1]); ia.var[1] = (int*)(A + L.dev_off[2]);
-    ia.flags = (int*)(A + L.in_off[1]);
-    ia.l_ptr[0] = (int*)(A + L.in_off[1] + al16(16 * S));
-    ia.l_ptr[1] = (int*)(A + L.in_off[1] + al16(16 * S) + al16(4 * ((size_t)T.n_cons + 1)));
+    ia.flags = (int*)at.zero;
+    ia.l_ptr[0] = (int*)(at.zero + al16(16 * S));
+    ia.l_ptr[1] = (int*)(at.zero + al16(16 * S) + al16(4 * ((size_t)T.n_cons + 1)));
     ia.iota = (int*)(A + L.dev_off[3]);
-    ia.f_col_in = (const int*)(A + L.in_off[10]); ia.f_col = (int*)(A + L.dev_off[9]);
+    ia.f_col_in = (const int*)at.forced[1]; ia.f_col = (int*)(A + L.dev_off[9]);
     {
         const long long items = (long long)E1 + E2 + 2 * n_states + FE;
         ProfScope prof("k_ib_unpack", st);
@@ -125,9 +131,9 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
         LAUNCHCHK();
     }
     gcnn_graph cg, kg; memset(&cg, 0, sizeof(cg)); memset(&kg, 0, sizeof(kg));
-    cg.l_ptr = ia.l_ptr[0]; cg.l_oth = ia.var[0]; cg.l_coef = (const float*)(A + L.in_off[4]);
+    cg.l_ptr = ia.l_ptr[0]; cg.l_oth = ia.var[0]; cg.l_coef = (const float*)at.arr[2];
     cg.v_ptr = (int*)(A + L.dev_off[6]); cg.v_oth = (int*)(A + L.dev_off[7]); cg.v_coef = (float*)(A + L.dev_off[8]);
-    kg.l_ptr = ia.l_ptr[1]; kg.l_oth = ia.var[1]; kg.l_coef = (const float*)(A + L.in_off[8]);
+    kg.l_ptr = ia.l_ptr[1]; kg.l_oth = ia.var[1]; kg.l_coef = (const float*)at.arr[6];
     kg.v_ptr = cg.v_ptr;   // never read: conv v->k gathers by cut only and nothing is differentiated
     if (E1 > 0) {          // gcnn_graph_build's by-variable stage on the union's list
         ProfScope prof("k_ib_by_variable", st);
@@ -136,10 +142,10 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
     } else {
         HIPCHK(hipMemsetAsync((void*)cg.v_ptr, 0, ((size_t)V + 1) * sizeof(int), st));
     }
-    char* out = A + L.dev_off[11];
+    char* out = at.out;
     float* scores = (float*)(out + L.out_off[0]);
     // ONE forward pass over the union (the longest segments are not known here: 0)
-    rc = forward_impl(&T, params, (const float*)(A + L.in_off[2]), (const float*)(A + L.in_off[5]), (const float*)(A + L.in_off[6]),
+    rc = forward_impl(&T, params, (const float*)at.arr[0], (const float*)at.arr[3], (const float*)at.arr[4],
                       &cg, &kg, (float*)(A + L.dev_off[12]), gcnn_workspace_floats(&T), scores, 0, nullptr, 0.f, st);
     if (rc) return rc;
     if (mode == GCNN_IBATCH_RANK && K > 0) {
@@ -149,13 +155,37 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
     }
     if (mode == GCNN_IBATCH_SELECT) {
         SelArgs a = sel_args(scores, SelRows{kg.l_ptr, kg.l_oth, kg.l_coef, table + IB_K * IB_TS},
-                             SelRows{(const int*)(A + L.in_off[9]), ia.f_col, (const float*)(A + L.in_off[11]),
+                             SelRows{(const int*)at.forced[0], ia.f_col, (const float*)at.forced[2],
                                      L.n_forced > 0 ? table + IB_F * IB_TS : nullptr},
                              n_states, K, L.n_forced, L.max_cuts, V, p_max, p_max_ub, A + L.dev_off[13], (int*)(out + L.out_off[1]),
                              (int*)(out + L.out_off[2]));
         if ((rc = launch_select(a, st))) return rc;
     }
     HIPCHK(hipMemcpyAsync(out + L.out_off[3], ia.flags, 16 * S, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));   // ONE download: scores | order | n_kept | flags
     return 0;
 }
+
+extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                                int32_t mode, const float* params, const void* host_in, void* host_out, void* arena,
+                                size_t arena_bytes, double p_max, double p_max_ub, void* stream) {
+    gcnn_ibatch_layout L;
+    int rc = ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, &L);
+    if (rc) return rc;
+    if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L.arena_bytes, mode == GCNN_IBATCH_SELECT, p_max, p_max_ub))) return rc;
+    if ((rc = ibatch_precheck(L, params, arena))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* A = (char*)arena;
+    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload
+    IbAt at;
+    at.table = (const int*)(A + L.in_off[0]); at.zero = A + L.in_off[1];
+    for (int i = 0; i < 7; ++i) at.arr[i] = A + L.in_off[2 + i];
+    for (int i = 0; i < 3; ++i) at.forced[i] = A + L.in_off[9 + i];
+    at.out = A + L.dev_off[11];
+    if ((rc = ibatch_run(n_states, mode, L, params, A, at, p_max, p_max_ub, st))) return rc;
+    HIPCHK(hipMemcpyAsync(host_out, at.out, L.out_bytes, hipMemcpyDeviceToHost, st));   // ONE download: scores | order | n_kept | flags
+    return 0;
+}
+
+// gcnn_lp_batch: the union's states built from raw LP snapshots.  Included from here because it needs this file's statics and
+// gcnn_lpstate.hpp's, and gcnn_capi.hip ends with this file.
+#include "gcnn_lpbatch.hpp"

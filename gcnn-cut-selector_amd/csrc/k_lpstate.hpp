@@ -118,12 +118,15 @@ __device__ __forceinline__ void lp_chunk_prefix(const int* part, int n_chunks, i
     __syncthreads();
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lp_stats(LpArgs a) {
+// The two launches' bodies as functions of (arguments, block index within the snapshot's share of the launch): the solo kernels
+// below run them on their own grid, k_lpbatch.hpp's kernels on each snapshot's share of one grid.  Everything that depends on the
+// block partition -- the chunking in 256s, the pre[] / tot[] terms, the order of the column partials -- is a function of these two
+// alone, so a snapshot's state has the same bits in either launch.  The chunk counts are the arguments' nrc / ncc / nkc.
+__device__ __forceinline__ void lp_stats_body(const LpArgs& a, const int blk) {
     __shared__ double sd[LP_NT];
     __shared__ int si[5];
     const int t = threadIdx.x;
-    if (a.zero) for (int i = blockIdx.x * LP_NT + t; i < a.zero_words; i += gridDim.x * LP_NT) a.zero[i] = 0;
-    int b = blockIdx.x;
+    int b = blk;
     if (b < a.ncc) {                                            // ---- columns
         const int j = b * LP_NT + t;
         double o2 = 0.0, d2 = 0.0;
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(LP_NT) void k_lp_stats(LpArgs a) {
         }
         o2 = lp_block_sum(o2, sd);
         d2 = lp_block_sum(d2, sd);
-        if (t == 0) { a.col_part[2 * b] = o2; a.col_part[2 * b + 1] = d2; a.blk_flags[blockIdx.x] = 0; }
+        if (t == 0) { a.col_part[2 * b] = o2; a.col_part[2 * b + 1] = d2; a.blk_flags[blk] = 0; }
         return;
     }
     b -= a.ncc;
@@ -201,16 +204,21 @@ __global__ __launch_bounds__(LP_NT) void k_lp_stats(LpArgs a) {
     if (flag) atomicOr(&si[4], flag);                          // (LDS)
     __syncthreads();
     if (t < 4) (rows ? a.row_part : a.cut_part)[4 * b + t] = si[t];
-    if (t == 0) a.blk_flags[blockIdx.x] = si[4];               // every block writes its word: nothing to clear, nothing shared
+    if (t == 0) a.blk_flags[blk] = si[4];               // every block writes its word: nothing to clear, nothing shared
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lp_emit(LpArgs a) {
+__global__ __launch_bounds__(LP_NT) void k_lp_stats(LpArgs a) {
+    if (a.zero) for (int i = blockIdx.x * LP_NT + threadIdx.x; i < a.zero_words; i += gridDim.x * LP_NT) a.zero[i] = 0;
+    lp_stats_body(a, blockIdx.x);
+}
+
+__device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
     __shared__ int si[4 * LP_NT];
     __shared__ double sd[LP_NT];
     __shared__ int s_pos[LP_NT], s_ofs[2][LP_NT];      // per row: state position of the lhs copy (-1: none), edge offsets (-1: none)
     __shared__ int s_pos2[LP_NT];
     const int t = threadIdx.x;
-    int b = blockIdx.x;
+    int b = blk;
     int pre[4], tot[4];
     if (b == a.nrc + a.nkc) {                          // ---- the totals against the host's sizes, and the flag words
         lp_chunk_prefix(a.row_part, a.nrc, 0, pre, tot, si);
@@ -325,3 +333,5 @@ __global__ __launch_bounds__(LP_NT) void k_lp_emit(LpArgs a) {
         }
     }
 }
+
+__global__ __launch_bounds__(LP_NT) void k_lp_emit(LpArgs a) { lp_emit_body(a, blockIdx.x); }

@@ -1,5 +1,5 @@
-"""Host arrays in, one C call, host arrays out: the host side of gcnn_infer, gcnn_infer_select and gcnn_infer_batch
-(include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
+"""Host arrays in, one C call, host arrays out: the host side of gcnn_infer, gcnn_infer_select, gcnn_infer_batch, the LP-snapshot
+calls and gcnn_lp_batch (include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
 of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers."""
 
 from __future__ import annotations
@@ -415,3 +415,113 @@ class _LPSession(_Staging):
             flags = outs[8].cpu().numpy()      # waits for the stream: the staging buffer is free again
         lpstate.raise_for_flags(flags)
         return tuple(outs[:7]) + (c, v, k), outs[7]
+
+
+class _LPBatchSession(_Staging):
+    """Host side of gcnn_lp_batch: one C call for up to 64 LP snapshots -- one upload of the tables and the packed snapshots, the
+    states built in the arena where gcnn_infer_batch keeps its uploaded ones, one download.  `run` answers per snapshot, in STATE
+    order: ("ok", scores, order, n_kept, cut_index), ("error", ValueError) for what the device flags in the snapshot,
+    ("bad_index",) or ("declined",)."""
+    MAX = _lib.IBATCH_MAX
+    CAP = 64
+
+    def __init__(self, model):
+        super().__init__(model)
+        self.calls = 0            # C calls made (tools and tests read it)
+        self.deep_check = False   # as _LPSession.deep_check
+        self.last = None          # (layout, state keys) of the last call
+
+    def check(self, snap):
+        """-> (arrays, dims) of `lpstate.check_snapshot`."""
+        from . import lpstate
+        return lpstate.check_snapshot(snap, self.deep_check)
+
+    @staticmethod
+    def _dims_array(dims):
+        return (_lib.LpDims * len(dims))(*(_lib.LpDims(**d) for d in dims))
+
+    @staticmethod
+    def _one(dims):
+        from . import lpstate
+        return list(lpstate.lp_layout(dims)[1].snap_off)
+
+    def _layout(self, dims, fshapes, mode):
+        from . import lpstate
+        n = len(dims)
+        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
+        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        L = _lib.LpBatchLayout()
+        if _unsupported(_lib.lib().gcnn_lp_batch_layout_for(n, self._dims_array(dims), nf, nfe, mode, C.byref(L)), "gcnn_lp_batch_layout_for"):
+            return False
+        base = list(L.snap_base)
+        snap_at = [[base[s] + o for o in self.cached(("one",) + _int_key(d), self._one, d)] for s, d in enumerate(dims)]
+        prefix = lambda xs: [sum(xs[:i]) for i in range(n + 1)]  # noqa: E731
+        k_off = prefix([d["n_cuts"] for d in dims])
+        f_off, fe_off = (prefix([f[j] for f in fshapes]) if fshapes else [0] * (n + 1) for j in (0, 1))
+        return nf, nfe, L, snap_at, k_off, f_off, fe_off, list(L.forced_off), list(L.out_off), [lpstate.state_key(d) for d in dims]
+
+    def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
+        """checked: [(arrays, dims)] as `check` returns them; forced: None or [(ptr, col, val)] per snapshot.
+        Returns None when the library declines the union as a whole (too large: the caller splits it)."""
+        from . import lpstate
+        n = len(checked)
+        dims = [d for _, d in checked]
+        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        lay = self.cached((mode, tuple(_int_key(d) for d in dims), fshapes), self._layout, dims, fshapes, mode)
+        if lay is False:
+            return None
+        nf, nfe, L, snap_at, k_off, f_off, fe_off, forced_off, out_off, keys = lay
+        d = self._dims_array(dims)         # (the scalars are not part of the layout's key: the array is this call's)
+        self._buffers(L)
+        buf = self.in_np
+        _lib.check(_lib.lib().gcnn_lp_batch_fill_table(n, d, nf, nfe, mode, self.pin_in.data_ptr()), "gcnn_lp_batch_fill_table")
+        for s, (arrays, _) in enumerate(checked):
+            lpstate.pack_snapshot(buf, snap_at[s], arrays)
+            if forced is not None:
+                fptr, fcol, fval = forced[s]
+                o = forced_off[0] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next snapshot's first
+                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
+                self._put_forced((forced_off[1] + 4 * fe_off[s], forced_off[2] + 4 * fe_off[s]), (fcol, fval))
+        if forced is None:
+            buf[forced_off[0]:forced_off[0] + 4] = 0
+        self._enqueue_wait("gcnn_lp_batch", (n, d, nf, nfe, mode), (float(p_max), float(p_max_ub)))
+        self.calls += 1
+        self.last = (L, keys)
+        out, res = self.out_np, []
+        for s in range(n):
+            lo, cuts = 4 * k_off[s], k_off[s + 1] - k_off[s]
+            try:
+                lpstate.raise_for_flags(out[out_off[4] + 16 * s:out_off[4] + 16 * s + 16].view(np.int32))
+            except ValueError as exc:
+                res.append(("error", exc))
+                continue
+            verdict = self._verdict(out_off[3] + 16 * s)
+            if verdict:
+                res.append((verdict,))
+                continue
+            answer = self._read(out_off[0] + lo, out_off[1] + lo if mode else None,
+                                out_off[2] + 4 * s if mode == _lib.IBATCH_SELECT else None, cuts)
+            res.append(("ok",) + answer + (out[out_off[5] + lo:out_off[5] + lo + 4 * cuts].view(np.int32).copy(),))
+        return res
+
+    def last_states(self):
+        """The seven arrays of every state the last call built in the arena, as host arrays (tests compare them with gcnn_lp_state's)."""
+        L, keys = self.last
+        off = list(L.state.in_off)
+        kinds = (torch.float32, torch.int32, torch.float32, torch.float32, torch.float32, torch.int32, torch.float32)
+        at, out = [0] * 5, []
+        for key in keys:
+            c, v, k, e1, e2 = key
+            shapes = ((c, 4), (2, e1), (e1, 1), (v, 14), (k, 6), (2, e2), (e2, 1))
+            arrays = []
+            for j, ((col, size), shape, dt) in enumerate(zip(_BatchSession.PLACES, shapes, kinds)):
+                o = off[2 + j] + size * at[col]
+                arrays.append(self.arena[o:o + 4 * shape[0] * shape[1]].view(dt).view(shape).cpu().numpy())
+            out.append(tuple(arrays))
+            at = [a + b for a, b in zip(at, key)]
+        return out
+
+
+def _int_key(dims):
+    """The sizes of a snapshot's dims (what a layout depends on; the three scalars are not part of it)."""
+    return tuple(v for v in dims.values() if isinstance(v, int))

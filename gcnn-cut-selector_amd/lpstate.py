@@ -3,15 +3,14 @@
 `LPSnapshot` holds the LP rows and the candidate cuts as CSR over LP column positions plus per-row, per-column and per-cut vectors
 in the solver's own float64 (include/gcnn_hip.h: gcnn_lp_state).  This module is the host side only -- the checks, the five sizes
 the entry points need on the host, and the packer of the one upload; the arithmetic that turns a snapshot into the model's ten
-inputs runs on the device (csrc/k_lpstate.hpp) behind `GCNN.state_from_lp`, `GCNN.score_lp` and `GCNN.select_cuts_lp`."""
+inputs runs on the device (csrc/k_lpstate.hpp) behind `GCNN.state_from_lp`, `GCNN.score_lp` and `GCNN.select_cuts_lp`.
+It imports NumPy only (the library binding is loaded inside `lp_layout`), so the scoring server's torch-free clients use it too."""
 
 from __future__ import annotations
 
 from dataclasses import dataclass
 
 import numpy as np
-
-from . import _lib
 
 # the packed order: GCNN_LP_* of include/gcnn_hip.h (index 0 is the reserved header)
 FIELDS = (("row_ptr", np.int32), ("row_col", np.int32), ("row_val", np.float64), ("row_lhs", np.float64), ("row_rhs", np.float64),
@@ -163,7 +162,9 @@ def raise_for_flags(flags):
 
 def lp_layout(dims, n_forced=-1, n_entries=0):
     """(LpDims, LpLayout) of the library for these dims."""
-    d, L = _lib.LpDims(**dims), _lib.LpLayout()
     import ctypes as C
+
+    from . import _lib
+    d, L = _lib.LpDims(**dims), _lib.LpLayout()
     _lib.check(_lib.lib().gcnn_lp_layout_for(C.byref(d), n_forced, n_entries, C.byref(L)), "gcnn_lp_layout_for")
     return d, L

@@ -21,8 +21,8 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPSession, _UseGeneralPath, check_feature_shapes,
-                    check_state, is_host_state, n_selected, normalize_forced, stable_ranking)
+from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPSession, _UseGeneralPath,
+                    check_feature_shapes, check_state, is_host_state, n_selected, normalize_forced, stable_ranking)
 
 EMB = 64
 
@@ -165,6 +165,7 @@ class GCNN:
         self._session = None      # single-state inference (gcnn_infer): pinned staging + device arena, created on first use
         self._batch_session = None   # many host states per call (gcnn_infer_batch), created on first use
         self._lp_session = None   # calls that start from a raw LP snapshot (gcnn_lp_*), created on first use
+        self._lp_batch_session = None   # many LP snapshots per call (gcnn_lp_batch), created on first use
         self._pin = None          # pinned host staging buffer for prepare()
         self._pin_event = None
         self._prenorm_state = None
@@ -556,33 +557,45 @@ class GCNN:
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
     # ---- many host states in one call (gcnn_infer_batch): what a scoring server does with the requests that queued up ----------
-    def _many(self, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0):
-        """Common part of `score_states` / `select_cuts_many`: results per state -- ("ok", scores, order, n_kept), or an exception.
+    @staticmethod
+    def _admit_state(st, mode):
+        """A host state for the batched call: (arrays, key), or None where it goes to the solo entry point."""
+        if not is_host_state(st) or len(st) != 10:
+            return None                     # device tensors, prepared batches, malformed tuples: the solo path answers (or raises)
+        arrays, key = check_state(st)
+        n_cons, n_vars, n_cuts, e1, e2 = key
+        declined = (n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096)
+                    or (e1 and (n_cons == 0 or n_vars == 0)) or (e2 and n_vars == 0))
+        return None if declined else (arrays, key)
+
+    def _many(self, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0, lp=False):
+        """Common part of `score_states` / `select_cuts_many` and, with `lp`, of `score_lps` / `select_cuts_lp_many`: results per
+        state -- ("ok", scores, order, n_kept[, cut_index]), or an exception.
         `solo(i)`: the existing single-state entry point for state i (a state the batch declines goes there and comes back in
         place).  `forced`: None or per state a packed (ptr, col, val) / an exception raised while it was packed."""
         n = len(states)
         results, checked, batch_ids, solo_ids = [None] * n, {}, [], []
+        session = self._sess("_lp_batch_session", _LPBatchSession) if lp else self._sess("_batch_session", _BatchSession)
         for i, st in enumerate(states):
             try:
                 if forced is not None and isinstance(forced[i], Exception):
                     raise forced[i]
-                if not is_host_state(st) or len(st) != 10:
-                    solo_ids.append(i)          # device tensors, prepared batches, malformed tuples: the solo path answers (or raises)
-                    continue
-                arrays, key = check_state(st)
+                if lp:
+                    entry = session.check(st)
+                    n_cuts = entry[1]["n_cuts"]
+                    if n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096):
+                        entry = None
+                else:
+                    entry = self._admit_state(st, mode)
             except Exception as exc:  # noqa: BLE001 -- the error belongs to this state's slot
                 results[i] = exc
                 continue
-            n_cons, n_vars, n_cuts, e1, e2 = key
-            declined = (n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096)
-                        or (e1 and (n_cons == 0 or n_vars == 0)) or (e2 and n_vars == 0))
-            if declined:
+            if entry is None:
                 solo_ids.append(i)
             else:
-                checked[i] = (arrays, key)
+                checked[i] = entry
                 batch_ids.append(i)
-        session = self._sess("_batch_session", _BatchSession)
-        todo = [batch_ids[j:j + _BatchSession.MAX] for j in range(0, len(batch_ids), _BatchSession.MAX)]
+        todo = [batch_ids[j:j + session.MAX] for j in range(0, len(batch_ids), session.MAX)]
         while todo:
             ids = todo.pop(0)
             got = session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode, p_max, p_max_ub)
@@ -595,6 +608,8 @@ class GCNN:
             for i, r in zip(ids, got):
                 if r[0] == "ok":
                     results[i] = r
+                elif r[0] == "error":
+                    results[i] = r[1]
                 elif r[0] == "bad_index":
                     results[i] = ValueError(BAD_INDEX)
                 else:
@@ -655,6 +670,51 @@ class GCNN:
             if isinstance(r, tuple):
                 _, scores, order, n_kept = r
                 results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
+        return self._finish_many(results, return_exceptions)
+
+    # ---- many LP snapshots in one call (gcnn_lp_batch): what a scoring server does with the snapshots that queued up ----------
+    def score_lps(self, snapshots, rank=False, return_exceptions=False):
+        """`score_lp` for many `LPSnapshot`s at once: one upload of the packed snapshots, two launches build all their states where
+        gcnn_infer_batch keeps its uploaded ones, ONE forward pass over the union, one download (gcnn_lp_batch; up to 64 per call,
+        more are served in several calls).  Returns a list of `ScoreArray` in STATE order with `.cut_index`, and `.rankings` when
+        `rank`.  There is no variable limit.  Errors per snapshot as in `score_states`.  Snapshots the batch declines (no cuts,
+        more than 4,096 cuts when ranking) go through `score_lp` and come back in place."""
+        snapshots = list(snapshots)
+        mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
+        results = self._many(snapshots, mode, lambda i: self.score_lp(snapshots[i], rank), lp=True)
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                scores = r[1]
+                scores.cut_index = r[4]
+                if rank:
+                    scores.rankings = r[2]
+                results[i] = scores
+        return self._finish_many(results, return_exceptions)
+
+    def select_cuts_lp_many(self, snapshots, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
+        """`select_cuts_lp` for many `LPSnapshot`s at once (gcnn_lp_batch in selection mode).  `forced`: None, or one entry per
+        snapshot in the forms `select_cuts` accepts.  Returns a list of `SelectResult` with `.cut_index`; errors per snapshot as in
+        `select_cuts_many`."""
+        ops.check_thresholds(p_max, p_max_ub)
+        snapshots = list(snapshots)
+        forced = [None] * len(snapshots) if forced is None else list(forced)
+        if len(forced) != len(snapshots):
+            raise ValueError(f"forced: one entry per snapshot expected, got {len(forced)} for {len(snapshots)} snapshots")
+        packed = []
+        for sn, f in zip(snapshots, forced):
+            try:
+                packed.append(normalize_forced(f, int(np.asarray(sn.col_type).shape[0])))
+            except Exception as exc:  # noqa: BLE001
+                packed.append(exc)
+
+        def solo(i):
+            return self.select_cuts_lp(snapshots[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
+
+        results = self._many(snapshots, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub, lp=True)
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                _, scores, order, n_kept, cut_index = r
+                results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
         return self._finish_many(results, return_exceptions)
 
     def get_concrete_function(self):

@@ -4,9 +4,11 @@ worker, one selector call per separation round) share ONE process that owns the 
     server = ScoringServer({"setcov": model}, "/tmp/gcnn.sock"); server.start()          # the GPU process
     client = ScoringClient("/tmp/gcnn.sock", "setcov")                                    # a worker: NumPy only, no torch
     CustomCutsel(function=client.get_concrete_function(), ...)                            # model_evaluator.py:310-314
+    client.select_cuts_lp(lpstate.LPSnapshot(...), max_selected=10)                       # or: the raw LP, get_state left to the GPU
 
 The server takes every request that is waiting, groups them by model and kind, answers each group with one
-`GCNN.score_states` / `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) and goes back
+`GCNN.score_states` / `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP
+kinds one `GCNN.score_lps` / `GCNN.select_cuts_lp_many` call, which also builds the states on the device -- and goes back
 for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.
 
 Wire format (AF_UNIX stream; little-endian; no pickle -- nothing a peer sends is ever executed): a message is a uint32 byte count
@@ -23,15 +25,23 @@ import threading
 
 import numpy as np
 
+from . import lpstate      # NumPy only
+
 MAGIC = b"GCS1"
 KIND_SCORE, KIND_RANK, KIND_SELECT = 0, 1, 2
+# the same three from a raw LP snapshot (lpstate.LPSnapshot): its 21 arrays (19 without an incumbent), one float64 array of the
+# scalars (infinity, sum_epsilon, n_model_vars, obj_norm), then the optional forced pair; the header's n_cons slot says whether
+# there is an incumbent.  Replies carry cut_index as one more array.
+KIND_LP_SCORE, KIND_LP_RANK, KIND_LP_SELECT = 3, 4, 5
+_LP_BASE = {KIND_LP_SCORE: KIND_SCORE, KIND_LP_RANK: KIND_RANK, KIND_LP_SELECT: KIND_SELECT}
+_PRIMAL = (14, 15)         # positions of col_primal / col_primal_avg among lpstate.FIELDS
 MAX_MESSAGE = 1 << 30
 # request: magic, kind, n_arrays, key length, p_max, p_max_ub, max_selected (-1: none), n_forced (-1: no forced rows), n_cons, n_vars, n_cuts
 _REQ = struct.Struct("<4sBBHddiiiii")
 # reply: magic, status (0 ok, else an error class), n_arrays, pad, n_kept, n_selected
 _REP = struct.Struct("<4sBBHii")
 _ARR = struct.Struct("<BBHIIQ4x")      # dtype code, ndim, pad, dim0, dim1, bytes
-_DTYPES = ("<f4", "<f8", "<i4", "<i8", "|u1")
+_DTYPES = ("<f4", "<f8", "<i4", "<i8", "|u1", "|i1")
 _CODES = {np.dtype(d): i for i, d in enumerate(_DTYPES)}
 ERR_VALUE, ERR_GCNN, ERR_OTHER = 1, 2, 3
 
@@ -85,29 +95,60 @@ def _get_arrays(buf, at, count):
 
 
 def encode_request(model_key, kind, state, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
-    """-> the message's bytes (without the length prefix).  `state`: the model's 10-tuple of host arrays; `forced`: None or
-    (edge_inds [2,E], values [E][, n_forced]) as `GCNN.select_cuts` takes it."""
+    """-> the message's bytes (without the length prefix).  `state`: the model's 10-tuple of host arrays (an LP snapshot goes
+    through `encode_lp_request`); `forced`: None or (edge_inds [2,E], values [E][, n_forced]) as `GCNN.select_cuts` takes it."""
     if len(state) != 10:
         raise ValueError(f"expected the 10-tuple state, got {len(state)} items")
     key = model_key.encode("utf-8")
-    arrays = list(state[:7])
-    n_forced = -1
-    if forced is not None:
-        fi = np.asarray(forced[0])
-        n_forced = int(forced[2]) if len(forced) > 2 else (int(fi[0].max()) + 1 if fi.size else 0)
-        arrays += [fi, np.asarray(forced[1])]
+    n_forced, pair = _forced_pair(forced)
+    arrays = list(state[:7]) + pair
     parts = [_REQ.pack(MAGIC, kind, len(arrays), len(key), float(p_max), float(p_max_ub), -1 if max_selected is None else int(max_selected),
                        n_forced, int(state[7]), int(state[8]), int(state[9])), key]
     _put_arrays(parts, arrays)
     return b"".join(parts)
 
 
+def _forced_pair(forced):
+    """Forced rows as `GCNN.select_cuts` takes them -> (n_forced or -1, the arrays to send)."""
+    if forced is None:
+        return -1, []
+    fi = np.asarray(forced[0])
+    return int(forced[2]) if len(forced) > 2 else (int(fi[0].max()) + 1 if fi.size else 0), [fi, np.asarray(forced[1])]
+
+
+def encode_lp_request(model_key, kind, snapshot, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
+    """-> the message's bytes of an LP request (kind KIND_LP_*).  The snapshot is checked here as the server will check it again
+    (`lpstate.check_snapshot` without the O(nnz) facts), so its ValueError is raised in the worker."""
+    arrays, dims = lpstate.check_snapshot(snapshot, deep=False)
+    inc = dims["has_incumbent"]
+    arrays = [a for i, a in enumerate(arrays) if inc or i not in _PRIMAL]
+    arrays.append(np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64))
+    n_forced, pair = _forced_pair(forced)
+    key = model_key.encode("utf-8")
+    parts = [_REQ.pack(MAGIC, kind, len(arrays) + len(pair), len(key), float(p_max), float(p_max_ub),
+                       -1 if max_selected is None else int(max_selected), n_forced, inc, 0, 0), key]
+    _put_arrays(parts, arrays + pair)
+    return b"".join(parts)
+
+
+def _decode_lp(arrays, inc, n_forced):
+    names = [n for i, (n, _) in enumerate(lpstate.FIELDS) if inc or i not in _PRIMAL]
+    scalars = arrays[len(names)]
+    if scalars.dtype != np.float64 or scalars.shape != (4,) or not np.isfinite(scalars[2]):
+        raise ProtocolError("malformed snapshot scalars")
+    snap = lpstate.LPSnapshot(**dict(zip(names, arrays)), infinity=float(scalars[0]), sum_epsilon=float(scalars[1]),
+                              n_model_vars=int(scalars[2]), obj_norm=float(scalars[3]), has_incumbent=bool(inc))
+    return snap, ((arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
+
+
 def decode_request(buf):
-    """-> dict(model_key, kind, state, forced, p_max, p_max_ub, max_selected); raises ProtocolError on anything malformed."""
+    """-> dict(model_key, kind, state | snapshot, forced, p_max, p_max_ub, max_selected); raises ProtocolError on anything malformed."""
     if len(buf) < _REQ.size:
         raise ProtocolError("truncated header")
     magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, n_cons, n_vars, n_cuts = _REQ.unpack_from(buf, 0)
-    if magic != MAGIC or kind > KIND_SELECT or n_arrays != (9 if n_forced >= 0 else 7):
+    lp = kind in _LP_BASE
+    expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else 7) + (2 if n_forced >= 0 else 0)
+    if magic != MAGIC or kind > KIND_LP_SELECT or n_arrays != expected or (lp and n_cons not in (0, 1)):
         raise ProtocolError("not a request of this protocol")
     at = _REQ.size + key_len
     if at > len(buf):
@@ -116,6 +157,10 @@ def decode_request(buf):
     arrays, at = _get_arrays(buf, at, n_arrays)
     if at != len(buf):
         raise ProtocolError("trailing bytes")
+    if lp:
+        snap, forced = _decode_lp(arrays, n_cons, n_forced)
+        return dict(model_key=key, kind=kind, snapshot=snap, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
+                    max_selected=None if max_selected < 0 else max_selected)
     return dict(model_key=key, kind=kind, state=tuple(arrays[:7]) + (n_cons, n_vars, n_cuts),
                 forced=(arrays[7], arrays[8], n_forced) if n_forced >= 0 else None, p_max=p_max, p_max_ub=p_max_ub,
                 max_selected=None if max_selected < 0 else max_selected)
@@ -165,16 +210,18 @@ def _recv_exact(sock, n):
 class Scores(np.ndarray):
     """Scores as the plugins use them: an ndarray that answers `.numpy()` (model_evaluator.py:103); `rankings` when asked for."""
     rankings = None
+    cut_index = None      # the LP calls: state position -> input cut (scores are in STATE order)
 
     def numpy(self):
         return np.asarray(self)
 
 
 class Selection:
-    """`order` (kept cuts first, best first, then the removed ones), `n_kept`, `n_selected` = min(n_kept, max_selected), `scores`."""
+    """`order` (kept cuts first, best first, then the removed ones), `n_kept`, `n_selected` = min(n_kept, max_selected), `scores`;
+    from `select_cuts_lp` also `cut_index`: `cut_index[order[:n_selected]]` are the selected input cuts."""
 
-    def __init__(self, order, n_kept, n_selected, scores):
-        self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
+    def __init__(self, order, n_kept, n_selected, scores, cut_index=None):
+        self.order, self.n_kept, self.n_selected, self.scores, self.cut_index = order, n_kept, n_selected, scores, cut_index
 
 
 class ScoringClient:
@@ -199,6 +246,20 @@ class ScoringClient:
     def select_cuts(self, state, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
         arrays, n_kept, n_selected = self._call(encode_request(self.model_key, KIND_SELECT, state, forced, p_max, p_max_ub, max_selected))
         return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores))
+
+    def score_lp(self, snapshot, rank=False):
+        """`GCNN.score_lp` behind the server: the raw LP goes over the wire, get_state's arithmetic runs on the GPU."""
+        arrays, _, _ = self._call(encode_lp_request(self.model_key, KIND_LP_RANK if rank else KIND_LP_SCORE, snapshot))
+        scores = arrays[0].view(Scores)
+        scores.cut_index = arrays[-1]
+        if rank:
+            scores.rankings = arrays[1]
+        return scores
+
+    def select_cuts_lp(self, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        arrays, n_kept, n_selected = self._call(encode_lp_request(self.model_key, KIND_LP_SELECT, snapshot, forced, p_max, p_max_ub,
+                                                                  max_selected))
+        return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
 
     def get_concrete_function(self):
         """The `(state10, training) -> scores` callable `CustomCutsel(function=...)` stores (model_evaluator.py:310-314)."""
@@ -315,20 +376,22 @@ class ScoringServer:
     def _serve(self, pending):
         groups = {}
         for conn, req in pending:
-            gkey = (req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if req["kind"] == KIND_SELECT else ())
+            selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT)
+            gkey = (req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
             groups.setdefault(gkey, []).append((conn, req))
         for gkey, items in groups.items():
-            model, kind = self.models[gkey[0]], gkey[1]
-            states = [r["state"] for _, r in items]
+            model, lp = self.models[gkey[0]], gkey[1] in _LP_BASE
+            kind = _LP_BASE.get(gkey[1], gkey[1])
+            states = [r["snapshot" if lp else "state"] for _, r in items]
+            score_many, select_many = (model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)
             self.stats["calls"] += 1
             self.stats["batched_calls"] += len(items) > 1
             self.stats["max_batch"] = max(self.stats["max_batch"], len(items))
             try:
                 if kind == KIND_SELECT:
-                    results = model.select_cuts_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3],
-                                                     return_exceptions=True)
+                    results = select_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3], return_exceptions=True)
                 else:
-                    results = model.score_states(states, rank=kind == KIND_RANK, return_exceptions=True)
+                    results = score_many(states, rank=kind == KIND_RANK, return_exceptions=True)
             except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
                 results = [exc] * len(items)
             for (conn, req), res in zip(items, results):
@@ -338,10 +401,12 @@ class ScoringServer:
                     self.stats["errors"] += 1
                     self._reply(conn, encode_reply(error=res))
                 elif kind == KIND_SELECT:
-                    self._reply(conn, encode_reply([np.asarray(res.scores), np.asarray(res.order, np.int32)], res.n_kept,
-                                                   _n_selected(res.n_kept, req["max_selected"])))
+                    arrays = [np.asarray(res.scores), np.asarray(res.order, np.int32)]
+                    arrays += [np.asarray(res.cut_index, np.int32)] if lp else []
+                    self._reply(conn, encode_reply(arrays, res.n_kept, _n_selected(res.n_kept, req["max_selected"])))
                 else:
                     arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if kind == KIND_RANK else [])
+                    arrays += [np.asarray(res.cut_index, np.int32)] if lp else []
                     self._reply(conn, encode_reply(arrays))
 
     def serve_forever(self):

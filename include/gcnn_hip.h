@@ -520,6 +520,45 @@ int gcnn_lp_infer_select(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_f
                          const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max, double p_max_ub,
                          void* stream);
 
+/* ---- many LP snapshots in one call: gcnn_infer_batch in front of which the device builds every state ------------------------------
+ * What a scoring server does with the LP snapshots that queued up (model_evaluator.py:157-241: one selector call per worker and
+ * separation round): 1..GCNN_IBATCH_MAX snapshots in ONE host->device copy, two launches that run gcnn_lp_state's arithmetic for all
+ * of them and leave state s exactly where gcnn_infer_batch's upload would have put it (features at the union's rows, each edge list as
+ * the state's own [2,E_s] block with state-local ids), then gcnn_infer_batch's index pass, by-variable sort, ONE forward pass and
+ * ranking / selection unchanged, ONE device->host copy.  Nothing is synchronised, nothing allocated.  Every state has the bits
+ * gcnn_lp_state gives it alone.  There is no variable limit (gcnn_lp_infer's 32,768 is the single-state plan's).
+ * dims[s]: snapshot s as gcnn_lp_state takes it; n_forced[s] / n_forced_entries[s] and mode as in gcnn_infer_batch.
+ *
+ * host_in (pinned, in_bytes): [0, table_bytes) the tables -- gcnn_lp_batch_fill_table writes them: the union's table of
+ *   gcnn_infer_batch, then one descriptor per snapshot (sizes, scalars, where its arrays, scratch and outputs lie in the arena as
+ *   byte positions from the arena's start, its first block in either launch); snapshot s packed as gcnn_lp_layout_for(dims[s]) says, its
+ *   array i at snap_base[s] + snap_off[i]; forced_off[0..2]: forced_ptr | forced_col | forced_val as gcnn_infer_batch's O[9..11].
+ * host_out (pinned, out_bytes): out_off[0..3] as gcnn_infer_batch's (scores, order, n_kept, flags [n][4]); out_off[4] the LP flags
+ *   [n][4] of gcnn_lp_state; out_off[5] cut_index [K] int32, state s at k_off[s], state-local.  Scores and order are in STATE order.
+ * A snapshot with an LP flag set has no valid results and changes no other snapshot's: it leaves parts of its own state unwritten,
+ * and whatever ids lie there are confined to its own ranges (gcnn_infer_batch).  Otherwise the four batch flags decide as there.
+ * state: the union's layout for the built states' sizes: in_off[1] the zero block (cleared by the first launch) and in_off[2..8] the
+ *   seven arrays, inside the arena; nothing of it is uploaded.
+ * Returned before anything is enqueued: what gcnn_infer_batch returns for the built states' sizes (n outside 1..GCNN_IBATCH_MAX, a
+ * union past 2^24 rows or 2^30 edges, edges with nothing to point at, thresholds, buffers), and GCNN_E_BADARG for a gcnn_lp_dims
+ * gcnn_lp_layout_for refuses. */
+typedef struct gcnn_lp_batch_layout {
+    gcnn_ibatch_layout state;
+    int32_t n_snapshots, reserved;
+    size_t table_bytes;
+    size_t in_bytes, snap_base[GCNN_IBATCH_MAX], forced_off[3];
+    size_t out_bytes, out_off[6];
+    size_t arena_bytes, up_off, out_dev_off, scratch_off, scratch_base[GCNN_IBATCH_MAX];   /* internal carving of the arena */
+} gcnn_lp_batch_layout;
+int gcnn_lp_batch_layout_for(int32_t n, const gcnn_lp_dims* dims /* host [n] */, const int32_t* n_forced,
+                             const int32_t* n_forced_entries, int32_t mode, gcnn_lp_batch_layout* layout /* host */);
+/* table: host_in (host), table_bytes bytes.  No device work. */
+int gcnn_lp_batch_fill_table(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                             int32_t mode, void* table /* host */);
+int gcnn_lp_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int32_t mode,
+                  const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
+                  double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
