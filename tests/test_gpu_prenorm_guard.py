@@ -3,44 +3,13 @@
 Layers 6, 8 and 10 (post_conv_module's PreNorm) read the scatter-sum outputs A, which only gcnn_forward(save_for_backward=2)
 stores; after any other form the workspace holds whatever A an earlier forward left.  The library records the form of the last
 forward per workspace and refuses (GCNN_E_BADARG) instead of returning statistics of stale memory (include/gcnn_hip.h)."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
 from gcnn_cut_selector_amd import synthetic  # noqa: E402
-from oracle import gcnn_oracle as O  # noqa: E402  (checker only)
-from gpucommon import dev, make_model  # noqa: E402
-
-
-def _stats(m, batch, ws, layer):
-    from gcnn_cut_selector_amd import _lib
-    from gcnn_cut_selector_amd.graph import _ptr, _stream
-    units = O.PRENORM_LAYERS[layer][2]
-    out = torch.full((2 * units,), float("nan"), dtype=torch.float64, device=m.device)
-    with torch.cuda.device(m.device):
-        _lib.check(_lib.lib().gcnn_prenorm_stats(C.byref(batch.dims), _ptr(m.flat_parameters.detach()), _ptr(batch.cons_feats),
-                                                 _ptr(batch.var_feats), _ptr(batch.cut_feats), C.byref(batch.cons_graph.c),
-                                                 C.byref(batch.cut_graph.c), _ptr(ws), ws.numel(), layer, _ptr(out),
-                                                 _stream(m.device)), "gcnn_prenorm_stats")
-    host = out.cpu().numpy()
-    return host[:units], host[units:]
-
-
-def _oracle_stats(params, state, layer):
-    """Population mean and variance of one layer's input in fp64 (PreNormFit after a single batch)."""
-    key, units = O.PRENORM_LAYERS[layer][1], O.PRENORM_LAYERS[layer][2]
-    fit = {key: O.PreNormFit(units, torch.float64)}
-    with pytest.raises(O.PreNormAbsorb):
-        with torch.no_grad():
-            O.forward(O.to_torch({k: np.asarray(v, np.float64) for k, v in params.items()}, torch.float64),
-                      O.as_inputs(state, torch.float64), hook=fit)
-    mean = fit[key].mean.reshape(-1).expand(units).numpy()
-    var = fit[key].var.reshape(-1).expand(units).numpy()
-    return mean, var
+from gpucommon import dev, make_model, oracle_prenorm_stats as _oracle_stats, prenorm_stats as _stats  # noqa: E402
 
 
 def _other_batch(state, seed):
