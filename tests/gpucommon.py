@@ -95,3 +95,46 @@ def fp64_moments(x):
         return np.zeros(x.shape[1]), np.zeros(x.shape[1])
     mean = x.mean(0)
     return mean.numpy(), ((x - mean) ** 2).mean(0).numpy()
+
+
+# ---- a training step through a NaN-filled, guarded workspace (tests/test_gpu_write_through.py, tests/test_gpu_wgrad_seams.py) ----------
+PATTERN = 0x7FC5A5A5           # a quiet NaN no arithmetic produces
+GUARD = 16 * 64                # 16 guard rows behind the workspace
+
+
+def make_state(n_cons, n_vars, n_cuts, seed):
+    """A state 10-tuple with these row counts: every row has 1-4 edges to distinct variables, rows and columns sorted."""
+    rng = np.random.default_rng(seed)
+
+    def edges(n_rows):
+        deg = rng.integers(1, 5, n_rows).clip(max=n_vars)
+        rows = np.repeat(np.arange(n_rows), deg)
+        cols = np.concatenate([np.sort(rng.choice(n_vars, d, replace=False)) for d in deg])
+        return np.stack([rows, cols]).astype(np.int32), rng.standard_normal((len(rows), 1)).astype(np.float32)
+
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    cei, cef = edges(n_cons)
+    kei, kef = edges(n_cuts)
+    return (f(n_cons, 4), cei, cef, f(n_vars, 14), f(n_cuts, 6), kei, kef, n_cons, n_vars, n_cuts), rng.uniform(0, 0.2, n_cuts)
+
+
+def run_step(model, state, y, ws=None, floats=0):
+    """One train_step (no optimizer) through a pattern-filled workspace of the library's size (or `floats`, if that is more) plus
+    the guard rows, or through `ws` as it is.  Returns (results, workspace words on the host, words the library asked for, the workspace)."""
+    import ctypes as C
+    from gcnn_cut_selector_amd import _lib
+    from gcnn_cut_selector_amd.trainer import TrainState, train_step
+    dev = model.device
+    batch = model.prepare(state)
+    need = int(_lib.lib().gcnn_workspace_floats(C.byref(batch.dims)))
+    if ws is None:
+        ws = torch.empty(max(need, floats) + GUARD, dtype=torch.float32, device=dev)
+        ws.view(torch.int32).fill_(PATTERN)
+    assert ws.numel() >= need + GUARD
+    model._ws_pool[:] = [ws]
+    ts = TrainState(model)
+    loss, scores = train_step(model, batch, torch.as_tensor(y, dtype=torch.float32).to(dev), None, ts)
+    torch.cuda.synchronize()
+    assert model._ws_pool and model._ws_pool[-1] is ws, "the step ran through another workspace"
+    res = {"loss": loss.cpu().numpy(), "scores": scores.cpu().numpy(), "grads": ts.grads.cpu().numpy()}
+    return res, ws.view(torch.int32).cpu().numpy(), need, ws
