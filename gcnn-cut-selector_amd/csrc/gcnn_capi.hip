@@ -140,80 +140,66 @@ static inline bool edge_needs_long_pass(int slots, int max_deg) {
 // blocks that find and serve them, riding at the front of the pass's launch: a multiple of 8 (the other blocks' XCD remap)
 static inline int edge_long_grid(int n_own) { return (std::max(1, std::min(cdiv(n_own, 4), MAX_GRID)) + 7) & ~7; }
 static_assert(GCNN_EDGE_DW_PARTS >= EDGE_MAX_GRID + MAX_GRID + 8, "dw partial rows: main blocks + long-segment blocks");
-// forward (owner = receiver); `count` also emits the N rows (active edges per receiver and channel) for the backward pass
-static int launch_plan_place(const IplanArgs& ia, hipStream_t st);
-static int launch_edge_fwd(const EdgeArgs& a, int n_edges, int max_deg, bool count, hipStream_t st, const IplanArgs* plan = nullptr) {
-    if (plan) {   // single-state inference: the plan's place step rides in this launch as extra blocks (k_infer_s2)
-        const bool blockseg = a.n_own <= 1024 && n_edges >= 48ll * a.n_own;
-        if (!count && a.n_own <= 16384 && plan->n_vars <= IPLAN_FUSE_MAX_VARS) {
-            const int edge_blocks = a.n_own <= 0 ? 0 : (blockseg ? a.n_own : std::min(cdiv(a.n_own, 4), MAX_GRID));
-            const int place_blocks = std::max(1, std::min(cdiv(plan->s[0].n_edges, 256), 256));   // one returning atomic per thread
-            static PerDeviceOnce attr;
-            if (attr.first()) {
-                HIPCHK(hipFuncSetAttribute((const void*)k_infer_s2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (IPLAN_MAX_VARS + 1)));
-                HIPCHK(hipFuncSetAttribute((const void*)k_infer_s2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (IPLAN_MAX_VARS + 1)));
-            }
-            ProfScope prof("k_infer_s2 (conv v->c edge pass + plan: place)", st);
-            const size_t smem = 4 * (size_t)(plan->n_vars + 1);
-            if (blockseg) hipLaunchKernelGGL(k_infer_s2<true>, dim3(edge_blocks + place_blocks), dim3(256), smem, st, a, *plan, edge_blocks);
-            else hipLaunchKernelGGL(k_infer_s2<false>, dim3(edge_blocks + place_blocks), dim3(256), smem, st, a, *plan, edge_blocks);
-            LAUNCHCHK();
-            return 0;
-        }
-        int rc = launch_plan_place(*plan, st);   // a graph too large for the fused form: the step as a launch of its own
-        if (rc) return rc;
+// ---- launching: one function, one table per kernel family -----------------------------------------------------------------------
+template <class T> struct AsIs { using type = T; };   // keeps a parameter out of template argument deduction
+// One launch of the forward pass or the training step: its name on the launch record, the kernel's dynamic-LDS limit once per
+// device (lds_max > 0), then the launch -- or, while a group step collects its members, its record: the solo kernel's pointer and
+// a copy of its arguments (k_group.hpp).  The arguments arrive as the kernel's own parameter types (P, from the table entry's
+// type: a wrong argument list does not compile), so hipLaunchKernel reads objects of exactly those types.
+template <class... P>
+static int launch(const char* name, void (*k)(P...), PerDeviceOnce& lds_once, int lds_max, int grid, int block, size_t smem,
+                  hipStream_t st, typename AsIs<P>::type... args) {
+    if (!k) return GCNN_E_UNSUPPORTED;   // an empty table entry: the variant does not exist
+    ProfScope prof(name, st);
+    if (lds_max > 0 && lds_once.first()) HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    if (g_group_rec) group_record(g_group_rec, k, dim3(grid), dim3(block), smem, args...);
+    else {
+        void* argv[] = {(void*)&args...};
+        (void)hipLaunchKernel((const void*)k, dim3(grid), dim3(block), argv, smem, st);
     }
-    if (a.n_own <= 0) return 0;
-    if (count && !a.cnt_rows) return GCNN_E_BADARG;
+    LAUNCHCHK();
+    return 0;
+}
+
+// Edge passes.  What a pass launches: a block per segment (forward only, `grid` = segments), or the main kernel with 16 * slots
+// lanes per segment on `grid` blocks behind `lb` long-segment blocks.  tests/edgecases.py restates the three functions below.
+struct EdgePlan { bool block; int slots, grid, lb; };
+static EdgePlan edge_main_plan(int slots, int n_own, int max_deg) {
+    return EdgePlan{false, slots, std::min(cdiv(cdiv(n_own, 4 / slots), 4), EDGE_MAX_GRID),
+                    edge_needs_long_pass(slots, max_deg) ? edge_long_grid(n_own) : 0};   // long-segment blocks, first in the grid
+}
+// forward (owner = receiver); `count` also emits the N rows (active edges per receiver and channel) for the backward pass
+static EdgePlan edge_fwd_plan(int n_own, int n_edges, int max_deg, bool count) {
     // inference on a small graph (one sampled state): latency, not lane efficiency, decides -- a whole wave per segment needs no
     // long-segment launch and finishes a hub row in a quarter of the gather rounds
-    const int slots = (!count && a.n_own <= 16384) ? 4 : edge_slots(a.n_own, n_edges);
+    const int slots = (!count && n_own <= 16384) ? 4 : edge_slots(n_own, n_edges);
     // a few long segments: a block each (k_edge_fwd_block) -- the cut rows of one sampled state or of a stacked batch (1,893
     // segments of ~105 edges at setcov x 32: a wave per segment walks seven dependent gather rounds on under two waves per SIMD,
     // four waves per segment two).  The same rule with and without counts: training and inference forward add in the same order.
-    if (a.n_own <= 4096 && n_edges >= 48ll * a.n_own) {
-        ProfScope prof(count ? "k_edge_fwd_block<count>" : "k_edge_fwd_block", st);
-        if (count) GCNN_LAUNCH(k_edge_fwd_block<true>, dim3(a.n_own), dim3(256), 0, st, a);
-        else GCNN_LAUNCH(k_edge_fwd_block<false>, dim3(a.n_own), dim3(256), 0, st, a);
-        LAUNCHCHK();
-        return 0;
-    }
-    const int grid = std::min(cdiv(cdiv(a.n_own, 4 / slots), 4), EDGE_MAX_GRID);
-    const int lb = edge_needs_long_pass(slots, max_deg) ? edge_long_grid(a.n_own) : 0;   // long-segment blocks, first in the grid
-    {
-        ProfScope prof(count ? (lb ? "k_edge_fwd<count> + long segments" : "k_edge_fwd<count>") : "k_edge_fwd", st);
-#define EDGE_LAUNCH(S, V)                                                                                              \
-        do {                                                                                                            \
-            if (lb) GCNN_LAUNCH((k_edge_fwd<S, V, (S < 4)>), dim3(grid + lb), dim3(256), 0, st, a, lb);                 \
-            else GCNN_LAUNCH((k_edge_fwd<S, V, false>), dim3(grid), dim3(256), 0, st, a, 0);                            \
-        } while (0)
-        if (count) { if (slots == 4) EDGE_LAUNCH(4, true); else if (slots == 2) EDGE_LAUNCH(2, true); else EDGE_LAUNCH(1, true); }
-        else { if (slots == 4) EDGE_LAUNCH(4, false); else if (slots == 2) EDGE_LAUNCH(2, false); else EDGE_LAUNCH(1, false); }
-#undef EDGE_LAUNCH
-        LAUNCHCHK();
-    }
-    return 0;
+    if (n_own <= 4096 && n_edges >= 48ll * n_own) return EdgePlan{true, 4, n_own, 0};
+    return edge_main_plan(slots, n_own, max_deg);
 }
 // backward, sender-ordered (owner = sender)
-// *n_parts = rows of a.dw_partial written (one per block of the launch(es)): what k_reduce has to sum into d w_edge
-// (rows [0, *n_main) of the main blocks, then one per long-segment block; n_main = NULL: not wanted)
-static int launch_edge_bwd_send(EdgeArgs a, int n_edges, int max_deg, int* n_parts, hipStream_t st, int* n_main = nullptr) {
-    *n_parts = 0;
-    if (n_main) *n_main = 0;
-    if (a.n_own <= 0) return 0;
-    const int slots = edge_slots(a.n_own, n_edges);
-    const int grid = std::min(cdiv(cdiv(a.n_own, 4 / slots), 4), EDGE_MAX_GRID);
-    const int lb = edge_needs_long_pass(slots, max_deg) ? edge_long_grid(a.n_own) : 0;
-    *n_parts = grid + lb;
-    if (n_main) *n_main = grid;
-    ProfScope prof(lb ? "k_edge_bwd_send + long segments" : "k_edge_bwd_send", st);
-    if (slots == 4) GCNN_LAUNCH((k_edge_bwd_send<4, false>), dim3(grid), dim3(256), 0, st, a, 0);
-    else if (slots == 2 && lb) GCNN_LAUNCH((k_edge_bwd_send<2, true>), dim3(grid + lb), dim3(256), 0, st, a, lb);
-    else if (slots == 2) GCNN_LAUNCH((k_edge_bwd_send<2, false>), dim3(grid), dim3(256), 0, st, a, 0);
-    else if (lb) GCNN_LAUNCH((k_edge_bwd_send<1, true>), dim3(grid + lb), dim3(256), 0, st, a, lb);
-    else GCNN_LAUNCH((k_edge_bwd_send<1, false>), dim3(grid), dim3(256), 0, st, a, 0);
-    LAUNCHCHK();
-    return 0;
+static EdgePlan edge_send_plan(int n_own, int n_edges, int max_deg) { return edge_main_plan(edge_slots(n_own, n_edges), n_own, max_deg); }
+
+template <class... P> struct EdgeKernel { void (*k)(P...); const char* name; PerDeviceOnce lds_once; };   // k == nullptr: no such variant
+static EdgeKernel<EdgeArgs, int> g_edge_fwd[3][2][2] = {   // [slots 1, 2, 4][count][long segments]
+    {{{k_edge_fwd<1, false, false>, "k_edge_fwd"}, {k_edge_fwd<1, false, true>, "k_edge_fwd"}},
+     {{k_edge_fwd<1, true, false>, "k_edge_fwd<count>"}, {k_edge_fwd<1, true, true>, "k_edge_fwd<count> + long segments"}}},
+    {{{k_edge_fwd<2, false, false>, "k_edge_fwd"}, {k_edge_fwd<2, false, true>, "k_edge_fwd"}},
+     {{k_edge_fwd<2, true, false>, "k_edge_fwd<count>"}, {k_edge_fwd<2, true, true>, "k_edge_fwd<count> + long segments"}}},
+    {{{k_edge_fwd<4, false, false>, "k_edge_fwd"}, {}}, {{k_edge_fwd<4, true, false>, "k_edge_fwd<count>"}, {}}}};
+static EdgeKernel<EdgeArgs> g_edge_fwd_block[2] = {   // [count]
+    {k_edge_fwd_block<false>, "k_edge_fwd_block"}, {k_edge_fwd_block<true>, "k_edge_fwd_block<count>"}};
+static EdgeKernel<EdgeArgs, int> g_edge_bwd_send[3][2] = {   // [slots 1, 2, 4][long segments]
+    {{k_edge_bwd_send<1, false>, "k_edge_bwd_send"}, {k_edge_bwd_send<1, true>, "k_edge_bwd_send + long segments"}},
+    {{k_edge_bwd_send<2, false>, "k_edge_bwd_send"}, {k_edge_bwd_send<2, true>, "k_edge_bwd_send + long segments"}},
+    {{k_edge_bwd_send<4, false>, "k_edge_bwd_send"}, {}}};
+static EdgeKernel<EdgeArgs, IplanArgs, int> g_infer_s2[2] = {   // [block per segment]
+    {k_infer_s2<false>, "k_infer_s2 (conv v->c edge pass + plan: place)"}, {k_infer_s2<true>, "k_infer_s2 (conv v->c edge pass + plan: place)"}};
+template <class... P, class... A>
+static int launch_edge(EdgeKernel<P...>& e, int lds_max, int grid, size_t smem, hipStream_t st, const A&... args) {
+    return launch(e.name, e.k, e.lds_once, lds_max, grid, 256, smem, st, args...);
 }
 
 static int launch_plan_place(const IplanArgs& ia, hipStream_t st) {
@@ -223,6 +209,32 @@ static int launch_plan_place(const IplanArgs& ia, hipStream_t st) {
     hipLaunchKernelGGL(k_iplan_place, dim3(std::max(1, std::min(cdiv(ia.s[0].n_edges, 1024), 64))), dim3(1024), 4 * (size_t)(ia.n_vars + 1), st, ia);
     LAUNCHCHK();
     return 0;
+}
+static int launch_edge_fwd(const EdgeArgs& a, int n_edges, int max_deg, bool count, hipStream_t st, const IplanArgs* plan = nullptr) {
+    if (plan) {   // single-state inference: the plan's place step rides in this launch as extra blocks (k_infer_s2)
+        const bool blockseg = a.n_own <= 1024 && n_edges >= 48ll * a.n_own;
+        if (!count && a.n_own <= 16384 && plan->n_vars <= IPLAN_FUSE_MAX_VARS) {
+            const int edge_blocks = a.n_own <= 0 ? 0 : (blockseg ? a.n_own : std::min(cdiv(a.n_own, 4), MAX_GRID));
+            const int place_blocks = std::max(1, std::min(cdiv(plan->s[0].n_edges, 256), 256));   // one returning atomic per thread
+            return launch_edge(g_infer_s2[blockseg], 4 * (IPLAN_MAX_VARS + 1), edge_blocks + place_blocks, 4 * (size_t)(plan->n_vars + 1), st,
+                               a, *plan, edge_blocks);
+        }
+        int rc = launch_plan_place(*plan, st);   // a graph too large for the fused form: the step as a launch of its own
+        if (rc) return rc;
+    }
+    if (a.n_own <= 0) return 0;
+    if (count && !a.cnt_rows) return GCNN_E_BADARG;
+    const EdgePlan p = edge_fwd_plan(a.n_own, n_edges, max_deg, count);
+    if (p.block) return launch_edge(g_edge_fwd_block[count], 0, p.grid, 0, st, a);
+    return launch_edge(g_edge_fwd[p.slots >> 1][count][p.lb > 0], 0, p.grid + p.lb, 0, st, a, p.lb);
+}
+// *n_parts = rows of a.dw_partial written (one per block of the launch): what k_reduce has to sum into d w_edge
+// (rows [0, *n_main) of the main blocks, then one per long-segment block; n_main = NULL: not wanted)
+static int launch_edge_bwd_send(const EdgeArgs& a, int n_edges, int max_deg, int* n_parts, hipStream_t st, int* n_main = nullptr) {
+    const EdgePlan p = a.n_own > 0 ? edge_send_plan(a.n_own, n_edges, max_deg) : EdgePlan{};
+    *n_parts = p.grid + p.lb;
+    if (n_main) *n_main = p.grid;
+    return a.n_own > 0 ? launch_edge(g_edge_bwd_send[p.slots >> 1][p.lb > 0], 0, p.grid + p.lb, 0, st, a, p.lb) : 0;
 }
 
 // ---- workspace carving ------------------------------------------------------------------------------------------
@@ -250,7 +262,6 @@ static inline size_t al4(size_t x) { return (x + 3) & ~(size_t)3; }
 
 // weight-gradient slabs: one per block of the k_wgrad launch, which is sized to one resident round (place_wg) -- a constant bound
 #define WG_MAX_SLABS 1024
-static size_t wg_slabs(const gcnn_dims*) { return WG_MAX_SLABS; }
 
 static void carve(const gcnn_dims* d, float* base, Work* w) {
     const size_t C = d->n_cons, V = d->n_vars, K = d->n_cuts;
@@ -275,7 +286,7 @@ static void carve(const gcnn_dims* d, float* base, Work* w) {
         for (auto q : mv) *q = (mask16*)take(2 * V);
         for (auto q : mk) *q = (mask16*)take(2 * K);
     }
-    w->partial = take(wg_slabs(d) * WG_SLAB);
+    w->partial = take((size_t)WG_MAX_SLABS * WG_SLAB);
     const size_t nrecv[3] = {C, V, K};
     for (int i = 0; i < 3; ++i) {
         w->dwp[i] = take((size_t)GCNN_EDGE_DW_PARTS * EMB); w->dwp2[i] = take((size_t)(GCNN_EDGE_DW_PARTS / DW_CHUNK) * EMB);
@@ -562,26 +573,15 @@ static bool rows_split(const int* n, int ngroups, int* blk0) {
     for (int i = 0; i < ngroups; ++i) { const int t = n[i] > 0 ? cdiv(n[i], 16) : 0; total += t; blk0[i + 1] = blk0[i] + t; }
     return total <= max_tiles;
 }
-#define SPLIT_LAUNCH(NAME, KERNEL, GRID, SMEM, ST, ...)                                                                \
-    do {                                                                                                                \
-        ProfScope prof(NAME, ST);                                                                                       \
-        static PerDeviceOnce attr;                                                                                      \
-        if (attr.first()) HIPCHK(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024)); \
-        GCNN_LAUNCH(KERNEL, dim3(GRID), dim3(256), SMEM, ST, __VA_ARGS__);                                              \
-        LAUNCHCHK();                                                                                                    \
-    } while (0)
-#define ROWS_LAUNCH(NAME, KERNEL8, KERNEL4, NWAVES, GRID, SMEM, ST, ...)                                                \
-    do {                                                                                                                \
-        ProfScope prof(NAME, ST);                                                                                       \
-        static PerDeviceOnce attr;                                                                                      \
-        if (attr.first()) {                                                                                             \
-            HIPCHK(hipFuncSetAttribute((const void*)KERNEL8, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));  \
-            HIPCHK(hipFuncSetAttribute((const void*)KERNEL4, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));  \
-        }                                                                                                               \
-        if ((NWAVES) == 8) GCNN_LAUNCH(KERNEL8, dim3(GRID), dim3(512), SMEM, ST, __VA_ARGS__);                          \
-        else GCNN_LAUNCH(KERNEL4, dim3(GRID), dim3(256), SMEM, ST, __VA_ARGS__);                                        \
-        LAUNCHCHK();                                                                                                    \
-    } while (0)
+// split (one block of four waves per tile) or blocks of four or eight waves; blk0 = the programs' first blocks.  `cap` is asked
+// only for the latter.
+struct RowsForm { bool split; int nwaves; };
+template <class Cap>
+static RowsForm rows_form(const int* n, const int* nstage, int ngroups, int* blk0, Cap cap) {
+    if (rows_split(n, ngroups, blk0)) return RowsForm{true, 4};
+    return RowsForm{false, rows_blocks(n, nstage, ngroups, blk0, cap())};
+}
+static RowsForm rows_form(const int* n, const int* nstage, int ngroups, int* blk0) { return rows_form(n, nstage, ngroups, blk0, [] { return 256; }); }
 
 // The write-through form of a training launch (k_*_wt, k_rows.hpp): while the launch's largest row set is one resident round of
 // about a tile per wave (GCNN_WT_MAX_ROWS, gcnn_common.hpp).  A group step records the plain kernels (k_group.hpp runs those bodies).
@@ -594,70 +594,74 @@ static bool rows_write_through(const int* n, int ngroups) {
     return !g_group_rec && rows <= GCNN_WT_MAX_ROWS;
 #endif
 }
+// One row program: its kernels in the three forms (nullptr: no such form), its launch name and the dynamic LDS bytes of a block
+template <class... P> struct RowProgram {
+    const char* name;
+    void (*k[3])(P...);       // eight waves, four waves, split
+    size_t lds, lds_split;    // of the eight- and four-wave forms; of the split form
+    PerDeviceOnce lds_once[3];
+};
+#define EMB_LDS (EMB_LDS_FLOATS * sizeof(float))
+#define EMB_SPLIT_LDS (EMB_SPLIT_LDS_FLOATS * sizeof(float))
+#define CONV_LDS (ROWS_LDS_FLOATS(5, 5) * sizeof(float))
+#define CONV_SPLIT_LDS (CONV_SPLIT_LDS_FLOATS * sizeof(float))
+static RowProgram<EmbGroupArgs> g_embed[2] = {   // [write-through]; + fuse_weights
+    {"k_embed_fwd", {k_embed_fwd<8>, k_embed_fwd<4>, nullptr}, EMB_LDS, 0},
+    {"k_embed_fwd", {k_embed_fwd_wt<8>, k_embed_fwd_wt<4>, nullptr}, EMB_LDS, 0}};
+static RowProgram<EmbGroupArgs> g_embed_split = {"k_embed_fwd_split", {nullptr, nullptr, k_embed_fwd_split}, 0, EMB_SPLIT_LDS};
+static RowProgram<EmbGroupArgs, IplanArgs> g_infer_s1 = {
+    "k_infer_s1 (embeddings + plan: count)", {k_infer_s1<8>, k_infer_s1<4>, k_infer_s1<4, true>}, EMB_LDS, EMB_SPLIT_LDS};
+enum { CONV_PLAIN, CONV_WT, CONV_KEEP_A };   // keep A: the two-layer form that materialises A (PreNorm fitting)
+static RowProgram<ConvFArgs> g_conv_fwd[2][3] = {   // [tail: CF_PROJ, CF_READOUT][CONV_*]
+    {{"k_conv_fwd<proj>", {k_conv_fwd<8, CF_PROJ>, k_conv_fwd<4, CF_PROJ>, k_conv_fwd_split<CF_PROJ>}, CONV_LDS, CONV_SPLIT_LDS},
+     {"k_conv_fwd<proj>", {k_conv_fwd_wt<8, CF_PROJ>, k_conv_fwd_wt<4, CF_PROJ>, nullptr}, CONV_LDS, 0},
+     {"k_conv_fwd<proj, keep A>", {k_conv_fwd<8, CF_PROJ, true>, k_conv_fwd<4, CF_PROJ, true>, k_conv_fwd_split<CF_PROJ, true>}, CONV_LDS, CONV_SPLIT_LDS}},
+    {{"k_conv_fwd<readout>", {k_conv_fwd<8, CF_READOUT>, k_conv_fwd<4, CF_READOUT>, k_conv_fwd_split<CF_READOUT>}, CONV_LDS, CONV_SPLIT_LDS},
+     {"k_conv_fwd<readout>", {k_conv_fwd_wt<8, CF_READOUT>, k_conv_fwd_wt<4, CF_READOUT>, nullptr}, CONV_LDS, 0},
+     {"k_conv_fwd<readout, keep A>", {k_conv_fwd<8, CF_READOUT, true>, k_conv_fwd<4, CF_READOUT, true>, k_conv_fwd_split<CF_READOUT, true>}, CONV_LDS, CONV_SPLIT_LDS}}};
+static RowProgram<ConvFArgs, IplanArgs, int> g_infer_s3 = {
+    "k_infer_s3 (conv row program + plan: order)", {k_infer_s3<8>, k_infer_s3<4>, k_infer_s3<4, true>}, CONV_LDS, CONV_SPLIT_LDS};
+static RowProgram<ConvFArgs, ConvBArgs> g_conv_turn = {
+    "k_conv_turn (readout + loss head + cut-row gradients)", {k_conv_turn<8>, k_conv_turn<4>, k_conv_turn_split}, CONV_LDS, CONV_SPLIT_LDS};
+static RowProgram<ConvBGroupArgs> g_conv_bwd[2] = {   // [write-through]
+    {"k_conv_bwd", {k_conv_bwd<8>, k_conv_bwd<4>, nullptr}, ROWS_LDS_FLOATS(5, 1) * sizeof(float), 0},
+    {"k_conv_bwd", {k_conv_bwd_wt<8>, k_conv_bwd_wt<4>, nullptr}, ROWS_LDS_FLOATS(5, 1) * sizeof(float), 0}};
+static RowProgram<TailGroupArgs> g_tail_bwd[2] = {   // [write-through]
+    {"k_tail_bwd", {k_tail_bwd<8>, k_tail_bwd<4>, nullptr}, ROWS_LDS_FLOATS(3, 1) * sizeof(float), 0},
+    {"k_tail_bwd", {k_tail_bwd_wt<8>, k_tail_bwd_wt<4>, nullptr}, ROWS_LDS_FLOATS(3, 1) * sizeof(float), 0}};
+template <class... P, class... A>
+static int launch_rows(RowProgram<P...>& r, RowsForm f, int grid, hipStream_t st, const A&... args) {
+    const int i = f.split ? 2 : (f.nwaves == 8 ? 0 : 1);
+    return launch(r.name, r.k[i], r.lds_once[i], 120 * 1024, grid, f.nwaves * 64, f.split ? r.lds_split : r.lds, st, args...);
+}
+
 // `plan` (single-state inference, gcnn_infer): the plan's count step rides in this launch as extra blocks
 static int launch_embed_fwd(EmbGroupArgs& m, IplanArgs* plan, hipStream_t st) {
     const int n[3] = {m.v.n, m.c.n, m.k.n}, ns[3] = {4, 3, 3};
-    if (rows_split(n, 3, m.blk0)) {
-        const size_t smem = EMB_SPLIT_LDS_FLOATS * sizeof(float);
-        if (plan) {
-            plan->blocks0 = std::min(cdiv(plan->s[0].n_edges + 1, 256), 32);
-            plan->blocks1 = std::min(cdiv(plan->s[1].n_edges + 1, 256), 8);
-            SPLIT_LAUNCH("k_infer_s1 (embeddings + plan: count)", (k_infer_s1<4, true>), m.blk0[3] + 3 + plan->blocks0 + plan->blocks1, smem, st, m, *plan);
-        } else if (m.blk0[3] > 0) SPLIT_LAUNCH("k_embed_fwd_split", k_embed_fwd_split, m.blk0[3] + 3, smem, st, m);   // + fuse_weights
-        return 0;
-    }
     // the embedding programs stage three matrices (52 KB): two blocks fit a CU, and with many tiles per wave four waves per SIMD
     // overlap the store-heavy epilogues with the MFMAs better than two (capfac x 32, indset x 64)
-    const int cap_knob = GCNN_KNOB("GCNN_EMB_CAP", 0);
-    const int tiles = cdiv(std::max(m.v.n, 0), 16) + cdiv(std::max(m.c.n, 0), 16) + cdiv(std::max(m.k.n, 0), 16);
-    const int cap = cap_knob > 0 ? cap_knob : (tiles >= 8192 ? 2 * device_cus() - 3 : 256);   // (- 3: the fuse_weights blocks are resident too)
-    const int nwaves = rows_blocks(n, ns, 3, m.blk0, cap);
-    if (plan) {
-        const int nt = nwaves * 64;
-        plan->blocks0 = std::min(cdiv(plan->s[0].n_edges + 1, nt), 32);   // few blocks, looping: they hold a CU slot of this launch's size
-        plan->blocks1 = std::min(cdiv(plan->s[1].n_edges + 1, nt), 8);
-        const int grid = m.blk0[3] + 3 + plan->blocks0 + plan->blocks1;
-        ROWS_LAUNCH("k_infer_s1 (embeddings + plan: count)", k_infer_s1<8>, k_infer_s1<4>, nwaves, grid, EMB_LDS_FLOATS * sizeof(float), st, m, *plan);
-        return 0;
+    const RowsForm f = rows_form(n, ns, 3, m.blk0, [&] {
+        const int cap_knob = GCNN_KNOB("GCNN_EMB_CAP", 0);
+        const int tiles = cdiv(std::max(m.v.n, 0), 16) + cdiv(std::max(m.c.n, 0), 16) + cdiv(std::max(m.k.n, 0), 16);
+        return cap_knob > 0 ? cap_knob : (tiles >= 8192 ? 2 * device_cus() - 3 : 256);   // (- 3: the fuse_weights blocks are resident too)
+    });
+    // + 3 blocks: fuse_weights, the folded matrices of the three convolutions (two blocks of the 4- or 8-wave launch fit a CU, so
+    // they do not queue behind the embedding blocks)
+    if (plan) {   // few blocks, looping: they hold a CU slot of this launch's size
+        plan->blocks0 = std::min(cdiv(plan->s[0].n_edges + 1, f.nwaves * 64), 32);
+        plan->blocks1 = std::min(cdiv(plan->s[1].n_edges + 1, f.nwaves * 64), 8);
+        return launch_rows(g_infer_s1, f, m.blk0[3] + 3 + plan->blocks0 + plan->blocks1, st, m, *plan);
     }
     if (m.blk0[3] == 0) return 0;
-    // + 3 blocks: fuse_weights, the folded matrices of the three convolutions (two blocks of this launch fit a CU, so they do not
-    // queue behind the embedding blocks)
-    if (rows_write_through(n, 3)) ROWS_LAUNCH("k_embed_fwd", k_embed_fwd_wt<8>, k_embed_fwd_wt<4>, nwaves, m.blk0[3] + 3, EMB_LDS_FLOATS * sizeof(float), st, m);
-    else ROWS_LAUNCH("k_embed_fwd", k_embed_fwd<8>, k_embed_fwd<4>, nwaves, m.blk0[3] + 3, EMB_LDS_FLOATS * sizeof(float), st, m);
-    return 0;
+    return launch_rows(f.split ? g_embed_split : g_embed[rows_write_through(n, 3)], f, m.blk0[3] + 3, st, m);
 }
-// keep_a: the two-layer form that materialises A (PreNorm fitting); never together with a plan
 static int launch_conv_fwd(const ConvFArgs& a, int tail, const IplanArgs* plan, hipStream_t st, bool keep_a = false) {
     int blk0[2];
     const int ns = 4;
-    if (rows_split(&a.n, 1, blk0)) {
-        const size_t smem = CONV_SPLIT_LDS_FLOATS * sizeof(float);
-        if (plan && tail == CF_PROJ && plan->n_vars <= IPLAN_FUSE_MAX_VARS) {   // the plan's order step rides in this launch
-            const int grid = blk0[1] + std::min(cdiv(plan->n_vars, 16), 48);
-            if (grid > 0) SPLIT_LAUNCH("k_infer_s3 (conv row program + plan: order)", (k_infer_s3<4, true>), grid, smem, st, a, *plan, blk0[1]);
-            return 0;
-        }
-        if (plan && tail == CF_PROJ && plan->n_vars > 0) {
-            ProfScope prof("k_iplan_order", st);
-            hipLaunchKernelGGL(k_iplan_order, dim3(std::min(cdiv(plan->n_vars, 16), 2048)), dim3(256), 0, st, *plan);
-            LAUNCHCHK();
-        }
-        if (blk0[1] == 0) return 0;
-        if (keep_a) {
-            if (tail == CF_READOUT) SPLIT_LAUNCH("k_conv_fwd<readout, keep A>", (k_conv_fwd_split<CF_READOUT, true>), blk0[1], smem, st, a);
-            else SPLIT_LAUNCH("k_conv_fwd<proj, keep A>", (k_conv_fwd_split<CF_PROJ, true>), blk0[1], smem, st, a);
-        } else if (tail == CF_READOUT) SPLIT_LAUNCH("k_conv_fwd<readout>", k_conv_fwd_split<CF_READOUT>, blk0[1], smem, st, a);
-        else SPLIT_LAUNCH("k_conv_fwd<proj>", k_conv_fwd_split<CF_PROJ>, blk0[1], smem, st, a);
-        return 0;
-    }
-    const int nwaves = rows_blocks(&a.n, &ns, 1, blk0);
-    const size_t smem = ROWS_LDS_FLOATS(5, 5) * sizeof(float);
-    if (plan && tail == CF_PROJ && plan->n_vars <= IPLAN_FUSE_MAX_VARS) {   // the plan's order step rides in this launch
-        const int grid = blk0[1] + std::min(cdiv(plan->n_vars, nwaves * 4), 48);
-        if (grid == 0) return 0;
-        ROWS_LAUNCH("k_infer_s3 (conv row program + plan: order)", k_infer_s3<8>, k_infer_s3<4>, nwaves, grid, smem, st, a, *plan, blk0[1]);
-        return 0;
+    const RowsForm f = rows_form(&a.n, &ns, 1, blk0);
+    if (plan && tail == CF_PROJ && plan->n_vars <= IPLAN_FUSE_MAX_VARS) {   // the plan's order step rides in this launch: a block of it
+        const int grid = blk0[1] + std::min(cdiv(plan->n_vars, f.nwaves * 4), 48);   // serves threads / 16 variables
+        return grid > 0 ? launch_rows(g_infer_s3, f, grid, st, a, *plan, blk0[1]) : 0;
     }
     if (plan && tail == CF_PROJ && plan->n_vars > 0) {   // many variables: the order step wants every lane group resident at once
         ProfScope prof("k_iplan_order", st);
@@ -665,46 +669,26 @@ static int launch_conv_fwd(const ConvFArgs& a, int tail, const IplanArgs* plan, 
         LAUNCHCHK();
     }
     if (blk0[1] == 0) return 0;
-    if (keep_a) {
-        if (tail == CF_READOUT) ROWS_LAUNCH("k_conv_fwd<readout, keep A>", (k_conv_fwd<8, CF_READOUT, true>), (k_conv_fwd<4, CF_READOUT, true>), nwaves, blk0[1], smem, st, a);
-        else ROWS_LAUNCH("k_conv_fwd<proj, keep A>", (k_conv_fwd<8, CF_PROJ, true>), (k_conv_fwd<4, CF_PROJ, true>), nwaves, blk0[1], smem, st, a);
-    } else if (rows_write_through(&a.n, 1)) {
-        if (tail == CF_READOUT) ROWS_LAUNCH("k_conv_fwd<readout>", (k_conv_fwd_wt<8, CF_READOUT>), (k_conv_fwd_wt<4, CF_READOUT>), nwaves, blk0[1], smem, st, a);
-        else ROWS_LAUNCH("k_conv_fwd<proj>", (k_conv_fwd_wt<8, CF_PROJ>), (k_conv_fwd_wt<4, CF_PROJ>), nwaves, blk0[1], smem, st, a);
-    } else if (tail == CF_READOUT) ROWS_LAUNCH("k_conv_fwd<readout>", (k_conv_fwd<8, CF_READOUT>), (k_conv_fwd<4, CF_READOUT>), nwaves, blk0[1], smem, st, a);
-    else ROWS_LAUNCH("k_conv_fwd<proj>", (k_conv_fwd<8, CF_PROJ>), (k_conv_fwd<4, CF_PROJ>), nwaves, blk0[1], smem, st, a);
-    return 0;
+    // (never keep A together with a plan)
+    const int form = keep_a ? CONV_KEEP_A : (!f.split && rows_write_through(&a.n, 1) ? CONV_WT : CONV_PLAIN);
+    return launch_rows(g_conv_fwd[tail == CF_READOUT][form], f, blk0[1], st, a);
 }
 // training turnaround: the last forward program and the first backward program of the cut rows in one launch (k_rows.hpp)
 static int launch_conv_turn(const ConvFArgs& a, const ConvBArgs& b, hipStream_t st) {
     int blk0[2];
     const int ns = 10;
-    if (rows_split(&a.n, 1, blk0)) {
-        if (blk0[1] > 0)
-            SPLIT_LAUNCH("k_conv_turn (readout + loss head + cut-row gradients)", k_conv_turn_split, blk0[1], CONV_SPLIT_LDS_FLOATS * sizeof(float), st, a, b);
-        return 0;
-    }
-    const int nwaves = rows_blocks(&a.n, &ns, 1, blk0);
-    if (blk0[1] == 0) return 0;
-    ROWS_LAUNCH("k_conv_turn (readout + loss head + cut-row gradients)", k_conv_turn<8>, k_conv_turn<4>, nwaves, blk0[1],
-                ROWS_LDS_FLOATS(5, 5) * sizeof(float), st, a, b);
-    return 0;
+    const RowsForm f = rows_form(&a.n, &ns, 1, blk0);
+    return blk0[1] > 0 ? launch_rows(g_conv_turn, f, blk0[1], st, a, b) : 0;
 }
 static int launch_conv_bwd(ConvBGroupArgs& m, hipStream_t st) {
     const int n[2] = {m.cb.n, m.tail.n}, ns[2] = {5, 2};
-    const int nwaves = rows_blocks(n, ns, 2, m.blk0);
-    if (m.blk0[2] == 0) return 0;
-    if (rows_write_through(n, 2)) ROWS_LAUNCH("k_conv_bwd", k_conv_bwd_wt<8>, k_conv_bwd_wt<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(5, 1) * sizeof(float), st, m);
-    else ROWS_LAUNCH("k_conv_bwd", k_conv_bwd<8>, k_conv_bwd<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(5, 1) * sizeof(float), st, m);
-    return 0;
+    const RowsForm f = {false, rows_blocks(n, ns, 2, m.blk0)};
+    return m.blk0[2] > 0 ? launch_rows(g_conv_bwd[rows_write_through(n, 2)], f, m.blk0[2], st, m) : 0;
 }
 static int launch_tail_bwd(TailGroupArgs& m, hipStream_t st) {
     const int n[2] = {m.a.n, m.b.n}, ns[2] = {3, 2};
-    const int nwaves = rows_blocks(n, ns, 2, m.blk0);
-    if (m.blk0[2] == 0) return 0;
-    if (rows_write_through(n, 2)) ROWS_LAUNCH("k_tail_bwd", k_tail_bwd_wt<8>, k_tail_bwd_wt<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(3, 1) * sizeof(float), st, m);
-    else ROWS_LAUNCH("k_tail_bwd", k_tail_bwd<8>, k_tail_bwd<4>, nwaves, m.blk0[2], ROWS_LDS_FLOATS(3, 1) * sizeof(float), st, m);
-    return 0;
+    const RowsForm f = {false, rows_blocks(n, ns, 2, m.blk0)};
+    return m.blk0[2] > 0 ? launch_rows(g_tail_bwd[rows_write_through(n, 2)], f, m.blk0[2], st, m) : 0;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------
@@ -759,12 +743,22 @@ static int conv_forward(const float* p, const ConvIO& c, bool save, hipStream_t 
 
 static void conv_setup(ConvIO cv[3], const gcnn_dims* d, const Work& w, const gcnn_graph* cg, const gcnn_graph* kg) {
     const Acts &A = w.a, &G = w.g;
-    cv[0] = ConvIO{P_CONV0, A.Xc, A.Xv, d->n_cons, d->n_vars, d->n_cons_edges, true, cg, P_CONS_EDGE,
-                   A.PL1, A.PR1, A.S1, A.A1, A.Z1c, A.Xc2, G.PL1, G.PR1, G.S1, G.A1, G.Z1c, G.Xc2, G.Xc, G.Xv, w.dwp[0], w.dwp2[0], w.nrow[0], w.fuse[0], w.m.Z1c, w.m.Xc2};
-    cv[1] = ConvIO{P_CONV1, A.Xc2, A.Xv, d->n_cons, d->n_vars, d->n_cons_edges, false, cg, P_CONS_EDGE,
-                   A.PL2, A.PR2, A.S2, A.A2, A.Z1v, A.Xv2, G.PL2, G.PR2, G.S2, G.A2, G.Z1v, G.Xv2, G.Xc2, G.Xv, w.dwp[1], w.dwp2[1], w.nrow[1], w.fuse[1], w.m.Z1v, w.m.Xv2};
-    cv[2] = ConvIO{P_CONV2, A.Xk, A.Xv2, d->n_cuts, d->n_vars, d->n_cut_edges, true, kg, P_CUT_EDGE,
-                   A.PL3, A.PR3, A.S3, A.A3, A.Z1k, A.Xk2, G.PL3, G.PR3, G.S3, G.A3, G.Z1k, G.Xk2, G.Xk, G.Xv2, w.dwp[2], w.dwp2[2], w.nrow[2], w.fuse[2], w.m.Z1k, w.m.Xk2};
+    ConvIO *c = &cv[0], *v = &cv[1], *k = &cv[2];   // conv v->c, conv c->v, conv v->k
+    for (int i = 0; i < 3; ++i) {
+        cv[i] = ConvIO{};
+        cv[i].DWP = w.dwp[i]; cv[i].DWP2 = w.dwp2[i]; cv[i].N = w.nrow[i]; cv[i].FZ = w.fuse[i];
+        cv[i].nl = i < 2 ? d->n_cons : d->n_cuts; cv[i].nv = d->n_vars; cv[i].ne = i < 2 ? d->n_cons_edges : d->n_cut_edges;
+        cv[i].g = i < 2 ? cg : kg; cv[i].pedge = i < 2 ? P_CONS_EDGE : P_CUT_EDGE; cv[i].recv_left = i != 1;
+    }
+    c->pbase = P_CONV0; c->xl = A.Xc; c->xv = A.Xv; c->gXL = G.Xc; c->gXV = G.Xv;
+    c->PL = A.PL1; c->PR = A.PR1; c->S = A.S1; c->A = A.A1; c->Z1 = A.Z1c; c->OUT = A.Xc2; c->mZ1 = w.m.Z1c; c->mOUT = w.m.Xc2;
+    c->gPL = G.PL1; c->gPR = G.PR1; c->gS = G.S1; c->gA = G.A1; c->gZ1 = G.Z1c; c->gOUT = G.Xc2;
+    v->pbase = P_CONV1; v->xl = A.Xc2; v->xv = A.Xv; v->gXL = G.Xc2; v->gXV = G.Xv;
+    v->PL = A.PL2; v->PR = A.PR2; v->S = A.S2; v->A = A.A2; v->Z1 = A.Z1v; v->OUT = A.Xv2; v->mZ1 = w.m.Z1v; v->mOUT = w.m.Xv2;
+    v->gPL = G.PL2; v->gPR = G.PR2; v->gS = G.S2; v->gA = G.A2; v->gZ1 = G.Z1v; v->gOUT = G.Xv2;
+    k->pbase = P_CONV2; k->xl = A.Xk; k->xv = A.Xv2; k->gXL = G.Xk; k->gXV = G.Xv2;
+    k->PL = A.PL3; k->PR = A.PR3; k->S = A.S3; k->A = A.A3; k->Z1 = A.Z1k; k->OUT = A.Xk2; k->mZ1 = w.m.Z1k; k->mOUT = w.m.Xk2;
+    k->gPL = G.PL3; k->gPR = G.PR3; k->gS = G.S3; k->gA = G.A3; k->gZ1 = G.Z1k; k->gOUT = G.Xk2;
 }
 
 static int check_common(const gcnn_dims* d, const float* params, const gcnn_graph* cg, const gcnn_graph* kg,
@@ -988,7 +982,7 @@ struct JobList {
     PendWg pend[WG_MAX_JOBS]; int npend;   // weight-gradient jobs as collected; ordered and placed by place_wg
 };
 static void add_wg(JobList& jl, const float* x, const float* sx, const float* dmat, const int* seg_ptr,
-                   int n, float* gw, float* gb, float* g2, float* /*partial*/) {
+                   int n, float* gw, float* gb, float* g2) {
     if (n <= 0) return;  // empty input: gradients are exactly zero
     jl.pend[jl.npend++] = PendWg{x, sx, dmat, seg_ptr, n, gw, gb, g2, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0};
 }
@@ -1010,7 +1004,7 @@ static void add_wg_emb2(JobList& jl, const float* x, const float* shift, const f
 // k_wgrad rotates each job's block -> row-block mapping so that (row block) = (block index) mod 8: blocks are dealt to the eight
 // XCDs round-robin, so the same rows of two adjacent jobs are read on the same XCD at about the same time and the second read
 // hits that XCD's L2 instead of going to memory.  Values do not depend on the order.
-static void place_wg(JobList& jl, float* partial) {
+static void place_wg(JobList& jl) {
     bool used[WG_MAX_JOBS] = {};
     int order[WG_MAX_JOBS], last = -1;
     for (int k = 0; k < jl.npend; ++k) {
@@ -1053,7 +1047,7 @@ static void place_wg(JobList& jl, float* partial) {
         j.nb = nb; j.rows = (cdiv(q.n, nb * WG_WAVES) + 15) & ~15;
         j.x = q.x; j.sx = q.sx; j.d = q.d; j.seg_ptr = q.seg_ptr; j.n = q.n; j.blk0 = jl.wg.nblocks; j.slab0 = jl.nslab;
         j.mask = q.mask; j.shift = q.shift; j.scale = q.scale; j.f = q.f; j.w1 = q.w1; j.b1 = q.b1; j.f2 = q.f2;
-        const float* src = partial + (size_t)jl.nslab * WG_SLAB;
+        const float* src = jl.wg.partial + (size_t)jl.nslab * WG_SLAB;
         jl.wg.nblocks += nb; jl.nslab += nb;
         auto rd = [&](const float* s, float* dst, int len) {
             RdJob& r = jl.rd.job[jl.rd.njobs++];
@@ -1109,12 +1103,12 @@ static int conv_backward_edges(const float* p, float* grads, const ConvIO& c, co
         add_rd(jl, c.DWP2, grads + poff(c.pbase + C_WE), nmc, EMB, EMB);
     }
     const int* seg = c.recv_left ? c.g->l_ptr : c.g->v_ptr;
-    add_wg(jl, c.Z1, nullptr, c.gOUT, nullptr, nr, grads + poff(c.pbase + C_W2), grads + poff(c.pbase + C_B2), nullptr, w.partial);
+    add_wg(jl, c.Z1, nullptr, c.gOUT, nullptr, nr, grads + poff(c.pbase + C_W2), grads + poff(c.pbase + C_B2), nullptr);
     // the folded layers: ONE product S^T dZ1 (-> G1) with the column sum (-> d b1) and the degree-weighted column sum (-> g2) of
     // dZ1; fold_block turns G1 | g2 into the gradients of Wf, bf and the upper half of W1 (the two-layer form needed A^T dZ1 and
     // S^T dA: two products, and A and dA in memory)
     if (nr > 0) {
-        add_wg(jl, c.S, nullptr, c.gZ1, seg, nr, nullptr, grads + poff(c.pbase + C_B1), nullptr, w.partial);
+        add_wg(jl, c.S, nullptr, c.gZ1, seg, nr, nullptr, grads + poff(c.pbase + C_B1), nullptr);
         const int k = jl.fold.n++;
         jl.pend[jl.npend - 1].fold = k + 1;
         // (the forward's copies of Wf, bf, W1a: the launch that reads them also applies Adam to the originals)
@@ -1122,9 +1116,9 @@ static int conv_backward_edges(const float* p, float* grads, const ConvIO& c, co
         jl.fold.w1a[k] = c.FZ + FUSE_W1A; jl.fold.s2[k] = p + poff(c.pbase + C_S2);
         jl.fold.gwf[k] = grads + poff(c.pbase + C_WF); jl.fold.gbf[k] = grads + poff(c.pbase + C_BF); jl.fold.gw1a[k] = grads + poff(c.pbase + C_W1);
     }
-    add_wg(jl, xrecv, nullptr, c.gZ1, nullptr, nr, grads + poff(c.pbase + C_W1) + EMB * EMB, nullptr, nullptr, w.partial);
-    add_wg(jl, c.xl, nullptr, c.gPL, nullptr, c.nl, grads + poff(c.pbase + C_WL), grads + poff(c.pbase + C_BL), nullptr, w.partial);
-    add_wg(jl, c.xv, nullptr, c.gPR, nullptr, c.nv, grads + poff(c.pbase + C_WR), nullptr, nullptr, w.partial);
+    add_wg(jl, xrecv, nullptr, c.gZ1, nullptr, nr, grads + poff(c.pbase + C_W1) + EMB * EMB, nullptr, nullptr);
+    add_wg(jl, c.xl, nullptr, c.gPL, nullptr, c.nl, grads + poff(c.pbase + C_WL), grads + poff(c.pbase + C_BL), nullptr);
+    add_wg(jl, c.xv, nullptr, c.gPR, nullptr, c.nv, grads + poff(c.pbase + C_WR), nullptr, nullptr);
     return 0;
 }
 
@@ -1187,7 +1181,7 @@ extern "C" int gcnn_backward(const gcnn_dims* d, const float* p, const float* co
     }
     add_rd(jl, w.score_partial, grads + poff(P_OUT + 2), head_parts, HEAD_SLAB, EMB);
     add_rd(jl, w.score_partial + EMB, grads + poff(P_OUT + 3), head_parts, HEAD_SLAB, 1);
-    add_wg(jl, A.Xk2, nullptr, G.O1, nullptr, d->n_cuts, grads + poff(P_OUT), grads + poff(P_OUT + 1), nullptr, w.partial);
+    add_wg(jl, A.Xk2, nullptr, G.O1, nullptr, d->n_cuts, grads + poff(P_OUT), grads + poff(P_OUT + 1), nullptr);
     auto tail = [&](TailBArgs& t, const float* in_a, const float* wa, const float* in_b, const float* wb, float* gx, const mask16* mx,
                     int pb, float* ge1, int n) {
         t.in_a = in_a; t.wa = wa; t.in_b = in_b; t.wb = wb; t.add = gx; t.m_x = mx; t.g_x = gx; t.w2 = p + poff(pb + E_W2);
@@ -1230,8 +1224,8 @@ extern "C" int gcnn_backward(const gcnn_dims* d, const float* p, const float* co
     for (int i = 0; i < 3; ++i)   // E1^T dX with E1 recomputed from the raw features: the forward pass does not store it
         add_wg_emb2(jl, em[i].x, p + poff(em[i].pb + E_SHIFT), p + poff(em[i].pb + E_SCALE), p + poff(em[i].pb + E_W1), p + poff(em[i].pb + E_B1),
                     em[i].gx, em[i].n, em[i].f, grads + poff(em[i].pb + E_W2), grads + poff(em[i].pb + E_B2));
-    place_wg(jl, w.partial);
-    if ((size_t)jl.nslab > wg_slabs(d)) return GCNN_E_WORKSPACE;
+    place_wg(jl);
+    if (jl.nslab > WG_MAX_SLABS) return GCNN_E_WORKSPACE;
     for (int k = jl.ndw; k < 3; ++k) jl.dw.blk0[k + 1] = jl.dw.blk0[k];
     if (jl.wg.nblocks + jl.dw.blk0[3] > 0) {
         static PerDeviceOnce attr;
