@@ -892,6 +892,12 @@ static int infer_layout(const gcnn_dims* d, size_t extra_in, size_t extra_out, g
     return 0;
 }
 extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) { return infer_layout(d, 0, 0, L); }
+// Edges with nothing to point at: every id of such a list is out of range, and there is no row of its own to park it on -- the
+// plan's substitute id 0 would send the forward to row 0 of an empty table (k_infer.hpp).  The calls that upload a host state
+// refuse such a state before anything is enqueued (state_call, gcnn_select.hpp; ibatch_sums, gcnn_ibatch.hpp).
+static bool edges_without_nodes(const gcnn_dims& d) {
+    return (d.n_cons_edges > 0 && (d.n_cons == 0 || d.n_vars == 0)) || (d.n_cut_edges > 0 && (d.n_cuts == 0 || d.n_vars == 0));
+}
 
 // infer_run: the graph plan and the forward pass on a state that already lies in the arena (zero block + the seven arrays at
 // L.in_off, however they got there: gcnn_infer and gcnn_infer_select upload them, gcnn_select.hpp; the LP calls build them there,

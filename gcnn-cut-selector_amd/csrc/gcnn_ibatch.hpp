@@ -34,8 +34,7 @@ static int ibatch_sums(int n_states, const gcnn_dims* dims, const int32_t* n_for
         if (d.n_cons < 0 || d.n_vars < 0 || d.n_cuts < 0 || d.n_cons_edges < 0 || d.n_cut_edges < 0 || nf < 0 || nfe < 0) return GCNN_E_BADARG;
         if (nf == 0 && nfe > 0) return GCNN_E_BADARG;
         // edges with nothing to point at: every id would be out of range and there is no node of the state's own to park them on
-        if ((d.n_cons_edges > 0 && (d.n_cons == 0 || d.n_vars == 0)) || (d.n_cut_edges > 0 && (d.n_cuts == 0 || d.n_vars == 0)))
-            return GCNN_E_UNSUPPORTED;
+        if (edges_without_nodes(d)) return GCNN_E_UNSUPPORTED;
         s.c += d.n_cons; s.v += d.n_vars; s.k += d.n_cuts; s.e1 += d.n_cons_edges; s.e2 += d.n_cut_edges; s.f += nf; s.fe += nfe;
         if (d.n_cuts <= SEL_MAX_CUTS) s.max_cuts = std::max(s.max_cuts, d.n_cuts);
         // (checked as the sums grow, so that the table's int32 entries cannot wrap)

@@ -128,6 +128,7 @@ static int state_call(const gcnn_dims* d, int32_t n_forced, int32_t n_forced_ent
     const gcnn_infer_layout& L = SL.infer;
     if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L.arena_bytes, select, p_max, p_max_ub))) return rc;
     if (!select && want_order && d->n_cuts > 4096) return GCNN_E_UNSUPPORTED;
+    if (edges_without_nodes(*d)) return GCNN_E_BADARG;   // (the Python session raises its index error for these before it gets here)
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
     gcnn_graph kg;

@@ -42,6 +42,7 @@ struct IplanArgs {
 // structure the forward reads must stay inside its arrays.  Out-of-range ids are replaced by 0 in the uploaded copy (and
 // counted as such), the by-left offset arrays arrive zero-filled with the upload (an unsorted list leaves gaps), and an
 // over-long variable segment is filled with zeros.  The flags tell the host that the scores of such a call mean nothing.
+// (Id 0 must exist for that: a state with edges but no row or no variable of its own is refused on the host, edges_without_nodes.)
 // block `bid` of blocks0 + blocks1 blocks of `nt` threads: the first blocks0 sweep the constraint list, the others the cut list
 __device__ __forceinline__ void iplan_count_body(const IplanArgs& a, const int bid, const int nt) {
     const int set = bid >= a.blocks0;

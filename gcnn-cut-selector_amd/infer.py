@@ -86,6 +86,14 @@ def check_state(inputs):
     return (c, cei, cef, v, k, kei, kef), key
 
 
+def edges_without_nodes(key):
+    """True for a state (key of `check_state`) with edges but no rows or no variables for them: every id of such a list is out of
+    range.  The single-state session raises BAD_INDEX for it on the host and the batched call hands it to that session
+    (`GCNN._admit_state`); the library refuses it as well (edges_without_nodes, gcnn_capi.hip)."""
+    n_cons, n_vars, n_cuts, e1, e2 = key
+    return bool((e1 and (n_cons == 0 or n_vars == 0)) or (e2 and (n_cuts == 0 or n_vars == 0)))
+
+
 def pack_state(buf, base, arrays, key, where, scratch):
     """Write one checked state into a staging buffer.  `buf`: writable uint8 array, `base`: its address; `where`: the byte offset
     of each of the seven arrays.  Features are cast to fp32; an edge set lands as [rows | cols] int32 and fp32 values, brought
@@ -126,6 +134,13 @@ def normalize_forced(forced, n_vars):
     return ops.pack_rows(fi, fv, int(n_forced), n_vars)
 
 
+def _carve(arena, blocks, floats):
+    """{name: host copy of the `n` 32-bit words at byte offset `off` of a device arena} for blocks = {name: (off, n)}; int32 but for
+    the names in `floats`."""
+    return {name: arena[off:off + 4 * n].view(torch.float32 if name in floats else torch.int32).cpu().numpy()
+            for name, (off, n) in blocks.items()}
+
+
 def _unsupported(rc, what):
     """True when a layout function declines the sizes (-4); any other failure raises."""
     if rc != -4:
@@ -143,6 +158,7 @@ class _Staging:
         self.in_np = self.out_np = None
         self.scratch = None
         self.layouts = {}
+        self.last = None          # what the last call left in the arena: the layout and its sizes (`last_plan`, `last_state`)
 
     def cached(self, key, make, *args):
         """The layout entry of `key`; `make(*args)` builds a missing one, or returns False where the library declines."""
@@ -243,6 +259,8 @@ class _InferenceSession(_Staging):
         """check -> layout -> pack -> call -> (scores, order | None, n_kept | None); with `forced` the call is gcnn_infer_select."""
         t0 = time.perf_counter()
         arrays, key = check_state(inputs)
+        if edges_without_nodes(key):
+            raise ValueError(BAD_INDEX)        # before anything is enqueued: the device plan has no row to park such ids on
         fshape = () if forced is None else (forced[0].size - 1, forced[1].size)
         lay = self.cached(key + fshape, _solo_layout, key, *fshape)
         if lay is False or (want_order and key[2] > 4096):
@@ -257,8 +275,19 @@ class _InferenceSession(_Staging):
         else:
             self._put_forced(SL.forced_off, forced)
             self._enqueue_wait("gcnn_infer_select", (C.byref(dims), *fshape), (float(p_max), float(p_max_ub)), timings, t0)
+        self.last = (L, key)
         return self._answer(out_off[2], out_off[0], out_off[1] if want_order else None, SL.n_kept_off if forced is not None else None,
                             key[2])
+
+    def last_plan(self):
+        """The graph plan the last call left in the arena, as host arrays by name (tests compare it with a restatement entry by
+        entry): the by-left offsets, both uploaded lists as the count step left them, the plan's counters and the device flags,
+        and the by-variable structure of the constraint edges."""
+        L, (c, v, k, e1, e2) = self.last
+        i, d, z = list(L.in_off), list(L.dev_off), L.in_off[0]
+        blocks = dict(vcount=(z, v), cursor=(z + 4 * v, v), flags=(z + 8 * v, 4), l_ptr0=(d[0], c + 1), l_ptr1=(d[1], k + 1),
+                      inds0=(i[2], 2 * e1), inds1=(i[6], 2 * e2), v_ptr=(d[2], v + 1), v_pos=(d[3], e1), v_oth=(d[4], e1), v_coef=(d[5], e1))
+        return _carve(self.arena, blocks, ("v_coef",))
 
     def run(self, inputs, want_order, timings=None):
         """Scores of ONE host state (`.rankings` from the device when `want_order`).  `timings` (optional dict): filled with the
@@ -326,6 +355,7 @@ class _BatchSession(_Staging):
             buf[in_off[9]:in_off[9] + 4] = 0
         self._enqueue_wait("gcnn_infer_batch", (len(checked), dims, nf, nfe, mode), (float(p_max), float(p_max_ub)))
         self.calls += 1
+        self.last = (L, len(checked))
         res = []
         for s in range(len(checked)):
             lo, n = 4 * k_off[s], k_off[s + 1] - k_off[s]
@@ -335,13 +365,26 @@ class _BatchSession(_Staging):
         return res
 
 
+    def last_plan(self):
+        """The union's graph plan as the last call left it in the arena, as host arrays by name (`_InferenceSession.last_plan`'s
+        counterpart): what k_ib_unpack wrote and the by-variable structure behind it."""
+        L, s = self.last
+        t, i, d = L.total, list(L.in_off), list(L.dev_off)
+        e1, e2, v = t.n_cons_edges, t.n_cut_edges, t.n_vars
+        al16 = lambda x: (x + 15) & ~15  # noqa: E731
+        l0 = i[1] + al16(16 * s)
+        blocks = dict(flags=(i[1], 4 * s), l_ptr0=(l0, t.n_cons + 1), l_ptr1=(l0 + al16(4 * (t.n_cons + 1)), t.n_cuts + 1),
+                      left=(d[0], e1), var0=(d[1], e1), var1=(d[2], e2), iota=(d[3], e1), v_ptr=(d[6], v + 1), v_oth=(d[7], e1),
+                      v_coef=(d[8], e1), f_col=(d[9], L.n_forced_entries))
+        return _carve(self.arena, blocks, ("v_coef",))
+
+
 class _LPSession(_Staging):
     """Host side of the calls that start from a raw LP snapshot (lpstate.py): gcnn_lp_infer / gcnn_lp_infer_select -- one upload of
     the packed snapshot, the state built in the arena, one download -- and gcnn_lp_state, which leaves the state in device tensors."""
     def __init__(self, model):
         super().__init__(model)
         self.deep_check = False   # True: the O(nnz) facts are checked on the host as well (lpstate.check_snapshot)
-        self.last = None          # (layout, state key) of the last single call
 
     @staticmethod
     def _layout(dims, n_forced, n_entries):
@@ -429,7 +472,6 @@ class _LPBatchSession(_Staging):
         super().__init__(model)
         self.calls = 0            # C calls made (tools and tests read it)
         self.deep_check = False   # as _LPSession.deep_check
-        self.last = None          # (layout, state keys) of the last call
 
     def check(self, snap):
         """-> (arrays, dims) of `lpstate.check_snapshot`."""

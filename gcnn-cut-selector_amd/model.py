@@ -22,7 +22,7 @@ import torch
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
 from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPSession, _UseGeneralPath,
-                    check_feature_shapes, check_state, is_host_state, n_selected, normalize_forced, stable_ranking)
+                    check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
 
 EMB = 64
 
@@ -563,9 +563,8 @@ class GCNN:
         if not is_host_state(st) or len(st) != 10:
             return None                     # device tensors, prepared batches, malformed tuples: the solo path answers (or raises)
         arrays, key = check_state(st)
-        n_cons, n_vars, n_cuts, e1, e2 = key
-        declined = (n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096)
-                    or (e1 and (n_cons == 0 or n_vars == 0)) or (e2 and n_vars == 0))
+        n_cuts = key[2]
+        declined = n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096) or edges_without_nodes(key)
         return None if declined else (arrays, key)
 
     def _many(self, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0, lp=False):

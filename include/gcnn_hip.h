@@ -179,7 +179,9 @@ int gcnn_mse_loss(const float* scores, const float* targets, int32_t n, float sc
  *          [0] an edge index out of range, [1] / [2] constraint / cut edges not sorted by row, [3] a variable with more than
  *          2,048 edges.  Any flag set => the scores are NOT valid: raise on [0], otherwise use gcnn_graph_build + gcnn_forward.
  * arena    (device, 256-byte aligned, arena_bytes): inputs, plan, outputs and the forward workspace; caller-owned, reusable.
- * Returns GCNN_E_UNSUPPORTED for more than 32,768 variables (or want_order with more than 4,096 cuts). */
+ * Returns GCNN_E_UNSUPPORTED for more than 32,768 variables (or want_order with more than 4,096 cuts), and GCNN_E_BADARG, before
+ * anything is enqueued, for a state that has edges but no row or no variable they could refer to (every id of it is out of range,
+ * and the plan has no row of the state's own to park such ids on). */
 typedef struct gcnn_infer_layout {
     size_t in_bytes, in_off[8];
     size_t out_bytes, out_off[3];

@@ -26,6 +26,28 @@ def oracle_scores(params, state):
     return O.scores({k: v.astype(np.float64) for k, v in params.items()}, state, torch.float64)
 
 
+def union_of(inputs):
+    """utils.collate of host states -> the model's 10-tuple with total counts, and the cut offsets."""
+    from gcnn_cut_selector_amd import utils
+    samples = [(({"values": c}, {"indices": cei, "values": cef}, {"values": v}, {"values": k}, {"indices": kei, "values": kef}),
+                np.zeros(nk)) for c, cei, cef, v, k, kei, kef, nc, nv, nk in inputs]
+    b = utils.collate(samples)
+    return b[:7] + (int(b[7].sum()), int(b[8].sum()), int(b[9].sum())), np.concatenate([[0], np.cumsum(b[9])]).astype(np.int32)
+
+
+def general_batch(m, inputs):
+    """prepare() of the collated union, in the batch call's state of knowledge: gcnn_infer_batch does not know the union's longest
+    segments (l_max_deg = v_max_deg = 0, "unknown": the edge passes' long-segment launch always runs), while a prepared Batch adopts
+    them whenever their asynchronous copy happens to have landed.  The comparison graphs are therefore pinned to "unknown" too,
+    so both sides issue the same launches whatever the timing -- the equality itself stays exact."""
+    union, k_off = union_of(inputs)
+    batch = m.prepare(union)
+    for g in (batch.cons_graph, batch.cut_graph):
+        g._md_ticket, g.l_max_deg, g.v_max_deg = None, 0, 0
+        g._bind()
+    return batch, k_off
+
+
 def prenorm_stats(m, batch, ws, layer):
     """(mean[units], variance[units]) of one PreNorm layer's input from gcnn_prenorm_stats, as fp64 host arrays."""
     import ctypes as C

@@ -14,7 +14,7 @@ from gcnn_cut_selector_amd import _lib, ops, synthetic, utils  # noqa: E402
 from gcnn_cut_selector_amd.graph import BipartiteGraph  # noqa: E402
 from gcnn_cut_selector_amd.model import SelectResult  # noqa: E402
 
-from gpucommon import dev, make_model, oracle_scores as _oracle  # noqa: E402
+from gpucommon import dev, general_batch as _general_batch, make_model, oracle_scores as _oracle  # noqa: E402
 
 PROBLEMS = ("setcov", "combauc", "capfac", "indset")
 SCALES = (0.2, 1.0, 0.5)
@@ -34,27 +34,6 @@ def _mixed(S, first=0):
         keep = kei[0] == 0
         out[2] = (c, cei, cef, v, k[:1], kei[:, keep], kef[keep], nc, nv, 1)
     return out
-
-
-def _union(inputs):
-    """utils.collate of the same states -> the model's 10-tuple with total counts, and the cut offsets."""
-    samples = [(({"values": c}, {"indices": cei, "values": cef}, {"values": v}, {"values": k}, {"indices": kei, "values": kef}),
-                np.zeros(nk)) for c, cei, cef, v, k, kei, kef, nc, nv, nk in inputs]
-    b = utils.collate(samples)
-    return b[:7] + (int(b[7].sum()), int(b[8].sum()), int(b[9].sum())), np.concatenate([[0], np.cumsum(b[9])]).astype(i32)
-
-
-def _general_batch(m, inputs):
-    """prepare() of the collated union, in the batch call's state of knowledge: gcnn_infer_batch does not know the union's longest
-    segments (l_max_deg = v_max_deg = 0, "unknown": the edge passes' long-segment launch always runs), while a prepared Batch adopts
-    them whenever their asynchronous copy happens to have landed.  The comparison graphs are therefore pinned to "unknown" too,
-    so both sides issue the same launches whatever the timing -- the equality itself stays exact."""
-    union, k_off = _union(inputs)
-    batch = m.prepare(union)
-    for g in (batch.cons_graph, batch.cut_graph):
-        g._md_ticket, g.l_max_deg, g.v_max_deg = None, 0, 0
-        g._bind()
-    return batch, k_off
 
 
 class _Spy:
