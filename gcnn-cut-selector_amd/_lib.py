@@ -89,6 +89,23 @@ class LpBatchLayout(C.Structure):
                 ("out_dev_off", C.c_size_t), ("scratch_off", C.c_size_t), ("scratch_base", C.c_size_t * IBATCH_MAX)]
 
 
+HYBRID_ARRAYS = 8   # GCNN_HYBRID_ARRAYS
+HYBRID_QUALITY, HYBRID_RANK, HYBRID_SELECT = 0, 1, 2
+
+
+class HybridDims(C.Structure):
+    _fields_ = [("n_cols", C.c_int32), ("n_cuts", C.c_int32), ("cut_nnz", C.c_int32), ("reserved", C.c_int32), ("infinity", C.c_double)]
+
+
+class HybridLayout(C.Structure):
+    _fields_ = [("n_snapshots", C.c_int32), ("total_cuts", C.c_int32), ("total_nnz", C.c_int32), ("max_cuts", C.c_int32),
+                ("max_cols", C.c_int32), ("n_forced", C.c_int32), ("n_forced_entries", C.c_int32), ("reserved", C.c_int32),
+                ("table_bytes", C.c_size_t), ("in_bytes", C.c_size_t), ("snap_off", (C.c_size_t * HYBRID_ARRAYS) * IBATCH_MAX),
+                ("forced_off", C.c_size_t * 3), ("out_bytes", C.c_size_t), ("out_off", C.c_size_t * 5), ("arena_bytes", C.c_size_t),
+                ("out_dev_off", C.c_size_t), ("rows_off", C.c_size_t * 3), ("ws_off", C.c_size_t), ("scratch_off", C.c_size_t),
+                ("scratch_base", C.c_size_t * IBATCH_MAX)]
+
+
 GROUP_MAX = 8   # GCNN_GROUP_MAX
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
@@ -154,6 +171,9 @@ SIGNATURES = {
     "gcnn_lp_batch_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(LpBatchLayout)]),
     "gcnn_lp_batch_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P]),
     "gcnn_lp_batch": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _D, _D, _P]),
+    "gcnn_hybrid_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(HybridLayout)]),
+    "gcnn_hybrid_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P]),
+    "gcnn_hybrid_select": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _Z, _D, _D, _P]),
 }
 
 _lib = None

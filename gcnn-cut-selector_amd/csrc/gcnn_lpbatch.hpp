@@ -149,3 +149,7 @@ extern "C" int gcnn_lp_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t*
     HIPCHK(hipMemcpyAsync(host_out, at.out, L.out_bytes, hipMemcpyDeviceToHost, st));
     return 0;
 }
+
+// the cut-row path shares this file's table conventions and nothing of its state (tests/test_lpbatch_build.py pins the chain of
+// includes down to here: gcnn_capi.hip ends with gcnn_ibatch.hpp, that one with this file)
+#include "gcnn_hybrid.hpp"

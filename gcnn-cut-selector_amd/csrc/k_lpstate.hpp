@@ -118,6 +118,57 @@ __device__ __forceinline__ void lp_chunk_prefix(const int* part, int n_chunks, i
     __syncthreads();
 }
 
+// What the cut-row path (k_hybrid.hpp) shares with this one, so that both hold the same bits.
+// The sums of one row or cut over its entries [beg, end): the LP_SUB lanes of the row stride over them and lp_sub_sum adds the
+// lanes in its fixed order.  A row takes n2 and dob only; a cut also act, the integer support and, with an incumbent, ddir.
+// The violations met on the way are ORed into flag.
+struct LpRowSums { double n2, act, dob, ddir; int nint; };
+__device__ __forceinline__ LpRowSums lp_row_sums(const int* col, const double* val, int beg, int end, int l, int V, bool rows,
+                                                 bool has_inc, const double* col_obj, const double* col_lp,
+                                                 const double* col_primal, const signed char* col_type, int& flag) {
+    double n2 = 0.0, act = 0.0, dob = 0.0, ddir = 0.0; int nint = 0;
+    for (int e = beg + l; e < end; e += LP_SUB) {
+        const int c = col[e]; const double v = val[e];
+        if (e > beg && col[e - 1] >= c) flag |= 1 << LP_F_ORDER;
+        n2 += v * v;
+        if (c < 0 || c >= V) { flag |= 1 << LP_F_COLUMN; continue; }
+        dob += v * col_obj[c];
+        if (!rows) {
+            const double x = col_lp[c];
+            act += v * x;
+            if (has_inc) ddir += v * (col_primal[c] - x);
+            nint += col_type[c] != 3;
+        }
+    }
+    LpRowSums s;
+    s.n2 = lp_sub_sum(n2); s.dob = lp_sub_sum(dob); s.act = 0.0; s.ddir = 0.0; s.nint = 0;
+    if (!rows) { s.act = lp_sub_sum(act); s.ddir = lp_sub_sum(ddir); s.nint = lp_sub_sum(nint); }
+    return s;
+}
+
+// A column norm from the per-chunk partial sums part[stride * i], i < n_chunks: strided over the threads, then the block tree.  Every
+// block that calls it adds the same partials in the same order and holds identical bits.  s: LP_NT doubles.
+__device__ __forceinline__ double lp_part_norm(const double* part, int stride, int n_chunks, double* s) {
+    double x = 0.0;
+    for (int i = threadIdx.x; i < n_chunks; i += LP_NT) x += part[(size_t)stride * i];
+    return sqrt(lp_block_sum(x, s));
+}
+
+// The three fp64 features of a cut that the hybrid rule adds up, from its sums: what cut_feats[:, 3], [:, 2] and [:, 5] round.
+struct LpCutTerms { double norm, feas, efficacy, int_support, parallelism; };
+__device__ __forceinline__ LpCutTerms lp_cut_terms(double n2, double act, double dob, int nint, int len, double lo, double hi,
+                                                   double objn) {
+    LpCutTerms f;
+    const double raw = sqrt(n2);
+    f.norm = raw == 0.0 ? 1.0 : raw;
+    f.feas = fmin(hi - act, act - lo);
+    f.efficacy = -f.feas / f.norm;
+    f.int_support = (double)nint / (double)len;
+    const double prod = raw * objn;
+    f.parallelism = prod == 0.0 ? 0.0 : fabs(dob) / prod;
+    return f;
+}
+
 // The two launches' bodies as functions of (arguments, block index within the snapshot's share of the launch): the solo kernels
 // below run them on their own grid, k_lpbatch.hpp's kernels on each snapshot's share of one grid.  Everything that depends on the
 // block partition -- the chunking in 256s, the pre[] / tot[] terms, the order of the column partials -- is a function of these two
@@ -167,22 +218,9 @@ __device__ __forceinline__ void lp_stats_body(const LpArgs& a, const int blk) {
         int beg = 0, end = 0; bool bad = false;
         if (r < n) lp_row_range(ptr, r, nnz, beg, end, bad);
         if (bad) flag |= 1 << LP_F_OFFSETS;
-        double n2 = 0.0, act = 0.0, dob = 0.0, ddir = 0.0; int nint = 0;
-        for (int e = beg + l; e < end; e += LP_SUB) {
-            const int c = col[e]; const double v = val[e];
-            if (e > beg && col[e - 1] >= c) flag |= 1 << LP_F_ORDER;
-            n2 += v * v;
-            if (c < 0 || c >= a.V) { flag |= 1 << LP_F_COLUMN; continue; }
-            dob += v * a.col_obj[c];
-            if (!rows) {
-                const double x = a.col_lp[c];
-                act += v * x;
-                if (a.has_inc) ddir += v * (a.col_primal[c] - x);
-                nint += a.col_type[c] != 3;
-            }
-        }
-        n2 = lp_sub_sum(n2); dob = lp_sub_sum(dob);
-        if (!rows) { act = lp_sub_sum(act); ddir = lp_sub_sum(ddir); nint = lp_sub_sum(nint); }
+        const LpRowSums m = lp_row_sums(col, val, beg, end, l, a.V, rows, a.has_inc != 0, a.col_obj, a.col_lp, a.col_primal,
+                                        a.col_type, flag);
+        const double n2 = m.n2, act = m.act, dob = m.dob, ddir = m.ddir; const int nint = m.nint;
         if (l == 0 && r < n) {
             const int len = end - beg;
             const double lo = lhs[r], hi = rhs[r];
@@ -247,10 +285,8 @@ __device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
     if (!rows) {                                       // |col_obj| and |primal - lp|: the column chunks' sums in a fixed order.
         // Every cut block recomputes both from the same partials in the same order, so all blocks hold identical bits; nothing
         // is shared between blocks (one block computing them for all would need a third launch).
-        double o2 = 0.0, d2 = 0.0;
-        for (int i = t; i < a.ncc; i += LP_NT) { o2 += a.col_part[2 * i]; d2 += a.col_part[2 * i + 1]; }
-        objn = sqrt(lp_block_sum(o2, sd));
-        dirn = sqrt(lp_block_sum(d2, sd));
+        objn = lp_part_norm(a.col_part, 2, a.ncc, sd);
+        dirn = lp_part_norm(a.col_part + 1, 2, a.ncc, sd);
     }
     const int r = b * LP_NT + t;
     int beg = 0, end = 0; bool bad = false;
@@ -283,24 +319,22 @@ __device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
                 ((float4*)a.cons_feats)[pos_r] = make_float4((float)(hi / norm), bs == 2, (float)cosine, (float)dual);
         } else {
             const double* s = a.cut_stat + 4 * (size_t)r;
-            const double act = s[1];
-            const double feas = fmin(hi - act, act - lo);
+            const LpCutTerms f64 = lp_cut_terms(s[0], s[1], s[2], a.cut_aux[2 * r], len, lo, hi, objn);
             double cutoff = 0.0;
             if (a.has_inc) {
                 double d = dirn > 0.0 ? s[3] / dirn : 0.0;
                 if (fabs(d) <= a.eps) d = copysign(a.eps, d);
-                cutoff = fmin(-feas / fabs(d), a.infinity);
+                cutoff = fmin(-f64.feas / fabs(d), a.infinity);
             }
-            const double prod = raw * objn;
             const int pos = has_l ? pos_l : pos_r;
             if (lp_in(pos, n_left)) {
                 float* f = a.cut_feats + (size_t)pos * 6;
                 f[0] = (float)(has_l ? -(lo / norm) : hi / norm);
                 f[1] = (float)((double)len / (double)a.n_model_vars);
-                f[2] = (float)((double)a.cut_aux[2 * r] / (double)len);
-                f[3] = (float)(-feas / norm);
+                f[2] = (float)f64.int_support;
+                f[3] = (float)f64.efficacy;
                 f[4] = (float)cutoff;
-                f[5] = (float)(prod == 0.0 ? 0.0 : fabs(s[2]) / prod);
+                f[5] = (float)f64.parallelism;
                 a.cut_index[pos] = r;
             }
         }

@@ -177,14 +177,19 @@ __device__ int sel_remove(int* ord, int* tmp, int* scan, int K, int n, Flag flag
     return total;
 }
 
-__global__ __launch_bounds__(SEL_NT) void k_sel_filter(SelArgs a) {
-    __shared__ float v[SEL_MAX_CUTS];
+// The filter of one sample (block s) over a key of type T: q holds the stacked qualities (a.q is not read), compared as they are --
+// an fp64 key is never narrowed.  k_sel_filter runs it on the model's fp32 scores, k_hyb_filter (k_hybrid.hpp) on the fp64 hybrid
+// quality.  filter = false stops behind the ranking: order = the ranking, n_kept = K, no pair bit is read.
+// LDS: (12 + sizeof(T)) * SEL_MAX_CUTS + a few words -- 52 KiB for fp32, 68 KiB for fp64: two blocks per CU either way.
+template <class T>
+__device__ __forceinline__ void sel_filter_body(const SelArgs& a, const T* q, const int s, const bool filter) {
+    __shared__ T v[SEL_MAX_CUTS];
     __shared__ int ord[SEL_MAX_CUTS];
     __shared__ int tmp[SEL_MAX_CUTS];
     __shared__ unsigned char low[SEL_MAX_CUTS];
     __shared__ int scan[SEL_NW];
     __shared__ int best;
-    const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c0 = sel_off(a.c_off, s, a.total_cuts), K = sel_off(a.c_off, s + 1, a.total_cuts) - c0;
     const int f0 = sel_off(a.f_off, s, a.total_forced), F = sel_off(a.f_off, s + 1, a.total_forced) - f0;
     if (K > a.max_cuts || K < 0) {
@@ -195,11 +200,17 @@ __global__ __launch_bounds__(SEL_NT) void k_sel_filter(SelArgs a) {
         if (threadIdx.x == 0) a.n_kept[s] = 0;
         return;
     }
-    rank_desc_lds<SEL_NT>(a.q + c0, K, v, ord);
-    // low-quality flags by POSITION, from the raw scores in ranked order: Q[p] < t in fp32, t = fp32(0.9 * double(Q[0]))
-    // (NumPy 1.22: 0.9 * a float32 scalar is a float64; comparing the float32 array with it rounds it to float32)
-    const float t = (float)(0.9 * (double)a.q[c0 + ord[0]]);
-    for (int p = threadIdx.x; p < K; p += SEL_NT) low[p] = a.q[c0 + ord[p]] < t;
+    rank_desc_lds<SEL_NT>(q + c0, K, v, ord);
+    if (!filter) {
+        for (int p = threadIdx.x; p < K; p += SEL_NT) a.order[c0 + p] = ord[p];
+        if (threadIdx.x == 0) a.n_kept[s] = K;
+        return;
+    }
+    // low-quality flags by POSITION, from the raw scores in ranked order: Q[p] < t in T, t = T(0.9 * double(Q[0]))
+    // (NumPy 1.22: 0.9 * a float32 scalar is a float64; comparing the float32 array with it rounds it to float32.  A float64
+    // array is compared with the float64 product as it is.)
+    const T t = (T)(0.9 * (double)q[c0 + ord[0]]);
+    for (int p = threadIdx.x; p < K; p += SEL_NT) low[p] = q[c0 + ord[p]] < t;
     __syncthreads();
     const unsigned long long* bits = a.bits + (size_t)(c0 + f0) * a.words * 2;
     const int words = a.words;
@@ -242,3 +253,5 @@ __global__ __launch_bounds__(SEL_NT) void k_sel_filter(SelArgs a) {
     for (int p = threadIdx.x; p < K; p += SEL_NT) a.order[c0 + p] = ord[p];
     if (threadIdx.x == 0) a.n_kept[s] = n;
 }
+
+__global__ __launch_bounds__(SEL_NT) void k_sel_filter(SelArgs a) { sel_filter_body<float>(a, a.q, blockIdx.x, true); }

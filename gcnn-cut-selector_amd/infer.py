@@ -30,6 +30,8 @@ class SelectResult:
     """What `GCNN.select_cuts` returns: `order` (int32 cut indices in STATE order: the kept cuts first, best first, then the
     removed ones), `n_selected` = min(n_kept, max_selected) -- the reference's 'nselectedcuts' --, `n_kept` and the `scores`."""
 
+    features = None       # `HybridSelector` (hybrid.py): [K, 3] float64 efficacy, integer support, objective parallelism
+
     def __init__(self, order, n_kept, n_selected, scores, cut_index=None):
         self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
         self.cut_index = cut_index     # `select_cuts_lp`: state position -> input cut, so cut_index[order[:n_selected]] are the inputs

@@ -140,6 +140,55 @@ def check_snapshot(snap: LPSnapshot, deep: bool = True):
     return arrays, dims
 
 
+# ---- the cuts alone: what the hybrid selection reads (hybrid.py, csrc/k_hybrid.hpp) ------------------------------------------------
+CUT_FIELDS = (("cut_ptr", np.int32), ("cut_col", np.int32), ("cut_val", np.float64), ("cut_lhs", np.float64), ("cut_rhs", np.float64),
+              ("col_type", np.int8), ("col_obj", np.float64), ("col_lp", np.float64))      # GCNN_HYBRID_* order
+
+
+@dataclass
+class CutSnapshot:
+    """The eight arrays of an `LPSnapshot` that SCIP's hybrid cut quality and the parallelism filter need, under the same contract:
+    the cuts as CSR over LP column positions (`cut_ptr`, `cut_col`, `cut_val`, `cut_lhs`, `cut_rhs`; columns strictly increasing
+    within a cut, every cut has an entry, constants already in lhs / rhs) and per column `col_type`, `col_obj`, `col_lp`.
+    An `LPSnapshot` is accepted wherever a `CutSnapshot` is."""
+    cut_ptr: np.ndarray
+    cut_col: np.ndarray
+    cut_val: np.ndarray
+    cut_lhs: np.ndarray
+    cut_rhs: np.ndarray
+    col_type: np.ndarray
+    col_obj: np.ndarray
+    col_lp: np.ndarray
+    infinity: float = 1e20
+
+
+def check_cut_snapshot(snap, deep: bool = True):
+    """`check_snapshot` for the fields of a `CutSnapshot` (or of an `LPSnapshot`: its other fields are not looked at) -> (the
+    eight arrays in packed order with their packed dtypes, dims) where dims is the dict of `_lib.HybridDims` fields."""
+    arrays = []
+    for name, dt in CUT_FIELDS:
+        a = np.asarray(getattr(snap, name))
+        if a.dtype != dt:
+            if dt != np.float64 and a.size and a.dtype.kind in "iu" and (int(a.max()) > np.iinfo(dt).max or int(a.min()) < np.iinfo(dt).min):
+                raise ValueError(f"{name}: a value does not fit {np.dtype(dt).name}")
+            a = a.astype(dt)
+        arrays.append(np.ascontiguousarray(a))
+    cut_ptr, cut_col, cut_val, cut_lhs, cut_rhs, col_type, col_obj, col_lp = arrays
+    infinity = float(snap.infinity)
+    if not infinity > 0:
+        raise ValueError("infinity must be positive")
+    V, K = col_type.shape[0], cut_lhs.shape[0]
+    for name, a, n in (("cut_lhs", cut_lhs, K), ("cut_rhs", cut_rhs, K), ("col_type", col_type, V), ("col_obj", col_obj, V), ("col_lp", col_lp, V)):
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"{name} must be a vector of {n} values, got shape {tuple(a.shape)}")
+    if col_type.size and (int(col_type.min()) < 0 or int(col_type.max()) > 3):
+        raise ValueError("col_type: codes are 0..3")
+    nnz = _check_csr("cut", cut_ptr, cut_col, cut_val, K, V, deep)
+    if K and np.any(cut_ptr[1:] == cut_ptr[:-1]):
+        raise ValueError("every cut must have at least one entry")
+    return arrays, dict(n_cols=V, n_cuts=K, cut_nnz=nnz, reserved=0, infinity=infinity)
+
+
 def state_key(dims):
     """(n_cons, n_vars, n_cuts, E1, E2) of the state a snapshot of these dims builds."""
     return dims["n_state_rows"], dims["n_cols"], dims["n_cuts"], dims["n_state_edges"], dims["cut_nnz"]

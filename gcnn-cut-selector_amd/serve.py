@@ -9,7 +9,9 @@ worker, one selector call per separation round) share ONE process that owns the 
 The server takes every request that is waiting, groups them by model and kind, answers each group with one
 `GCNN.score_states` / `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP
 kinds one `GCNN.score_lps` / `GCNN.select_cuts_lp_many` call, which also builds the states on the device -- and goes back
-for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.
+for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
+hybrid quality from the cut rows, `client.select_cuts_hybrid`) need no model: those that are waiting are grouped by thresholds and
+answered with one `HybridSelector.select_cuts_many`.
 
 Wire format (AF_UNIX stream; little-endian; no pickle -- nothing a peer sends is ever executed): a message is a uint32 byte count
 followed by that many bytes: a fixed header, the model key, then arrays, each a 24-byte descriptor (dtype code, ndim, two
@@ -34,6 +36,11 @@ KIND_SCORE, KIND_RANK, KIND_SELECT = 0, 1, 2
 # there is an incumbent.  Replies carry cut_index as one more array.
 KIND_LP_SCORE, KIND_LP_RANK, KIND_LP_SELECT = 3, 4, 5
 _LP_BASE = {KIND_LP_SCORE: KIND_SCORE, KIND_LP_RANK: KIND_RANK, KIND_LP_SELECT: KIND_SELECT}
+# SCIP's hybrid selection from the cut rows alone (hybrid.HybridSelector; no model: the model key is ignored): the eight arrays of a
+# lpstate.CutSnapshot, one float64 array with `infinity`, then the optional forced pair.  Replies carry the float64 quality, order,
+# cut_index (the identity) and the features [K, 3].
+KIND_HYBRID_SELECT = 6
+_HYBRID_ARRAYS = len(lpstate.CUT_FIELDS) + 1
 _PRIMAL = (14, 15)         # positions of col_primal / col_primal_avg among lpstate.FIELDS
 MAX_MESSAGE = 1 << 30
 # request: magic, kind, n_arrays, key length, p_max, p_max_ub, max_selected (-1: none), n_forced (-1: no forced rows), n_cons, n_vars, n_cuts
@@ -131,6 +138,27 @@ def encode_lp_request(model_key, kind, snapshot, forced=None, p_max=0.1, p_max_u
     return b"".join(parts)
 
 
+def encode_hybrid_request(model_key, snapshot, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
+    """-> the message's bytes of a hybrid selection request.  `snapshot`: a `lpstate.CutSnapshot` or `LPSnapshot`, checked here as
+    the server will check it again (without the O(nnz) facts), so its ValueError is raised in the worker."""
+    arrays, dims = lpstate.check_cut_snapshot(snapshot, deep=False)
+    arrays = list(arrays) + [np.array([dims["infinity"]], np.float64)]
+    n_forced, pair = _forced_pair(forced)
+    key = model_key.encode("utf-8")
+    parts = [_REQ.pack(MAGIC, KIND_HYBRID_SELECT, len(arrays) + len(pair), len(key), float(p_max), float(p_max_ub),
+                       -1 if max_selected is None else int(max_selected), n_forced, 0, 0, 0), key]
+    _put_arrays(parts, arrays + pair)
+    return b"".join(parts)
+
+
+def _decode_hybrid(arrays, n_forced):
+    scalars = arrays[_HYBRID_ARRAYS - 1]
+    if scalars.dtype != np.float64 or scalars.shape != (1,):
+        raise ProtocolError("malformed snapshot scalars")
+    snap = lpstate.CutSnapshot(**dict(zip((n for n, _ in lpstate.CUT_FIELDS), arrays)), infinity=float(scalars[0]))
+    return snap, ((arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
+
+
 def _decode_lp(arrays, inc, n_forced):
     names = [n for i, (n, _) in enumerate(lpstate.FIELDS) if inc or i not in _PRIMAL]
     scalars = arrays[len(names)]
@@ -147,8 +175,9 @@ def decode_request(buf):
         raise ProtocolError("truncated header")
     magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, n_cons, n_vars, n_cuts = _REQ.unpack_from(buf, 0)
     lp = kind in _LP_BASE
-    expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else 7) + (2 if n_forced >= 0 else 0)
-    if magic != MAGIC or kind > KIND_LP_SELECT or n_arrays != expected or (lp and n_cons not in (0, 1)):
+    hybrid = kind == KIND_HYBRID_SELECT
+    expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0)
+    if magic != MAGIC or kind > KIND_HYBRID_SELECT or n_arrays != expected or (lp and n_cons not in (0, 1)):
         raise ProtocolError("not a request of this protocol")
     at = _REQ.size + key_len
     if at > len(buf):
@@ -157,8 +186,8 @@ def decode_request(buf):
     arrays, at = _get_arrays(buf, at, n_arrays)
     if at != len(buf):
         raise ProtocolError("trailing bytes")
-    if lp:
-        snap, forced = _decode_lp(arrays, n_cons, n_forced)
+    if lp or hybrid:
+        snap, forced = _decode_hybrid(arrays, n_forced) if hybrid else _decode_lp(arrays, n_cons, n_forced)
         return dict(model_key=key, kind=kind, snapshot=snap, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
                     max_selected=None if max_selected < 0 else max_selected)
     return dict(model_key=key, kind=kind, state=tuple(arrays[:7]) + (n_cons, n_vars, n_cuts),
@@ -220,6 +249,8 @@ class Selection:
     """`order` (kept cuts first, best first, then the removed ones), `n_kept`, `n_selected` = min(n_kept, max_selected), `scores`;
     from `select_cuts_lp` also `cut_index`: `cut_index[order[:n_selected]]` are the selected input cuts."""
 
+    features = None       # from `select_cuts_hybrid`: [K, 3] float64 efficacy, integer support, objective parallelism
+
     def __init__(self, order, n_kept, n_selected, scores, cut_index=None):
         self.order, self.n_kept, self.n_selected, self.scores, self.cut_index = order, n_kept, n_selected, scores, cut_index
 
@@ -261,6 +292,14 @@ class ScoringClient:
                                                                   max_selected))
         return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
 
+    def select_cuts_hybrid(self, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        """`HybridSelector.select_cuts` behind the server: SCIP's hybrid quality (float64, input cut order) and the parallelism
+        filter from a `lpstate.CutSnapshot` or `LPSnapshot`.  The `Selection` also carries `.features` [K, 3]."""
+        arrays, n_kept, n_selected = self._call(encode_hybrid_request(self.model_key, snapshot, forced, p_max, p_max_ub, max_selected))
+        res = Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
+        res.features = arrays[3]
+        return res
+
     def get_concrete_function(self):
         """The `(state10, training) -> scores` callable `CustomCutsel(function=...)` stores (model_evaluator.py:310-314)."""
         def get_improvements(state, training=False, rank=False):
@@ -296,6 +335,13 @@ class ScoringServer:
         self._closing = False
         self._thread = None
         self._buffers = {}
+        self._hybrid = None            # the HybridSelector, built on first use on the device of the first model
+
+    def _hybrid_selector(self):
+        if self._hybrid is None:
+            from .hybrid import HybridSelector
+            self._hybrid = HybridSelector(next(iter(self.models.values())).device)
+        return self._hybrid
 
     def start(self):
         self._thread = threading.Thread(target=self.serve_forever, name="gcnn-scoring-server", daemon=True)
@@ -366,7 +412,7 @@ class ScoringServer:
             self.stats["requests"] += 1
             try:
                 req = decode_request(message)
-                if req["model_key"] not in self.models:
+                if req["kind"] != KIND_HYBRID_SELECT and req["model_key"] not in self.models:
                     raise KeyError(f"no model {req['model_key']!r}")
                 pending.append((conn, req))
             except Exception as exc:  # noqa: BLE001 -- a bad request gets its error; the server keeps serving
@@ -376,18 +422,24 @@ class ScoringServer:
     def _serve(self, pending):
         groups = {}
         for conn, req in pending:
-            selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT)
-            gkey = (req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
+            selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT, KIND_HYBRID_SELECT)
+            hybrid = req["kind"] == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
+            gkey = (None if hybrid else req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
             groups.setdefault(gkey, []).append((conn, req))
         for gkey, items in groups.items():
-            model, lp = self.models[gkey[0]], gkey[1] in _LP_BASE
-            kind = _LP_BASE.get(gkey[1], gkey[1])
+            hybrid = gkey[1] == KIND_HYBRID_SELECT
+            lp = gkey[1] in _LP_BASE or hybrid
+            kind = KIND_SELECT if hybrid else _LP_BASE.get(gkey[1], gkey[1])
             states = [r["snapshot" if lp else "state"] for _, r in items]
-            score_many, select_many = (model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)
             self.stats["calls"] += 1
             self.stats["batched_calls"] += len(items) > 1
             self.stats["max_batch"] = max(self.stats["max_batch"], len(items))
             try:
+                if hybrid:
+                    score_many, select_many = None, self._hybrid_selector().select_cuts_many
+                else:
+                    model = self.models[gkey[0]]
+                    score_many, select_many = (model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)
                 if kind == KIND_SELECT:
                     results = select_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3], return_exceptions=True)
                 else:
@@ -403,6 +455,7 @@ class ScoringServer:
                 elif kind == KIND_SELECT:
                     arrays = [np.asarray(res.scores), np.asarray(res.order, np.int32)]
                     arrays += [np.asarray(res.cut_index, np.int32)] if lp else []
+                    arrays += [np.asarray(res.features, np.float64)] if hybrid else []
                     self._reply(conn, encode_reply(arrays, res.n_kept, _n_selected(res.n_kept, req["max_selected"])))
                 else:
                     arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if kind == KIND_RANK else [])

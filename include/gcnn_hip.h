@@ -561,6 +561,73 @@ int gcnn_lp_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, 
                   const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
                   double p_max_ub, void* stream);
 
+/* ---- hybrid cut selection from cut rows: SCIP's hybrid quality and the parallelism filter, no LP rows, no model -----------------
+ * The `function=None` arm of the reference's selector (model_evaluator.py:104-154), the baseline arm of model_benchmarker.py and
+ * every non-expert round of data_collector.py:145-195, for 1..GCNN_IBATCH_MAX snapshots in ONE host->device copy, at most four
+ * launches whatever n is, ONE device->host copy.  Nothing is synchronised, nothing allocated.
+ * Input per snapshot (the gcnn_lp_state contract for these fields): the cuts as CSR over LP column positions (cut_ptr, cut_col,
+ * cut_val, cut_lhs, cut_rhs; columns strictly increasing within a cut, every cut has an entry, constants already in lhs / rhs), the
+ * columns' col_type, col_obj, col_lp, and `infinity`.
+ * Per cut, in fp64: sum a^2, act = a.lp, a.obj and nint (columns of type != 3) exactly as gcnn_lp_state adds them (16 lanes a cut),
+ * |obj| exactly as it adds it (256-column chunks, the chunk sums strided over 256 threads, a block tree); then
+ *   efficacy    = -min(rhs - act, act - lhs) / norm,  norm = sqrt(sum a^2), or 1 when that is 0
+ *   int_support = nint / nnz
+ *   parallelism = 0 when sqrt(sum a^2) * |obj| = 0, else |a.obj| / (sqrt(sum a^2) * |obj|)
+ * -- the doubles gcnn_lp_state rounds into cut_feats[:, 3], [:, 2] and [:, 5] -- and
+ *   quality     = (efficacy + (0.1 * nint) / nnz) + 0.1 * parallelism
+ * with every operation rounded on its own in this association (Python's evaluation of the reference's line; no fused multiply-add).
+ * The rows of the filter are cut_val / norm rounded to fp32, in INPUT cut order with their columns as given: get_state's stored
+ * rows up to a sign that |a.b| removes.  The selection is gcnn_select_cuts' with a float64 key: order = the descending stable
+ * ranking of quality (NaN as -inf, ties in input order), low[p] = quality[order[p]] < 0.9 * quality[order[0]] compared in fp64 (no
+ * fp32 rounding of the threshold: the plugin's quality array is float64 here), forced phase and main phase as there.  All outputs
+ * are in input cut order.
+ * mode: GCNN_HYBRID_QUALITY (quality and features; two launches), GCNN_HYBRID_RANK (also order = the ranking, n_kept = n_cuts;
+ * three), GCNN_HYBRID_SELECT (the selection; four).  Forced rows (GCNN_HYBRID_SELECT only; n_forced may be NULL = none) as
+ * gcnn_infer_batch takes them.
+ *
+ * host_in (pinned, in_bytes): [0, table_bytes) the table, written by gcnn_hybrid_fill_table; array i of snapshot s at
+ *   snap_off[s][i] in the order GCNN_HYBRID_CUT_PTR .. GCNN_HYBRID_COL_LP (int32, int32, f64, f64, f64, int8, f64, f64);
+ *   forced_off[0..2]: forced_ptr [F+1] int32 (offsets over the stacked entries of all snapshots) | forced_col | forced_val f32.
+ * host_out (pinned, out_bytes): out_off[0] quality f64 [total_cuts] | out_off[1] features f64 [total_cuts][3] (efficacy,
+ *   int_support, parallelism) | out_off[2] order int32 [total_cuts], snapshot-local | out_off[3] n_kept int32 [n] | out_off[4] flags
+ *   int32 [n][4]: words 0-2 as gcnn_lp_state's (a column out of range, columns not strictly increasing, offsets not monotone), word 3
+ *   is 0.  Snapshot s starts at cut c_off[s] = n_cuts[0] + .. + n_cuts[s-1].  A flagged snapshot has no valid results and changes
+ *   no other snapshot's bits.
+ * Returned before anything is enqueued: GCNN_E_BADARG for n outside 1..GCNN_IBATCH_MAX, a negative size, an infinity that is not
+ * positive, an unknown mode, forced entries without a row, a missing buffer, an arena shorter than arena_bytes or not 256-byte
+ * aligned, or (GCNN_HYBRID_SELECT) a threshold that is not finite; GCNN_E_UNSUPPORTED for a snapshot of more than 4,096 cuts when
+ * an order is wanted, or a union of more than 2^30 cuts or entries. */
+#define GCNN_HYBRID_ARRAYS 8
+#define GCNN_HYBRID_CUT_PTR 0
+#define GCNN_HYBRID_CUT_COL 1
+#define GCNN_HYBRID_CUT_VAL 2
+#define GCNN_HYBRID_CUT_LHS 3
+#define GCNN_HYBRID_CUT_RHS 4
+#define GCNN_HYBRID_COL_TYPE 5
+#define GCNN_HYBRID_COL_OBJ 6
+#define GCNN_HYBRID_COL_LP 7
+#define GCNN_HYBRID_QUALITY 0
+#define GCNN_HYBRID_RANK 1
+#define GCNN_HYBRID_SELECT 2
+typedef struct gcnn_hybrid_dims {
+    int32_t n_cols, n_cuts, cut_nnz, reserved;
+    double infinity;
+} gcnn_hybrid_dims;
+typedef struct gcnn_hybrid_layout {
+    int32_t n_snapshots, total_cuts, total_nnz, max_cuts, max_cols, n_forced, n_forced_entries, reserved;
+    size_t table_bytes, in_bytes, snap_off[GCNN_IBATCH_MAX][GCNN_HYBRID_ARRAYS], forced_off[3];
+    size_t out_bytes, out_off[5];
+    size_t arena_bytes, out_dev_off, rows_off[3], ws_off, scratch_off, scratch_base[GCNN_IBATCH_MAX];   /* internal carving of the arena (the upload lies at 0) */
+} gcnn_hybrid_layout;
+int gcnn_hybrid_layout_for(int32_t n, const gcnn_hybrid_dims* dims /* host [n] */, const int32_t* n_forced,
+                           const int32_t* n_forced_entries, int32_t mode, gcnn_hybrid_layout* layout /* host */);
+/* table: host_in (host), table_bytes bytes.  No device work. */
+int gcnn_hybrid_fill_table(int32_t n, const gcnn_hybrid_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                           int32_t mode, void* table /* host */);
+int gcnn_hybrid_select(int32_t n, const gcnn_hybrid_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                       int32_t mode, const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
+                       double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
