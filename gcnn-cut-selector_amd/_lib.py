@@ -107,6 +107,15 @@ class HybridLayout(C.Structure):
 
 
 GROUP_MAX = 8   # GCNN_GROUP_MAX
+MBATCH_HEAD = 16                                                              # model words in front of the states' models
+MBATCH_TABLE_WORDS = IBATCH_TABLE_COLS * IBATCH_TABLE_STRIDE + MBATCH_HEAD + IBATCH_MAX   # GCNN_MBATCH_TABLE_WORDS
+
+
+class MbatchLayout(C.Structure):
+    _fields_ = [("u", IbatchLayout), ("n_models", C.c_int32), ("first_state", C.c_int32 * (GROUP_MAX + 1)),
+                ("model", Dims * GROUP_MAX), ("ws_off", C.c_size_t * GROUP_MAX), ("table_off", C.c_size_t),
+                ("table_bytes", C.c_size_t)]
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -174,6 +183,9 @@ SIGNATURES = {
     "gcnn_hybrid_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(HybridLayout)]),
     "gcnn_hybrid_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P]),
     "gcnn_hybrid_select": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _Z, _D, _D, _P]),
+    "gcnn_infer_models_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, C.POINTER(MbatchLayout)]),
+    "gcnn_infer_models_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P, _P]),
+    "gcnn_infer_models": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }
 
 _lib = None

@@ -148,15 +148,20 @@ struct GroupRecScope {   // installs a recorder on this thread for one member's 
     ~GroupRecScope() { g_group_rec = nullptr; }
 };
 
-// The group call proper, after group_check: member_step(i) enqueues member i's solo work (or records it)
+// The group call proper, after group_check, in two halves.  group_plan records every regular member's step and builds the launch
+// tables in the caller's staging buffer: host work only, so whatever it refuses is refused before anything is enqueued.
+// group_issue uploads the tables and launches.  member_step(i) enqueues member i's solo work (or records it).
+struct GroupLaunch { GroupKernel* k; size_t off; int grid, block; size_t smem; };
+struct GroupPlan { GroupLaunch launches[GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES]; int nl; size_t bytes; };
+
 template <class Step>
-static int group_run(int n, const gcnn_group_member* mem, void* host, void* dev, Step member_step, hipStream_t st) {
+static int group_plan(int n, const gcnn_group_member* mem, void* host, Step member_step, GroupPlan* P) {
     int rc;
     // 1. record every regular member's step (nothing is enqueued)
     static thread_local std::vector<GroupRecord> recs;
     recs.resize((size_t)GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES);
     GroupRecorder r[GCNN_GROUP_MAX];
-    int regular[GCNN_GROUP_MAX], nreg = 0, nstage = 0;
+    int nreg = 0, nstage = 0;
     for (int i = 0; i < n; ++i) {
         if (group_degenerate(mem[i].dims)) continue;
         GroupRecorder& q = r[nreg];
@@ -169,11 +174,9 @@ static int group_run(int n, const gcnn_group_member* mem, void* host, void* dev,
         if (q.bad) return GCNN_E_UNSUPPORTED;
         for (int s = 0; s < q.n; ++s) if (!group_kernel(q.rec[s].kern)) return GCNN_E_UNSUPPORTED;
         nstage = std::max(nstage, q.n);
-        regular[nreg++] = i;
+        ++nreg;
     }
     // 2. the launch tables, stage by stage: the members whose s-th launch runs the same kernel share one launch
-    struct Launch { GroupKernel* k; size_t off; int grid, block; size_t smem; };
-    Launch launches[GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES];
     int nl = 0;
     size_t off = 0;
     char* h = (char*)host;
@@ -196,14 +199,21 @@ static int group_run(int n, const gcnn_group_member* mem, void* host, void* dev,
                 ++head->n;
                 done[j] = true;
             }
-            launches[nl++] = Launch{group_kernel(first.kern), off, head->blk0[head->n], first.block, first.smem};
+            P->launches[nl++] = GroupLaunch{group_kernel(first.kern), off, head->blk0[head->n], first.block, first.smem};
             off = (off + sizeof(GroupHead) + (size_t)head->n * stride + 63) & ~(size_t)63;
         }
     }
-    // 3. one upload, then the launches; the members with an empty node set run their solo steps behind them
-    if (off) HIPCHK(hipMemcpyAsync(dev, host, off, hipMemcpyHostToDevice, st));
-    for (int k = 0; k < nl; ++k) {
-        const Launch& L = launches[k];
+    P->nl = nl; P->bytes = off;
+    return 0;
+}
+
+// 3. one upload, then the launches; the members with an empty node set run their solo steps behind them
+template <class Step>
+static int group_issue(int n, const gcnn_group_member* mem, void* host, void* dev, const GroupPlan& P, Step member_step, hipStream_t st) {
+    int rc;
+    if (P.bytes) HIPCHK(hipMemcpyAsync(dev, host, P.bytes, hipMemcpyHostToDevice, st));
+    for (int k = 0; k < P.nl; ++k) {
+        const GroupLaunch& L = P.launches[k];
         if (L.grid <= 0) continue;
         if (L.smem > 0 && L.k->attr.first())
             HIPCHK(hipFuncSetAttribute(L.k->group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.smem));
@@ -215,6 +225,13 @@ static int group_run(int n, const gcnn_group_member* mem, void* host, void* dev,
     for (int i = 0; i < n; ++i)
         if (group_degenerate(mem[i].dims) && (rc = member_step(i))) return rc;
     return 0;
+}
+
+template <class Step>
+static int group_run(int n, const gcnn_group_member* mem, void* host, void* dev, Step member_step, hipStream_t st) {
+    static thread_local GroupPlan plan;
+    const int rc = group_plan(n, mem, host, member_step, &plan);
+    return rc ? rc : group_issue(n, mem, host, dev, plan, member_step, st);
 }
 
 static int group_step(int n, const gcnn_group_member* mem, void* host, void* dev, size_t table_bytes, bool train, hipStream_t st) {

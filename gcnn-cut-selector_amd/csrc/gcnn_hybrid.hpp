@@ -172,3 +172,7 @@ extern "C" int gcnn_hybrid_select(int32_t n, const gcnn_hybrid_dims* dims, const
     HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));
     return 0;
 }
+
+// states of several models in one call: it needs gcnn_ibatch.hpp's statics and gcnn_group.hpp's, and the chain of includes from
+// gcnn_capi.hip is pinned down to this file (tests/test_hybrid_build.py)
+#include "gcnn_mbatch.hpp"

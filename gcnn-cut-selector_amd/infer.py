@@ -329,19 +329,17 @@ class _BatchSession(_Staging):
         _lib.check(_lib.lib().gcnn_infer_batch_fill_table(n, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
         cols = table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :n + 1].tolist()
         in_off = list(L.in_off)
-        where = [tuple(in_off[2 + j] + size * cols[col][s] for j, (col, size) in enumerate(self.PLACES)) for s in range(n)]
-        return dims, nf, nfe, L, in_off, list(L.out_off), table, cols, where
+        return dims, nf, nfe, L, in_off, list(L.out_off), table, cols, self._where(in_off, cols, n)
 
-    def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
-        """checked: [(arrays, key)] as `check_state` returns them; forced: None or [(ptr, col, val)] per state.
-        Returns None when the library declines the union as a whole (too large: the caller splits it)."""
-        keys = tuple(k for _, k in checked)
-        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
-        lay = self.cached((mode, keys, fshapes), self._layout, keys, fshapes, mode)
-        if lay is False:
-            return None
-        dims, nf, nfe, L, in_off, out_off, table, cols, where = lay
-        k_off, f_off, fe_off = cols[2], cols[5], cols[6]
+    @classmethod
+    def _where(cls, in_off, cols, n):
+        """Per state the byte offsets of its seven arrays in the upload (`pack_state`'s `where`)."""
+        return [tuple(in_off[2 + j] + size * cols[col][s] for j, (col, size) in enumerate(cls.PLACES)) for s in range(n)]
+
+    def _pack(self, lay, checked, forced):
+        """The upload of one call into the pinned buffer: the table, the zeroed block, every state, the forced rows."""
+        dims, nf, nfe, L, in_off, out_off, table, cols, where = lay[:9]
+        f_off, fe_off = cols[5], cols[6]
         self._buffers(L)
         buf, base = self.in_np, self.pin_in.data_ptr()
         buf[in_off[0]:in_off[0] + table.nbytes] = table.view(np.uint8)
@@ -355,17 +353,32 @@ class _BatchSession(_Staging):
                 self._put_forced((in_off[10] + 4 * fe_off[s], in_off[11] + 4 * fe_off[s]), (fcol, fval))
         if forced is None:
             buf[in_off[9]:in_off[9] + 4] = 0
-        self._enqueue_wait("gcnn_infer_batch", (len(checked), dims, nf, nfe, mode), (float(p_max), float(p_max_ub)))
-        self.calls += 1
-        self.last = (L, len(checked))
+
+    def _collect(self, lay, n_states, mode):
+        """Per state of the download: ("ok", scores, order, n_kept), ("bad_index",) or ("declined",)."""
+        out_off, k_off = lay[5], lay[7][2]
         res = []
-        for s in range(len(checked)):
+        for s in range(n_states):
             lo, n = 4 * k_off[s], k_off[s + 1] - k_off[s]
             verdict = self._verdict(out_off[3] + 16 * s)
             res.append((verdict,) if verdict else ("ok",) + self._read(
                 out_off[0] + lo, out_off[1] + lo if mode else None, out_off[2] + 4 * s if mode == _lib.IBATCH_SELECT else None, n))
         return res
 
+    def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
+        """checked: [(arrays, key)] as `check_state` returns them; forced: None or [(ptr, col, val)] per state.
+        Returns None when the library declines the union as a whole (too large: the caller splits it)."""
+        keys = tuple(k for _, k in checked)
+        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        lay = self.cached((mode, keys, fshapes), self._layout, keys, fshapes, mode)
+        if lay is False:
+            return None
+        dims, nf, nfe, L = lay[:4]
+        self._pack(lay, checked, forced)
+        self._enqueue_wait("gcnn_infer_batch", (len(checked), dims, nf, nfe, mode), (float(p_max), float(p_max_ub)))
+        self.calls += 1
+        self.last = (L, len(checked))
+        return self._collect(lay, len(checked), mode)
 
     def last_plan(self):
         """The union's graph plan as the last call left it in the arena, as host arrays by name (`_InferenceSession.last_plan`'s
@@ -379,6 +392,94 @@ class _BatchSession(_Staging):
                       left=(d[0], e1), var0=(d[1], e1), var1=(d[2], e2), iota=(d[3], e1), v_ptr=(d[6], v + 1), v_oth=(d[7], e1),
                       v_coef=(d[8], e1), f_col=(d[9], L.n_forced_entries))
         return _carve(self.arena, blocks, ("v_coef",))
+
+
+class _ModelsSession:
+    """Host side of gcnn_infer_models: one C call for up to 64 host states of up to 8 models.  It packs with a `_BatchSession`'s
+    packer into that session's pinned buffers and arena (`base`: the batch session of one of the models -- every model of the
+    call lives on its device), and adds what the call needs beyond them: the model words of the table and the pinned staging
+    buffer of the grouped forward passes' launch tables."""
+    MAX = _lib.IBATCH_MAX
+    MAX_MODELS = _lib.GROUP_MAX
+    CAP = _BatchSession.CAP
+    UNSUPPORTED = "unsupported"
+    cached = _Staging.cached          # the same bounded cache of layouts
+
+    def __init__(self, base):
+        self.base = base
+        self.layouts = {}
+        self.staging = None
+        self.calls = 0
+        self.last = None
+
+    def _layout(self, keys, fshapes, mode, model_of):
+        n, n_models = len(keys), model_of[-1] + 1
+        dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
+        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
+        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        mos = (C.c_int32 * n)(*model_of)
+        ML = _lib.MbatchLayout()
+        if _unsupported(_lib.lib().gcnn_infer_models_layout_for(n, dims, nf, nfe, mode, n_models, mos, C.byref(ML)),
+                        "gcnn_infer_models_layout_for"):
+            return False
+        table = np.zeros(_lib.MBATCH_TABLE_WORDS, np.int32)
+        _lib.check(_lib.lib().gcnn_infer_models_fill_table(n, dims, nf, nfe, n_models, mos, table.ctypes.data),
+                   "gcnn_infer_models_fill_table")
+        cols = table[:_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE].reshape(_lib.IBATCH_TABLE_COLS, -1)[:, :n + 1].tolist()
+        L = ML.u
+        in_off = list(L.in_off)
+        return dims, nf, nfe, L, in_off, list(L.out_off), table, cols, _BatchSession._where(in_off, cols, n), ML, mos, n_models
+
+    def run(self, checked, forced, mode, model_of, models, p_max=0.0, p_max_ub=0.0):
+        """checked, forced: as `_BatchSession.run` takes them, sorted by model; model_of: the model number of every state
+        (non-decreasing, from 0, no gaps); models: the `GCNN` of every number.  Returns `_BatchSession.run`'s list, None when the
+        library declines the union's sizes (the caller splits it) or UNSUPPORTED when it declines the call as a whole."""
+        base = self.base
+        keys = tuple(k for _, k in checked)
+        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        lay = self.cached((mode, keys, fshapes, tuple(model_of)), self._layout, keys, fshapes, mode, model_of)
+        if lay is False:
+            return None
+        dims, nf, nfe, L = lay[:4]
+        ML, mos, n_models = lay[9:]
+        base._pack(lay, checked, forced)
+        self.staging, _ = base._pin(self.staging, None, ML.table_bytes, 1 << 16)
+        P = C.c_void_p
+        params = (P * n_models)(*(m._flat.data_ptr() for m in models))
+        dev = base.model.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            rc = _lib.lib().gcnn_infer_models(len(checked), dims, nf, nfe, mode, n_models, mos, params, P(base.pin_in.data_ptr()),
+                                              P(base.pin_out.data_ptr()), P(base.arena.data_ptr()), base.arena.numel(),
+                                              P(self.staging.data_ptr()), float(p_max), float(p_max_ub), P(stream.cuda_stream))
+            if rc == -4:
+                return self.UNSUPPORTED
+            _lib.check(rc, "gcnn_infer_models")
+            stream.synchronize()
+        self.calls += 1
+        self.last = (ML, len(checked))
+        base.last = None          # the arena no longer holds that session's own plan
+        return base._collect(lay, len(checked), mode)
+
+    def last_plan(self):
+        """Every model's graph plan as the last call left it in the arena: a list with, per model, the arrays of
+        `_BatchSession.last_plan` for that model's sub-union (ids relative to the model), as host arrays by name."""
+        ML, s = self.last
+        L, t = ML.u, ML.u.total
+        i, d, M = list(L.in_off), list(L.dev_off), ML.n_models
+        al16 = lambda x: (x + 15) & ~15  # noqa: E731
+        l0 = i[1] + al16(16 * s)
+        l1 = l0 + al16(4 * (t.n_cons + M))
+        plans, c, v, k, e1, e2 = [], 0, 0, 0, 0, 0
+        for m in range(M):
+            dm = ML.model[m]
+            blocks = dict(l_ptr0=(l0 + 4 * (c + m), dm.n_cons + 1), l_ptr1=(l1 + 4 * (k + m), dm.n_cuts + 1),
+                          left=(d[0] + 4 * e1, dm.n_cons_edges), var0=(d[1] + 4 * e1, dm.n_cons_edges),
+                          var1=(d[2] + 4 * e2, dm.n_cut_edges), v_ptr=(d[6] + 4 * (v + m), dm.n_vars + 1),
+                          v_oth=(d[7] + 4 * e1, dm.n_cons_edges), v_coef=(d[8] + 4 * e1, dm.n_cons_edges))
+            plans.append(_carve(self.base.arena, blocks, ("v_coef",)))
+            c, v, k, e1, e2 = c + dm.n_cons, v + dm.n_vars, k + dm.n_cuts, e1 + dm.n_cons_edges, e2 + dm.n_cut_edges
+        return plans
 
 
 class _LPSession(_Staging):

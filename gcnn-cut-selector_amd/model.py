@@ -21,7 +21,8 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPSession, _UseGeneralPath,
+from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPSession, _ModelsSession,
+                    _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
 
 EMB = 64
@@ -131,6 +132,51 @@ class _GCNNFunction(torch.autograd.Function):
         model._give_workspace(ws)
         ctx.ws = None
         return grads, None, None
+
+
+def _serve_many(n, admit, split, run, solo):
+    """The driver of every `*_many` entry point (`GCNN._many`, `ModelSet._many`): results per state, each ("ok", ...) or an exception.
+    `admit(i)`: the checked entry of state i for the batched call, None where it goes to the solo entry point; what it raises
+    belongs to that state's slot.  `split(ids)`: the admitted states as the calls that serve them.  `run(ids, checked)`: one call's
+    answers per state -- ("ok", ...), ("error", exc), ("bad_index",), anything else = declined -- or None where the library
+    declines the union as a whole (too large: halves, and a single state goes solo).  `solo(i)`: the single-state entry point."""
+    results, checked, batch_ids, solo_ids = [None] * n, {}, [], []
+    for i in range(n):
+        try:
+            entry = admit(i)
+        except Exception as exc:  # noqa: BLE001 -- the error belongs to this state's slot
+            results[i] = exc
+            continue
+        if entry is None:
+            solo_ids.append(i)
+        else:
+            checked[i] = entry
+            batch_ids.append(i)
+    todo = split(batch_ids)
+    while todo:
+        ids = todo.pop(0)
+        got = run(ids, checked)
+        if got is None:
+            if len(ids) == 1:
+                solo_ids.append(ids[0])
+            else:
+                todo[:0] = [ids[:len(ids) // 2], ids[len(ids) // 2:]]
+            continue
+        for i, r in zip(ids, got):
+            if r[0] == "ok":
+                results[i] = r
+            elif r[0] == "error":
+                results[i] = r[1]
+            elif r[0] == "bad_index":
+                results[i] = ValueError(BAD_INDEX)
+            else:
+                solo_ids.append(i)
+    for i in solo_ids:
+        try:
+            results[i] = solo(i)
+        except Exception as exc:  # noqa: BLE001
+            results[i] = exc
+    return results
 
 
 class GCNN:
@@ -572,53 +618,21 @@ class GCNN:
         state -- ("ok", scores, order, n_kept[, cut_index]), or an exception.
         `solo(i)`: the existing single-state entry point for state i (a state the batch declines goes there and comes back in
         place).  `forced`: None or per state a packed (ptr, col, val) / an exception raised while it was packed."""
-        n = len(states)
-        results, checked, batch_ids, solo_ids = [None] * n, {}, [], []
         session = self._sess("_lp_batch_session", _LPBatchSession) if lp else self._sess("_batch_session", _BatchSession)
-        for i, st in enumerate(states):
-            try:
-                if forced is not None and isinstance(forced[i], Exception):
-                    raise forced[i]
-                if lp:
-                    entry = session.check(st)
-                    n_cuts = entry[1]["n_cuts"]
-                    if n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096):
-                        entry = None
-                else:
-                    entry = self._admit_state(st, mode)
-            except Exception as exc:  # noqa: BLE001 -- the error belongs to this state's slot
-                results[i] = exc
-                continue
-            if entry is None:
-                solo_ids.append(i)
-            else:
-                checked[i] = entry
-                batch_ids.append(i)
-        todo = [batch_ids[j:j + session.MAX] for j in range(0, len(batch_ids), session.MAX)]
-        while todo:
-            ids = todo.pop(0)
-            got = session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode, p_max, p_max_ub)
-            if got is None:                     # the union is past the library's limits: halves, and a single state goes solo
-                if len(ids) == 1:
-                    solo_ids.append(ids[0])
-                else:
-                    todo[:0] = [ids[:len(ids) // 2], ids[len(ids) // 2:]]
-                continue
-            for i, r in zip(ids, got):
-                if r[0] == "ok":
-                    results[i] = r
-                elif r[0] == "error":
-                    results[i] = r[1]
-                elif r[0] == "bad_index":
-                    results[i] = ValueError(BAD_INDEX)
-                else:
-                    solo_ids.append(i)
-        for i in solo_ids:
-            try:
-                results[i] = solo(i)
-            except Exception as exc:  # noqa: BLE001
-                results[i] = exc
-        return results
+
+        def admit(i):
+            if forced is not None and isinstance(forced[i], Exception):
+                raise forced[i]
+            if not lp:
+                return self._admit_state(states[i], mode)
+            entry = session.check(states[i])
+            n_cuts = entry[1]["n_cuts"]
+            return None if n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096) else entry
+
+        def run(ids, checked):
+            return session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode, p_max, p_max_ub)
+
+        return _serve_many(len(states), admit, lambda ids: [ids[j:j + session.MAX] for j in range(0, len(ids), session.MAX)], run, solo)
 
     @staticmethod
     def _finish_many(results, return_exceptions):
@@ -726,3 +740,115 @@ class GCNN:
             with torch.no_grad():
                 return self.call(state, training)
         return get_improvements
+
+
+class ModelSet:
+    """Several models behind one call: `ModelSet({"setcov/0": m0, "setcov/1": m1, ...})`.  The evaluators' task farm runs `seed`
+    innermost (model_evaluator.py:211-219), so the states that wait at a scoring server belong to different models; `score_states`
+    and `select_cuts_many` take them together with the key of each state's model and answer them with ONE gcnn_infer_models call
+    per 8 models / 64 states: one upload, one index pass and one by-variable stage, the models' forward passes as a group, one
+    download.  Every state's result has the bits of its own model's `GCNN.score_states` / `select_cuts_many` on that model's
+    states alone.  All models live on one device."""
+    MAX_MODELS = _ModelsSession.MAX_MODELS
+
+    def __init__(self, models):
+        self.models = dict(models)
+        if not self.models:
+            raise ValueError("ModelSet: no model")
+        devices = {str(m.device) for m in self.models.values()}
+        if len(devices) != 1:
+            raise ValueError(f"ModelSet: all models must be on one device, got {sorted(devices)}")
+        self._number = {k: i for i, k in enumerate(self.models)}
+        self._session = None
+        self.calls = 0                    # gcnn_infer_models calls made
+        self.max_models_per_call = 0      # the most models one of them served
+
+    def _sess(self):
+        if self._session is None:
+            first = next(iter(self.models.values()))
+            self._session = _ModelsSession(first._sess("_batch_session", _BatchSession))
+        return self._session
+
+    def _many(self, keys, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0):
+        """`GCNN._many` over states of several models: results per state in the caller's order."""
+        if len(keys) != len(states):
+            raise ValueError(f"keys: one model key per state expected, got {len(keys)} for {len(states)} states")
+        session = self._sess()
+
+        def admit(i):
+            if keys[i] not in self.models:
+                raise KeyError(f"no model {keys[i]!r}")
+            if forced is not None and isinstance(forced[i], Exception):
+                raise forced[i]
+            return GCNN._admit_state(states[i], mode)
+
+        def split(ids):
+            """Sorted stably by model (a model's states keep their relative order), at most 8 models and 64 states per call."""
+            calls, cur, cur_models = [], [], set()
+            for i in sorted(ids, key=lambda i: self._number[keys[i]]):
+                if len(cur) == session.MAX or (keys[i] not in cur_models and len(cur_models) == self.MAX_MODELS):
+                    calls.append(cur)
+                    cur, cur_models = [], set()
+                cur.append(i)
+                cur_models.add(keys[i])
+            return calls + [cur] if cur else calls
+
+        def run(ids, checked):
+            order = list(dict.fromkeys(keys[i] for i in ids))     # the call's models, numbered as they appear
+            number = {k: m for m, k in enumerate(order)}
+            got = session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode,
+                              [number[keys[i]] for i in ids], [self.models[k] for k in order], p_max, p_max_ub)
+            if got is session.UNSUPPORTED:      # the grouped forward declines: one call per model, each with its own solo tail
+                got = [None] * len(ids)
+                for k in order:
+                    mine = [j for j, i in enumerate(ids) if keys[i] == k]
+                    sub = self.models[k]._many([states[ids[j]] for j in mine], mode, lambda x, mine=mine: solo(ids[mine[x]]),
+                                               None if forced is None else [forced[ids[j]] for j in mine], p_max, p_max_ub)
+                    for j, r in zip(mine, sub):
+                        got[j] = ("error", r) if isinstance(r, Exception) else r
+            elif got is not None:
+                self.calls += 1
+                self.max_models_per_call = max(self.max_models_per_call, len(order))
+            return got
+
+        return _serve_many(len(states), admit, split, run, solo)
+
+    def score_states(self, keys, states, rank=False, return_exceptions=False):
+        """`GCNN.score_states` for states of several models: `keys[i]` names the model of `states[i]`, in any order.  Returns a
+        list of `ScoreArray` in the caller's order, with `.rankings` when `rank`; errors per state as `GCNN.score_states` reports
+        them (an unknown key is its state's KeyError).  States the call declines go through their own model's `score_state`."""
+        keys, states = list(keys), list(states)
+        mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
+        results = self._many(keys, states, mode, lambda i: self.models[keys[i]].score_state(states[i], rank))
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                scores = r[1]
+                if rank:
+                    scores.rankings = r[2]
+                results[i] = scores
+        return GCNN._finish_many(results, return_exceptions)
+
+    def select_cuts_many(self, keys, states, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
+        """`GCNN.select_cuts_many` for states of several models (`keys[i]` names the model of `states[i]`).  Returns a list of
+        `SelectResult` in the caller's order."""
+        ops.check_thresholds(p_max, p_max_ub)
+        keys, states = list(keys), list(states)
+        forced = [None] * len(states) if forced is None else list(forced)
+        if len(forced) != len(states):
+            raise ValueError(f"forced: one entry per state expected, got {len(forced)} for {len(states)} states")
+        packed = []
+        for st, f in zip(states, forced):
+            try:
+                packed.append(normalize_forced(f, st.dims.n_vars if isinstance(st, Batch) else int(np.asarray(st[3]).shape[0])))
+            except Exception as exc:  # noqa: BLE001
+                packed.append(exc)
+
+        def solo(i):
+            return self.models[keys[i]].select_cuts(states[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
+
+        results = self._many(keys, states, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub)
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                _, scores, order, n_kept = r
+                results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
+        return GCNN._finish_many(results, return_exceptions)

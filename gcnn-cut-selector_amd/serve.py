@@ -6,10 +6,13 @@ worker, one selector call per separation round) share ONE process that owns the 
     CustomCutsel(function=client.get_concrete_function(), ...)                            # model_evaluator.py:310-314
     client.select_cuts_lp(lpstate.LPSnapshot(...), max_selected=10)                       # or: the raw LP, get_state left to the GPU
 
-The server takes every request that is waiting, groups them by model and kind, answers each group with one
-`GCNN.score_states` / `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP
-kinds one `GCNN.score_lps` / `GCNN.select_cuts_lp_many` call, which also builds the states on the device -- and goes back
-for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
+The server takes every request that is waiting and groups them by kind: the host-state requests of ALL models share one
+`ModelSet.score_states` / `ModelSet.select_cuts_many` call (a group of one model's requests takes that model's own call) (the farm's queue runs `seed` innermost, model_evaluator.py:211-219, so
+the workers that wait hold different models; one upload, the models' forward passes as a group, one download).  With
+`cross_model=False`, and for the LP kinds, it groups by model and kind and answers each group with one `GCNN.score_states` /
+`GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP kinds one
+`GCNN.score_lps` / `GCNN.select_cuts_lp_many` call, which also builds the states on the device -- and goes back for whatever
+queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
 hybrid quality from the cut rows, `client.select_cuts_hybrid`) need no model: those that are waiting are grouped by thresholds and
 answered with one `HybridSelector.select_cuts_many`.
 
@@ -24,6 +27,7 @@ import selectors
 import socket
 import struct
 import threading
+from functools import partial
 
 import numpy as np
 
@@ -322,12 +326,20 @@ class ScoringServer:
     """Owns the models (and with them the GPU).  `address`: path of the AF_UNIX socket, bound and listening from construction on, so
     that requests sent before `start()` simply wait.  `start()` serves in a thread of this process; `serve_forever()` in the
     calling thread.  `stats`: requests, calls (one per group served) and batched_calls (calls that served more than one request),
-    max_batch."""
+    max_batch, max_models_per_call (the most models one batched call served: what the `ModelSet` reports, which splits a group of
+    more than 8 models; 1 for a call on one model).  `cross_model`: host-state requests of all models share one group per kind
+    (and thresholds), served by a `ModelSet` over the models -- a group that holds requests of ONE model still takes that model's
+    own call, which is the faster one for it (profiles/mixed_models.txt); False, or models on more than one device, groups by
+    model.  `model_set`: the set to use instead of `ModelSet(models)` (built on first use)."""
 
-    def __init__(self, models, address, backlog=128):
+    def __init__(self, models, address, backlog=128, cross_model=True, model_set=None):
         self.models = dict(models)
         self.address = address
-        self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0)
+        # a ModelSet needs all models on one device: models spread over several devices are served per model, as before
+        one_device = len({str(getattr(m, "device", None)) for m in self.models.values()}) <= 1
+        self.cross_model = bool(cross_model) and (model_set is not None or one_device)
+        self._model_set = model_set
+        self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0)
         self._listen = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
         self._listen.bind(address)
         self._listen.listen(backlog)
@@ -342,6 +354,12 @@ class ScoringServer:
             from .hybrid import HybridSelector
             self._hybrid = HybridSelector(next(iter(self.models.values())).device)
         return self._hybrid
+
+    def _set(self):
+        if self._model_set is None:
+            from .model import ModelSet
+            self._model_set = ModelSet(self.models)
+        return self._model_set
 
     def start(self):
         self._thread = threading.Thread(target=self.serve_forever, name="gcnn-scoring-server", daemon=True)
@@ -424,7 +442,8 @@ class ScoringServer:
         for conn, req in pending:
             selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT, KIND_HYBRID_SELECT)
             hybrid = req["kind"] == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
-            gkey = (None if hybrid else req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
+            shared = hybrid or (self.cross_model and req["kind"] not in _LP_BASE)   # host states: one ModelSet call for all models
+            gkey = (None if shared else req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
             groups.setdefault(gkey, []).append((conn, req))
         for gkey, items in groups.items():
             hybrid = gkey[1] == KIND_HYBRID_SELECT
@@ -434,11 +453,16 @@ class ScoringServer:
             self.stats["calls"] += 1
             self.stats["batched_calls"] += len(items) > 1
             self.stats["max_batch"] = max(self.stats["max_batch"], len(items))
+            mkeys = [r["model_key"] for _, r in items]
+            mset = None
             try:
                 if hybrid:
                     score_many, select_many = None, self._hybrid_selector().select_cuts_many
+                elif gkey[0] is None and len(set(mkeys)) > 1:
+                    mset = self._set()
+                    score_many, select_many = partial(mset.score_states, mkeys), partial(mset.select_cuts_many, mkeys)
                 else:
-                    model = self.models[gkey[0]]
+                    model = self.models[mkeys[0]]
                     score_many, select_many = (model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)
                 if kind == KIND_SELECT:
                     results = select_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3], return_exceptions=True)
@@ -446,6 +470,9 @@ class ScoringServer:
                     results = score_many(states, rank=kind == KIND_RANK, return_exceptions=True)
             except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
                 results = [exc] * len(items)
+            if not hybrid:
+                served = 1 if mset is None else getattr(mset, "max_models_per_call", len(set(mkeys)))
+                self.stats["max_models_per_call"] = max(self.stats["max_models_per_call"], served)
             for (conn, req), res in zip(items, results):
                 if conn not in self._buffers:
                     continue

@@ -628,6 +628,46 @@ int gcnn_hybrid_select(int32_t n, const gcnn_hybrid_dims* dims, const int32_t* n
                        int32_t mode, const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
                        double p_max_ub, void* stream);
 
+/* ---- host states of several models in one call: the task farm as the reference fills it (model_evaluator.py:211-219) --------------
+ * The evaluators' queue runs `seed` innermost, so the states that wait at a scoring server belong to DIFFERENT models.
+ * gcnn_infer_models is gcnn_infer_batch's contract for 1..GCNN_IBATCH_MAX states of 1..GCNN_GROUP_MAX models: model_of_state[s] in
+ * 0..n_models-1, NON-DECREASING (a model's states are contiguous; the caller sorts) and without gaps (a model without a state is
+ * refused); params[m] (host array of device pointers; two entries may be equal).  Two host->device copies (the states; the launch
+ * tables of the grouped forward passes), one device->host copy, nothing synchronised, nothing allocated.
+ *
+ * host_in / host_out: gcnn_infer_batch's, at layout.u.in_off / out_off, with two differences.  in_off[0], the table, has
+ * GCNN_MBATCH_TABLE_WORDS int32: gcnn_infer_batch's columns, then n_models, the first state of every model (entry n_models =
+ * n_states) from word +1, and from word +16 the model of every state; gcnn_infer_models_fill_table writes it.  in_off[1], the block
+ * the caller keeps zero up to in_off[2], is larger (one closing by-left offset per model).  State s still lies at the union's
+ * c/v/k/e1/e2_off[s], and its results at k_off[s].
+ * host_staging: pinned, 16-byte aligned, layout.table_bytes bytes (as gcnn_group_forward takes it); the device table lives in the
+ * arena.
+ * Device work: one index pass over all states (ids relative to the state's model), one stable radix sort of the union's constraint
+ * edges by union variable id, one launch that splits its offsets per model, the models' forward passes as a group (one launch per
+ * distinct kernel and stage, each model on the sub-union of its own states, with the bits gcnn_infer_batch gives for those states
+ * alone), one ranking launch or one selection launch pair over all states.
+ * Returned before anything is enqueued: what gcnn_infer_batch returns; GCNN_E_BADARG for n_models outside 1..GCNN_GROUP_MAX, a
+ * model_of_state that decreases, skips a model, does not start at 0 or does not end at n_models-1, a missing buffer or an arena
+ * shorter than layout.u.arena_bytes; GCNN_E_UNSUPPORTED for a forward pass the group recorder cannot take. */
+#define GCNN_MBATCH_TABLE_WORDS (GCNN_IBATCH_TABLE_COLS * GCNN_IBATCH_TABLE_STRIDE + 16 + GCNN_IBATCH_MAX)
+typedef struct gcnn_mbatch_layout {
+    gcnn_ibatch_layout u;                          /* the union: sizes, upload, download, arena (dev_off: internal) */
+    int32_t n_models, first_state[GCNN_GROUP_MAX + 1];
+    gcnn_dims model[GCNN_GROUP_MAX];               /* the sizes of every model's sub-union */
+    size_t ws_off[GCNN_GROUP_MAX], table_off;      /* internal: the models' forward workspaces and the launch tables in the arena */
+    size_t table_bytes;                            /* host_staging holds this much */
+} gcnn_mbatch_layout;
+int gcnn_infer_models_layout_for(int32_t n_states, const gcnn_dims* dims /* host [n_states] */, const int32_t* n_forced,
+                                 const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
+                                 const int32_t* model_of_state /* host [n_states] */, gcnn_mbatch_layout* layout /* host */);
+/* table: host_in + u.in_off[0] (host), GCNN_MBATCH_TABLE_WORDS int32.  No device work. */
+int gcnn_infer_models_fill_table(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                                 int32_t n_models, const int32_t* model_of_state, int32_t* table /* host */);
+int gcnn_infer_models(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                      int32_t mode, int32_t n_models, const int32_t* model_of_state, const float* const* params /* host [n_models] */,
+                      const void* host_in, void* host_out, void* arena, size_t arena_bytes, void* host_staging, double p_max,
+                      double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
