@@ -1374,3 +1374,9 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_rank.hpp"
 // many host states in one call (include/gcnn_hip.h: gcnn_infer_batch): launch names k_ib_*
 #include "gcnn_ibatch.hpp"
+// raw LP snapshots as the states of that call (include/gcnn_hip.h: gcnn_lp_batch): launch names k_lpset_*
+#include "gcnn_lpbatch.hpp"
+// hybrid cut selection from the cut rows of many snapshots (include/gcnn_hip.h: gcnn_hybrid_select): launch names k_hyb_*
+#include "gcnn_hybrid.hpp"
+// host states of several models in one call (include/gcnn_hip.h: gcnn_infer_models): launch names k_mb_*
+#include "gcnn_mbatch.hpp"

@@ -1,8 +1,8 @@
 // gcnn_hybrid.hpp -- host side of gcnn_hybrid_select (include/gcnn_hip.h): SCIP's hybrid quality and the parallelism filter from the cut
 // rows of 1..64 snapshots in one upload, at most four launches (k_hybrid.hpp, k_sel_pairs unchanged) and one download.  No model, no
-// LP rows.  Included at the end of gcnn_lpbatch.hpp (it shares that file's table conventions, gcnn_lpstate.hpp's chunking and
-// gcnn_select.hpp's SelArgs builder and workspace size), kept apart so that its launch names form their own inventory
-// (tests/test_hybrid_build.py).
+// LP rows.  Included from gcnn_capi.hip's list of host files, after gcnn_lpbatch.hpp (it shares that file's table conventions,
+// gcnn_lpstate.hpp's chunking and gcnn_select.hpp's SelArgs builder and workspace size), kept apart so that its launch names form
+// their own inventory (tests/test_hybrid_build.py).
 //
 // The arena: the upload | the output block | the stacked fp32 rows (row_ptr, row_col, row_val) | the pair bits | the snapshots' scratch.
 // The upload: the table (head, one entry per snapshot) | the packed snapshots | the forced rows.
@@ -172,7 +172,3 @@ extern "C" int gcnn_hybrid_select(int32_t n, const gcnn_hybrid_dims* dims, const
     HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));
     return 0;
 }
-
-// states of several models in one call: it needs gcnn_ibatch.hpp's statics and gcnn_group.hpp's, and the chain of includes from
-// gcnn_capi.hip is pinned down to this file (tests/test_hybrid_build.py)
-#include "gcnn_mbatch.hpp"

@@ -1,7 +1,9 @@
 // gcnn_ibatch.hpp -- host side of gcnn_infer_batch (include/gcnn_hip.h): 1..64 host states in one upload, one forward pass over their
-// disjoint union, one download.  Included at the end of gcnn_capi.hip (it shares that file's statics: ProfScope, the carver,
-// by_key_stage, forward_impl; and gcnn_select.hpp's call_check, sel_args and launcher), kept apart so that its launch names form
-// their own inventory (tests/test_ibatch_build.py).
+// disjoint union, one download.  Included from gcnn_capi.hip's list of host files (it shares that file's statics: ProfScope, the
+// carver, by_key_stage, forward_impl; and gcnn_select.hpp's call_check, sel_args and launcher), kept apart so that its launch names
+// form their own inventory (tests/test_ibatch_build.py).  It also holds what every call on a union shares -- gcnn_lpbatch.hpp and
+// gcnn_mbatch.hpp, included after it, use them: the sums and the table (ibatch_sums), the one layout (union_layout), where an
+// uploaded union lies (union_at), the index pass's arguments and grid (union_args, union_grid) and the end of a run (union_tail).
 //
 // By-variable order of the union: the by-variable stage of gcnn_graph_build (by_key_stage: a stable rocprim radix sort of (variable
 // id, input position), k_seg_offsets and k_gather_edges) on the shifted list, not a generalised k_iplan_*.  The single-state plan
@@ -15,7 +17,10 @@
 static_assert(IB_MAX_STATES == GCNN_IBATCH_MAX && IB_TS == GCNN_IBATCH_TABLE_STRIDE && IB_COLS == GCNN_IBATCH_TABLE_COLS, "table shape");
 static_assert(IB_TS >= IB_MAX_STATES + 1 && IB_TS % 4 == 0, "one offset per state and the total, 16-byte columns");
 
-struct IbSums { long long c, v, k, e1, e2, f, fe; int max_cuts; };
+struct IbSums {
+    long long c, v, k, e1, e2, f, fe; int max_cuts;
+    gcnn_dims dims() const { return gcnn_dims{(int)c, (int)v, (int)k, (int)e1, (int)e2}; }   // the union's totals
+};
 static int ibatch_sums(int n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
                        IbSums* t, int32_t* table) {
     if (n_states < 1 || n_states > GCNN_IBATCH_MAX || !dims) return GCNN_E_BADARG;
@@ -45,18 +50,18 @@ static int ibatch_sums(int n_states, const gcnn_dims* dims, const int32_t* n_for
     return 0;
 }
 
-static int ibatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
-                         gcnn_ibatch_layout* L) {
-    if (!L) return GCNN_E_BADARG;
-    IbSums t;
-    const int rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, mode, &t, nullptr);
-    if (rc) return rc;
-    memset(L, 0, sizeof(*L));
-    L->total = gcnn_dims{(int)t.c, (int)t.v, (int)t.k, (int)t.e1, (int)t.e2};
+// union_layout: the one layout of a union of t's sizes -- every offset of gcnn_ibatch_layout.  What tells gcnn_infer_batch's union
+// from gcnn_infer_models': `n_close` closing by-left and by-variable entries (1, or one per model), `table_bytes`, `sel_offsets`
+// (the zero block also carries the cut rows' offsets over the whole union), `fwd_ws_bytes` (dev_off[12]) and `extra` arena blocks
+// behind the selection workspace, whose offsets go to `extra_off`.
+static void union_layout(const IbSums& t, int n_states, int mode, size_t n_close, size_t table_bytes, bool sel_offsets, size_t fwd_ws_bytes,
+                         std::initializer_list<size_t> extra, size_t* extra_off, gcnn_ibatch_layout* L) {
+    L->total = t.dims();
     L->n_forced = (int)t.f; L->n_forced_entries = (int)t.fe; L->max_cuts = t.max_cuts; L->n_states = n_states;
-    const size_t S = n_states, C = t.c, V = t.v, K = t.k, E1 = t.e1, E2 = t.e2, F = t.f, FE = t.fe;
-    // the table; the zero block: flags | l_ptr cons | l_ptr cut; the seven arrays of gcnn_infer's upload, stacked; the forced rows
-    const size_t sizes[9] = {4 * (size_t)IB_COLS * IB_TS, al16(16 * S) + al16(4 * (C + 1)) + al16(4 * (K + 1)),
+    const size_t S = n_states, M = n_close, C = t.c, V = t.v, K = t.k, E1 = t.e1, E2 = t.e2, F = t.f, FE = t.fe;
+    // the table; the zero block: flags | l_ptr cons | l_ptr cut | the union's cut offsets; the seven arrays of gcnn_infer's upload,
+    // stacked; the forced rows
+    const size_t sizes[9] = {table_bytes, al16(16 * S) + al16(4 * (C + M)) + al16(4 * (K + M)) + (sel_offsets ? al16(4 * (K + 1)) : 0),
                              16 * C, 8 * E1, 4 * E1, 56 * V, 24 * K, 8 * E2, 4 * E2};
     Carver in{0};
     for (int i = 0; i < 9; ++i) L->in_off[i] = in.take(sizes[i], 16);
@@ -68,12 +73,24 @@ static int ibatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_f
     // left: union row ids of the constraint edges | var, constraint edges (= by-left oth) | var, cut edges | iota | sorted keys |
     // permutation | v_ptr | v_oth | v_coef | forced columns in the union's column space | sort temp | outputs | forward workspace |
     // selection workspace
-    const size_t blocks[14] = {4 * E1, 4 * E1, 4 * E2, 4 * E1, 4 * E1, 4 * E1, 4 * (V + 1), 4 * E1, 4 * E1, 4 * FE,
-                               sort_temp_bytes((int)E1), L->out_bytes, sizeof(float) * gcnn_workspace_floats(&L->total),
+    const size_t blocks[14] = {4 * E1, 4 * E1, 4 * E2, 4 * E1, 4 * E1, 4 * E1, 4 * (V + M), 4 * E1, 4 * E1, 4 * FE,
+                               sort_temp_bytes((int)E1), L->out_bytes, fwd_ws_bytes,
                                mode == GCNN_IBATCH_SELECT ? select_ws_bytes((int)K, (int)F, t.max_cuts) : 0};
     Carver dev{(in.off + 255) & ~(size_t)255};
     for (int i = 0; i < 14; ++i) L->dev_off[i] = dev.take(blocks[i], 256);
+    for (size_t bytes : extra) *extra_off++ = dev.take(bytes, 256);
     L->arena_bytes = dev.off;
+}
+
+static int ibatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
+                         gcnn_ibatch_layout* L) {
+    if (!L) return GCNN_E_BADARG;
+    IbSums t;
+    const int rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, mode, &t, nullptr);
+    if (rc) return rc;
+    memset(L, 0, sizeof(*L));
+    const gcnn_dims total = t.dims();
+    union_layout(t, n_states, mode, 1, 4 * (size_t)IB_COLS * IB_TS, false, sizeof(float) * gcnn_workspace_floats(&total), {}, nullptr, L);
     return 0;
 }
 
@@ -105,28 +122,65 @@ static int ibatch_precheck(const gcnn_ibatch_layout& L, const float* params, voi
     return check_common(&L.total, params, &g, &g, (float*)arena, gcnn_workspace_floats(&L.total));
 }
 
+// an upload that lies at the arena's start (gcnn_infer_batch, gcnn_infer_models)
+static IbAt union_at(char* A, const gcnn_ibatch_layout& L) {
+    IbAt at;
+    at.table = (const int*)(A + L.in_off[0]); at.zero = A + L.in_off[1];
+    for (int i = 0; i < 7; ++i) at.arr[i] = A + L.in_off[2 + i];
+    for (int i = 0; i < 3; ++i) at.forced[i] = A + L.in_off[9 + i];
+    at.out = A + L.dev_off[11];
+    return at;
+}
+
+// the index pass's arguments for a union at `at` whose by-left arrays carry `n_close` closing entries each (union_layout)
+static IbArgs union_args(const IbAt& at, const gcnn_ibatch_layout& L, char* A, size_t n_close) {
+    IbArgs ia; memset(&ia, 0, sizeof(ia));
+    ia.table = at.table; ia.n_states = L.n_states;
+    ia.packed[0] = (const int*)at.arr[1]; ia.packed[1] = (const int*)at.arr[5];
+    ia.left = (int*)(A + L.dev_off[0]); ia.var[0] = (int*)(A + L.dev_off[1]); ia.var[1] = (int*)(A + L.dev_off[2]);
+    ia.flags = (int*)at.zero;
+    ia.l_ptr[0] = (int*)(at.zero + al16(16 * (size_t)L.n_states));
+    ia.l_ptr[1] = ia.l_ptr[0] + al16(4 * ((size_t)L.total.n_cons + n_close)) / 4;
+    ia.iota = (int*)(A + L.dev_off[3]);
+    ia.f_col_in = (const int*)at.forced[1]; ia.f_col = (int*)(A + L.dev_off[9]);
+    return ia;
+}
+
+// the index pass's grid: one item per edge of either set, one closing position per state and set, one per forced entry
+static dim3 union_grid(const gcnn_ibatch_layout& L) {
+    const long long items = (long long)L.total.n_cons_edges + L.total.n_cut_edges + 2 * L.n_states + L.n_forced_entries;
+    return dim3((unsigned)std::min<long long>((items + 255) / 256, 1024));
+}
+
+// union_tail: how a run on a union ends -- in selection mode the launch pair over all states (`cut_ptr`: the cut rows' offsets
+// over the whole union), then the flags into the output block.
+static int union_tail(int mode, const gcnn_ibatch_layout& L, char* A, const IbAt& at, const IbArgs& ia, const int* cut_ptr,
+                      double p_max, double p_max_ub, hipStream_t st) {
+    if (mode == GCNN_IBATCH_SELECT) {
+        SelArgs a = sel_args((const float*)(at.out + L.out_off[0]),
+                             SelRows{cut_ptr, ia.var[1], (const float*)at.arr[6], at.table + IB_K * IB_TS},
+                             SelRows{(const int*)at.forced[0], ia.f_col, (const float*)at.forced[2],
+                                     L.n_forced > 0 ? at.table + IB_F * IB_TS : nullptr},
+                             L.n_states, L.total.n_cuts, L.n_forced, L.max_cuts, L.total.n_vars, p_max, p_max_ub, A + L.dev_off[13],
+                             (int*)(at.out + L.out_off[1]), (int*)(at.out + L.out_off[2]));
+        const int rc = launch_select(a, st);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(at.out + L.out_off[3], ia.flags, 16 * (size_t)L.n_states, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
 // ibatch_run: everything of gcnn_infer_batch between its upload and its download, on a union that lies at `at` (infer_run's
 // counterpart): the index pass, the by-variable stage, ONE forward pass, ranking or selection, the flags into the output block.
 static int ibatch_run(int n_states, int mode, const gcnn_ibatch_layout& L, const float* params, char* A, const IbAt& at, double p_max,
                       double p_max_ub, hipStream_t st) {
     int rc;
     const gcnn_dims& T = L.total;
-    const size_t S = n_states;
-    const int E1 = T.n_cons_edges, E2 = T.n_cut_edges, V = T.n_vars, K = T.n_cuts, FE = L.n_forced_entries;
-    const int* table = at.table;
-    IbArgs ia; memset(&ia, 0, sizeof(ia));
-    ia.table = table; ia.n_states = n_states;
-    ia.packed[0] = (const int*)at.arr[1]; ia.packed[1] = (const int*)at.arr[5];
-    ia.left = (int*)(A + L.dev_off[0]); ia.var[0] = (int*)(A + L.dev_off[1]); ia.var[1] = (int*)(A + L.dev_off[2]);
-    ia.flags = (int*)at.zero;
-    ia.l_ptr[0] = (int*)(at.zero + al16(16 * S));
-    ia.l_ptr[1] = (int*)(at.zero + al16(16 * S) + al16(4 * ((size_t)T.n_cons + 1)));
-    ia.iota = (int*)(A + L.dev_off[3]);
-    ia.f_col_in = (const int*)at.forced[1]; ia.f_col = (int*)(A + L.dev_off[9]);
+    const int E1 = T.n_cons_edges, V = T.n_vars;
+    const IbArgs ia = union_args(at, L, A, 1);
     {
-        const long long items = (long long)E1 + E2 + 2 * n_states + FE;
         ProfScope prof("k_ib_unpack", st);
-        hipLaunchKernelGGL(k_ib_unpack, dim3((unsigned)std::min<long long>((items + 255) / 256, 1024)), dim3(256), 0, st, ia);
+        hipLaunchKernelGGL(k_ib_unpack, union_grid(L), dim3(256), 0, st, ia);
         LAUNCHCHK();
     }
     gcnn_graph cg, kg; memset(&cg, 0, sizeof(cg)); memset(&kg, 0, sizeof(kg));
@@ -141,27 +195,17 @@ static int ibatch_run(int n_states, int mode, const gcnn_ibatch_layout& L, const
     } else {
         HIPCHK(hipMemsetAsync((void*)cg.v_ptr, 0, ((size_t)V + 1) * sizeof(int), st));
     }
-    char* out = at.out;
-    float* scores = (float*)(out + L.out_off[0]);
+    float* scores = (float*)(at.out + L.out_off[0]);
     // ONE forward pass over the union (the longest segments are not known here: 0)
     rc = forward_impl(&T, params, (const float*)at.arr[0], (const float*)at.arr[3], (const float*)at.arr[4],
                       &cg, &kg, (float*)(A + L.dev_off[12]), gcnn_workspace_floats(&T), scores, 0, nullptr, 0.f, st);
     if (rc) return rc;
-    if (mode == GCNN_IBATCH_RANK && K > 0) {
+    if (mode == GCNN_IBATCH_RANK && T.n_cuts > 0) {
         ProfScope prof("k_ib_rank", st);
-        hipLaunchKernelGGL(k_ib_rank, dim3(n_states), dim3(256), 0, st, (const float*)scores, table, (int*)(out + L.out_off[1]));
+        hipLaunchKernelGGL(k_ib_rank, dim3(n_states), dim3(256), 0, st, (const float*)scores, at.table, (int*)(at.out + L.out_off[1]));
         LAUNCHCHK();
     }
-    if (mode == GCNN_IBATCH_SELECT) {
-        SelArgs a = sel_args(scores, SelRows{kg.l_ptr, kg.l_oth, kg.l_coef, table + IB_K * IB_TS},
-                             SelRows{(const int*)at.forced[0], ia.f_col, (const float*)at.forced[2],
-                                     L.n_forced > 0 ? table + IB_F * IB_TS : nullptr},
-                             n_states, K, L.n_forced, L.max_cuts, V, p_max, p_max_ub, A + L.dev_off[13], (int*)(out + L.out_off[1]),
-                             (int*)(out + L.out_off[2]));
-        if ((rc = launch_select(a, st))) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out + L.out_off[3], ia.flags, 16 * S, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return union_tail(mode, L, A, at, ia, kg.l_ptr, p_max, p_max_ub, st);
 }
 
 extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
@@ -175,16 +219,8 @@ extern "C" int gcnn_infer_batch(int32_t n_states, const gcnn_dims* dims, const i
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
     HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload
-    IbAt at;
-    at.table = (const int*)(A + L.in_off[0]); at.zero = A + L.in_off[1];
-    for (int i = 0; i < 7; ++i) at.arr[i] = A + L.in_off[2 + i];
-    for (int i = 0; i < 3; ++i) at.forced[i] = A + L.in_off[9 + i];
-    at.out = A + L.dev_off[11];
+    const IbAt at = union_at(A, L);
     if ((rc = ibatch_run(n_states, mode, L, params, A, at, p_max, p_max_ub, st))) return rc;
     HIPCHK(hipMemcpyAsync(host_out, at.out, L.out_bytes, hipMemcpyDeviceToHost, st));   // ONE download: scores | order | n_kept | flags
     return 0;
 }
-
-// gcnn_lp_batch: the union's states built from raw LP snapshots.  Included from here because it needs this file's statics and
-// gcnn_lpstate.hpp's, and gcnn_capi.hip ends with this file.
-#include "gcnn_lpbatch.hpp"

@@ -1,7 +1,8 @@
 // gcnn_lpbatch.hpp -- host side of gcnn_lp_batch (include/gcnn_hip.h): 1..64 raw LP snapshots in one upload, their states built in
 // the arena by one pair of launches (k_lpbatch.hpp) exactly where gcnn_infer_batch's upload would have put them, then that call's
-// run half (ibatch_run) unchanged, one download.  Included at the end of gcnn_ibatch.hpp (it shares that file's statics and
-// gcnn_lpstate.hpp's), kept apart so that its launch names form their own inventory (tests/test_lpbatch_build.py).
+// run half (ibatch_run) unchanged, one download.  Included from gcnn_capi.hip's list of host files, after gcnn_lpstate.hpp and
+// gcnn_ibatch.hpp (it shares their statics), kept apart so that its launch names form their own inventory
+// (tests/test_lpbatch_build.py).
 //
 // The arena: the union's layout for the built states' sizes (gcnn_ibatch_layout; its table and forced slots stay unused, its zero
 // block and seven arrays are written by the device, never uploaded) | the upload | the output block | the snapshots' scratch.
@@ -149,7 +150,3 @@ extern "C" int gcnn_lp_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t*
     HIPCHK(hipMemcpyAsync(host_out, at.out, L.out_bytes, hipMemcpyDeviceToHost, st));
     return 0;
 }
-
-// the cut-row path shares this file's table conventions and nothing of its state (tests/test_lpbatch_build.py pins the chain of
-// includes down to here: gcnn_capi.hip ends with gcnn_ibatch.hpp, that one with this file)
-#include "gcnn_hybrid.hpp"

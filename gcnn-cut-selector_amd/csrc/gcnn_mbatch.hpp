@@ -2,9 +2,10 @@
 // belong to 1..GCNN_GROUP_MAX models -- what a scoring server holds when the evaluators' task farm runs with `seed` as its innermost
 // loop (model_evaluator.py:211-219).  One upload of the states, one index pass over all of them and one by-variable stage for the
 // whole union (k_mbatch.hpp), the models' forward passes as ONE group (gcnn_group.hpp: one launch per distinct kernel and stage,
-// each member's solo bits), one ranking or selection over all states, one download.  Included at the end of gcnn_hybrid.hpp (it
-// needs gcnn_ibatch.hpp's statics, and the include chain from gcnn_capi.hip is pinned up to there), kept apart so that its launch
-// names form their own inventory (tests/test_mbatch_build.py).
+// each member's solo bits), one ranking or selection over all states, one download.  Included from gcnn_capi.hip's list of host
+// files, after gcnn_group.hpp and gcnn_ibatch.hpp: the layout, the index pass's arguments and the end of a run are that file's
+// (union_layout, union_at, union_args, union_tail).  Kept apart so that its launch names form their own inventory
+// (tests/test_mbatch_build.py).
 //
 // The upload and the download are gcnn_infer_batch's (gcnn_ibatch_layout), with two differences: the table carries the model words
 // behind its seven columns (MB_TABLE_WORDS), and the zero block holds one closing by-left entry per MODEL (C + n_models and
@@ -47,40 +48,22 @@ static int mbatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_f
     if ((rc = mbatch_models(n_states, dims, n_models, model_of_state, &mm))) return rc;
     memset(ML, 0, sizeof(*ML));
     gcnn_ibatch_layout* L = &ML->u;
-    L->total = gcnn_dims{(int)t.c, (int)t.v, (int)t.k, (int)t.e1, (int)t.e2};
-    L->n_forced = (int)t.f; L->n_forced_entries = (int)t.fe; L->max_cuts = t.max_cuts; L->n_states = n_states;
     ML->n_models = n_models;
     for (int m = 0; m <= n_models; ++m) ML->first_state[m] = mm.first[m];
-    const bool select = mode == GCNN_IBATCH_SELECT;
-    const size_t S = n_states, M = n_models, C = t.c, V = t.v, K = t.k, E1 = t.e1, E2 = t.e2, F = t.f, FE = t.fe;
-    // the table with its model words; the zero block: flags | l_ptr cons | l_ptr cut | the union's cut offsets (selection); the
-    // seven arrays of gcnn_infer's upload, stacked; the forced rows
-    const size_t sizes[9] = {al16(4 * (size_t)MB_TABLE_WORDS),
-                             al16(16 * S) + al16(4 * (C + M)) + al16(4 * (K + M)) + (select ? al16(4 * (K + 1)) : 0),
-                             16 * C, 8 * E1, 4 * E1, 56 * V, 24 * K, 8 * E2, 4 * E2};
-    Carver in{0};
-    for (int i = 0; i < 9; ++i) L->in_off[i] = in.take(sizes[i], 16);
-    forced_block(in, F, FE, &L->in_off[9]);
-    L->in_bytes = in.off;
-    L->out_off[0] = 0; L->out_off[1] = al16(4 * K); L->out_off[2] = L->out_off[1] + al16(4 * K);
-    L->out_off[3] = L->out_off[2] + al16(4 * S);
-    L->out_bytes = L->out_off[3] + 16 * S;
     size_t ws = 0;
     for (int m = 0; m < n_models; ++m) {
         ML->model[m] = mm.dims[m];
         ML->ws_off[m] = ws;
         ws += (sizeof(float) * gcnn_workspace_floats(&mm.dims[m]) + 255) & ~(size_t)255;
     }
-    // gcnn_infer_batch's blocks ([6]: one v_ptr per model, [12]: the models' forward workspaces) | the sort keys | the union's v_ptr
-    const size_t blocks[16] = {4 * E1, 4 * E1, 4 * E2, 4 * E1, 4 * E1, 4 * E1, 4 * (V + M), 4 * E1, 4 * E1, 4 * FE,
-                               sort_temp_bytes((int)E1), L->out_bytes, ws, select ? select_ws_bytes((int)K, (int)F, t.max_cuts) : 0,
-                               4 * E1, 4 * (V + 1)};
-    Carver dev{(in.off + 255) & ~(size_t)255};
-    for (int i = 0; i < 16; ++i) L->dev_off[i] = dev.take(blocks[i], 256);
-    for (int m = 0; m < n_models; ++m) ML->ws_off[m] += L->dev_off[12];
     ML->table_bytes = group_table_bytes(n_models);
-    ML->table_off = dev.take(ML->table_bytes, 256);
-    L->arena_bytes = dev.off;
+    // gcnn_infer_batch's layout with the model words behind the table, one closing entry per model ([6]: one v_ptr per model) and
+    // the models' forward workspaces at [12]; behind it the sort keys [14] | the union's v_ptr [15] | the group's launch tables
+    size_t extra[3];
+    union_layout(t, n_states, mode, n_models, al16(4 * (size_t)MB_TABLE_WORDS), mode == GCNN_IBATCH_SELECT, ws,
+                 {4 * (size_t)t.e1, 4 * ((size_t)t.v + 1), ML->table_bytes}, extra, L);
+    L->dev_off[14] = extra[0]; L->dev_off[15] = extra[1]; ML->table_off = extra[2];
+    for (int m = 0; m < n_models; ++m) ML->ws_off[m] += L->dev_off[12];
     return 0;
 }
 
@@ -123,18 +106,10 @@ static int mbatch_prepare(int n_states, int mode, const gcnn_mbatch_layout& ML, 
                           void* host_staging, hipStream_t st, MbCall* c) {
     const gcnn_ibatch_layout& L = ML.u;
     const gcnn_dims& T = L.total;
-    const size_t S = n_states, M = ML.n_models;
-    memset(&c->ma, 0, sizeof(c->ma));
+    const size_t M = ML.n_models;
     memset(c->mem, 0, sizeof(c->mem));
+    c->ma.ib = union_args(at, L, A, M);
     IbArgs& ia = c->ma.ib;
-    ia.table = at.table; ia.n_states = n_states;
-    ia.packed[0] = (const int*)at.arr[1]; ia.packed[1] = (const int*)at.arr[5];
-    ia.left = (int*)(A + L.dev_off[0]); ia.var[0] = (int*)(A + L.dev_off[1]); ia.var[1] = (int*)(A + L.dev_off[2]);
-    ia.flags = (int*)at.zero;
-    ia.l_ptr[0] = (int*)(at.zero + al16(16 * S));
-    ia.l_ptr[1] = ia.l_ptr[0] + al16(4 * ((size_t)T.n_cons + M)) / 4;
-    ia.iota = (int*)(A + L.dev_off[3]);
-    ia.f_col_in = (const int*)at.forced[1]; ia.f_col = (int*)(A + L.dev_off[9]);
     c->ma.key = (int*)(A + L.dev_off[14]);
     c->ma.sel_ptr = mode == GCNN_IBATCH_SELECT ? ia.l_ptr[1] + al16(4 * ((size_t)T.n_cuts + M)) / 4 : nullptr;
     c->v_ptr = (int*)(A + L.dev_off[6]); c->v_oth = (int*)(A + L.dev_off[7]); c->v_coef = (float*)(A + L.dev_off[8]);
@@ -168,13 +143,12 @@ static int mbatch_run(int n_states, int mode, const gcnn_mbatch_layout& ML, char
     int rc;
     const gcnn_ibatch_layout& L = ML.u;
     const gcnn_dims& T = L.total;
-    const size_t S = n_states, M = ML.n_models;
-    const int E1 = T.n_cons_edges, E2 = T.n_cut_edges, V = T.n_vars, K = T.n_cuts, FE = L.n_forced_entries;
+    const size_t M = ML.n_models;
+    const int E1 = T.n_cons_edges, V = T.n_vars;
     IbArgs& ia = c.ma.ib;
     {
-        const long long items = (long long)E1 + E2 + 2 * n_states + FE;
         ProfScope prof("k_mb_unpack", st);
-        hipLaunchKernelGGL(k_mb_unpack, dim3((unsigned)std::min<long long>((items + 255) / 256, 1024)), dim3(256), 0, st, c.ma);
+        hipLaunchKernelGGL(k_mb_unpack, union_grid(L), dim3(256), 0, st, c.ma);
         LAUNCHCHK();
     }
     if (E1 > 0) {   // gcnn_graph_build's by-variable stage on the union's list, keyed by the union's variable ids
@@ -192,23 +166,13 @@ static int mbatch_run(int n_states, int mode, const gcnn_mbatch_layout& ML, char
     // the second upload: the launch tables; then every stage of the forward passes as one launch per distinct kernel
     if ((rc = group_issue(ML.n_models, c.mem, host_staging, A + ML.table_off, c.plan,
                           [&](int i) { return group_member_step(c.mem[i], false, st); }, st))) return rc;
-    char* out = at.out;
-    const float* scores = (const float*)(out + L.out_off[0]);
-    if (mode == GCNN_IBATCH_RANK && K > 0) {
+    if (mode == GCNN_IBATCH_RANK && T.n_cuts > 0) {
         ProfScope prof("k_mb_rank", st);
-        hipLaunchKernelGGL(k_ib_rank, dim3(n_states), dim3(256), 0, st, scores, at.table, (int*)(out + L.out_off[1]));
+        hipLaunchKernelGGL(k_ib_rank, dim3(n_states), dim3(256), 0, st, (const float*)(at.out + L.out_off[0]), at.table,
+                           (int*)(at.out + L.out_off[1]));
         LAUNCHCHK();
     }
-    if (mode == GCNN_IBATCH_SELECT) {
-        SelArgs a = sel_args(scores, SelRows{c.ma.sel_ptr, ia.var[1], (const float*)at.arr[6], at.table + IB_K * IB_TS},
-                             SelRows{(const int*)at.forced[0], ia.f_col, (const float*)at.forced[2],
-                                     L.n_forced > 0 ? at.table + IB_F * IB_TS : nullptr},
-                             n_states, K, L.n_forced, L.max_cuts, V, p_max, p_max_ub, A + L.dev_off[13], (int*)(out + L.out_off[1]),
-                             (int*)(out + L.out_off[2]));
-        if ((rc = launch_select(a, st))) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out + L.out_off[3], ia.flags, 16 * S, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return union_tail(mode, L, A, at, ia, c.ma.sel_ptr, p_max, p_max_ub, st);
 }
 
 extern "C" int gcnn_infer_models(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
@@ -223,11 +187,7 @@ extern "C" int gcnn_infer_models(int32_t n_states, const gcnn_dims* dims, const 
     if ((rc = call_check(params[0], host_in, host_out, arena, arena_bytes, L.arena_bytes, mode == GCNN_IBATCH_SELECT, p_max, p_max_ub))) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
-    IbAt at;   // the upload lies at the arena's start
-    at.table = (const int*)(A + L.in_off[0]); at.zero = A + L.in_off[1];
-    for (int i = 0; i < 7; ++i) at.arr[i] = A + L.in_off[2 + i];
-    for (int i = 0; i < 3; ++i) at.forced[i] = A + L.in_off[9 + i];
-    at.out = A + L.dev_off[11];
+    const IbAt at = union_at(A, L);
     static thread_local MbCall call;
     if ((rc = mbatch_prepare(n_states, mode, ML, params, A, at, host_staging, st, &call))) return rc;   // host work only
     HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));       // upload 1: the states

@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib, lpstate, ops
-from .infer import SelectResult, _Staging, n_selected, normalize_forced
-from .model import GCNN
+from .infer import SelectResult, _Staging, forced_counts, forced_shapes, n_selected, prefix
+from .model import GCNN, _packed_forced, _snapshot_vars
 
 
 class _HybridSession(_Staging):
@@ -36,13 +36,11 @@ class _HybridSession(_Staging):
 
     def _layout(self, dims, fshapes, mode):
         n = len(dims)
-        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
-        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        nf, nfe = forced_counts(fshapes)
         L = _lib.HybridLayout()
         _lib.check(_lib.lib().gcnn_hybrid_layout_for(n, self._dims_array(dims), nf, nfe, mode, C.byref(L)), "gcnn_hybrid_layout_for")
-        prefix = lambda xs: [sum(xs[:i]) for i in range(n + 1)]  # noqa: E731
-        k_off = prefix([d["n_cuts"] for d in dims])
-        f_off, fe_off = (prefix([f[j] for f in fshapes]) if fshapes else [0] * (n + 1) for j in (0, 1))
+        k_off = prefix(d["n_cuts"] for d in dims)
+        f_off, fe_off = (prefix(f[j] for f in fshapes) for j in (0, 1))
         return nf, nfe, L, [list(L.snap_off[s]) for s in range(n)], k_off, f_off, fe_off, list(L.forced_off), list(L.out_off)
 
     def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0, arena=None):
@@ -50,33 +48,19 @@ class _HybridSession(_Staging):
         `arena` (tests): a device uint8 tensor to run in instead of the session's own."""
         n = len(checked)
         dims = [d for _, d in checked]
-        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        fshapes = forced_shapes(forced)
         key = (mode, tuple((d["n_cols"], d["n_cuts"], d["cut_nnz"]) for d in dims), fshapes)
         nf, nfe, L, snap_at, k_off, f_off, fe_off, forced_off, out_off = self.cached(key, self._layout, dims, fshapes, mode)
         d = self._dims_array(dims)          # (infinity is not part of the layout's key: the array is this call's)
         self._buffers(L)
         buf = self.in_np
         _lib.check(_lib.lib().gcnn_hybrid_fill_table(n, d, nf, nfe, mode, self.pin_in.data_ptr()), "gcnn_hybrid_fill_table")
-        for s, (arrays, _) in enumerate(checked):
-            for off, a in zip(snap_at[s], arrays):
+        for (arrays, _), at in zip(checked, snap_at):
+            for off, a in zip(at, arrays):
                 if a.size:
                     buf[off:off + a.nbytes] = a.view(np.uint8)
-            if forced is not None:
-                fptr, fcol, fval = forced[s]
-                o = forced_off[0] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next snapshot's first
-                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
-                self._put_forced((forced_off[1] + 4 * fe_off[s], forced_off[2] + 4 * fe_off[s]), (fcol, fval))
-        if forced is None:
-            buf[forced_off[0]:forced_off[0] + 4] = 0
-        dev = self.model.device
-        arena = self.arena if arena is None else arena
-        P = C.c_void_p
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            _lib.check(_lib.lib().gcnn_hybrid_select(n, d, nf, nfe, mode, P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()),
-                                                     P(arena.data_ptr()), arena.numel(), float(p_max), float(p_max_ub),
-                                                     P(stream.cuda_stream)), "gcnn_hybrid_select")
-            stream.synchronize()
+        self._put_forced_stacked(forced_off, f_off, fe_off, forced)
+        self._enqueue_wait("gcnn_hybrid_select", (n, d, nf, nfe, mode), (float(p_max), float(p_max_ub)), params=None, arena=arena)
         self.calls += 1
         self.upload_bytes = int(L.in_bytes)
         self.last = L
@@ -166,15 +150,7 @@ class HybridSelector:
         than 4,096 cuts holds the `GcnnError` of the size check, one the device flags its `ValueError`."""
         ops.check_thresholds(p_max, p_max_ub)
         snapshots = list(snapshots)
-        forced = [None] * len(snapshots) if forced is None else list(forced)
-        if len(forced) != len(snapshots):
-            raise ValueError(f"forced: one entry per snapshot expected, got {len(forced)} for {len(snapshots)} snapshots")
-        packed = []
-        for sn, f in zip(snapshots, forced):
-            try:
-                packed.append(normalize_forced(f, int(np.asarray(sn.col_type).shape[0])))
-            except Exception as exc:  # noqa: BLE001
-                packed.append(exc)
+        forced, packed = _packed_forced(snapshots, forced, _snapshot_vars, "snapshot")
         results = self._many(snapshots, _lib.HYBRID_SELECT, packed, p_max, p_max_ub)
         for i, r in enumerate(results):
             if isinstance(r, tuple):

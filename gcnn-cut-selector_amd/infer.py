@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -136,6 +137,29 @@ def normalize_forced(forced, n_vars):
     return ops.pack_rows(fi, fv, int(n_forced), n_vars)
 
 
+def al16(x):
+    return (x + 15) & ~15
+
+
+def prefix(xs):
+    """[0, xs[0], xs[0] + xs[1], ...]: the offset of every item of a stack and, last, its total."""
+    out = [0]
+    for x in xs:
+        out.append(out[-1] + x)
+    return out
+
+
+def forced_shapes(forced):
+    """(rows, entries) per state of packed forced rows [(ptr, col, val)]; () for None."""
+    return tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+
+
+def forced_counts(fshapes):
+    """`forced_shapes` as the (n_forced, n_forced_entries) int32 arrays of a many-state call; (None, None) without forced rows."""
+    n = len(fshapes)
+    return tuple((C.c_int32 * n)(*(f[j] for f in fshapes)) for j in (0, 1)) if fshapes else (None, None)
+
+
 def _carve(arena, blocks, floats):
     """{name: host copy of the `n` 32-bit words at byte offset `off` of a device arena} for blocks = {name: (off, n)}; int32 but for
     the names in `floats`."""
@@ -187,30 +211,52 @@ class _Staging:
             self.arena = None
             self.arena = torch.empty(max(2 * L.arena_bytes, 1 << 24), dtype=torch.uint8, device=self.model.device)
 
-    def _pointers(self):
-        P = C.c_void_p
-        return (P(self.model._flat.data_ptr()), P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(self.arena.data_ptr()),
-                self.arena.numel())
-
     def _put_forced(self, offsets, arrays):
         """Forced-row arrays (host, packed) into the upload at their byte offsets."""
         for off, a in zip(offsets, arrays):
             self.in_np[off:off + a.nbytes] = a.view(np.uint8)
 
-    def _enqueue_wait(self, name, head, tail, timings=None, t0=0.0, **extra):
-        """The C call `name`(*head, params and the three buffers, *tail, stream) on the model's device and its current stream, then
-        the wait for the download.  `timings` (optional dict): filled with the host-side phases in seconds -- `pack` (since `t0`),
-        `enqueue`, `wait` -- and with `extra`."""
-        t1 = time.perf_counter()
-        dev = self.model.device
+    def _put_forced_stacked(self, offsets, f_off, fe_off, forced):
+        """The forced rows of every state of a many-state call, stacked, into the upload at the byte `offsets` of ptr | col | val.
+        `f_off`, `fe_off`: the states' offsets over the stacked rows and entries.  A state's row offsets are shifted by the entries
+        in front of it; its closing one is the next state's first.  `forced` None: the one offset of no rows."""
+        buf = self.in_np
+        if forced is None:
+            buf[offsets[0]:offsets[0] + 4] = 0
+            return
+        o_ptr, o_col, o_val = offsets
+        for s, (fptr, fcol, fval) in enumerate(forced):
+            o, e = o_ptr + 4 * f_off[s], 4 * fe_off[s]
+            buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
+            buf[o_col + e:o_col + e + fcol.nbytes] = fcol.view(np.uint8)
+            buf[o_val + e:o_val + e + fval.nbytes] = fval.view(np.uint8)
+
+    def _enqueue_wait(self, name, head, tail, timings=None, t0=0.0, params=True, arena=None, may_decline=False, **extra):
+        """The C call `name`(*head, params, the two staging buffers, the arena and its size, *tail, stream) on the model's device
+        and its current stream, then the wait for the download.  `params`: True for the model's own, the argument itself for a
+        call of several models, None for a call that takes none.  `arena`: a device uint8 tensor to run in instead of the
+        session's own.  `may_decline`: a call that returns -4 is not an error -- nothing was enqueued and True is returned.
+        `timings` (optional dict): filled with the host-side phases in seconds -- `pack` (since `t0`), `enqueue`, `wait` -- and
+        with `extra`."""
+        t1 = time.perf_counter() if timings is not None else 0.0
+        dev, P = self.model.device, C.c_void_p
+        arena = self.arena if arena is None else arena
+        first = () if params is None else (P(self.model._flat.data_ptr()) if params is True else params,)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
-            _lib.check(getattr(_lib.lib(), name)(*head, *self._pointers(), *tail, C.c_void_p(stream.cuda_stream)), name)
+            rc = getattr(_lib.lib(), name)(*head, *first, P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(arena.data_ptr()),
+                                           arena.numel(), *tail, P(stream.cuda_stream))
+            if rc:
+                if may_decline and rc == -4:
+                    return True
+                _lib.check(rc, name)
+            if timings is None:
+                stream.synchronize()
+                return False
             t2 = time.perf_counter()
             stream.synchronize()
-        t3 = time.perf_counter()
-        if timings is not None:
-            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=t3 - t2, **extra)
+        timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=time.perf_counter() - t2, **extra)
+        return False
 
     def _verdict(self, flags_off):
         """The flag policy on one state's four plan flags in the download: "bad_index" (an index out of range), "declined"
@@ -236,6 +282,23 @@ class _Staging:
         if verdict:
             raise _UseGeneralPath()
         return self._read(*where)
+
+    def _collect(self, out_off, k_off, n_states, mode, more=None):
+        """Per state of a many-state call's download: ("ok", scores, order, n_kept), ("bad_index",) or ("declined",).  `k_off`: the
+        states' offsets over the stacked cuts.  `more(s, lo, n)` (the LP call): what it returns is appended to the state's "ok"
+        answer, the ValueError it raises becomes the state's ("error", exc)."""
+        res = []
+        for s in range(n_states):
+            lo, n = 4 * k_off[s], k_off[s + 1] - k_off[s]
+            try:
+                tail = more(s, lo, n) if more else ()
+            except ValueError as exc:
+                res.append(("error", exc))
+                continue
+            verdict = self._verdict(out_off[3] + 16 * s)
+            res.append((verdict,) if verdict else ("ok",) + self._read(
+                out_off[0] + lo, out_off[1] + lo if mode else None, out_off[2] + 4 * s if mode == _lib.IBATCH_SELECT else None, n) + tail)
+        return res
 
 
 def _solo_layout(key, n_forced=None, n_entries=None):
@@ -320,16 +383,22 @@ class _BatchSession(_Staging):
     def _layout(self, keys, fshapes, mode):
         n = len(keys)
         dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
-        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
-        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        nf, nfe = forced_counts(fshapes)
         L = _lib.IbatchLayout()
         if _unsupported(_lib.lib().gcnn_infer_batch_layout_for(n, dims, nf, nfe, mode, C.byref(L)), "gcnn_infer_batch_layout_for"):
             return False
         table = np.zeros(_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE, np.int32)
         _lib.check(_lib.lib().gcnn_infer_batch_fill_table(n, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
         cols = table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :n + 1].tolist()
+        return self._entry(dims, nf, nfe, L, table, cols)
+
+    @classmethod
+    def _entry(cls, dims, nf, nfe, L, table, cols, **more):
+        """A layout entry: the call's arguments, the layout with its offsets as lists, the table, its columns as lists (c, v, k, e1,
+        e2, f, fe offsets per state) and `where` every state's arrays go."""
         in_off = list(L.in_off)
-        return dims, nf, nfe, L, in_off, list(L.out_off), table, cols, self._where(in_off, cols, n)
+        return SimpleNamespace(dims=dims, nf=nf, nfe=nfe, L=L, in_off=in_off, out_off=list(L.out_off), table=table, cols=cols,
+                               where=cls._where(in_off, cols, len(dims)), **more)
 
     @classmethod
     def _where(cls, in_off, cols, n):
@@ -338,47 +407,28 @@ class _BatchSession(_Staging):
 
     def _pack(self, lay, checked, forced):
         """The upload of one call into the pinned buffer: the table, the zeroed block, every state, the forced rows."""
-        dims, nf, nfe, L, in_off, out_off, table, cols, where = lay[:9]
-        f_off, fe_off = cols[5], cols[6]
-        self._buffers(L)
+        in_off = lay.in_off
+        self._buffers(lay.L)
         buf, base = self.in_np, self.pin_in.data_ptr()
-        buf[in_off[0]:in_off[0] + table.nbytes] = table.view(np.uint8)
+        buf[in_off[0]:in_off[0] + lay.table.nbytes] = lay.table.view(np.uint8)
         buf[in_off[1]:in_off[2]] = 0          # flags and by-left offsets travel zeroed inside the upload
-        for s, (arrays, key) in enumerate(checked):
-            self.scratch = pack_state(buf, base, arrays, key, where[s], self.scratch)
-            if forced is not None:
-                fptr, fcol, fval = forced[s]
-                o = in_off[9] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next state's first
-                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
-                self._put_forced((in_off[10] + 4 * fe_off[s], in_off[11] + 4 * fe_off[s]), (fcol, fval))
-        if forced is None:
-            buf[in_off[9]:in_off[9] + 4] = 0
-
-    def _collect(self, lay, n_states, mode):
-        """Per state of the download: ("ok", scores, order, n_kept), ("bad_index",) or ("declined",)."""
-        out_off, k_off = lay[5], lay[7][2]
-        res = []
-        for s in range(n_states):
-            lo, n = 4 * k_off[s], k_off[s + 1] - k_off[s]
-            verdict = self._verdict(out_off[3] + 16 * s)
-            res.append((verdict,) if verdict else ("ok",) + self._read(
-                out_off[0] + lo, out_off[1] + lo if mode else None, out_off[2] + 4 * s if mode == _lib.IBATCH_SELECT else None, n))
-        return res
+        for (arrays, key), where in zip(checked, lay.where):
+            self.scratch = pack_state(buf, base, arrays, key, where, self.scratch)
+        self._put_forced_stacked(in_off[9:12], lay.cols[5], lay.cols[6], forced)
 
     def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
         """checked: [(arrays, key)] as `check_state` returns them; forced: None or [(ptr, col, val)] per state.
         Returns None when the library declines the union as a whole (too large: the caller splits it)."""
         keys = tuple(k for _, k in checked)
-        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        fshapes = forced_shapes(forced)
         lay = self.cached((mode, keys, fshapes), self._layout, keys, fshapes, mode)
         if lay is False:
             return None
-        dims, nf, nfe, L = lay[:4]
         self._pack(lay, checked, forced)
-        self._enqueue_wait("gcnn_infer_batch", (len(checked), dims, nf, nfe, mode), (float(p_max), float(p_max_ub)))
+        self._enqueue_wait("gcnn_infer_batch", (len(checked), lay.dims, lay.nf, lay.nfe, mode), (float(p_max), float(p_max_ub)))
         self.calls += 1
-        self.last = (L, len(checked))
-        return self._collect(lay, len(checked), mode)
+        self.last = (lay.L, len(checked))
+        return self._collect(lay.out_off, lay.cols[2], len(checked), mode)
 
     def last_plan(self):
         """The union's graph plan as the last call left it in the arena, as host arrays by name (`_InferenceSession.last_plan`'s
@@ -386,7 +436,6 @@ class _BatchSession(_Staging):
         L, s = self.last
         t, i, d = L.total, list(L.in_off), list(L.dev_off)
         e1, e2, v = t.n_cons_edges, t.n_cut_edges, t.n_vars
-        al16 = lambda x: (x + 15) & ~15  # noqa: E731
         l0 = i[1] + al16(16 * s)
         blocks = dict(flags=(i[1], 4 * s), l_ptr0=(l0, t.n_cons + 1), l_ptr1=(l0 + al16(4 * (t.n_cons + 1)), t.n_cuts + 1),
                       left=(d[0], e1), var0=(d[1], e1), var1=(d[2], e2), iota=(d[3], e1), v_ptr=(d[6], v + 1), v_oth=(d[7], e1),
@@ -415,8 +464,7 @@ class _ModelsSession:
     def _layout(self, keys, fshapes, mode, model_of):
         n, n_models = len(keys), model_of[-1] + 1
         dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
-        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
-        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        nf, nfe = forced_counts(fshapes)
         mos = (C.c_int32 * n)(*model_of)
         ML = _lib.MbatchLayout()
         if _unsupported(_lib.lib().gcnn_infer_models_layout_for(n, dims, nf, nfe, mode, n_models, mos, C.byref(ML)),
@@ -426,9 +474,7 @@ class _ModelsSession:
         _lib.check(_lib.lib().gcnn_infer_models_fill_table(n, dims, nf, nfe, n_models, mos, table.ctypes.data),
                    "gcnn_infer_models_fill_table")
         cols = table[:_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE].reshape(_lib.IBATCH_TABLE_COLS, -1)[:, :n + 1].tolist()
-        L = ML.u
-        in_off = list(L.in_off)
-        return dims, nf, nfe, L, in_off, list(L.out_off), table, cols, _BatchSession._where(in_off, cols, n), ML, mos, n_models
+        return _BatchSession._entry(dims, nf, nfe, ML.u, table, cols, ML=ML, mos=mos, n_models=n_models)
 
     def run(self, checked, forced, mode, model_of, models, p_max=0.0, p_max_ub=0.0):
         """checked, forced: as `_BatchSession.run` takes them, sorted by model; model_of: the model number of every state
@@ -436,30 +482,20 @@ class _ModelsSession:
         library declines the union's sizes (the caller splits it) or UNSUPPORTED when it declines the call as a whole."""
         base = self.base
         keys = tuple(k for _, k in checked)
-        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        fshapes = forced_shapes(forced)
         lay = self.cached((mode, keys, fshapes, tuple(model_of)), self._layout, keys, fshapes, mode, model_of)
         if lay is False:
             return None
-        dims, nf, nfe, L = lay[:4]
-        ML, mos, n_models = lay[9:]
         base._pack(lay, checked, forced)
-        self.staging, _ = base._pin(self.staging, None, ML.table_bytes, 1 << 16)
-        P = C.c_void_p
-        params = (P * n_models)(*(m._flat.data_ptr() for m in models))
-        dev = base.model.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            rc = _lib.lib().gcnn_infer_models(len(checked), dims, nf, nfe, mode, n_models, mos, params, P(base.pin_in.data_ptr()),
-                                              P(base.pin_out.data_ptr()), P(base.arena.data_ptr()), base.arena.numel(),
-                                              P(self.staging.data_ptr()), float(p_max), float(p_max_ub), P(stream.cuda_stream))
-            if rc == -4:
-                return self.UNSUPPORTED
-            _lib.check(rc, "gcnn_infer_models")
-            stream.synchronize()
+        self.staging, _ = base._pin(self.staging, None, lay.ML.table_bytes, 1 << 16)
+        params = (C.c_void_p * lay.n_models)(*(m._flat.data_ptr() for m in models))
+        if base._enqueue_wait("gcnn_infer_models", (len(checked), lay.dims, lay.nf, lay.nfe, mode, lay.n_models, lay.mos),
+                              (C.c_void_p(self.staging.data_ptr()), float(p_max), float(p_max_ub)), params=params, may_decline=True):
+            return self.UNSUPPORTED
         self.calls += 1
-        self.last = (ML, len(checked))
+        self.last = (lay.ML, len(checked))
         base.last = None          # the arena no longer holds that session's own plan
-        return base._collect(lay, len(checked), mode)
+        return base._collect(lay.out_off, lay.cols[2], len(checked), mode)
 
     def last_plan(self):
         """Every model's graph plan as the last call left it in the arena: a list with, per model, the arrays of
@@ -467,7 +503,6 @@ class _ModelsSession:
         ML, s = self.last
         L, t = ML.u, ML.u.total
         i, d, M = list(L.in_off), list(L.dev_off), ML.n_models
-        al16 = lambda x: (x + 15) & ~15  # noqa: E731
         l0 = i[1] + al16(16 * s)
         l1 = l0 + al16(4 * (t.n_cons + M))
         plans, c, v, k, e1, e2 = [], 0, 0, 0, 0, 0
@@ -593,16 +628,14 @@ class _LPBatchSession(_Staging):
     def _layout(self, dims, fshapes, mode):
         from . import lpstate
         n = len(dims)
-        nf = (C.c_int32 * n)(*(f[0] for f in fshapes)) if fshapes else None
-        nfe = (C.c_int32 * n)(*(f[1] for f in fshapes)) if fshapes else None
+        nf, nfe = forced_counts(fshapes)
         L = _lib.LpBatchLayout()
         if _unsupported(_lib.lib().gcnn_lp_batch_layout_for(n, self._dims_array(dims), nf, nfe, mode, C.byref(L)), "gcnn_lp_batch_layout_for"):
             return False
         base = list(L.snap_base)
         snap_at = [[base[s] + o for o in self.cached(("one",) + _int_key(d), self._one, d)] for s, d in enumerate(dims)]
-        prefix = lambda xs: [sum(xs[:i]) for i in range(n + 1)]  # noqa: E731
-        k_off = prefix([d["n_cuts"] for d in dims])
-        f_off, fe_off = (prefix([f[j] for f in fshapes]) if fshapes else [0] * (n + 1) for j in (0, 1))
+        k_off = prefix(d["n_cuts"] for d in dims)
+        f_off, fe_off = (prefix(f[j] for f in fshapes) for j in (0, 1))
         return nf, nfe, L, snap_at, k_off, f_off, fe_off, list(L.forced_off), list(L.out_off), [lpstate.state_key(d) for d in dims]
 
     def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
@@ -611,43 +644,28 @@ class _LPBatchSession(_Staging):
         from . import lpstate
         n = len(checked)
         dims = [d for _, d in checked]
-        fshapes = tuple((f[0].size - 1, f[1].size) for f in forced) if forced is not None else ()
+        fshapes = forced_shapes(forced)
         lay = self.cached((mode, tuple(_int_key(d) for d in dims), fshapes), self._layout, dims, fshapes, mode)
         if lay is False:
             return None
         nf, nfe, L, snap_at, k_off, f_off, fe_off, forced_off, out_off, keys = lay
         d = self._dims_array(dims)         # (the scalars are not part of the layout's key: the array is this call's)
         self._buffers(L)
-        buf = self.in_np
         _lib.check(_lib.lib().gcnn_lp_batch_fill_table(n, d, nf, nfe, mode, self.pin_in.data_ptr()), "gcnn_lp_batch_fill_table")
-        for s, (arrays, _) in enumerate(checked):
-            lpstate.pack_snapshot(buf, snap_at[s], arrays)
-            if forced is not None:
-                fptr, fcol, fval = forced[s]
-                o = forced_off[0] + 4 * f_off[s]      # offsets over the stacked entries; the closing one is the next snapshot's first
-                buf[o:o + 4 * fptr.size].view(np.int32)[:] = fptr + fe_off[s]
-                self._put_forced((forced_off[1] + 4 * fe_off[s], forced_off[2] + 4 * fe_off[s]), (fcol, fval))
-        if forced is None:
-            buf[forced_off[0]:forced_off[0] + 4] = 0
+        for (arrays, _), at in zip(checked, snap_at):
+            lpstate.pack_snapshot(self.in_np, at, arrays)
+        self._put_forced_stacked(forced_off, f_off, fe_off, forced)
         self._enqueue_wait("gcnn_lp_batch", (n, d, nf, nfe, mode), (float(p_max), float(p_max_ub)))
         self.calls += 1
         self.last = (L, keys)
-        out, res = self.out_np, []
-        for s in range(n):
-            lo, cuts = 4 * k_off[s], k_off[s + 1] - k_off[s]
-            try:
-                lpstate.raise_for_flags(out[out_off[4] + 16 * s:out_off[4] + 16 * s + 16].view(np.int32))
-            except ValueError as exc:
-                res.append(("error", exc))
-                continue
-            verdict = self._verdict(out_off[3] + 16 * s)
-            if verdict:
-                res.append((verdict,))
-                continue
-            answer = self._read(out_off[0] + lo, out_off[1] + lo if mode else None,
-                                out_off[2] + 4 * s if mode == _lib.IBATCH_SELECT else None, cuts)
-            res.append(("ok",) + answer + (out[out_off[5] + lo:out_off[5] + lo + 4 * cuts].view(np.int32).copy(),))
-        return res
+        out = self.out_np
+
+        def lp_part(s, lo, cuts):
+            """What the snapshot itself is flagged for (ValueError); else its cut_index."""
+            lpstate.raise_for_flags(out[out_off[4] + 16 * s:out_off[4] + 16 * s + 16].view(np.int32))
+            return (out[out_off[5] + lo:out_off[5] + lo + 4 * cuts].view(np.int32).copy(),)
+
+        return self._collect(out_off, k_off, n, mode, lp_part)
 
     def last_states(self):
         """The seven arrays of every state the last call built in the arena, as host arrays (tests compare them with gcnn_lp_state's)."""

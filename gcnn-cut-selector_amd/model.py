@@ -179,6 +179,50 @@ def _serve_many(n, admit, split, run, solo):
     return results
 
 
+def _state_vars(state):
+    return state.dims.n_vars if isinstance(state, Batch) else int(np.asarray(state[3]).shape[0])
+
+
+def _snapshot_vars(snapshot):
+    return int(np.asarray(snapshot.col_type).shape[0])
+
+
+def _packed_forced(items, forced, n_vars_of, noun):
+    """The forced rows of a `*_many` selection over `items` (`noun`s): (`forced` as a list with one entry per item, those entries
+    packed by `normalize_forced`).  An entry that cannot be packed holds its exception: it belongs to that item's slot."""
+    forced = [None] * len(items) if forced is None else list(forced)
+    if len(forced) != len(items):
+        raise ValueError(f"forced: one entry per {noun} expected, got {len(forced)} for {len(items)} {noun}s")
+    packed = []
+    for item, f in zip(items, forced):
+        try:
+            packed.append(normalize_forced(f, n_vars_of(item)))
+        except Exception as exc:  # noqa: BLE001
+            packed.append(exc)
+    return forced, packed
+
+
+def _as_scores(results, rank, cut_index=False):
+    """`_serve_many`'s ("ok", scores, order, n_kept[, cut_index]) answers as `ScoreArray`s, in place; exceptions stay."""
+    for i, r in enumerate(results):
+        if isinstance(r, tuple):
+            scores = r[1]
+            if cut_index:
+                scores.cut_index = r[4]
+            if rank:
+                scores.rankings = r[2]
+            results[i] = scores
+    return results
+
+
+def _as_selections(results, max_selected, cut_index=False):
+    """`_serve_many`'s ("ok", scores, order, n_kept[, cut_index]) answers as `SelectResult`s, in place; exceptions stay."""
+    for i, r in enumerate(results):
+        if isinstance(r, tuple):
+            results[i] = SelectResult(r[2], r[3], n_selected(r[3], max_selected), r[1], r[4] if cut_index else None)
+    return results
+
+
 class GCNN:
     """Bipartite GCNN cut scorer (the reference's `GCNN(BaseModel)`, model.py:136-300) on MI355X."""
 
@@ -651,13 +695,7 @@ class GCNN:
         states = list(states)
         mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
         results = self._many(states, mode, lambda i: self.score_state(states[i], rank))
-        for i, r in enumerate(results):
-            if isinstance(r, tuple):
-                scores = r[1]
-                if rank:
-                    scores.rankings = r[2]
-                results[i] = scores
-        return self._finish_many(results, return_exceptions)
+        return self._finish_many(_as_scores(results, rank), return_exceptions)
 
     def select_cuts_many(self, states, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
         """`select_cuts` for many host states at once (gcnn_infer_batch in selection mode).  `forced`: None, or one entry per state
@@ -665,25 +703,13 @@ class GCNN:
         `score_states` (a state with more than 4,096 cuts holds the `GcnnError` `select_cuts` raises for it)."""
         ops.check_thresholds(p_max, p_max_ub)
         states = list(states)
-        forced = [None] * len(states) if forced is None else list(forced)
-        if len(forced) != len(states):
-            raise ValueError(f"forced: one entry per state expected, got {len(forced)} for {len(states)} states")
-        packed = []
-        for st, f in zip(states, forced):
-            try:
-                packed.append(normalize_forced(f, st.dims.n_vars if isinstance(st, Batch) else int(np.asarray(st[3]).shape[0])))
-            except Exception as exc:  # noqa: BLE001
-                packed.append(exc)
+        forced, packed = _packed_forced(states, forced, _state_vars, "state")
 
         def solo(i):
             return self.select_cuts(states[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
 
         results = self._many(states, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub)
-        for i, r in enumerate(results):
-            if isinstance(r, tuple):
-                _, scores, order, n_kept = r
-                results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
-        return self._finish_many(results, return_exceptions)
+        return self._finish_many(_as_selections(results, max_selected), return_exceptions)
 
     # ---- many LP snapshots in one call (gcnn_lp_batch): what a scoring server does with the snapshots that queued up ----------
     def score_lps(self, snapshots, rank=False, return_exceptions=False):
@@ -695,14 +721,7 @@ class GCNN:
         snapshots = list(snapshots)
         mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
         results = self._many(snapshots, mode, lambda i: self.score_lp(snapshots[i], rank), lp=True)
-        for i, r in enumerate(results):
-            if isinstance(r, tuple):
-                scores = r[1]
-                scores.cut_index = r[4]
-                if rank:
-                    scores.rankings = r[2]
-                results[i] = scores
-        return self._finish_many(results, return_exceptions)
+        return self._finish_many(_as_scores(results, rank, cut_index=True), return_exceptions)
 
     def select_cuts_lp_many(self, snapshots, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
         """`select_cuts_lp` for many `LPSnapshot`s at once (gcnn_lp_batch in selection mode).  `forced`: None, or one entry per
@@ -710,25 +729,13 @@ class GCNN:
         `select_cuts_many`."""
         ops.check_thresholds(p_max, p_max_ub)
         snapshots = list(snapshots)
-        forced = [None] * len(snapshots) if forced is None else list(forced)
-        if len(forced) != len(snapshots):
-            raise ValueError(f"forced: one entry per snapshot expected, got {len(forced)} for {len(snapshots)} snapshots")
-        packed = []
-        for sn, f in zip(snapshots, forced):
-            try:
-                packed.append(normalize_forced(f, int(np.asarray(sn.col_type).shape[0])))
-            except Exception as exc:  # noqa: BLE001
-                packed.append(exc)
+        forced, packed = _packed_forced(snapshots, forced, _snapshot_vars, "snapshot")
 
         def solo(i):
             return self.select_cuts_lp(snapshots[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
 
         results = self._many(snapshots, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub, lp=True)
-        for i, r in enumerate(results):
-            if isinstance(r, tuple):
-                _, scores, order, n_kept, cut_index = r
-                results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
-        return self._finish_many(results, return_exceptions)
+        return self._finish_many(_as_selections(results, max_selected, cut_index=True), return_exceptions)
 
     def get_concrete_function(self):
         """Counterpart of `tf.function(model.call).get_concrete_function()` (model_evaluator.py:310-311): an inference
@@ -820,35 +827,17 @@ class ModelSet:
         keys, states = list(keys), list(states)
         mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
         results = self._many(keys, states, mode, lambda i: self.models[keys[i]].score_state(states[i], rank))
-        for i, r in enumerate(results):
-            if isinstance(r, tuple):
-                scores = r[1]
-                if rank:
-                    scores.rankings = r[2]
-                results[i] = scores
-        return GCNN._finish_many(results, return_exceptions)
+        return GCNN._finish_many(_as_scores(results, rank), return_exceptions)
 
     def select_cuts_many(self, keys, states, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
         """`GCNN.select_cuts_many` for states of several models (`keys[i]` names the model of `states[i]`).  Returns a list of
         `SelectResult` in the caller's order."""
         ops.check_thresholds(p_max, p_max_ub)
         keys, states = list(keys), list(states)
-        forced = [None] * len(states) if forced is None else list(forced)
-        if len(forced) != len(states):
-            raise ValueError(f"forced: one entry per state expected, got {len(forced)} for {len(states)} states")
-        packed = []
-        for st, f in zip(states, forced):
-            try:
-                packed.append(normalize_forced(f, st.dims.n_vars if isinstance(st, Batch) else int(np.asarray(st[3]).shape[0])))
-            except Exception as exc:  # noqa: BLE001
-                packed.append(exc)
+        forced, packed = _packed_forced(states, forced, _state_vars, "state")
 
         def solo(i):
             return self.models[keys[i]].select_cuts(states[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
 
         results = self._many(keys, states, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub)
-        for i, r in enumerate(results):
-            if isinstance(r, tuple):
-                _, scores, order, n_kept = r
-                results[i] = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores)
-        return GCNN._finish_many(results, return_exceptions)
+        return GCNN._finish_many(_as_selections(results, max_selected), return_exceptions)

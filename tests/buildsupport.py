@@ -2,7 +2,7 @@
 gcnn_capi.hip to gfx950 assembly and reports registers, occupancy, LDS and scratch per function with
 -Rpass-analysis=kernel-resource-usage.  `device_build()` runs that compile once per Python process -- pytest imports this module
 once per session, so every module that asks shares it -- and remembers a failure as well as a success.  Also the check that a
-set of entry points is declared in the header, bound, exported and at ABI 13."""
+set of entry points is declared in the header, bound, exported and at ABI 13, and the check of where a host file is included."""
 from __future__ import annotations
 
 import atexit
@@ -97,3 +97,14 @@ def declared_everywhere(symbols) -> str:
         assert re.search(rf"\b{sym}\s*\(", header) and sym in _lib.SIGNATURES and hasattr(lib, sym)
     assert _lib.ABI_VERSION == 13 and lib.gcnn_abi_version() == 13
     return header
+
+
+def included_once_after(name, *needs):
+    """The host file `name` (gcnn_*.hpp) is included exactly once, from gcnn_capi.hip's list, behind every file of `needs` -- those
+    whose statics it uses -- and no host file includes another host file."""
+    include = re.compile(r'^[ \t]*#include "(gcnn_\w+\.hpp)"', re.M)
+    order = include.findall(open(os.path.join(CSRC, "gcnn_capi.hip")).read())
+    assert order.count(name) == 1 and all(order.count(n) == 1 and order.index(n) < order.index(name) for n in needs), order
+    for host in sorted(os.listdir(CSRC)):
+        if re.fullmatch(r"gcnn_\w+\.hpp", host):
+            assert not include.findall(open(os.path.join(CSRC, host)).read()), host

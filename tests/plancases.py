@@ -84,8 +84,9 @@ SOURCE_PINS = {
         "if (d->n_vars > IPLAN_MAX_VARS) return GCNN_E_UNSUPPORTED;",
     ),
     "gcnn_ibatch.hpp": (
-        "const long long items = (long long)E1 + E2 + 2 * n_states + FE;",
-        "hipLaunchKernelGGL(k_ib_unpack, dim3((unsigned)std::min<long long>((items + 255) / 256, 1024)), dim3(256), 0, st, ia);",
+        "const long long items = (long long)L.total.n_cons_edges + L.total.n_cut_edges + 2 * L.n_states + L.n_forced_entries;",
+        "return dim3((unsigned)std::min<long long>((items + 255) / 256, 1024));",
+        "hipLaunchKernelGGL(k_ib_unpack, union_grid(L), dim3(256), 0, st, ia);",
         "if (E1 > 0) {          // gcnn_graph_build's by-variable stage on the union's list",
     ),
     "k_infer.hpp": (
@@ -114,13 +115,18 @@ SOURCE_PINS = {
         "for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long long)gridDim.x * 256) {",
         "while (hi - s > 1) { const int mid = (s + hi) >> 1; if (tab[IB_FE][mid] <= i) s = mid; else hi = mid; }",
         "while (hi - s > 1) { const int mid = (s + hi) >> 1; if (eoff[mid] + mid <= item) s = mid; else hi = mid; }",
-        "a.f_col[i] = (c >= 0 && c < nv) ? c + tab[IB_V][s] : -1;",
-        "if (j == 0) l_ptr[l0] = e0;",
+        "int vr = tab[IB_V][s];",
+        "a.f_col[i] = (c >= 0 && c < nv) ? c + vr : -1;",
+        "int m = 0, er = e0, lr = l0, vr = v0;",                 # without models: the union's own offsets
+        "int* l_ptr = a.l_ptr[set] + l0 + m;",
+        "l_ptr[0] = er;",
         "const int lo = j == 0 ? -1 : min(max(src[j - 1], -1), n_left);",
         "const int hb = j == E ? n_left : min(max(src[j], -1), n_left);",
-        "for (int k = max(lo + 1, 1); k <= min(hb, n_left - 1); ++k) l_ptr[l0 + k] = e0 + j;",
-        "a.var[set][e0 + j] = v0 + (bad_v ? 0 : v);",
-        "a.left[e0 + j] = l0 + min(max(l, 0), max(n_left - 1, 0));",
+        "for (int k = max(lo + 1, 1); k <= min(hb, n_left - 1); ++k) {",
+        "l_ptr[k] = er + j;",
+        "a.var[set][e0 + j] = vr + (bad_v ? 0 : v);",
+        "a.left[e0 + j] = lr + min(max(l, 0), max(n_left - 1, 0));",
+        "ib_unpack_body<false>(a, tab, nullptr, nullptr, nullptr);",
     ),
 }
 

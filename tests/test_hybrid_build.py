@@ -38,7 +38,7 @@ def test_launch_names_are_its_own():
     for other in sorted(os.listdir(CSRC)):
         if other.startswith("gcnn_") and other.endswith(".hpp") and other != "gcnn_hybrid.hpp":
             assert not names & launchnames.launch_names(os.path.join(CSRC, other)), other
-    assert open(os.path.join(CSRC, "gcnn_lpbatch.hpp")).read().rstrip().endswith('#include "gcnn_hybrid.hpp"')
+    buildsupport.included_once_after("gcnn_hybrid.hpp", "gcnn_select.hpp", "gcnn_lpstate.hpp")
 
 
 def test_kernels_compile_wave64_without_scratch_or_float_atomics():

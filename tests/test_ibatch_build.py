@@ -34,8 +34,7 @@ def test_launch_names_are_their_own():
     assert len(old) == 28 and not new & old
     for f in ("gcnn_select.hpp", "gcnn_group.hpp", "gcnn_rank.hpp", "gcnn_prenorm.hpp"):
         assert not new & launchnames.launch_names(os.path.join(CSRC, f))
-    capi = open(os.path.join(CSRC, "gcnn_capi.hip")).read()
-    assert capi.rstrip().endswith('#include "gcnn_ibatch.hpp"')
+    buildsupport.included_once_after("gcnn_ibatch.hpp", "gcnn_select.hpp")
 
 
 def _layout(shapes, forced=None, mode=0):

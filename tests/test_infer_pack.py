@@ -65,7 +65,7 @@ def test_pack_state_batch_layout():
     off = table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)
     in_off = list(L.in_off)
     got, want = np.full(L.in_bytes, 0xAB, np.uint8), np.full(L.in_bytes, 0xAB, np.uint8)
-    session_where = infer._BatchSession(None)._layout(tuple(key for _, key in checked), (), _lib.IBATCH_SCORES)[-1]
+    session_where = infer._BatchSession(None)._layout(tuple(key for _, key in checked), (), _lib.IBATCH_SCORES).where
     scratch = None
     for s, (arrays, key) in enumerate(checked):
         where = tuple(in_off[2 + j] + STRIDES[j] * int(off[COLUMNS[j], s]) for j in range(7))

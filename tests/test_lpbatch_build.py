@@ -35,9 +35,7 @@ def test_launch_names_are_its_own():
     for other in sorted(os.listdir(CSRC)):
         if other.startswith("gcnn_") and other.endswith(".hpp") and other != "gcnn_lpbatch.hpp":
             assert not names & launchnames.launch_names(os.path.join(CSRC, other)), other
-    capi = open(os.path.join(CSRC, "gcnn_capi.hip")).read()
-    assert capi.rstrip().endswith('#include "gcnn_ibatch.hpp"') and "gcnn_lpbatch.hpp" not in capi
-    assert open(os.path.join(CSRC, "gcnn_ibatch.hpp")).read().rstrip().endswith('#include "gcnn_lpbatch.hpp"')
+    buildsupport.included_once_after("gcnn_lpbatch.hpp", "gcnn_select.hpp", "gcnn_lpstate.hpp", "gcnn_ibatch.hpp")
 
 
 def test_kernels_compile_wave64_without_scratch_or_float_atomics():

@@ -35,7 +35,7 @@ def test_launch_names_are_its_own():
     for other in sorted(os.listdir(CSRC)):
         if other.startswith("gcnn_") and other.endswith(".hpp") and other != "gcnn_mbatch.hpp":
             assert not names & launchnames.launch_names(os.path.join(CSRC, other)), other
-    assert open(os.path.join(CSRC, "gcnn_hybrid.hpp")).read().rstrip().endswith('#include "gcnn_mbatch.hpp"')
+    buildsupport.included_once_after("gcnn_mbatch.hpp", "gcnn_select.hpp", "gcnn_group.hpp", "gcnn_ibatch.hpp")
     # the forward passes go out under the group kernels' names: this file spells none of them
     assert "k_group_" not in re.sub(r"//[^\n]*", "", open(MBATCH).read())
 
