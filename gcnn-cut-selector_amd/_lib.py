@@ -116,6 +116,11 @@ class MbatchLayout(C.Structure):
                 ("model", Dims * GROUP_MAX), ("ws_off", C.c_size_t * GROUP_MAX), ("table_off", C.c_size_t),
                 ("table_bytes", C.c_size_t)]
 
+
+class LpModelsLayout(C.Structure):
+    _fields_ = [("models", MbatchLayout), ("lp", LpBatchLayout)]   # lp.state == models.u
+
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -186,6 +191,9 @@ SIGNATURES = {
     "gcnn_infer_models_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, C.POINTER(MbatchLayout)]),
     "gcnn_infer_models_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P, _P]),
     "gcnn_infer_models": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_lp_models_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, C.POINTER(LpModelsLayout)]),
+    "gcnn_lp_models_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P]),
+    "gcnn_lp_models": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }
 
 _lib = None

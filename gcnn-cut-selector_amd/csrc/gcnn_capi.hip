@@ -1380,3 +1380,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_hybrid.hpp"
 // host states of several models in one call (include/gcnn_hip.h: gcnn_infer_models): launch names k_mb_*
 #include "gcnn_mbatch.hpp"
+// raw LP snapshots of several models in one call (include/gcnn_hip.h: gcnn_lp_models): launch names k_lpm_*
+#include "gcnn_lpmodels.hpp"

@@ -2,7 +2,10 @@
 // the arena by one pair of launches (k_lpbatch.hpp) exactly where gcnn_infer_batch's upload would have put them, then that call's
 // run half (ibatch_run) unchanged, one download.  Included from gcnn_capi.hip's list of host files, after gcnn_lpstate.hpp and
 // gcnn_ibatch.hpp (it shares their statics), kept apart so that its launch names form their own inventory
-// (tests/test_lpbatch_build.py).
+// (tests/test_lpbatch_build.py).  What a call that builds its union from snapshots needs whichever union it is -- the layout
+// (lpset_layout), the descriptor table (lpset_fill), the builder launches' arguments (lpset_launch) and where the built union lies
+// (lpset_at) -- takes the union's layout and the size of its table as parameters: gcnn_lpmodels.hpp, included after this file,
+// uses them with gcnn_infer_models' union.
 //
 // The arena: the union's layout for the built states' sizes (gcnn_ibatch_layout; its table and forced slots stay unused, its zero
 // block and seven arrays are written by the device, never uploaded) | the upload | the output block | the snapshots' scratch.
@@ -12,10 +15,14 @@
 static_assert(LPSET_MAX == GCNN_IBATCH_MAX && LPSET_TS == GCNN_IBATCH_TABLE_STRIDE, "one descriptor per state of the union");
 static_assert(GCNN_LP_ARRAYS == 22, "LpSetEntry::snap");
 
-static const size_t LPSET_IB_TABLE = 4 * (size_t)IB_COLS * IB_TS;     // the union's table comes first in the upload
+static const size_t LPSET_IB_TABLE = 4 * (size_t)IB_COLS * IB_TS;     // gcnn_lp_batch: the union's table comes first in the upload
 
-static int lpset_layout(int n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
-                        gcnn_lp_batch_layout* L, gcnn_lp_layout* each /* [n], optional */) {
+// lpset_layout: the layout of a call that builds its union from snapshots.  `front`: the bytes of the union's table, which lie in
+// front of the descriptor table in the upload; `union_of(sd, &L->state)`: the union's own layout for the built states' sizes
+// (gcnn_infer_batch's here; gcnn_infer_models' in gcnn_lpmodels.hpp, included after this file).
+template <class UnionOf>
+static int lpset_layout(int n, const gcnn_lp_dims* dims, size_t front, UnionOf union_of, gcnn_lp_batch_layout* L,
+                        gcnn_lp_layout* each /* [n], optional */) {
     if (!L || !dims || n < 1 || n > GCNN_IBATCH_MAX) return GCNN_E_BADARG;
     gcnn_dims sd[GCNN_IBATCH_MAX];
     for (int s = 0; s < n; ++s) {
@@ -23,11 +30,11 @@ static int lpset_layout(int n, const gcnn_lp_dims* dims, const int32_t* n_forced
         sd[s] = lp_state_dims(&dims[s]);
     }
     memset(L, 0, sizeof(*L));
-    int rc = ibatch_layout(n, sd, n_forced, n_forced_entries, mode, &L->state);
+    int rc = union_of(sd, &L->state);
     if (rc) return rc;
     const gcnn_ibatch_layout& S = L->state;
     L->n_snapshots = n;
-    L->table_bytes = LPSET_IB_TABLE + sizeof(LpSetHead) + (size_t)n * sizeof(LpSetEntry);
+    L->table_bytes = front + sizeof(LpSetHead) + (size_t)n * sizeof(LpSetEntry);
     Carver in{0}, scratch{0};
     in.take(L->table_bytes, 16);
     for (int s = 0; s < n; ++s) {
@@ -51,9 +58,15 @@ static int lpset_layout(int n, const gcnn_lp_dims* dims, const int32_t* n_forced
     return 0;
 }
 
+static int lpbatch_layout(int n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int mode,
+                          gcnn_lp_batch_layout* L, gcnn_lp_layout* each) {
+    return lpset_layout(n, dims, LPSET_IB_TABLE, [&](const gcnn_dims* sd, gcnn_ibatch_layout* S) {
+        return ibatch_layout(n, sd, n_forced, n_forced_entries, mode, S); }, L, each);
+}
+
 extern "C" int gcnn_lp_batch_layout_for(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
                                         int32_t mode, gcnn_lp_batch_layout* L) {
-    return lpset_layout(n, dims, n_forced, n_forced_entries, mode, L, nullptr);
+    return lpbatch_layout(n, dims, n_forced, n_forced_entries, mode, L, nullptr);
 }
 
 static void lpset_blocks(const gcnn_lp_dims& d, int* stats, int* emit) {
@@ -61,19 +74,11 @@ static void lpset_blocks(const gcnn_lp_dims& d, int* stats, int* emit) {
     *stats = std::max(1, ncc + nrc + nkc); *emit = nrc + nkc + 1;
 }
 
-extern "C" int gcnn_lp_batch_fill_table(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
-                                        int32_t mode, void* table) {
-    if (!table) return GCNN_E_BADARG;
-    gcnn_lp_batch_layout L;
-    gcnn_lp_layout each[GCNN_IBATCH_MAX];
-    int rc = lpset_layout(n, dims, n_forced, n_forced_entries, mode, &L, each);
-    if (rc) return rc;
-    gcnn_dims sd[GCNN_IBATCH_MAX];
-    for (int s = 0; s < n; ++s) sd[s] = lp_state_dims(&dims[s]);
-    int32_t* ib = (int32_t*)table;
-    memset(table, 0, L.table_bytes);
-    if ((rc = ibatch_sums(n, sd, n_forced, n_forced_entries, mode, nullptr, ib))) return rc;
-    LpSetHead* h = (LpSetHead*)((char*)table + LPSET_IB_TABLE);
+// lpset_fill: the descriptor table behind the union's table (`front` bytes, already written: its columns say where state s lies)
+static void lpset_fill(int n, const gcnn_lp_dims* dims, const gcnn_lp_batch_layout& L, const gcnn_lp_layout* each, size_t front,
+                       void* table) {
+    const int32_t* ib = (const int32_t*)table;
+    LpSetHead* h = (LpSetHead*)((char*)table + front);
     LpSetEntry* e = (LpSetEntry*)(h + 1);
     const gcnn_ibatch_layout& S = L.state;
     h->n = n;
@@ -92,7 +97,7 @@ extern "C" int gcnn_lp_batch_fill_table(int32_t n, const gcnn_lp_dims* dims, con
         for (int i = 0; i < 7; ++i) e->scratch[i] = (long long)(sb + parts[i]);
         const size_t c0 = ib[IB_C * IB_TS + s], v0 = ib[IB_V * IB_TS + s], k0 = ib[IB_K * IB_TS + s];
         const size_t e1 = ib[IB_E1 * IB_TS + s], e2 = ib[IB_E2 * IB_TS + s];
-        // where gcnn_infer_batch's upload keeps state s: features at the union's rows, each edge list as the state's own [2,E_s] block
+        // where the union's upload keeps state s: features at the union's rows, each edge list as the state's own [2,E_s] block
         const size_t dst[9] = {S.in_off[2] + 16 * c0, S.in_off[3] + 8 * e1, S.in_off[4] + 4 * e1, S.in_off[5] + 56 * v0,
                                S.in_off[6] + 24 * k0, S.in_off[7] + 8 * e2, S.in_off[8] + 4 * e2,
                                L.out_dev_off + L.out_off[5] + 4 * k0, L.out_dev_off + L.out_off[4] + 16 * (size_t)s};
@@ -103,31 +108,67 @@ extern "C" int gcnn_lp_batch_fill_table(int32_t n, const gcnn_lp_dims* dims, con
         e->nrc = lp_chunks(d.n_rows); e->ncc = lp_chunks(d.n_cols); e->nkc = lp_chunks(d.n_cuts); e->n_stat_blocks = ns;
     }
     h->blk0[0][n] = b_stats; h->blk0[1][n] = b_emit;
+}
+
+extern "C" int gcnn_lp_batch_fill_table(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                                        int32_t mode, void* table) {
+    if (!table) return GCNN_E_BADARG;
+    gcnn_lp_batch_layout L;
+    gcnn_lp_layout each[GCNN_IBATCH_MAX];
+    int rc = lpbatch_layout(n, dims, n_forced, n_forced_entries, mode, &L, each);
+    if (rc) return rc;
+    gcnn_dims sd[GCNN_IBATCH_MAX];
+    for (int s = 0; s < n; ++s) sd[s] = lp_state_dims(&dims[s]);
+    memset(table, 0, L.table_bytes);
+    if ((rc = ibatch_sums(n, sd, n_forced, n_forced_entries, mode, nullptr, (int32_t*)table))) return rc;
+    lpset_fill(n, dims, L, each, LPSET_IB_TABLE, table);
     return 0;
+}
+
+// What the two builder launches take for an upload that lies at L.up_off (`front` as in lpset_layout), and their grids.  They
+// clear the union's zero block, whichever union's it is.
+static LpSetArgs lpset_launch(int n, const gcnn_lp_dims* dims, const gcnn_lp_batch_layout& L, size_t front, char* A, int* n_stats,
+                              int* n_emit) {
+    const gcnn_ibatch_layout& S = L.state;
+    *n_stats = *n_emit = 0;
+    for (int s = 0; s < n; ++s) {
+        int a, b;
+        lpset_blocks(dims[s], &a, &b);
+        *n_stats += a; *n_emit += b;
+    }
+    LpSetArgs g;
+    g.table = A + L.up_off + front; g.base = A;
+    g.zero = (int*)(A + S.in_off[1]); g.zero_words = (int)((S.in_off[2] - S.in_off[1]) / 4);
+    return g;
+}
+
+// where the union lies once they have run: the table and the forced rows in the upload, the zero block and the seven arrays at the
+// union's own positions, the output block behind the upload
+static IbAt lpset_at(char* A, const gcnn_lp_batch_layout& L) {
+    const gcnn_ibatch_layout& S = L.state;
+    char* up = A + L.up_off;
+    IbAt at;
+    at.table = (const int*)up; at.zero = A + S.in_off[1];
+    for (int i = 0; i < 7; ++i) at.arr[i] = A + S.in_off[2 + i];
+    for (int i = 0; i < 3; ++i) at.forced[i] = up + L.forced_off[i];
+    at.out = A + L.out_dev_off;
+    return at;
 }
 
 extern "C" int gcnn_lp_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int32_t mode,
                              const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
                              double p_max_ub, void* stream) {
     gcnn_lp_batch_layout L;
-    int rc = lpset_layout(n, dims, n_forced, n_forced_entries, mode, &L, nullptr);
+    int rc = lpbatch_layout(n, dims, n_forced, n_forced_entries, mode, &L, nullptr);
     if (rc) return rc;
     const gcnn_ibatch_layout& S = L.state;
     if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L.arena_bytes, mode == GCNN_IBATCH_SELECT, p_max, p_max_ub))) return rc;
     if ((rc = ibatch_precheck(S, params, arena))) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
-    char* up = A + L.up_off;
-    HIPCHK(hipMemcpyAsync(up, host_in, L.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload: tables | snapshots | forced rows
-    int n_stats = 0, n_emit = 0;
-    for (int s = 0; s < n; ++s) {
-        int a, b;
-        lpset_blocks(dims[s], &a, &b);
-        n_stats += a; n_emit += b;
-    }
-    LpSetArgs g;
-    g.table = up + LPSET_IB_TABLE; g.base = A;
-    g.zero = (int*)(A + S.in_off[1]); g.zero_words = (int)((S.in_off[2] - S.in_off[1]) / 4);
+    HIPCHK(hipMemcpyAsync(A + L.up_off, host_in, L.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload: tables | snapshots | forced rows
+    int n_stats, n_emit;
+    const LpSetArgs g = lpset_launch(n, dims, L, LPSET_IB_TABLE, A, &n_stats, &n_emit);
     {
         ProfScope prof("k_lpset_stats", st);
         hipLaunchKernelGGL(k_lpset_stats, dim3(n_stats), dim3(LP_NT), 0, st, g);
@@ -140,11 +181,7 @@ extern "C" int gcnn_lp_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t*
     }
     // A flagged snapshot leaves parts of its own state unwritten: they keep what the arena held.  k_ib_unpack confines whatever ids
     // lie there to the state's own ranges, and the caller discards that state's results once an LP flag is set.
-    IbAt at;
-    at.table = (const int*)up; at.zero = A + S.in_off[1];
-    for (int i = 0; i < 7; ++i) at.arr[i] = A + S.in_off[2 + i];
-    for (int i = 0; i < 3; ++i) at.forced[i] = up + L.forced_off[i];
-    at.out = A + L.out_dev_off;
+    const IbAt at = lpset_at(A, L);
     if ((rc = ibatch_run(n, mode, S, params, A, at, p_max, p_max_ub, st))) return rc;
     // ONE download: scores | order | n_kept | batch flags | LP flags | cut_index
     HIPCHK(hipMemcpyAsync(host_out, at.out, L.out_bytes, hipMemcpyDeviceToHost, st));

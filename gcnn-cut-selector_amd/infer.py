@@ -1,5 +1,5 @@
 """Host arrays in, one C call, host arrays out: the host side of gcnn_infer, gcnn_infer_select, gcnn_infer_batch, the LP-snapshot
-calls and gcnn_lp_batch (include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
+calls, gcnn_lp_batch, gcnn_infer_models and gcnn_lp_models (include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
 of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers."""
 
 from __future__ import annotations
@@ -625,47 +625,63 @@ class _LPBatchSession(_Staging):
         from . import lpstate
         return list(lpstate.lp_layout(dims)[1].snap_off)
 
-    def _layout(self, dims, fshapes, mode):
+    def _entry(self, dims, fshapes, nf, nfe, L, **more):
+        """A layout entry: the forced counts, the layout `L` (an `LpBatchLayout`) and what the packer and the reader derive from
+        it -- where every array of every snapshot goes, the offsets of the states' cuts and forced rows, the built states' keys."""
         from . import lpstate
-        n = len(dims)
-        nf, nfe = forced_counts(fshapes)
-        L = _lib.LpBatchLayout()
-        if _unsupported(_lib.lib().gcnn_lp_batch_layout_for(n, self._dims_array(dims), nf, nfe, mode, C.byref(L)), "gcnn_lp_batch_layout_for"):
-            return False
         base = list(L.snap_base)
         snap_at = [[base[s] + o for o in self.cached(("one",) + _int_key(d), self._one, d)] for s, d in enumerate(dims)]
-        k_off = prefix(d["n_cuts"] for d in dims)
         f_off, fe_off = (prefix(f[j] for f in fshapes) for j in (0, 1))
-        return nf, nfe, L, snap_at, k_off, f_off, fe_off, list(L.forced_off), list(L.out_off), [lpstate.state_key(d) for d in dims]
+        return SimpleNamespace(nf=nf, nfe=nfe, L=L, snap_at=snap_at, k_off=prefix(d["n_cuts"] for d in dims), f_off=f_off, fe_off=fe_off,
+                               forced_off=list(L.forced_off), out_off=list(L.out_off), keys=[lpstate.state_key(d) for d in dims], **more)
+
+    def _layout(self, dims, fshapes, mode):
+        nf, nfe = forced_counts(fshapes)
+        L = _lib.LpBatchLayout()
+        if _unsupported(_lib.lib().gcnn_lp_batch_layout_for(len(dims), self._dims_array(dims), nf, nfe, mode, C.byref(L)),
+                        "gcnn_lp_batch_layout_for"):
+            return False
+        return self._entry(dims, fshapes, nf, nfe, L)
+
+    def _pack(self, lay, checked, forced, mode, fill, *model_args):
+        """The upload of one call into the pinned buffer: the tables (written by the library's `fill`, gcnn_lp_batch_fill_table or
+        its twin for several models, which takes `model_args` behind the mode), every snapshot, the forced rows.  Returns the
+        call's array of dims (the scalars are not part of the layout's key: the array is this call's)."""
+        from . import lpstate
+        d = self._dims_array([dims for _, dims in checked])
+        self._buffers(lay.L)
+        _lib.check(getattr(_lib.lib(), fill)(len(checked), d, lay.nf, lay.nfe, mode, *model_args, self.pin_in.data_ptr()), fill)
+        for (arrays, _), at in zip(checked, lay.snap_at):
+            lpstate.pack_snapshot(self.in_np, at, arrays)
+        self._put_forced_stacked(lay.forced_off, lay.f_off, lay.fe_off, forced)
+        return d
+
+    def _answers(self, lay, n, mode):
+        """`_collect` on the download of a call with `lay`'s output block: every snapshot's answer with its cut_index, or the
+        ValueError of what the device flags in the snapshot itself."""
+        from . import lpstate
+        out, out_off = self.out_np, lay.out_off
+
+        def lp_part(s, lo, cuts):
+            lpstate.raise_for_flags(out[out_off[4] + 16 * s:out_off[4] + 16 * s + 16].view(np.int32))
+            return (out[out_off[5] + lo:out_off[5] + lo + 4 * cuts].view(np.int32).copy(),)
+
+        return self._collect(out_off, lay.k_off, n, mode, lp_part)
 
     def run(self, checked, forced, mode, p_max=0.0, p_max_ub=0.0):
         """checked: [(arrays, dims)] as `check` returns them; forced: None or [(ptr, col, val)] per snapshot.
         Returns None when the library declines the union as a whole (too large: the caller splits it)."""
-        from . import lpstate
         n = len(checked)
         dims = [d for _, d in checked]
         fshapes = forced_shapes(forced)
         lay = self.cached((mode, tuple(_int_key(d) for d in dims), fshapes), self._layout, dims, fshapes, mode)
         if lay is False:
             return None
-        nf, nfe, L, snap_at, k_off, f_off, fe_off, forced_off, out_off, keys = lay
-        d = self._dims_array(dims)         # (the scalars are not part of the layout's key: the array is this call's)
-        self._buffers(L)
-        _lib.check(_lib.lib().gcnn_lp_batch_fill_table(n, d, nf, nfe, mode, self.pin_in.data_ptr()), "gcnn_lp_batch_fill_table")
-        for (arrays, _), at in zip(checked, snap_at):
-            lpstate.pack_snapshot(self.in_np, at, arrays)
-        self._put_forced_stacked(forced_off, f_off, fe_off, forced)
-        self._enqueue_wait("gcnn_lp_batch", (n, d, nf, nfe, mode), (float(p_max), float(p_max_ub)))
+        d = self._pack(lay, checked, forced, mode, "gcnn_lp_batch_fill_table")
+        self._enqueue_wait("gcnn_lp_batch", (n, d, lay.nf, lay.nfe, mode), (float(p_max), float(p_max_ub)))
         self.calls += 1
-        self.last = (L, keys)
-        out = self.out_np
-
-        def lp_part(s, lo, cuts):
-            """What the snapshot itself is flagged for (ValueError); else its cut_index."""
-            lpstate.raise_for_flags(out[out_off[4] + 16 * s:out_off[4] + 16 * s + 16].view(np.int32))
-            return (out[out_off[5] + lo:out_off[5] + lo + 4 * cuts].view(np.int32).copy(),)
-
-        return self._collect(out_off, k_off, n, mode, lp_part)
+        self.last = (lay.L, lay.keys)
+        return self._answers(lay, n, mode)
 
     def last_states(self):
         """The seven arrays of every state the last call built in the arena, as host arrays (tests compare them with gcnn_lp_state's)."""
@@ -683,6 +699,48 @@ class _LPBatchSession(_Staging):
             out.append(tuple(arrays))
             at = [a + b for a, b in zip(at, key)]
         return out
+
+
+class _LPModelsSession(_ModelsSession):
+    """Host side of gcnn_lp_models: one C call for up to 64 LP snapshots of up to 8 models.  `_ModelsSession` over an
+    `_LPBatchSession` (`base`: the LP batch session of one of the models; every model of the call lives on its device): that
+    session's checks, packer, pinned buffers, arena and reader, plus the model arguments and the launch tables' staging buffer.
+    `last_plan()` is `_ModelsSession`'s: the union lies at the same places of the arena whether it was uploaded or built there."""
+
+    def _layout(self, dims, fshapes, mode, model_of):
+        n, n_models = len(dims), model_of[-1] + 1
+        nf, nfe = forced_counts(fshapes)
+        mos = (C.c_int32 * n)(*model_of)
+        ML = _lib.LpModelsLayout()
+        if _unsupported(_lib.lib().gcnn_lp_models_layout_for(n, self.base._dims_array(dims), nf, nfe, mode, n_models, mos, C.byref(ML)),
+                        "gcnn_lp_models_layout_for"):
+            return False
+        return self.base._entry(dims, fshapes, nf, nfe, ML.lp, ML=ML, mos=mos, n_models=n_models)
+
+    def run(self, checked, forced, mode, model_of, models, p_max=0.0, p_max_ub=0.0):
+        """checked, forced: as `_LPBatchSession.run` takes them, sorted by model; model_of, models: as `_ModelsSession.run` takes
+        them.  Returns `_LPBatchSession.run`'s list, None when the library declines the union's sizes (the caller splits it) or
+        UNSUPPORTED when it declines the call as a whole."""
+        base, n = self.base, len(checked)
+        dims = [d for _, d in checked]
+        fshapes = forced_shapes(forced)
+        lay = self.cached((mode, tuple(_int_key(d) for d in dims), fshapes, tuple(model_of)), self._layout, dims, fshapes, mode, model_of)
+        if lay is False:
+            return None
+        d = base._pack(lay, checked, forced, mode, "gcnn_lp_models_fill_table", lay.n_models, lay.mos)
+        self.staging, _ = base._pin(self.staging, None, lay.ML.models.table_bytes, 1 << 16)
+        params = (C.c_void_p * lay.n_models)(*(m._flat.data_ptr() for m in models))
+        if base._enqueue_wait("gcnn_lp_models", (n, d, lay.nf, lay.nfe, mode, lay.n_models, lay.mos),
+                              (C.c_void_p(self.staging.data_ptr()), float(p_max), float(p_max_ub)), params=params, may_decline=True):
+            return self.UNSUPPORTED
+        self.calls += 1
+        self.last = (lay.ML.models, n)
+        base.last = (lay.L, lay.keys)      # the arena holds this call's states, at the places `base.last_states` reads
+        return base._answers(lay, n, mode)
+
+    def last_states(self):
+        """The seven arrays of every state the last call built in the arena (`_LPBatchSession.last_states`)."""
+        return self.base.last_states()
 
 
 def _int_key(dims):

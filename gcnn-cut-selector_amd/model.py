@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPSession, _ModelsSession,
+from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPModelsSession, _LPSession, _ModelsSession,
                     _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
 
@@ -755,7 +755,9 @@ class ModelSet:
     and `select_cuts_many` take them together with the key of each state's model and answer them with ONE gcnn_infer_models call
     per 8 models / 64 states: one upload, one index pass and one by-variable stage, the models' forward passes as a group, one
     download.  Every state's result has the bits of its own model's `GCNN.score_states` / `select_cuts_many` on that model's
-    states alone.  All models live on one device."""
+    states alone.  `score_lps` and `select_cuts_lp_many` are the same for raw `LPSnapshot`s (gcnn_lp_models: the states are built
+    on the device in front of the same work), with the bits of `GCNN.score_lps` / `select_cuts_lp_many`.  All models live on one
+    device."""
     MAX_MODELS = _ModelsSession.MAX_MODELS
 
     def __init__(self, models):
@@ -767,27 +769,37 @@ class ModelSet:
             raise ValueError(f"ModelSet: all models must be on one device, got {sorted(devices)}")
         self._number = {k: i for i, k in enumerate(self.models)}
         self._session = None
-        self.calls = 0                    # gcnn_infer_models calls made
+        self._lp_session = None
+        self.calls = 0                    # gcnn_infer_models and gcnn_lp_models calls made
         self.max_models_per_call = 0      # the most models one of them served
 
-    def _sess(self):
+    def _sess(self, lp=False):
+        first = next(iter(self.models.values()))
+        if lp:
+            if self._lp_session is None:
+                self._lp_session = _LPModelsSession(first._sess("_lp_batch_session", _LPBatchSession))
+            return self._lp_session
         if self._session is None:
-            first = next(iter(self.models.values()))
             self._session = _ModelsSession(first._sess("_batch_session", _BatchSession))
         return self._session
 
-    def _many(self, keys, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0):
-        """`GCNN._many` over states of several models: results per state in the caller's order."""
+    def _many(self, keys, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0, lp=False):
+        """`GCNN._many` over states -- with `lp`, LP snapshots -- of several models: results per state in the caller's order."""
         if len(keys) != len(states):
             raise ValueError(f"keys: one model key per state expected, got {len(keys)} for {len(states)} states")
-        session = self._sess()
+        session = self._sess(lp)
+        more = dict(lp=True) if lp else {}
 
         def admit(i):
             if keys[i] not in self.models:
                 raise KeyError(f"no model {keys[i]!r}")
             if forced is not None and isinstance(forced[i], Exception):
                 raise forced[i]
-            return GCNN._admit_state(states[i], mode)
+            if not lp:
+                return GCNN._admit_state(states[i], mode)
+            entry = session.base.check(states[i])
+            n_cuts = entry[1]["n_cuts"]
+            return None if n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096) else entry
 
         def split(ids):
             """Sorted stably by model (a model's states keep their relative order), at most 8 models and 64 states per call."""
@@ -810,7 +822,7 @@ class ModelSet:
                 for k in order:
                     mine = [j for j, i in enumerate(ids) if keys[i] == k]
                     sub = self.models[k]._many([states[ids[j]] for j in mine], mode, lambda x, mine=mine: solo(ids[mine[x]]),
-                                               None if forced is None else [forced[ids[j]] for j in mine], p_max, p_max_ub)
+                                               None if forced is None else [forced[ids[j]] for j in mine], p_max, p_max_ub, **more)
                     for j, r in zip(mine, sub):
                         got[j] = ("error", r) if isinstance(r, Exception) else r
             elif got is not None:
@@ -841,3 +853,29 @@ class ModelSet:
 
         results = self._many(keys, states, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub)
         return GCNN._finish_many(_as_selections(results, max_selected), return_exceptions)
+
+    # ---- LP snapshots of several models in one call (gcnn_lp_models) ------------------------------------------------------------
+    def score_lps(self, keys, snapshots, rank=False, return_exceptions=False):
+        """`GCNN.score_lps` for `LPSnapshot`s of several models: `keys[i]` names the model of `snapshots[i]`, in any order.  ONE
+        gcnn_lp_models call per 8 models / 64 snapshots: one upload of the packed snapshots, two launches build every state where
+        gcnn_infer_models keeps its uploaded ones, then that call's device work, one download.  Returns a list of `ScoreArray` in
+        the caller's order, each in STATE order with `.cut_index`, and `.rankings` when `rank`; errors per snapshot as
+        `GCNN.score_lps` reports them (an unknown key is its snapshot's KeyError).  Snapshots the call declines go through their
+        own model's `score_lp`."""
+        keys, snapshots = list(keys), list(snapshots)
+        mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
+        results = self._many(keys, snapshots, mode, lambda i: self.models[keys[i]].score_lp(snapshots[i], rank), lp=True)
+        return GCNN._finish_many(_as_scores(results, rank, cut_index=True), return_exceptions)
+
+    def select_cuts_lp_many(self, keys, snapshots, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
+        """`GCNN.select_cuts_lp_many` for `LPSnapshot`s of several models (`keys[i]` names the model of `snapshots[i]`).  Returns
+        a list of `SelectResult` with `.cut_index`, in the caller's order."""
+        ops.check_thresholds(p_max, p_max_ub)
+        keys, snapshots = list(keys), list(snapshots)
+        forced, packed = _packed_forced(snapshots, forced, _snapshot_vars, "snapshot")
+
+        def solo(i):
+            return self.models[keys[i]].select_cuts_lp(snapshots[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
+
+        results = self._many(keys, snapshots, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub, lp=True)
+        return GCNN._finish_many(_as_selections(results, max_selected, cut_index=True), return_exceptions)

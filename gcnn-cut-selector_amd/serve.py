@@ -8,11 +8,11 @@ worker, one selector call per separation round) share ONE process that owns the 
 
 The server takes every request that is waiting and groups them by kind: the host-state requests of ALL models share one
 `ModelSet.score_states` / `ModelSet.select_cuts_many` call (a group of one model's requests takes that model's own call) (the farm's queue runs `seed` innermost, model_evaluator.py:211-219, so
-the workers that wait hold different models; one upload, the models' forward passes as a group, one download).  With
-`cross_model=False`, and for the LP kinds, it groups by model and kind and answers each group with one `GCNN.score_states` /
+the workers that wait hold different models; one upload, the models' forward passes as a group, one download), and the LP
+requests of all models one `ModelSet.score_lps` / `ModelSet.select_cuts_lp_many` call, which also builds the states on the device
+(`cross_model_lp`).  With `cross_model=False` it groups by model and kind and answers each group with one `GCNN.score_states` /
 `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP kinds one
-`GCNN.score_lps` / `GCNN.select_cuts_lp_many` call, which also builds the states on the device -- and goes back for whatever
-queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
+`GCNN.score_lps` / `GCNN.select_cuts_lp_many` call -- and goes back for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
 hybrid quality from the cut rows, `client.select_cuts_hybrid`) need no model: those that are waiting are grouped by thresholds and
 answered with one `HybridSelector.select_cuts_many`.
 
@@ -330,14 +330,17 @@ class ScoringServer:
     more than 8 models; 1 for a call on one model).  `cross_model`: host-state requests of all models share one group per kind
     (and thresholds), served by a `ModelSet` over the models -- a group that holds requests of ONE model still takes that model's
     own call, which is the faster one for it (profiles/mixed_models.txt); False, or models on more than one device, groups by
-    model.  `model_set`: the set to use instead of `ModelSet(models)` (built on first use)."""
+    model.  `cross_model_lp`: with `cross_model`, the LP kinds share across models in the same way (`ModelSet.score_lps` /
+    `select_cuts_lp_many`; profiles/lp_models.txt); False keeps them grouped by model.  `model_set`: the set to use instead of
+    `ModelSet(models)` (built on first use)."""
 
-    def __init__(self, models, address, backlog=128, cross_model=True, model_set=None):
+    def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True):
         self.models = dict(models)
         self.address = address
         # a ModelSet needs all models on one device: models spread over several devices are served per model, as before
         one_device = len({str(getattr(m, "device", None)) for m in self.models.values()}) <= 1
         self.cross_model = bool(cross_model) and (model_set is not None or one_device)
+        self.cross_model_lp = bool(cross_model_lp)
         self._model_set = model_set
         self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0)
         self._listen = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
@@ -442,7 +445,8 @@ class ScoringServer:
         for conn, req in pending:
             selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT, KIND_HYBRID_SELECT)
             hybrid = req["kind"] == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
-            shared = hybrid or (self.cross_model and req["kind"] not in _LP_BASE)   # host states: one ModelSet call for all models
+            # one ModelSet call for all models: host states with `cross_model`, LP snapshots with `cross_model_lp` as well
+            shared = hybrid or (self.cross_model and (self.cross_model_lp or req["kind"] not in _LP_BASE))
             gkey = (None if shared else req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
             groups.setdefault(gkey, []).append((conn, req))
         for gkey, items in groups.items():
@@ -460,7 +464,8 @@ class ScoringServer:
                     score_many, select_many = None, self._hybrid_selector().select_cuts_many
                 elif gkey[0] is None and len(set(mkeys)) > 1:
                     mset = self._set()
-                    score_many, select_many = partial(mset.score_states, mkeys), partial(mset.select_cuts_many, mkeys)
+                    score_many, select_many = (mset.score_lps, mset.select_cuts_lp_many) if lp else (mset.score_states, mset.select_cuts_many)
+                    score_many, select_many = partial(score_many, mkeys), partial(select_many, mkeys)
                 else:
                     model = self.models[mkeys[0]]
                     score_many, select_many = (model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)

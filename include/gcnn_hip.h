@@ -668,6 +668,44 @@ int gcnn_infer_models(int32_t n_states, const gcnn_dims* dims, const int32_t* n_
                       const void* host_in, void* host_out, void* arena, size_t arena_bytes, void* host_staging, double p_max,
                       double p_max_ub, void* stream);
 
+/* ---- LP snapshots of several models in one call: gcnn_infer_models in front of which the device builds every state -----------------
+ * The same farm with workers that send the raw LP (no get_state in the worker): the snapshots that wait belong to DIFFERENT models.
+ * gcnn_lp_models is gcnn_lp_batch's contract for 1..GCNN_IBATCH_MAX snapshots of 1..GCNN_GROUP_MAX models, with the two model
+ * arguments of gcnn_infer_models: model_of_snapshot[s] under model_of_state's rules (non-decreasing from 0, no gaps; a model without
+ * a snapshot is refused), params[m] and host_staging as there.  No kernel of its own: the host half of gcnn_infer_models (nothing
+ * enqueued), ONE upload, gcnn_lp_batch's two builder launches -- they leave state s exactly where gcnn_infer_models' upload would
+ * have put it and clear that call's zero block --, then gcnn_infer_models' device work unchanged (index pass, by-variable sort and
+ * its split per model, the second upload: the launch tables, the forward passes as a group, one ranking launch or one selection
+ * launch pair), ONE download.  Every snapshot's state has the bits gcnn_lp_state gives it alone, its results the bits gcnn_lp_batch
+ * gives for its own model's snapshots alone.
+ *
+ * layout.models: gcnn_infer_models' layout for the built states' sizes (u.in_off[1] the zero block, u.in_off[2..8] the seven arrays,
+ *   inside the arena; nothing of it is uploaded; table_bytes: what host_staging holds).  layout.lp: every field as in
+ *   gcnn_lp_batch_layout, with lp.state == models.u.
+ * host_in (pinned, lp.in_bytes): [0, lp.table_bytes) the tables -- gcnn_lp_models_fill_table writes them: gcnn_infer_models' table
+ *   (GCNN_MBATCH_TABLE_WORDS int32), then gcnn_lp_batch's descriptor part; the snapshots at lp.snap_base[s], the forced rows at
+ *   lp.forced_off, as in gcnn_lp_batch.
+ * host_out (pinned, lp.out_bytes): lp.out_off[0..5] as gcnn_lp_batch's: scores, order, n_kept, flags [n][4], LP flags [n][4],
+ *   cut_index.  Flags mean what they mean there; a flagged snapshot changes no other snapshot's results.
+ * Returned before anything is enqueued: whatever gcnn_lp_batch or gcnn_infer_models returns before enqueueing (GCNN_E_BADARG for n
+ * outside 1..GCNN_IBATCH_MAX, a gcnn_lp_dims gcnn_lp_layout_for refuses, n_models outside 1..GCNN_GROUP_MAX, a model_of_snapshot that
+ * decreases, skips a model or leaves one without a snapshot, thresholds, buffers; GCNN_E_UNSUPPORTED for a union past 2^24 rows or 2^30
+ * edges, edges with nothing to point at, and a forward pass the group recorder cannot take). */
+typedef struct gcnn_lp_models_layout {
+    gcnn_mbatch_layout models;
+    gcnn_lp_batch_layout lp;
+} gcnn_lp_models_layout;
+int gcnn_lp_models_layout_for(int32_t n, const gcnn_lp_dims* dims /* host [n] */, const int32_t* n_forced,
+                              const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
+                              const int32_t* model_of_snapshot /* host [n] */, gcnn_lp_models_layout* layout /* host */);
+/* table: host_in (host), lp.table_bytes bytes.  No device work. */
+int gcnn_lp_models_fill_table(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                              int32_t mode, int32_t n_models, const int32_t* model_of_snapshot, void* table /* host */);
+int gcnn_lp_models(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int32_t mode,
+                   int32_t n_models, const int32_t* model_of_snapshot, const float* const* params /* host [n_models] */,
+                   const void* host_in, void* host_out, void* arena, size_t arena_bytes, void* host_staging, double p_max,
+                   double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
