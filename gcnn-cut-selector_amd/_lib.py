@@ -121,6 +121,26 @@ class LpModelsLayout(C.Structure):
     _fields_ = [("models", MbatchLayout), ("lp", LpBatchLayout)]   # lp.state == models.u
 
 
+LPR_LB, LPR_UB, LPR_PRIMAL, LPR_PRIMAL_AVG = 1, 2, 4, 8      # GCNN_LPR_*: the optional column arrays a round carries
+LPR_DERIVED, LPR_ARRAYS, LPR_BLOCKS = 7, 15, 11             # GCNN_LPR_DERIVED, GCNN_LPR_ARRAYS, GCNN_LPR_BLOCKS
+
+
+class LpRowsLayout(C.Structure):
+    _fields_ = [("bytes", C.c_size_t), ("off", C.c_size_t * LPR_DERIVED)]
+
+
+class LpResident(C.Structure):
+    _fields_ = [("row_place", C.c_void_p), ("row_scale", C.c_void_p), ("cons_feats", C.c_void_p), ("col_type", C.c_void_p),
+                ("col_obj", C.c_void_p), ("col_lb", C.c_void_p), ("col_ub", C.c_void_p), ("col_primal", C.c_void_p),
+                ("col_primal_avg", C.c_void_p), ("cons_graph", Graph)]
+
+
+class LpRoundLayout(C.Structure):
+    _fields_ = [("in_bytes", C.c_size_t), ("in_off", C.c_size_t * LPR_ARRAYS), ("forced_off", C.c_size_t * 3),
+                ("out_bytes", C.c_size_t), ("out_off", C.c_size_t * 6), ("arena_bytes", C.c_size_t),
+                ("dev_off", C.c_size_t * LPR_BLOCKS)]
+
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -194,6 +214,11 @@ SIGNATURES = {
     "gcnn_lp_models_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, C.POINTER(LpModelsLayout)]),
     "gcnn_lp_models_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P]),
     "gcnn_lp_models": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_lp_rows_layout_for": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpRowsLayout)]),
+    "gcnn_lp_rows_build": (C.c_int, [C.POINTER(LpDims), _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "gcnn_lp_round_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, C.POINTER(LpRoundLayout)]),
+    "gcnn_lp_round": (C.c_int, [C.POINTER(LpDims), _I, C.POINTER(LpResident), _P, _P, _P, _P, _Z, _I, _P]),
+    "gcnn_lp_round_select": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, C.POINTER(LpResident), _P, _P, _P, _P, _Z, _D, _D, _P]),
 }
 
 _lib = None

@@ -1382,3 +1382,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_mbatch.hpp"
 // raw LP snapshots of several models in one call (include/gcnn_hip.h: gcnn_lp_models): launch names k_lpm_*
 #include "gcnn_lpmodels.hpp"
+// an LP resident on the device across separation rounds (include/gcnn_hip.h: gcnn_lp_rows_build, gcnn_lp_round): launch names k_lpr_*
+#include "gcnn_lpres.hpp"

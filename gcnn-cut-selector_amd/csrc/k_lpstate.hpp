@@ -250,7 +250,12 @@ __global__ __launch_bounds__(LP_NT) void k_lp_stats(LpArgs a) {
     lp_stats_body(a, blockIdx.x);
 }
 
-__device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
+// What the resident-LP path (k_lpres.hpp) takes from the same body, so that both hold the same bits; every member null (the
+// default) is this file's own behaviour.  row_place [R][2] and row_scale [R]: the rows are emitted without their solve-dependent half
+// (row_dual and row_basis are not read, cons_feats columns 1 and 3 are zero) and every row's two state places (-1: side not listed)
+// and its dual divisor norm * obj_norm are recorded.  cut_l_ptr [K+1]: the cut edges' by-cut offsets, at the cuts' state places.
+struct LpEmitMore { int* row_place; double* row_scale; int* cut_l_ptr; };
+__device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk, const LpEmitMore more = LpEmitMore{nullptr, nullptr, nullptr}) {
     __shared__ int si[4 * LP_NT];
     __shared__ double sd[LP_NT];
     __shared__ int s_pos[LP_NT], s_ofs[2][LP_NT];      // per row: state position of the lhs copy (-1: none), edge offsets (-1: none)
@@ -271,6 +276,7 @@ __device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
             if (t == LP_F_SIZES && (tot[0] + tot[2] != a.C || tot[1] + tot[3] != a.E1)) w = 1;
             a.flags_out[t] = w;
         }
+        if (more.cut_l_ptr && t == 0) more.cut_l_ptr[a.K] = a.nnz_k;
         return;
     }
     const bool rows = b < a.nrc;
@@ -311,8 +317,14 @@ __device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
         norm = raw == 0.0 ? 1.0 : raw;
         if (rows) {
             const double den = norm * a.obj_norm;
-            const double cosine = a.row_stat[2 * (size_t)r + 1] / den, dual = a.row_dual[r] / den;
-            const int bs = a.row_basis[r];
+            const double cosine = a.row_stat[2 * (size_t)r + 1] / den;
+            const bool resident = more.row_place != nullptr;      // the solve-dependent half is left to the rounds: zeros here
+            const double dual = resident ? 0.0 : a.row_dual[r] / den;
+            const int bs = resident ? 1 : a.row_basis[r];
+            if (resident) {
+                more.row_place[2 * (size_t)r] = has_l ? pos_l : -1; more.row_place[2 * (size_t)r + 1] = has_r ? pos_r : -1;
+                more.row_scale[r] = den;
+            }
             if (has_l && lp_in(pos_l, n_left))
                 ((float4*)a.cons_feats)[pos_l] = make_float4((float)(-(lo / norm)), bs == 0, (float)(-cosine), (float)(-dual));
             if (has_r && lp_in(pos_r, n_left))
@@ -327,6 +339,7 @@ __device__ __forceinline__ void lp_emit_body(const LpArgs& a, const int blk) {
                 cutoff = fmin(-f64.feas / fabs(d), a.infinity);
             }
             const int pos = has_l ? pos_l : pos_r;
+            if (more.cut_l_ptr && lp_in(pos, n_left)) more.cut_l_ptr[pos] = min(max(has_l ? ofs_l : ofs_r, 0), n_edges);
             if (lp_in(pos, n_left)) {
                 float* f = a.cut_feats + (size_t)pos * 6;
                 f[0] = (float)(has_l ? -(lo / norm) : hi / norm);

@@ -1,11 +1,13 @@
 """Host arrays in, one C call, host arrays out: the host side of gcnn_infer, gcnn_infer_select, gcnn_infer_batch, the LP-snapshot
 calls, gcnn_lp_batch, gcnn_infer_models and gcnn_lp_models (include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
-of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers."""
+of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers.  `LPSession`
+(`GCNN.open_lp`) is the host side of gcnn_lp_rows_build and gcnn_lp_round: an LP that stays on the device across separation rounds."""
 
 from __future__ import annotations
 
 import ctypes as C
 import time
+import weakref
 from types import SimpleNamespace
 
 import numpy as np
@@ -741,6 +743,249 @@ class _LPModelsSession(_ModelsSession):
     def last_states(self):
         """The seven arrays of every state the last call built in the arena (`_LPBatchSession.last_states`)."""
         return self.base.last_states()
+
+
+class LPSession(_Staging):
+    """An LP resident on the device across the separation rounds of one node (`GCNN.open_lp`): the rows, `col_type` and `col_obj`
+    go up once, what depends on them alone -- the constraint features' static half, the constraint edges and both their CSR
+    orders -- is built once (gcnn_lp_rows_build + gcnn_graph_build), and a round (`lpstate.LPRound`) uploads only the solve and
+    the candidate cuts (gcnn_lp_round / gcnn_lp_round_select: one upload, two state launches, the forward pass, one download).
+    A round's result is by definition what `state_from_lp` / `score_lp` / `select_cuts_lp` give on
+    `lpstate.assemble(rows, round)`, bit for bit.  Rows can only be appended (`append_rows`); any other change of the LP -- a row
+    removed or changed, a column added, another objective -- means opening a new session.  There is no variable limit; an order
+    (ranking on the device, selection) takes at most 4,096 cuts, a table at most 2^24 rows.  The session holds no parameters:
+    every round reads the model's current flat parameter buffer.  After a rejected round (ValueError, GcnnError) the session
+    stays usable and the next round sees nothing of the rejected one."""
+    GUARD = 0                 # bytes of guard in front of and behind every device buffer of the session (tests set it)
+    GUARD_BYTE = 0xA5
+
+    def __init__(self, model, rows, deep=True):
+        from . import lpstate
+        super().__init__(model)
+        self.deep_check = bool(deep)
+        self._buffers_made = []           # (whole tensor, payload bytes) of every guarded buffer alive
+        arrays, dims = lpstate.check_rows(rows, self.deep_check)
+        self._dims = dims                 # the resident rows' dims: what a round's dims start from
+        self._raw = None                  # device: row_ptr, row_col, row_val, row_lhs, row_rhs (capacity >= the resident counts)
+        self._cap = (0, 0)
+        self._kept = {}                   # host copies of the optional column arrays as the last accepted rounds gave them
+        self._stale = set()               # optional arrays whose device copy a rejected round overwrote
+        self._derived = self._graph = self._res = None
+        self.closed = False
+        V = dims["n_cols"]
+        dev = model.device
+        with torch.cuda.device(dev):
+            self._col_type = self._alloc(V)
+            self._col_obj = self._alloc(8 * V)
+            self._opt = [self._alloc(8 * V) for _ in lpstate.OPTIONAL]
+            self._col_type[:V].copy_(torch.from_numpy(arrays[5].view(np.uint8)))
+            self._col_obj[:8 * V].copy_(torch.from_numpy(arrays[6].view(np.uint8)))
+        self._dims = dict(dims, n_rows=0, row_nnz=0, n_state_rows=0, n_state_edges=0)
+        self._append(arrays[:5], (dims["n_rows"], dims["row_nnz"], dims["n_state_rows"], dims["n_state_edges"]), first=True)
+
+    # ---- device buffers ----------------------------------------------------------------------------------------------------------
+    def _alloc(self, nbytes):
+        """A device uint8 tensor of `nbytes` (at least 16); with GUARD set it lies between two guard blocks of GUARD_BYTE."""
+        n, g = max(int(nbytes), 16), self.GUARD
+        if not g:
+            return torch.empty(n, dtype=torch.uint8, device=self.model.device)
+        whole = torch.full((n + 2 * g,), self.GUARD_BYTE, dtype=torch.uint8, device=self.model.device)
+        self._buffers_made.append((weakref.ref(whole), n))      # (the payload view keeps `whole` alive for as long as it is in use)
+        return whole[g:g + n]
+
+    def guards_intact(self):
+        """True when no guard byte of a live buffer of the session (resident buffers and the round arena) has changed."""
+        g = self.GUARD
+        live = [(ref(), n) for ref, n in self._buffers_made if ref() is not None]
+        return all(bool((w[:g] == self.GUARD_BYTE).all()) and bool((w[g + n:] == self.GUARD_BYTE).all()) for w, n in live)
+
+    def _buffers(self, L):
+        self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, L.in_bytes, 1 << 20)
+        self.pin_out, self.out_np = self._pin(self.pin_out, self.out_np, L.out_bytes, 1 << 16)
+        if self.arena is None or self.arena.numel() < L.arena_bytes:
+            self.arena = None
+            self.arena = self._alloc(max(2 * L.arena_bytes, 1 << 22))
+
+    # ---- rows --------------------------------------------------------------------------------------------------------------------
+    @property
+    def n_rows(self):
+        return self._dims["n_rows"]
+
+    @property
+    def n_cols(self):
+        return self._dims["n_cols"]
+
+    def append_rows(self, row_ptr, row_col, row_val, row_lhs, row_rhs):
+        """Append rows (CSR over the same columns, `row_ptr` from 0) behind the resident ones: only they are uploaded, then what is
+        derived from the rows is rebuilt on the device (an appended lhs-sided row moves every rhs-sided state row behind it).
+        Appending zero rows is a no-op."""
+        from . import lpstate
+        self._open()
+        arrays, counts = lpstate.check_row_block(row_ptr, row_col, row_val, row_lhs, row_rhs, self.n_cols, self._dims["infinity"],
+                                                 self.deep_check)
+        if counts[0] == 0:
+            return
+        self._append(arrays, counts, first=False)
+
+    def _append(self, arrays, counts, first):
+        from . import lpstate
+        dR, dN, dC, dE = counts
+        old = self._dims
+        R, N = old["n_rows"] + dR, old["row_nnz"] + dN
+        if old["n_state_edges"] + dE > 2 ** 31 - 1 or N > 2 ** 31 - 1:
+            raise ValueError("the state's constraint edges do not fit int32")
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            capR, capN = self._cap
+            if self._raw is None or R > capR or N > capN:       # amortised doubling, device to device: no resident row goes up again
+                capR, capN = max(R, 2 * capR if R > capR else capR), max(N, 2 * capN if N > capN else capN)
+                new = [self._alloc(4 * (capR + 1)), self._alloc(4 * capN), self._alloc(8 * capN), self._alloc(8 * capR), self._alloc(8 * capR)]
+                if self._raw is not None:
+                    used = (4 * (old["n_rows"] + 1), 4 * old["row_nnz"], 8 * old["row_nnz"], 8 * old["n_rows"], 8 * old["n_rows"])
+                    for dst, src, n in zip(new, self._raw, used):
+                        dst[:n].copy_(src[:n])
+                self._raw, self._cap = new, (capR, capN)
+            _, total = lpstate.rows_upload_layout(dR, dN, first)
+            self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, total, 1 << 20)
+            places = lpstate.pack_row_block(self.in_np, arrays, old["row_nnz"], first)
+            at = (4 * (old["n_rows"] + (0 if first else 1)), 4 * old["row_nnz"], 8 * old["row_nnz"], 8 * old["n_rows"], 8 * old["n_rows"])
+            for dst, (off, n), to in zip(self._raw, places, at):
+                if n:
+                    dst[to:to + n].copy_(self.pin_in[off:off + n], non_blocking=True)
+            dims = dict(old, n_rows=R, row_nnz=N, n_state_rows=old["n_state_rows"] + dC, n_state_edges=old["n_state_edges"] + dE)
+            self._rebuild(dims)         # raises for rows the device flags: the session then keeps the rows it had
+
+    def _rebuild(self, dims):
+        """gcnn_lp_rows_build + gcnn_graph_build on the raw rows for `dims`; adopts both (and `dims`) once the device has accepted
+        the rows.  Synchronises: the flags and the longest segments come home here, so that no round has to wait for them."""
+        from . import lpstate
+        from .graph import BipartiteGraph
+        d, L, P = _lib.LpDims(**dims), _lib.LpRowsLayout(), C.c_void_p
+        _lib.check(_lib.lib().gcnn_lp_rows_layout_for(C.byref(d), C.byref(L)), "gcnn_lp_rows_layout_for")
+        dev = self.model.device
+        derived = self._alloc(L.bytes)
+        off = list(L.off)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.lib().gcnn_lp_rows_build(C.byref(d), *(P(t.data_ptr()) for t in self._raw), P(self._col_obj.data_ptr()),
+                                                 P(derived.data_ptr()), derived.numel(), P(stream.cuda_stream)), "gcnn_lp_rows_build")
+        flags = derived[off[5]:off[5] + 16].view(torch.int32).cpu().numpy()      # waits: the staging buffer is free again
+        lpstate.raise_for_flags(flags)
+        c, e1 = dims["n_state_rows"], dims["n_state_edges"]
+        inds = derived[off[1]:off[1] + 8 * e1].view(torch.int32).view(2, e1)
+        feats = derived[off[2]:off[2] + 4 * e1].view(torch.float32)
+        graph = BipartiteGraph(inds, feats, c, dims["n_cols"], validate=False, sync_max_degree=True)
+        res = _lib.LpResident(derived.data_ptr() + off[3], derived.data_ptr() + off[4], derived.data_ptr() + off[0],
+                              self._col_type.data_ptr(), self._col_obj.data_ptr(), *(t.data_ptr() for t in self._opt), graph.c)
+        self._derived, self._derived_off, self._graph, self._res, self._dims = derived, off, graph, res, dims
+        self.layouts.clear()
+
+    # ---- rounds ------------------------------------------------------------------------------------------------------------------
+    def _open(self):
+        if self.closed:
+            raise _lib.GcnnError("the LP session is closed")
+
+    def _checked(self, rnd, n_forced=-1, n_entries=0):
+        """A round checked on the host -> (arrays, presence mask, dims, layout entry).  An optional array whose device copy a
+        rejected round overwrote travels again from the host copy of the last accepted one."""
+        from . import lpstate
+        self._open()
+        arrays, present, dims = lpstate.check_round(rnd, self._dims, self._kept, self.deep_check)
+        for q, name in enumerate(lpstate.OPTIONAL):
+            needed = not name.startswith("col_primal") or dims["has_incumbent"]
+            if name in self._stale and needed and not present >> q & 1:
+                arrays[5 + q] = self._kept[name]
+                present |= 1 << q
+        key = _int_key(dims) + (present, n_forced, n_entries)
+        lay = self.cached(key, self._layout, dims, present, n_forced, n_entries)
+        return arrays, present, dims, lay
+
+    @staticmethod
+    def _layout(dims, present, n_forced, n_entries):
+        from . import lpstate
+        _, L = lpstate.lp_round_layout(dims, present, n_forced, n_entries)
+        return L, list(L.in_off), list(L.forced_off), list(L.out_off), list(L.dev_off)
+
+    def upload_bytes(self, rnd, forced=None):
+        """Bytes the one upload of this round would carry (with `forced`: packed forced rows of a selection)."""
+        fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        return int(self._checked(rnd, *fshape)[3][0].in_bytes)
+
+    def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0):
+        """check -> layout -> pack -> one call -> the download's LP flags checked.  Returns (the round's dims, the download's
+        offsets, the arena's offsets); what the round gave of the optional column arrays is remembered once it is accepted."""
+        from . import lpstate
+        t0 = time.perf_counter()
+        fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        arrays, present, dims, (L, in_off, forced_off, out_off, dev_off) = self._checked(rnd, *fshape)
+        d = _lib.LpDims(**dims)
+        self._buffers(L)
+        lpstate.pack_round(self.in_np, in_off, arrays, present)
+        head = (C.byref(d), present)
+        if forced is None:
+            self._enqueue_wait("gcnn_lp_round", head + (C.byref(self._res),), (int(want_order),), timings, t0, upload_bytes=int(L.in_bytes))
+        else:
+            self._put_forced(forced_off, forced)
+            self._enqueue_wait("gcnn_lp_round_select", head + fshape + (C.byref(self._res),), (float(p_max), float(p_max_ub)), timings,
+                               t0, upload_bytes=int(L.in_bytes))
+        given = {name: arrays[5 + q] for q, name in enumerate(lpstate.OPTIONAL) if present >> q & 1}
+        out = self.out_np
+        try:
+            lpstate.raise_for_flags(out[out_off[4]:out_off[4] + 16].view(np.int32))
+        except ValueError:
+            self._stale.update(given)       # their device copies hold the rejected round's values
+            raise
+        self._kept.update(given)
+        self._stale.difference_update(given)
+        return dims, out_off, dev_off
+
+    def state(self, rnd):
+        """The model's 10-tuple as host arrays and `cut_index`, as `GCNN.state_from_lp` gives them for the assembled snapshot."""
+        dims, out_off, dev = self._run(rnd, -1)
+        c, v, k, e1, e2 = dims["n_state_rows"], dims["n_cols"], dims["n_cuts"], dims["n_state_edges"], dims["cut_nnz"]
+        f32, i32 = torch.float32, torch.int32
+        D, o, A = self._derived, self._derived_off, self.arena
+
+        def host(buf, off, shape, dt):
+            return buf[off:off + 4 * shape[0] * shape[1]].view(dt).view(shape).cpu().numpy()
+
+        arrays = (host(D, o[0], (c, 4), f32), host(D, o[1], (2, e1), i32), host(D, o[2], (e1, 1), f32), host(A, dev[1], (v, 14), f32),
+                  host(A, dev[2], (k, 6), f32), host(A, dev[3], (2, e2), i32), host(A, dev[4], (e2, 1), f32))
+        return arrays + (c, v, k), self.out_np[out_off[5]:out_off[5] + 4 * k].view(np.int32).copy()
+
+    def _results(self, dims, out_off, want_order, select):
+        n = dims["n_cuts"]
+        scores, order, n_kept = self._read(out_off[0], out_off[1] if want_order else None, out_off[3] if select else None, n)
+        return scores, order, n_kept, self.out_np[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
+
+    def score(self, rnd, rank=False, timings=None):
+        """`GCNN.score_lp` for the assembled snapshot: a `ScoreArray` in STATE order with `.cut_index` and, with `rank`,
+        `.rankings`."""
+        n = int(np.asarray(rnd.cut_lhs).shape[0])
+        on_device = self.model._rank_on_device(rank, n) and n <= 4096
+        dims, out_off, _ = self._run(rnd, int(on_device), timings)
+        scores, order, _, cut_index = self._results(dims, out_off, on_device, False)
+        scores.cut_index = cut_index
+        if rank:
+            scores.rankings = order if on_device else stable_ranking(scores)
+        return scores
+
+    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None):
+        """`GCNN.select_cuts_lp` for the assembled snapshot: a `SelectResult` with `cut_index`.  More than 4,096 cuts raise
+        `GcnnError` before anything is enqueued."""
+        ops.check_thresholds(p_max, p_max_ub)
+        self.model._check_select_size("LPSession.select_cuts", "round", int(np.asarray(rnd.cut_lhs).shape[0]))
+        packed = normalize_forced(forced, self.n_cols)
+        dims, out_off, _ = self._run(rnd, 1, timings, packed, p_max, p_max_ub)
+        scores, order, n_kept, cut_index = self._results(dims, out_off, True, True)
+        return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
+
+    def close(self):
+        """Release the device buffers; the session cannot be used afterwards."""
+        self.closed = True
+        self._raw = self._derived = self._graph = self._res = self.arena = None
+        self._col_type = self._col_obj = self._opt = None
+        self._buffers_made = []
+        self._kept, self._stale = {}, set()
 
 
 def _int_key(dims):

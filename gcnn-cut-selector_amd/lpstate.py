@@ -209,6 +209,232 @@ def raise_for_flags(flags):
             raise ValueError(f"LP snapshot rejected by the device: {text}")
 
 
+# ---- an LP that stays on the device across separation rounds (GCNN.open_lp, csrc/k_lpres.hpp) ------------------------------------------
+ROW_FIELDS = FIELDS[:5] + FIELDS[7:9]        # what stays: the rows, col_type, col_obj
+OPTIONAL = ("col_lb", "col_ub", "col_primal", "col_primal_avg")      # bit q of a round's presence mask (GCNN_LPR_*)
+ROUND_FIELDS = (("row_dual", np.float64), ("row_basis", np.int8), ("col_basis", np.int8), ("col_lp", np.float64),
+                ("col_redcost", np.float64), ("col_lb", np.float64), ("col_ub", np.float64), ("col_primal", np.float64),
+                ("col_primal_avg", np.float64)) + FIELDS[16:]          # the packed order behind the header (gcnn_lp_round)
+
+
+@dataclass
+class LPRows:
+    """The part of an `LPSnapshot` that does not change between the separation rounds of one LP: the rows, `col_type`, `col_obj`
+    and the scalars (defaults as `LPSnapshot`'s)."""
+    row_ptr: np.ndarray
+    row_col: np.ndarray
+    row_val: np.ndarray
+    row_lhs: np.ndarray
+    row_rhs: np.ndarray
+    col_type: np.ndarray
+    col_obj: np.ndarray
+    infinity: float = 1e20
+    sum_epsilon: float = 1e-6
+    n_model_vars: int | None = None
+    obj_norm: float | None = None
+
+    @classmethod
+    def from_snapshot(cls, snap):
+        return cls(**{name: getattr(snap, name) for name, _ in ROW_FIELDS}, infinity=snap.infinity, sum_epsilon=snap.sum_epsilon,
+                   n_model_vars=snap.n_model_vars, obj_norm=snap.obj_norm)
+
+    def scalars(self):
+        """(infinity, sum_epsilon, n_model_vars, obj_norm) with the defaults filled in as `LPSnapshot.scalars` fills them."""
+        norm = float(np.linalg.norm(np.asarray(self.col_obj, np.float64))) if self.obj_norm is None else float(self.obj_norm)
+        nmv = int(np.asarray(self.col_type).shape[0]) if self.n_model_vars is None else int(self.n_model_vars)
+        return float(self.infinity), float(self.sum_epsilon), nmv, (1.0 if norm <= 0 else norm)
+
+
+@dataclass
+class LPRound:
+    """What one separation round adds to an `LPRows`: the solve (`row_dual`, `row_basis`, `col_basis`, `col_lp`, `col_redcost`, the
+    bounds) and the candidate cuts.  In a round after the first `col_lb`, `col_ub`, `col_primal` and `col_primal_avg` may each be
+    None: unchanged since the last round that gave it.  `has_incumbent` None: whether `col_primal` is given -- so a round that
+    keeps the last incumbent arrays says `has_incumbent=True`; without an incumbent the two arrays are not looked at."""
+    row_dual: np.ndarray
+    row_basis: np.ndarray
+    col_basis: np.ndarray
+    col_lp: np.ndarray
+    col_redcost: np.ndarray
+    cut_ptr: np.ndarray
+    cut_col: np.ndarray
+    cut_val: np.ndarray
+    cut_lhs: np.ndarray
+    cut_rhs: np.ndarray
+    col_lb: np.ndarray | None = None
+    col_ub: np.ndarray | None = None
+    col_primal: np.ndarray | None = None
+    col_primal_avg: np.ndarray | None = None
+    has_incumbent: bool | None = None
+
+    @classmethod
+    def from_snapshot(cls, snap):
+        return cls(**{name: getattr(snap, name) for name, _ in ROUND_FIELDS}, has_incumbent=snap.has_incumbent)
+
+    def incumbent(self):
+        return self.col_primal is not None if self.has_incumbent is None else bool(self.has_incumbent)
+
+
+def assemble(rows: LPRows, rnd: LPRound, kept=None) -> LPSnapshot:
+    """The `LPSnapshot` a round stands for: the definition of what a session answers.  `kept`: {name: array} of the optional column
+    arrays as the last rounds gave them, for the ones this round leaves None."""
+    inc = rnd.incumbent()
+    opt = {}
+    for name in OPTIONAL:
+        a = getattr(rnd, name)
+        if name.startswith("col_primal") and not inc:
+            a = None
+        elif a is None:
+            a = (kept or {}).get(name)
+            if a is None:
+                raise ValueError(f"{name} is None and no earlier round gave it")
+        opt[name] = a
+    return LPSnapshot(**{name: getattr(rows, name) for name, _ in ROW_FIELDS},
+                      **{name: getattr(rnd, name) for name, _ in ROUND_FIELDS if name not in OPTIONAL}, **opt,
+                      infinity=rows.infinity, sum_epsilon=rows.sum_epsilon, n_model_vars=rows.n_model_vars, obj_norm=rows.obj_norm,
+                      has_incumbent=inc)
+
+
+def _cast(name, a, dt):
+    """`check_snapshot`'s cast of one array to its packed dtype."""
+    a = np.zeros(0, dt) if a is None else np.asarray(a)
+    if a.dtype != dt:
+        if dt != np.float64 and a.size and a.dtype.kind in "iu" and (int(a.max()) > np.iinfo(dt).max or int(a.min()) < np.iinfo(dt).min):
+            raise ValueError(f"{name}: a value does not fit {np.dtype(dt).name}")
+        a = a.astype(dt)
+    return np.ascontiguousarray(a)
+
+
+def _vector(name, a, n):
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f"{name} must be a vector of {n} values, got shape {tuple(a.shape)}")
+
+
+def check_row_block(row_ptr, row_col, row_val, row_lhs, row_rhs, n_cols, infinity, deep=True):
+    """The checks `check_snapshot` applies to the rows, on a block of rows (all of them at open, the new ones of an append) ->
+    (the five arrays with their packed dtypes, (R, nnz, C, E1) of the block)."""
+    arrays = [_cast(name, a, dt) for (name, dt), a in zip(FIELDS[:5], (row_ptr, row_col, row_val, row_lhs, row_rhs))]
+    row_ptr, row_col, row_val, row_lhs, row_rhs = arrays
+    if row_lhs.ndim != 1:
+        raise ValueError(f"row_lhs must be a vector, got shape {tuple(row_lhs.shape)}")
+    R = row_lhs.shape[0]
+    _vector("row_rhs", row_rhs, R)
+    nnz = _check_csr("row", row_ptr, row_col, row_val, R, n_cols, deep)
+    lens = np.diff(row_ptr)
+    has_lhs, has_rhs = finite(row_lhs, infinity), finite(row_rhs, infinity)
+    C = int(has_lhs.sum()) + int(has_rhs.sum())
+    E1 = int(lens[has_lhs].sum(dtype=np.int64)) + int(lens[has_rhs].sum(dtype=np.int64))
+    return arrays, (R, nnz, C, E1)
+
+
+def check_rows(rows: LPRows, deep: bool = True):
+    """`check_snapshot` for the resident half -> (the seven arrays in ROW_FIELDS order, dims) where dims is the dict of
+    `_lib.LpDims` fields with no cuts and no incumbent."""
+    infinity, eps, nmv, obj_norm = rows.scalars()
+    if not (infinity > 0 and eps > 0 and np.isfinite(obj_norm)) or nmv < 1:
+        raise ValueError("infinity and sum_epsilon must be positive, obj_norm finite, n_model_vars at least 1")
+    col_type, col_obj = _cast("col_type", rows.col_type, np.int8), _cast("col_obj", rows.col_obj, np.float64)
+    if col_type.ndim != 1:
+        raise ValueError(f"col_type must be a vector, got shape {tuple(col_type.shape)}")
+    V = col_type.shape[0]
+    _vector("col_obj", col_obj, V)
+    if col_type.size and (int(col_type.min()) < 0 or int(col_type.max()) > 3):
+        raise ValueError("col_type: codes are 0..3")
+    arrays, (R, nnz, C, E1) = check_row_block(rows.row_ptr, rows.row_col, rows.row_val, rows.row_lhs, rows.row_rhs, V, infinity, deep)
+    if E1 > 2 ** 31 - 1:
+        raise ValueError("the state's constraint edges do not fit int32")
+    dims = dict(n_rows=R, n_cols=V, n_cuts=0, row_nnz=nnz, cut_nnz=0, has_incumbent=0, n_model_vars=nmv, n_state_rows=C,
+                n_state_edges=E1, reserved=0, infinity=infinity, sum_epsilon=eps, obj_norm=obj_norm)
+    return arrays + [col_type, col_obj], dims
+
+
+def check_round(rnd: LPRound, row_dims, have=(), deep: bool = True):
+    """`check_snapshot` for a round against the resident rows' dims -> (the 14 arrays in ROUND_FIELDS order, None for an optional
+    one that does not travel; the presence mask; the round's dims: `row_dims` with the cuts and the incumbent filled in).
+    `have`: the optional arrays an earlier round gave -- one that is neither given nor held is a ValueError."""
+    R, V = row_dims["n_rows"], row_dims["n_cols"]
+    inc = rnd.incumbent()
+    arrays, present = [], 0
+    for name, dt in ROUND_FIELDS:
+        a = getattr(rnd, name)
+        if name in OPTIONAL:
+            if name.startswith("col_primal") and not inc:
+                arrays.append(None)
+                continue
+            if a is None:
+                if name not in have:
+                    raise ValueError(f"{name}: the first round must give it" if name in OPTIONAL[:2]
+                                     else f"{name}: has_incumbent is set and no round has given it")
+                arrays.append(None)
+                continue
+            present |= 1 << OPTIONAL.index(name)
+        arrays.append(_cast(name, a, dt))
+    by_name = dict(zip((n for n, _ in ROUND_FIELDS), arrays))
+    K = by_name["cut_lhs"].shape[0] if by_name["cut_lhs"].ndim == 1 else -1
+    if K < 0:
+        raise ValueError(f"cut_lhs must be a vector, got shape {tuple(by_name['cut_lhs'].shape)}")
+    for name, n in (("row_dual", R), ("row_basis", R), ("col_basis", V), ("col_lp", V), ("col_redcost", V), ("col_lb", V),
+                    ("col_ub", V), ("col_primal", V), ("col_primal_avg", V), ("cut_rhs", K)):
+        if by_name[name] is not None:
+            _vector(name, by_name[name], n)
+    for name in ("row_basis", "col_basis"):
+        a = by_name[name]
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 3):
+            raise ValueError(f"{name}: codes are 0..3")
+    cut_ptr = by_name["cut_ptr"]
+    nnz_k = _check_csr("cut", cut_ptr, by_name["cut_col"], by_name["cut_val"], K, V, deep)
+    if K and np.any(cut_ptr[1:] == cut_ptr[:-1]):
+        raise ValueError("every cut must have at least one entry")
+    return arrays, present, dict(row_dims, n_cuts=K, cut_nnz=nnz_k, has_incumbent=int(inc))
+
+
+def pack_round(buf, in_off, arrays, present):
+    """Write a checked round into a staging buffer at gcnn_lp_round_layout_for's offsets: the header with the presence mask, then
+    every array that travels."""
+    buf[in_off[0]:in_off[0] + 16] = 0
+    buf[in_off[0]:in_off[0] + 4].view(np.int32)[0] = present
+    for off, a in zip(in_off[1:], arrays):
+        if a is not None and a.size:
+            buf[off:off + a.nbytes] = a.view(np.uint8)
+
+
+def rows_upload_layout(n_rows, nnz, first):
+    """Byte offsets of (row_ptr, row_col, row_val, row_lhs, row_rhs) in the staging buffer of a block of rows and the total.  The
+    first block carries all R + 1 offsets, an appended one only the R behind the resident closing offset."""
+    sizes = (4 * (n_rows + (1 if first else 0)), 4 * nnz, 8 * nnz, 8 * n_rows, 8 * n_rows)
+    offs, at = [], 0
+    for s in sizes:
+        offs.append(at)
+        at += (s + 15) & ~15
+    return offs, at
+
+
+def pack_row_block(buf, arrays, entry_base, first):
+    """Write a checked block of rows into a staging buffer at `rows_upload_layout`'s offsets; its offsets are shifted by
+    `entry_base`, the entries already resident.  Returns the five (offset, bytes) pairs."""
+    row_ptr, row_col, row_val, row_lhs, row_rhs = arrays
+    ptr = (row_ptr if first else row_ptr[1:]).astype(np.int64) + entry_base
+    if ptr.size and int(ptr[-1]) > 2 ** 31 - 1:
+        raise ValueError("the rows' entries do not fit int32")
+    offs, _ = rows_upload_layout(row_lhs.shape[0], row_col.shape[0], first)
+    out = []
+    for off, a in zip(offs, (ptr.astype(np.int32), row_col, row_val, row_lhs, row_rhs)):
+        if a.size:
+            buf[off:off + a.nbytes] = a.view(np.uint8)
+        out.append((off, a.nbytes))
+    return out
+
+
+def lp_round_layout(dims, present, n_forced=-1, n_entries=0):
+    """(LpDims, LpRoundLayout) of the library for a round's dims; raises `_lib.GcnnError` where it declines the sizes."""
+    import ctypes as C
+
+    from . import _lib
+    d, L = _lib.LpDims(**dims), _lib.LpRoundLayout()
+    _lib.check(_lib.lib().gcnn_lp_round_layout_for(C.byref(d), present, n_forced, n_entries, C.byref(L)), "gcnn_lp_round_layout_for")
+    return d, L
+
+
 def lp_layout(dims, n_forced=-1, n_entries=0):
     """(LpDims, LpLayout) of the library for these dims."""
     import ctypes as C

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPModelsSession, _LPSession, _ModelsSession,
+from .infer import (BAD_INDEX, LPSession, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPModelsSession, _LPSession, _ModelsSession,
                     _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
 
@@ -645,6 +645,15 @@ class GCNN:
             scores, order, n_kept = self._select_general(state, packed, p_max, p_max_ub, n_cuts)
             cut_index = cut_index.cpu().numpy()
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
+
+    def open_lp(self, rows, *, deep=True):
+        """Keep an LP on the device across the separation rounds of one node: `rows` (`lpstate.LPRows`) goes up once, every
+        `lpstate.LPRound` then uploads only the solve and the candidate cuts.  Returns an `LPSession` (infer.py): `state`, `score`,
+        `select_cuts`, `append_rows`, `close`; a round's result is `state_from_lp` / `score_lp` / `select_cuts_lp` on
+        `lpstate.assemble(rows, round)`, bit for bit.  Rows can only be appended: any other change of the LP means a new session.
+        `deep`: check the O(nnz) facts (columns in range and strictly increasing) on the host too; without it the device finds
+        them and the call raises ValueError after the download."""
+        return LPSession(self, rows, deep)
 
     # ---- many host states in one call (gcnn_infer_batch): what a scoring server does with the requests that queued up ----------
     @staticmethod

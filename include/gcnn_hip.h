@@ -706,6 +706,67 @@ int gcnn_lp_models(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced,
                    const void* host_in, void* host_out, void* arena, size_t arena_bytes, void* host_staging, double p_max,
                    double p_max_ub, void* stream);
 
+/* ---- an LP that stays on the device across separation rounds ------------------------------------------------------------------------
+ * A solver calls its cut selector once per separation round on the same LP: the rows of round t + 1 are the rows of round t plus the
+ * selected cuts; what changes is the solve (row_dual, row_basis, the columns' bounds, basis, values and reduced costs) and the
+ * candidate cuts.  Of what gcnn_lp_state derives from the rows only is_tight and dual depend on the solve.  So the caller keeps, in
+ * device memory of its own (the library allocates nothing): the raw rows (row_ptr, row_col, row_val, row_lhs, row_rhs), col_type,
+ * col_obj, the last given col_lb / col_ub / col_primal / col_primal_avg, and the `derived` block gcnn_lp_rows_build writes from them:
+ *   off[0] cons_feats [C,4] f32 with columns 0 and 2 final and 1 and 3 zero | off[1] cons_edge_inds [2,E1] i32 | off[2]
+ *   cons_edge_feats [E1] f32 -- values and places exactly gcnn_lp_state's -- | off[3] row_place [R][2] i32: the state row of an LP row's
+ *   lhs side and of its rhs side, -1 where that side is not finite | off[4] row_scale [R] f64: norm * obj_norm, the dual's divisor |
+ *   off[5] flags [4] i32: gcnn_lp_state's flag words for the rows (any set: the block is NOT valid) | off[6] scratch.
+ * gcnn_lp_rows_build (two launches, nothing synchronised) runs at open and after every append of rows; dims: n_rows, n_cols, row_nnz,
+ * n_state_rows, n_state_edges and the scalars (the cut fields are not read).  The two CSR orders of the constraint edges then come
+ * from gcnn_graph_build on off[1], off[2].
+ * A round (gcnn_lp_round, gcnn_lp_round_select): ONE upload of host_in (pinned, in_bytes) -- in_off: header (word 0 = present) |
+ * row_dual | row_basis | col_basis | col_lp | col_redcost | col_lb | col_ub | col_primal | col_primal_avg (each of the four only when
+ * its GCNN_LPR_* bit of `present` is set: it is then also copied into the resident buffer; else the resident buffer is read) |
+ * cut_ptr | cut_col | cut_val | cut_lhs | cut_rhs, then forced_off as in gcnn_infer_select -- two launches that write is_tight and
+ * dual into cons_feats at row_place and build the variable and cut parts of the state in the arena (no pass touches a row entry),
+ * gcnn_forward's launches on the resident constraint graph and the round's cut graph, the ranking or selection, ONE download of
+ * host_out (pinned, out_bytes): out_off as gcnn_lp_layout's (the forward's flag block is always zero here).  dims: the full
+ * gcnn_lp_dims of the LP this round stands for.  The result has the bits of gcnn_lp_state / gcnn_lp_infer / gcnn_lp_infer_select on the
+ * snapshot assembled from the resident rows and the round.  There is no variable limit.  want_order: 1 ranking (at most 4,096
+ * cuts), 0 scores only, -1 the state only (no forward pass: the state's variable and cut parts stay at dev_off[1..5] of the arena).
+ * Returned before anything is enqueued: GCNN_E_BADARG (dims, present, pointers, thresholds, a short or misaligned arena, edges with
+ * nothing to point at) and GCNN_E_UNSUPPORTED (more than 2^24 state rows, columns or cuts; a selection or ranking of more than
+ * 4,096 cuts). */
+#define GCNN_LPR_LB 1
+#define GCNN_LPR_UB 2
+#define GCNN_LPR_PRIMAL 4
+#define GCNN_LPR_PRIMAL_AVG 8
+#define GCNN_LPR_DERIVED 7
+#define GCNN_LPR_ARRAYS 15
+#define GCNN_LPR_BLOCKS 11
+typedef struct gcnn_lp_rows_layout {
+    size_t bytes, off[GCNN_LPR_DERIVED];   /* of the derived block; every offset a multiple of 256 */
+} gcnn_lp_rows_layout;
+int gcnn_lp_rows_layout_for(const gcnn_lp_dims* dims, gcnn_lp_rows_layout* layout /* host */);
+int gcnn_lp_rows_build(const gcnn_lp_dims* dims, const int32_t* row_ptr, const int32_t* row_col, const double* row_val,
+                       const double* row_lhs, const double* row_rhs, const double* col_obj, void* derived /* device, 256-byte aligned */,
+                       size_t derived_bytes, void* stream);
+typedef struct gcnn_lp_resident {          /* device pointers */
+    const int32_t* row_place; const double* row_scale; float* cons_feats;
+    const int8_t* col_type; const double* col_obj;
+    double *col_lb, *col_ub, *col_primal, *col_primal_avg;   /* [V] each: the last given values */
+    gcnn_graph cons_graph;                 /* gcnn_graph_build of the derived edge list, C left nodes */
+} gcnn_lp_resident;
+typedef struct gcnn_lp_round_layout {
+    size_t in_bytes, in_off[GCNN_LPR_ARRAYS], forced_off[3];
+    size_t out_bytes, out_off[6];
+    /* the arena: upload | var_feats [V,14] | cut_feats [K,6] | cut_edge_inds [2,E2] | cut_edge_feats [E2] | cut l_ptr [K+1] | output
+     * block | forward workspace | the forward's flag block | scratch | selection workspace */
+    size_t arena_bytes, dev_off[GCNN_LPR_BLOCKS];
+} gcnn_lp_round_layout;
+int gcnn_lp_round_layout_for(const gcnn_lp_dims* dims, int32_t present, int32_t n_forced /* < 0: gcnn_lp_round */,
+                             int32_t n_forced_entries, gcnn_lp_round_layout* layout /* host */);
+int gcnn_lp_round(const gcnn_lp_dims* dims, int32_t present, const gcnn_lp_resident* resident /* host */, const float* params,
+                  const void* host_in, void* host_out, void* arena, size_t arena_bytes, int32_t want_order, void* stream);
+int gcnn_lp_round_select(const gcnn_lp_dims* dims, int32_t present, int32_t n_forced, int32_t n_forced_entries,
+                         const gcnn_lp_resident* resident /* host */, const float* params, const void* host_in, void* host_out,
+                         void* arena, size_t arena_bytes, double p_max, double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
