@@ -141,6 +141,24 @@ class LpRoundLayout(C.Structure):
                 ("dev_off", C.c_size_t * LPR_BLOCKS)]
 
 
+class LpAppendDims(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("row_nnz", C.c_int32), ("n_state_rows", C.c_int32), ("n_state_edges", C.c_int32),
+                ("n_lhs_rows", C.c_int32), ("n_lhs_edges", C.c_int32), ("res_lhs_rows", C.c_int32), ("res_lhs_edges", C.c_int32)]
+
+
+LP_SET_FIELDS = ("cons_feats", "edge_row", "edge_col", "edge_coef", "l_ptr", "v_ptr", "v_oth", "v_coef", "row_place", "row_scale")
+
+
+class LpRowsSet(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in LP_SET_FIELDS]
+
+
+class LpAppendLayout(C.Structure):
+    _fields_ = [("block_bytes", C.c_size_t), ("block_off", C.c_size_t * 5), ("in_bytes", C.c_size_t), ("out_bytes", C.c_size_t),
+                ("flags_off", C.c_size_t), ("scratch_bytes", C.c_size_t), ("arena_bytes", C.c_size_t), ("round_off", C.c_size_t),
+                ("scratch_off", C.c_size_t), ("round", LpRoundLayout)]
+
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -219,6 +237,11 @@ SIGNATURES = {
     "gcnn_lp_round_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, C.POINTER(LpRoundLayout)]),
     "gcnn_lp_round": (C.c_int, [C.POINTER(LpDims), _I, C.POINTER(LpResident), _P, _P, _P, _P, _Z, _I, _P]),
     "gcnn_lp_round_select": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, C.POINTER(LpResident), _P, _P, _P, _P, _Z, _D, _D, _P]),
+    "gcnn_lp_append_layout_for": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpAppendDims), _I, _I, _I, C.POINTER(LpAppendLayout)]),
+    "gcnn_lp_rows_append": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpAppendDims), _P, _P, _P, _P, _P, _P, C.POINTER(LpRowsSet),
+                                      C.POINTER(LpRowsSet), _P, _Z, _P, _P]),
+    "gcnn_lp_round_append": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpAppendDims), _I, _I, _I, _P, _P, _P, _P, _P, C.POINTER(LpRowsSet),
+                                       C.POINTER(LpRowsSet), C.POINTER(LpResident), _P, _P, _P, _P, _Z, _I, _D, _D, _P]),
 }
 
 _lib = None

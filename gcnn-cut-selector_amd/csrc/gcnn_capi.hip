@@ -1384,3 +1384,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lpmodels.hpp"
 // an LP resident on the device across separation rounds (include/gcnn_hip.h: gcnn_lp_rows_build, gcnn_lp_round): launch names k_lpr_*
 #include "gcnn_lpres.hpp"
+// rows appended to a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_append, gcnn_lp_round_append): launch names k_lpa_*
+#include "gcnn_lpappend.hpp"

@@ -57,7 +57,10 @@ extern "C" int gcnn_lp_rows_build(const gcnn_lp_dims* d, const int32_t* row_ptr,
 }
 
 // ---- a round ----------------------------------------------------------------------------------------------------------------------
-static int lpr_round_layout(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, gcnn_lp_round_layout* L) {
+// extra_out: a block behind the download's cut_index, for a caller that extends the call (gcnn_lpappend.hpp); it starts at the
+// out_bytes of the plain layout.
+static int lpr_round_layout(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, gcnn_lp_round_layout* L,
+                            size_t extra_out = 0) {
     if (!L || !lp_dims_ok(d) || present < 0 || present > 15 || (n_forced >= 0 && n_forced_entries < 0)) return GCNN_E_BADARG;
     if (!d->has_incumbent && (present & (GCNN_LPR_PRIMAL | GCNN_LPR_PRIMAL_AVG))) return GCNN_E_BADARG;
     memset(L, 0, sizeof(*L));
@@ -74,7 +77,7 @@ static int lpr_round_layout(const gcnn_lp_dims* d, int32_t present, int32_t n_fo
     // the download: scores | order | the forward's flag block (always zero here) | n_kept | the 4 LP flags | cut_index
     L->out_off[0] = 0; L->out_off[1] = al16(4 * K); L->out_off[2] = L->out_off[1] + al16(4 * K);
     L->out_off[3] = L->out_off[2] + 16; L->out_off[4] = L->out_off[2] + 32; L->out_off[5] = L->out_off[2] + 48;
-    L->out_bytes = L->out_off[5] + al16(4 * K);
+    L->out_bytes = L->out_off[5] + al16(4 * K) + extra_out;
     if (d->n_state_rows > (1 << 24) || d->n_cols > (1 << 24) || d->n_cuts > (1 << 24)) return GCNN_E_UNSUPPORTED;   // the edge passes' tables
     if (select && d->n_cuts > SEL_MAX_CUTS) return GCNN_E_UNSUPPORTED;
     const gcnn_dims sd = lp_state_dims(d);
@@ -93,16 +96,17 @@ extern "C" int gcnn_lp_round_layout_for(const gcnn_lp_dims* d, int32_t present, 
 }
 
 // want_order: 1 ranking, 0 scores only, -1 the state only (no forward pass; the download carries the flags and cut_index)
-static int lpr_call(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, const gcnn_lp_resident* res,
-                    const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, int32_t want_order,
-                    double p_max, double p_max_ub, void* stream) {
-    gcnn_lp_round_layout L;
-    int rc = lpr_round_layout(d, present, n_forced, n_forced_entries, &L);
+// lpr_check: everything a round call decides before anything is enqueued, and the layout.  lpr_run: what it enqueues; host_in null:
+// the upload already lies at dev_off[0] of the arena (gcnn_lpappend.hpp's fused call brings it up with the appended rows).
+static int lpr_check(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, const gcnn_lp_resident* res,
+                     const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, int32_t want_order,
+                     double p_max, double p_max_ub, size_t extra_out, gcnn_lp_round_layout* L) {
+    int rc = lpr_round_layout(d, present, n_forced, n_forced_entries, L, extra_out);
     if (rc) return rc;
     const bool select = n_forced >= 0;
     if (want_order < -1 || want_order > 1) return GCNN_E_BADARG;
     if (want_order > 0 && d->n_cuts > 4096) return GCNN_E_UNSUPPORTED;
-    if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L.arena_bytes, select, p_max, p_max_ub))) return rc;
+    if ((rc = call_check(params, host_in, host_out, arena, arena_bytes, L->arena_bytes, select, p_max, p_max_ub))) return rc;
     const gcnn_dims sd = lp_state_dims(d);
     if (!res || edges_without_nodes(sd)) return GCNN_E_BADARG;
     const gcnn_graph& cg = res->cons_graph;
@@ -111,11 +115,20 @@ static int lpr_call(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, in
         (d->n_cols > 0 && d->has_incumbent && (!res->col_primal || !res->col_primal_avg)) || !cg.l_ptr || !cg.v_ptr ||
         (sd.n_cons_edges > 0 && (!cg.l_oth || !cg.l_coef || !cg.v_oth || !cg.v_coef)))
         return GCNN_E_BADARG;
+    return 0;
+}
+
+static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t present, int32_t n_forced, const gcnn_lp_resident* res,
+                   const float* params, const void* host_in, void* host_out, void* arena, int32_t want_order, double p_max,
+                   double p_max_ub, void* stream) {
+    int rc = 0;
+    const gcnn_dims sd = lp_state_dims(d);
+    const gcnn_graph& cg = res->cons_graph;
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
     char* up = A + L.dev_off[0];
     char* out = A + L.dev_off[6];
-    HIPCHK(hipMemcpyAsync(up, host_in, L.in_bytes, hipMemcpyHostToDevice, st));     // ONE upload: the round | forced rows
+    if (host_in) HIPCHK(hipMemcpyAsync(up, host_in, L.in_bytes, hipMemcpyHostToDevice, st));     // ONE upload: the round | forced rows
     double* keep[4] = {res->col_lb, res->col_ub, res->col_primal, res->col_primal_avg};
     LprArgs x; memset(&x, 0, sizeof(x));
     const double* src[4];
@@ -172,6 +185,15 @@ static int lpr_call(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, in
     for (int i = 0; i < 3; ++i) IL.out_off[i] = L.out_off[i];
     return infer_tail(&sd, IL, A, kg, fwd_flags, want_order >= 0 ? n_forced : -1, forced_rows(up, L.forced_off), A + L.dev_off[10],
                       L.out_off[3], want_order > 0, p_max, p_max_ub, host_out, st);     // ONE download
+}
+
+static int lpr_call(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, const gcnn_lp_resident* res,
+                    const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, int32_t want_order,
+                    double p_max, double p_max_ub, void* stream) {
+    gcnn_lp_round_layout L;
+    const int rc = lpr_check(d, present, n_forced, n_forced_entries, res, params, host_in, host_out, arena, arena_bytes, want_order,
+                             p_max, p_max_ub, 0, &L);
+    return rc ? rc : lpr_run(d, L, present, n_forced, res, params, host_in, host_out, arena, want_order, p_max, p_max_ub, stream);
 }
 
 extern "C" int gcnn_lp_round(const gcnn_lp_dims* d, int32_t present, const gcnn_lp_resident* res, const float* params,

@@ -751,7 +751,9 @@ class LPSession(_Staging):
     orders -- is built once (gcnn_lp_rows_build + gcnn_graph_build), and a round (`lpstate.LPRound`) uploads only the solve and
     the candidate cuts (gcnn_lp_round / gcnn_lp_round_select: one upload, two state launches, the forward pass, one download).
     A round's result is by definition what `state_from_lp` / `score_lp` / `select_cuts_lp` give on
-    `lpstate.assemble(rows, round)`, bit for bit.  Rows can only be appended (`append_rows`); any other change of the LP -- a row
+    `lpstate.assemble(rows, round)`, bit for bit.  Rows can only be appended -- inside a round's own call (`append=` of
+    `select_cuts`, `score`, `state`: gcnn_lp_round_append derives only the new rows and copies, shifts and merges the resident
+    arrays into the session's other set of buffers) or on their own (`append_rows`); any other change of the LP -- a row
     removed or changed, a column added, another objective -- means opening a new session.  There is no variable limit; an order
     (ranking on the device, selection) takes at most 4,096 cuts, a table at most 2^24 rows.  The session holds no parameters:
     every round reads the model's current flat parameter buffer.  After a rejected round (ValueError, GcnnError) the session
@@ -771,6 +773,12 @@ class LPSession(_Staging):
         self._kept = {}                   # host copies of the optional column arrays as the last accepted rounds gave them
         self._stale = set()               # optional arrays whose device copy a rejected round overwrote
         self._derived = self._graph = self._res = None
+        self._cur = self._cur_struct = None     # {name: device tensor} of `_lib.LP_SET_FIELDS`: the derived arrays the rounds read
+        self._cur_set = -1                # which of `_sets` they are; -1: the rebuild's own block and graph
+        self._sets = [None, None]         # the two sets an incremental append alternates between: ({name: tensor}, (capR, capC, capE), structs)
+        self._lhs = (0, 0)                # lhs-sided state rows and their entries: where an appended lhs row goes
+        self._col_deg = np.zeros(dims["n_cols"], np.int64)      # listed entries per column, and the longest segments: kept on the host
+        self._max_deg = (0, 0)
         self.closed = False
         V = dims["n_cols"]
         dev = model.device
@@ -815,45 +823,79 @@ class LPSession(_Staging):
     def n_cols(self):
         return self._dims["n_cols"]
 
-    def append_rows(self, row_ptr, row_col, row_val, row_lhs, row_rhs):
-        """Append rows (CSR over the same columns, `row_ptr` from 0) behind the resident ones: only they are uploaded, then what is
-        derived from the rows is rebuilt on the device (an appended lhs-sided row moves every rhs-sided state row behind it).
-        Appending zero rows is a no-op."""
+    def append_rows(self, row_ptr, row_col, row_val, row_lhs, row_rhs, incremental=False):
+        """Append rows (CSR over the same columns, `row_ptr` from 0) behind the resident ones: only they are uploaded.  By default
+        what is derived from the rows is then rebuilt on the device (an appended lhs-sided row moves every rhs-sided state row
+        behind it); with `incremental` only the new rows are derived and the resident arrays are copied, shifted and merged into
+        the session's other set of buffers (gcnn_lp_rows_append), with one read of the flag words.  The resident state is the same
+        either way, bit for bit.  Appending zero rows is a no-op."""
         from . import lpstate
         self._open()
         arrays, counts = lpstate.check_row_block(row_ptr, row_col, row_val, row_lhs, row_rhs, self.n_cols, self._dims["infinity"],
                                                  self.deep_check)
         if counts[0] == 0:
             return
-        self._append(arrays, counts, first=False)
+        if incremental:
+            self._append_incremental(arrays, counts)
+        else:
+            self._append(arrays, counts, first=False)
 
-    def _append(self, arrays, counts, first):
+    def _grow_raw(self, R, N):
+        """Room for R rows and N entries in the raw buffers: amortised doubling, device to device: no resident row goes up again."""
+        old = self._dims
+        capR, capN = self._cap
+        if self._raw is None or R > capR or N > capN:
+            capR, capN = max(R, 2 * capR if R > capR else capR), max(N, 2 * capN if N > capN else capN)
+            new = [self._alloc(4 * (capR + 1)), self._alloc(4 * capN), self._alloc(8 * capN), self._alloc(8 * capR), self._alloc(8 * capR)]
+            if self._raw is not None:
+                used = (4 * (old["n_rows"] + 1), 4 * old["row_nnz"], 8 * old["row_nnz"], 8 * old["n_rows"], 8 * old["n_rows"])
+                for dst, src, n in zip(new, self._raw, used):
+                    dst[:n].copy_(src[:n])
+            self._raw, self._cap = new, (capR, capN)
+
+    def _upload_block(self, arrays, first):
+        """The block into the tail of the raw buffers (enqueued; `row_ptr` shifted to the resident entries)."""
         from . import lpstate
+        old = self._dims
+        dR, dN = arrays[3].shape[0], arrays[1].shape[0]
+        _, total = lpstate.rows_upload_layout(dR, dN, first)
+        self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, total, 1 << 20)
+        places = lpstate.pack_row_block(self.in_np, arrays, old["row_nnz"], first)
+        at = (4 * (old["n_rows"] + (0 if first else 1)), 4 * old["row_nnz"], 8 * old["row_nnz"], 8 * old["n_rows"], 8 * old["n_rows"])
+        for dst, (off, n), to in zip(self._raw, places, at):
+            if n:
+                dst[to:to + n].copy_(self.pin_in[off:off + n], non_blocking=True)
+
+    def _after(self, counts):
+        """The resident dims after a block of `counts`; ValueError where the sums leave int32."""
         dR, dN, dC, dE = counts
         old = self._dims
         R, N = old["n_rows"] + dR, old["row_nnz"] + dN
         if old["n_state_edges"] + dE > 2 ** 31 - 1 or N > 2 ** 31 - 1:
             raise ValueError("the state's constraint edges do not fit int32")
-        dev = self.model.device
-        with torch.cuda.device(dev):
-            capR, capN = self._cap
-            if self._raw is None or R > capR or N > capN:       # amortised doubling, device to device: no resident row goes up again
-                capR, capN = max(R, 2 * capR if R > capR else capR), max(N, 2 * capN if N > capN else capN)
-                new = [self._alloc(4 * (capR + 1)), self._alloc(4 * capN), self._alloc(8 * capN), self._alloc(8 * capR), self._alloc(8 * capR)]
-                if self._raw is not None:
-                    used = (4 * (old["n_rows"] + 1), 4 * old["row_nnz"], 8 * old["row_nnz"], 8 * old["n_rows"], 8 * old["n_rows"])
-                    for dst, src, n in zip(new, self._raw, used):
-                        dst[:n].copy_(src[:n])
-                self._raw, self._cap = new, (capR, capN)
-            _, total = lpstate.rows_upload_layout(dR, dN, first)
-            self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, total, 1 << 20)
-            places = lpstate.pack_row_block(self.in_np, arrays, old["row_nnz"], first)
-            at = (4 * (old["n_rows"] + (0 if first else 1)), 4 * old["row_nnz"], 8 * old["row_nnz"], 8 * old["n_rows"], 8 * old["n_rows"])
-            for dst, (off, n), to in zip(self._raw, places, at):
-                if n:
-                    dst[to:to + n].copy_(self.pin_in[off:off + n], non_blocking=True)
-            dims = dict(old, n_rows=R, row_nnz=N, n_state_rows=old["n_state_rows"] + dC, n_state_edges=old["n_state_edges"] + dE)
+        return dict(old, n_rows=R, row_nnz=N, n_state_rows=old["n_state_rows"] + dC, n_state_edges=old["n_state_edges"] + dE)
+
+    def _host_counts(self, arrays):
+        """What the host keeps of the resident state once `arrays` are part of it: (lhs rows, lhs entries), the per-column
+        degrees' update and the longest segments -- exact, without a device read."""
+        from . import lpstate
+        dL, dEL, longest, (cols, counts) = lpstate.block_sides(arrays, self.n_cols, self._dims["infinity"])
+        v_max = max(self._max_deg[1], int((self._col_deg[cols] + counts).max())) if cols.size else self._max_deg[1]
+        return (dL, dEL), (cols, counts), (max(self._max_deg[0], longest), v_max)
+
+    def _adopt_counts(self, host):
+        (dL, dEL), (cols, counts), self._max_deg = host
+        self._lhs = (self._lhs[0] + dL, self._lhs[1] + dEL)
+        self._col_deg[cols] += counts
+
+    def _append(self, arrays, counts, first):
+        dims = self._after(counts)
+        host = self._host_counts(arrays)
+        with torch.cuda.device(self.model.device):
+            self._grow_raw(dims["n_rows"], dims["row_nnz"])
+            self._upload_block(arrays, first)
             self._rebuild(dims)         # raises for rows the device flags: the session then keeps the rows it had
+        self._adopt_counts(host)
 
     def _rebuild(self, dims):
         """gcnn_lp_rows_build + gcnn_graph_build on the raw rows for `dims`; adopts both (and `dims`) once the device has accepted
@@ -876,27 +918,116 @@ class LPSession(_Staging):
         graph = BipartiteGraph(inds, feats, c, dims["n_cols"], validate=False, sync_max_degree=True)
         res = _lib.LpResident(derived.data_ptr() + off[3], derived.data_ptr() + off[4], derived.data_ptr() + off[0],
                               self._col_type.data_ptr(), self._col_obj.data_ptr(), *(t.data_ptr() for t in self._opt), graph.c)
-        self._derived, self._derived_off, self._graph, self._res, self._dims = derived, off, graph, res, dims
+        u8 = lambda t: t.view(torch.uint8)
+        cur = dict(cons_feats=derived[off[0]:], edge_row=derived[off[1]:], edge_col=derived[off[1] + 4 * e1:], edge_coef=derived[off[2]:],
+                   l_ptr=u8(graph.l_ptr), v_ptr=u8(graph.v_ptr), v_oth=u8(graph.v_oth), v_coef=u8(graph.v_coef),
+                   row_place=derived[off[3]:], row_scale=derived[off[4]:])
+        self._derived, self._graph, self._res, self._dims = derived, graph, res, dims
+        self._cur, self._cur_struct, self._cur_set = cur, self._set_struct(cur), -1
         self.layouts.clear()
+
+    # ---- the incremental append ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _set_struct(cur):
+        return _lib.LpRowsSet(*(cur[name].data_ptr() if cur[name].numel() else 0 for name in _lib.LP_SET_FIELDS))
+
+    def _other_set(self, dims, max_deg):
+        """(index, tensors, gcnn_lp_rows_set, gcnn_lp_resident) of the set of derived buffers an append into `dims` writes: the one
+        the rounds do not read, with room for `dims`.  One that is too small is replaced by one of twice the size needed, on
+        the device; nothing is copied, an append writes every array whole.  The two structs are made once per allocation; only
+        the longest segments change from append to append."""
+        i = 1 - self._cur_set if self._cur_set >= 0 else 0
+        need = (dims["n_rows"], dims["n_state_rows"], dims["n_state_edges"])
+        held = self._sets[i]
+        if held is None or any(n > c for n, c in zip(need, held[1])):
+            cap = tuple(2 * n if n > c else c for n, c in zip(need, held[1] if held else (0, 0, 0)))
+            self._sets[i] = held = None
+            capR, capC, capE = cap
+            sizes = dict(cons_feats=16 * capC, edge_row=4 * capE, edge_col=4 * capE, edge_coef=4 * capE, l_ptr=4 * (capC + 1),
+                         v_ptr=4 * (dims["n_cols"] + 1), v_oth=4 * capE, v_coef=4 * capE, row_place=8 * capR, row_scale=8 * capR)
+            cur = {name: self._alloc(sizes[name]) for name in _lib.LP_SET_FIELDS}
+            p = {name: t.data_ptr() for name, t in cur.items()}
+            res = _lib.LpResident(p["row_place"], p["row_scale"], p["cons_feats"], self._col_type.data_ptr(), self._col_obj.data_ptr(),
+                                  *(t.data_ptr() for t in self._opt),
+                                  _lib.Graph(p["l_ptr"], p["edge_col"], p["edge_coef"], p["v_ptr"], p["v_oth"], p["v_coef"], 0, 0))
+            self._sets[i] = held = (cur, cap, self._set_struct(cur), res)
+        res = held[3]
+        res.cons_graph.l_max_deg, res.cons_graph.v_max_deg = max_deg
+        return i, held[0], held[2], res
+
+    def _block_dims(self, counts, host):
+        return counts + host[0] + self._lhs
+
+    def _adopt_set(self, i, cur, struct, dims, host, res):
+        self._cur, self._cur_struct, self._cur_set, self._dims, self._res = cur, struct, i, dims, res
+        self._derived = self._graph = None          # the rebuild's block, if the rounds read it until now
+        self._adopt_counts(host)
+        self.layouts.clear()
+
+    def _append_incremental(self, arrays, counts):
+        from . import lpstate
+        dims = self._after(counts)
+        host = self._host_counts(arrays)
+        P = C.c_void_p
+        dev = self.model.device
+        with torch.cuda.device(dev):
+            self._grow_raw(dims["n_rows"], dims["row_nnz"])
+            i, dst, dst_struct, res = self._other_set(dims, host[2])
+            d, b, L = lpstate.lp_append_layout(self._dims, self._block_dims(counts, host), 0)
+            if self.arena is None or self.arena.numel() < L.scratch_bytes + 256:
+                self.arena = None
+                self.arena = self._alloc(max(2 * (L.scratch_bytes + 256), 1 << 22))
+            self._upload_block(arrays, False)
+            flags_at = (L.scratch_bytes + 15) & ~15
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib().gcnn_lp_rows_append(C.byref(d), C.byref(b), *(P(t.data_ptr()) for t in self._raw), P(self._col_obj.data_ptr()),
+                                                      C.byref(self._cur_struct), C.byref(dst_struct), P(self.arena.data_ptr()),
+                                                      L.scratch_bytes, P(self.arena.data_ptr() + flags_at),
+                                                      P(stream.cuda_stream)), "gcnn_lp_rows_append")
+            flags = self.arena[flags_at:flags_at + 16].view(torch.int32).cpu().numpy()      # the one read; waits
+        lpstate.raise_for_flags(flags)
+        self._adopt_set(i, dst, dst_struct, dims, host, res)
+
+    def resident_state(self):
+        """Host copies of what the session holds of the rows, as the rounds read it: the ten derived arrays (`cons_feats` [C, 4]
+        with the columns 1 and 3 as the last round left them), the longest segments and the sizes."""
+        self._open()
+        d, cur = self._dims, self._cur
+        r, c, e, v = d["n_rows"], d["n_state_rows"], d["n_state_edges"], d["n_cols"]
+        shape = dict(cons_feats=(torch.float32, 4 * c), edge_row=(torch.int32, e), edge_col=(torch.int32, e), edge_coef=(torch.float32, e),
+                     l_ptr=(torch.int32, c + 1), v_ptr=(torch.int32, v + 1), v_oth=(torch.int32, e), v_coef=(torch.float32, e),
+                     row_place=(torch.int32, 2 * r), row_scale=(torch.float64, r))
+        out = {name: cur[name][:n * torch.empty(0, dtype=dt).element_size()].view(dt).cpu().numpy() for name, (dt, n) in shape.items()}
+        out["cons_feats"] = out["cons_feats"].reshape(c, 4)
+        out["row_place"] = out["row_place"].reshape(r, 2)
+        g = self._res.cons_graph
+        out.update(l_max_deg=int(g.l_max_deg), v_max_deg=int(g.v_max_deg), n_rows=r, n_state_rows=c, n_state_edges=e)
+        return out
 
     # ---- rounds ------------------------------------------------------------------------------------------------------------------
     def _open(self):
         if self.closed:
             raise _lib.GcnnError("the LP session is closed")
 
-    def _checked(self, rnd, n_forced=-1, n_entries=0):
+    def _checked(self, rnd, n_forced=-1, n_entries=0, row_dims=None, block=None):
         """A round checked on the host -> (arrays, presence mask, dims, layout entry).  An optional array whose device copy a
-        rejected round overwrote travels again from the host copy of the last accepted one."""
+        rejected round overwrote travels again from the host copy of the last accepted one.  `row_dims`, `block`: the round
+        comes with an append -- the resident dims after it and the block's eight counts; the layout entry is then the fused
+        call's."""
         from . import lpstate
         self._open()
-        arrays, present, dims = lpstate.check_round(rnd, self._dims, self._kept, self.deep_check)
+        arrays, present, dims = lpstate.check_round(rnd, self._dims if row_dims is None else row_dims, self._kept, self.deep_check)
         for q, name in enumerate(lpstate.OPTIONAL):
             needed = not name.startswith("col_primal") or dims["has_incumbent"]
             if name in self._stale and needed and not present >> q & 1:
                 arrays[5 + q] = self._kept[name]
                 present |= 1 << q
-        key = _int_key(dims) + (present, n_forced, n_entries)
-        lay = self.cached(key, self._layout, dims, present, n_forced, n_entries)
+        key = _int_key(dims) + (present, n_forced, n_entries) + (block or ())
+        if block is None:
+            lay = self.cached(key, self._layout, dims, present, n_forced, n_entries)
+        else:
+            before = dict(self._dims, n_cuts=dims["n_cuts"], cut_nnz=dims["cut_nnz"], has_incumbent=dims["has_incumbent"])
+            lay = self.cached(key, self._append_layout, before, block, present, n_forced, n_entries)
         return arrays, present, dims, lay
 
     @staticmethod
@@ -905,50 +1036,101 @@ class LPSession(_Staging):
         _, L = lpstate.lp_round_layout(dims, present, n_forced, n_entries)
         return L, list(L.in_off), list(L.forced_off), list(L.out_off), list(L.dev_off)
 
-    def upload_bytes(self, rnd, forced=None):
-        """Bytes the one upload of this round would carry (with `forced`: packed forced rows of a selection)."""
+    @staticmethod
+    def _append_layout(before, block, present, n_forced, n_entries):
+        """The fused call's layout entry; the round's offsets are shifted to the whole upload and the whole arena."""
+        from . import lpstate
+        d, b, L = lpstate.lp_append_layout(before, block, present, n_forced, n_entries)
+        R = L.round
+        return (L, [L.block_bytes + o for o in R.in_off], [L.block_bytes + o for o in R.forced_off], list(R.out_off),
+                [L.round_off + o for o in R.dev_off], d, b)
+
+    def upload_bytes(self, rnd, forced=None, append=None):
+        """Bytes the one upload of this round would carry (with `forced`: packed forced rows of a selection; with `append`: the
+        block that goes up with it)."""
         fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        if append is not None:
+            blk = self._check_block(append)
+            if blk is not None:
+                return int(self._checked(rnd, *fshape, row_dims=blk[2], block=self._block_dims(blk[1], blk[3]))[3][0].in_bytes)
         return int(self._checked(rnd, *fshape)[3][0].in_bytes)
 
-    def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0):
+    def _check_block(self, block):
+        """An `LPRowBlock` checked on the host -> (arrays, counts, the resident dims after it, the host's counts); None for an
+        empty block."""
+        from . import lpstate
+        self._open()
+        arrays, counts = lpstate.check_row_block(*block.arrays(), self.n_cols, self._dims["infinity"], self.deep_check)
+        if counts[0] == 0:
+            return None
+        return arrays, counts, self._after(counts), self._host_counts(arrays)
+
+    def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0, append=None):
         """check -> layout -> pack -> one call -> the download's LP flags checked.  Returns (the round's dims, the download's
-        offsets, the arena's offsets); what the round gave of the optional column arrays is remembered once it is accepted."""
+        offsets, the arena's offsets); what the round gave of the optional column arrays is remembered once it is accepted.
+        With `append` the call is gcnn_lp_round_append: the block goes up with the round, the append's launches run in front of
+        the round's, and the session adopts the rows once the download shows that the device accepted the block and the round."""
         from . import lpstate
         t0 = time.perf_counter()
         fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
-        arrays, present, dims, (L, in_off, forced_off, out_off, dev_off) = self._checked(rnd, *fshape)
-        d = _lib.LpDims(**dims)
-        self._buffers(L)
-        lpstate.pack_round(self.in_np, in_off, arrays, present)
-        head = (C.byref(d), present)
-        if forced is None:
-            self._enqueue_wait("gcnn_lp_round", head + (C.byref(self._res),), (int(want_order),), timings, t0, upload_bytes=int(L.in_bytes))
+        blk = self._check_block(append) if append is not None else None
+        if blk is None:
+            arrays, present, dims, (L, in_off, forced_off, out_off, dev_off) = self._checked(rnd, *fshape)
+            d = _lib.LpDims(**dims)
+            self._buffers(L)
+            lpstate.pack_round(self.in_np, in_off, arrays, present)
+            head = (C.byref(d), present)
+            if forced is None:
+                self._enqueue_wait("gcnn_lp_round", head + (C.byref(self._res),), (int(want_order),), timings, t0, upload_bytes=int(L.in_bytes))
+            else:
+                self._put_forced(forced_off, forced)
+                self._enqueue_wait("gcnn_lp_round_select", head + fshape + (C.byref(self._res),), (float(p_max), float(p_max_ub)), timings,
+                                   t0, upload_bytes=int(L.in_bytes))
+            flag_words = (out_off[4],)
         else:
-            self._put_forced(forced_off, forced)
-            self._enqueue_wait("gcnn_lp_round_select", head + fshape + (C.byref(self._res),), (float(p_max), float(p_max_ub)), timings,
-                               t0, upload_bytes=int(L.in_bytes))
+            block_arrays, counts, row_dims, host = blk
+            arrays, present, dims, (L, in_off, forced_off, out_off, dev_off, d, b) = self._checked(
+                rnd, *fshape, row_dims=row_dims, block=self._block_dims(counts, host))
+            self._buffers(L)
+            lpstate.pack_append(self.in_np, L, block_arrays, arrays, present)
+            if forced is not None:
+                self._put_forced(forced_off, forced)
+            P = C.c_void_p
+            with torch.cuda.device(self.model.device):
+                self._grow_raw(row_dims["n_rows"], row_dims["row_nnz"])
+                i, dst, dst_struct, res = self._other_set(row_dims, host[2])
+            head = (C.byref(d), C.byref(b), present) + fshape + tuple(P(t.data_ptr()) for t in self._raw) + (
+                C.byref(self._cur_struct), C.byref(dst_struct), C.byref(res))
+            self._enqueue_wait("gcnn_lp_round_append", head, (int(want_order), float(p_max), float(p_max_ub)), timings, t0,
+                               upload_bytes=int(L.in_bytes))
+            flag_words = (int(L.flags_off), out_off[4])
         given = {name: arrays[5 + q] for q, name in enumerate(lpstate.OPTIONAL) if present >> q & 1}
         out = self.out_np
         try:
-            lpstate.raise_for_flags(out[out_off[4]:out_off[4] + 16].view(np.int32))
+            for at in flag_words:
+                lpstate.raise_for_flags(out[at:at + 16].view(np.int32))
         except ValueError:
             self._stale.update(given)       # their device copies hold the rejected round's values
             raise
+        if blk is not None:
+            self._adopt_set(i, dst, dst_struct, row_dims, host, res)
         self._kept.update(given)
         self._stale.difference_update(given)
         return dims, out_off, dev_off
 
-    def state(self, rnd):
-        """The model's 10-tuple as host arrays and `cut_index`, as `GCNN.state_from_lp` gives them for the assembled snapshot."""
-        dims, out_off, dev = self._run(rnd, -1)
+    def state(self, rnd, append=None):
+        """The model's 10-tuple as host arrays and `cut_index`, as `GCNN.state_from_lp` gives them for the assembled snapshot
+        (with `append`: the rows of the block appended first, in the same call)."""
+        dims, out_off, dev = self._run(rnd, -1, append=append)
         c, v, k, e1, e2 = dims["n_state_rows"], dims["n_cols"], dims["n_cuts"], dims["n_state_edges"], dims["cut_nnz"]
         f32, i32 = torch.float32, torch.int32
-        D, o, A = self._derived, self._derived_off, self.arena
+        cur, A = self._cur, self.arena
 
         def host(buf, off, shape, dt):
             return buf[off:off + 4 * shape[0] * shape[1]].view(dt).view(shape).cpu().numpy()
 
-        arrays = (host(D, o[0], (c, 4), f32), host(D, o[1], (2, e1), i32), host(D, o[2], (e1, 1), f32), host(A, dev[1], (v, 14), f32),
+        inds = np.stack([host(cur["edge_row"], 0, (1, e1), i32)[0], host(cur["edge_col"], 0, (1, e1), i32)[0]])
+        arrays = (host(cur["cons_feats"], 0, (c, 4), f32), inds, host(cur["edge_coef"], 0, (e1, 1), f32), host(A, dev[1], (v, 14), f32),
                   host(A, dev[2], (k, 6), f32), host(A, dev[3], (2, e2), i32), host(A, dev[4], (e2, 1), f32))
         return arrays + (c, v, k), self.out_np[out_off[5]:out_off[5] + 4 * k].view(np.int32).copy()
 
@@ -957,32 +1139,35 @@ class LPSession(_Staging):
         scores, order, n_kept = self._read(out_off[0], out_off[1] if want_order else None, out_off[3] if select else None, n)
         return scores, order, n_kept, self.out_np[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
 
-    def score(self, rnd, rank=False, timings=None):
+    def score(self, rnd, rank=False, timings=None, append=None):
         """`GCNN.score_lp` for the assembled snapshot: a `ScoreArray` in STATE order with `.cut_index` and, with `rank`,
-        `.rankings`."""
+        `.rankings`.  `append` (an `lpstate.LPRowBlock`): rows appended in the same call, in front of the round, whose `row_dual`
+        and `row_basis` cover them; all or nothing -- if the call raises, the session holds the rows it held before."""
         n = int(np.asarray(rnd.cut_lhs).shape[0])
         on_device = self.model._rank_on_device(rank, n) and n <= 4096
-        dims, out_off, _ = self._run(rnd, int(on_device), timings)
+        dims, out_off, _ = self._run(rnd, int(on_device), timings, append=append)
         scores, order, _, cut_index = self._results(dims, out_off, on_device, False)
         scores.cut_index = cut_index
         if rank:
             scores.rankings = order if on_device else stable_ranking(scores)
         return scores
 
-    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None):
+    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None):
         """`GCNN.select_cuts_lp` for the assembled snapshot: a `SelectResult` with `cut_index`.  More than 4,096 cuts raise
-        `GcnnError` before anything is enqueued."""
+        `GcnnError` before anything is enqueued.  `append`: as in `score` -- the separation loop's call, which appends the cuts
+        the last selection kept and selects among the new candidates in one upload, one run of launches and one download."""
         ops.check_thresholds(p_max, p_max_ub)
         self.model._check_select_size("LPSession.select_cuts", "round", int(np.asarray(rnd.cut_lhs).shape[0]))
         packed = normalize_forced(forced, self.n_cols)
-        dims, out_off, _ = self._run(rnd, 1, timings, packed, p_max, p_max_ub)
+        dims, out_off, _ = self._run(rnd, 1, timings, packed, p_max, p_max_ub, append=append)
         scores, order, n_kept, cut_index = self._results(dims, out_off, True, True)
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
     def close(self):
-        """Release the device buffers; the session cannot be used afterwards."""
+        """Release the device buffers (both derived sets included); the session cannot be used afterwards."""
         self.closed = True
-        self._raw = self._derived = self._graph = self._res = self.arena = None
+        self._raw = self._derived = self._graph = self._res = self.arena = self._cur = self._cur_struct = None
+        self._sets = [None, None]
         self._col_type = self._col_obj = self._opt = None
         self._buffers_made = []
         self._kept, self._stale = {}, set()

@@ -275,6 +275,35 @@ class LPRound:
         return self.col_primal is not None if self.has_incumbent is None else bool(self.has_incumbent)
 
 
+@dataclass
+class LPRowBlock:
+    """Rows to append behind the resident ones of an `LPSession`: CSR over the same columns with `row_ptr` from 0, under the
+    rows' contract of `LPSnapshot` (checked by `check_row_block`)."""
+    row_ptr: np.ndarray
+    row_col: np.ndarray
+    row_val: np.ndarray
+    row_lhs: np.ndarray
+    row_rhs: np.ndarray
+
+    def arrays(self):
+        return self.row_ptr, self.row_col, self.row_val, self.row_lhs, self.row_rhs
+
+
+def rows_with(rows: LPRows, *blocks: LPRowBlock) -> LPRows:
+    """`rows` with the blocks appended: what a session holds after appending them."""
+    ptr, col, val, lhs, rhs = ([np.asarray(getattr(rows, n))] for n in ("row_ptr", "row_col", "row_val", "row_lhs", "row_rhs"))
+    at = int(ptr[0][-1])
+    for b in blocks:
+        bp = np.asarray(b.row_ptr)
+        ptr.append(bp[1:].astype(np.int64) + at)
+        at += int(bp[-1])
+        for dst, a in zip((col, val, lhs, rhs), (b.row_col, b.row_val, b.row_lhs, b.row_rhs)):
+            dst.append(np.asarray(a))
+    return LPRows(np.concatenate(ptr).astype(np.int32), np.concatenate(col).astype(np.int32), np.concatenate(val).astype(np.float64),
+                  np.concatenate(lhs).astype(np.float64), np.concatenate(rhs).astype(np.float64), rows.col_type, rows.col_obj,
+                  infinity=rows.infinity, sum_epsilon=rows.sum_epsilon, n_model_vars=rows.n_model_vars, obj_norm=rows.obj_norm)
+
+
 def assemble(rows: LPRows, rnd: LPRound, kept=None) -> LPSnapshot:
     """The `LPSnapshot` a round stands for: the definition of what a session answers.  `kept`: {name: array} of the optional column
     arrays as the last rounds gave them, for the ones this round leaves None."""
@@ -423,6 +452,65 @@ def pack_row_block(buf, arrays, entry_base, first):
             buf[off:off + a.nbytes] = a.view(np.uint8)
         out.append((off, a.nbytes))
     return out
+
+
+def block_sides(arrays, n_cols, infinity):
+    """What the host keeps of a checked block of rows beside `check_row_block`'s counts: (lhs-sided rows, their entries, the
+    longest row that lists a side, per-column count of listed entries as (columns, counts)).  O(entries of the block); a block
+    that is not small against the columns is counted densely, O(columns), which is cheaper then."""
+    row_ptr, row_col, _, row_lhs, row_rhs = arrays
+    lens = row_ptr[1:] - row_ptr[:-1]
+    has_lhs, has_rhs = finite(row_lhs, infinity), finite(row_rhs, infinity)
+    sides = has_lhs.view(np.int8) + has_rhs.view(np.int8)
+    listed = lens[sides > 0]
+    longest = int(listed.max()) if listed.size else 0
+    weight = np.repeat(sides, lens)
+    in_range = not row_col.size or (int(row_col.min()) >= 0 and int(row_col.max()) < n_cols)     # (without the deep check: anything)
+    if in_range and n_cols <= 8 * row_col.size:
+        dense = np.bincount(row_col, weights=weight, minlength=n_cols).astype(np.int64)
+        cols = np.flatnonzero(dense)
+        counts = dense[cols]
+    else:
+        cols, inverse = np.unique(row_col, return_inverse=True)
+        counts = np.bincount(inverse, weights=weight, minlength=cols.size).astype(np.int64)
+        ok = (cols >= 0) & (cols < n_cols) & (counts > 0)
+        cols, counts = cols[ok], counts[ok]
+    return int(np.count_nonzero(has_lhs)), int(lens[has_lhs].sum()), longest, (cols, counts)
+
+
+def lp_append_layout(dims, block, present, n_forced=-1, n_entries=0):
+    """(LpDims, LpAppendDims, LpAppendLayout) of the library for the dims BEFORE an append (a round's cut fields filled in) and
+    the block's eight counts; raises `_lib.GcnnError` where it declines the sizes."""
+    import ctypes as C
+
+    from . import _lib
+    d, b, L = _lib.LpDims(**dims), _lib.LpAppendDims(*block), _lib.LpAppendLayout()
+    _lib.check(_lib.lib().gcnn_lp_append_layout_for(C.byref(d), C.byref(b), present, n_forced, n_entries, C.byref(L)),
+               "gcnn_lp_append_layout_for")
+    return d, b, L
+
+
+def pack_append(buf, L, block_arrays, round_arrays, present):
+    """Write a checked block and a checked round into a staging buffer at gcnn_lp_append_layout_for's offsets: the block (its
+    `row_ptr` from 0, all n + 1 offsets) in front, then the round as `pack_round` writes it, at `L.block_bytes`."""
+    for off, a in zip(L.block_off, block_arrays):
+        if a.size:
+            buf[off:off + a.nbytes] = a.view(np.uint8)
+    pack_round(buf[L.block_bytes:], list(L.round.in_off), round_arrays, present)
+
+
+def unpack_append(buf, L, counts, round_dims, present):
+    """The inverse of `pack_append` for a block of `counts` = (rows, entries) and a round of `round_dims` (after the append) ->
+    (the block's five arrays, the round's 14 arrays with None where one does not travel)."""
+    n, nnz = counts
+    shapes = ((n + 1, np.int32), (nnz, np.int32), (nnz, np.float64), (n, np.float64), (n, np.float64))
+    block = [buf[off:off + k * np.dtype(dt).itemsize].view(dt).copy() for off, (k, dt) in zip(L.block_off, shapes)]
+    R, V, K, NK = round_dims["n_rows"], round_dims["n_cols"], round_dims["n_cuts"], round_dims["cut_nnz"]
+    sizes = [R, R, V, V, V] + [V if present >> q & 1 else None for q in range(4)] + [K + 1, NK, NK, K, K]
+    base, rnd = L.block_bytes, []
+    for off, (name, dt), k in zip(list(L.round.in_off)[1:], ROUND_FIELDS, sizes):
+        rnd.append(None if k is None else buf[base + off:base + off + k * np.dtype(dt).itemsize].view(dt).copy())
+    return block, rnd
 
 
 def lp_round_layout(dims, present, n_forced=-1, n_entries=0):

@@ -767,6 +767,54 @@ int gcnn_lp_round_select(const gcnn_lp_dims* dims, int32_t present, int32_t n_fo
                          const gcnn_lp_resident* resident /* host */, const float* params, const void* host_in, void* host_out,
                          void* arena, size_t arena_bytes, double p_max, double p_max_ub, void* stream);
 
+/* ---- rows appended to a resident LP without deriving the resident rows again ---------------------------------------------------------
+ * What gcnn_lp_rows_build and gcnn_graph_build derive from a row is local to that row but its place: the state lists the lhs sides
+ * first, so appended lhs rows move every rhs row.  An append therefore copies, shifts and merges the resident arrays and derives only
+ * the new rows -- through the same functions as the rebuild, so the result has its bits.  The caller holds TWO sets of derived
+ * arrays (gcnn_lp_rows_set: what the rebuild's derived block and graph hold, as separate arrays; edge_col / edge_coef are the graph's
+ * l_oth / l_coef).  An append reads `src` and writes `dst`, which must hold the sizes after the append; src is not written, so a
+ * rejected block costs nothing to undo.  block: its rows, raw entries, state rows and state edges, how many of the state rows and
+ * edges are lhs sides, and the same two counts of the resident state.  dims: the resident LP BEFORE the append.
+ * gcnn_lp_rows_append: the raw row arrays already hold the block behind the resident rows (row_ptr absolute); one fill of the count
+ * tables and four launches (k_lpa_stats, k_lpa_scan, k_lpa_move, k_lpa_order); the four flag words (gcnn_lp_state's; any set: dst is
+ * NOT valid) go to the device address `flags`; nothing is synchronised.
+ * gcnn_lp_round_append: the append inside the call of the round that follows it.  ONE upload of host_in (in_bytes): the block at
+ * block_off[0..4] -- row_ptr [n_rows + 1] from 0, row_col, row_val, row_lhs, row_rhs, unpadded -- then, at block_bytes (a multiple of 256), the round's upload as
+ * gcnn_lp_round_layout_for lays it out for the dims AFTER the append (row_dual and row_basis cover the new rows), forced rows
+ * included.  The append's launches also copy the block behind the resident raw rows (whose buffers must have the room); then exactly
+ * what gcnn_lp_round / gcnn_lp_round_select enqueue on `resident`, which points at dst; ONE download of out_bytes: the round's, then the
+ * append's four flag words at flags_off.  n_forced >= 0: a selection (want_order is not read); else want_order as gcnn_lp_round's.
+ * The arena: the upload | at round_off the round's arena | at scratch_off the append's scratch.  Returned before anything is
+ * enqueued: GCNN_E_BADARG, GCNN_E_WORKSPACE and the round's GCNN_E_UNSUPPORTED limits on the dims after the append. */
+typedef struct gcnn_lp_append_dims {
+    int32_t n_rows, row_nnz, n_state_rows, n_state_edges;   /* the block */
+    int32_t n_lhs_rows, n_lhs_edges;                          /* of them, lhs sides */
+    int32_t res_lhs_rows, res_lhs_edges;                      /* lhs sides of the resident state */
+} gcnn_lp_append_dims;
+typedef struct gcnn_lp_rows_set {          /* device pointers */
+    float* cons_feats; int32_t* edge_row; int32_t* edge_col; float* edge_coef;
+    int32_t* l_ptr; int32_t* v_ptr; int32_t* v_oth; float* v_coef;
+    int32_t* row_place; double* row_scale;
+} gcnn_lp_rows_set;
+typedef struct gcnn_lp_append_layout {
+    size_t block_bytes, block_off[5], in_bytes;
+    size_t out_bytes, flags_off;
+    size_t scratch_bytes;                  /* what gcnn_lp_rows_append needs */
+    size_t arena_bytes, round_off, scratch_off;
+    gcnn_lp_round_layout round;            /* offsets relative to block_bytes (upload), 0 (download) and round_off (arena) */
+} gcnn_lp_append_layout;
+int gcnn_lp_append_layout_for(const gcnn_lp_dims* dims, const gcnn_lp_append_dims* block, int32_t present, int32_t n_forced,
+                              int32_t n_forced_entries, gcnn_lp_append_layout* layout /* host */);
+int gcnn_lp_rows_append(const gcnn_lp_dims* dims, const gcnn_lp_append_dims* block, const int32_t* row_ptr, const int32_t* row_col,
+                        const double* row_val, const double* row_lhs, const double* row_rhs, const double* col_obj,
+                        const gcnn_lp_rows_set* src /* host */, const gcnn_lp_rows_set* dst /* host */, void* scratch, size_t scratch_bytes,
+                        int32_t* flags /* device [4] */, void* stream);
+int gcnn_lp_round_append(const gcnn_lp_dims* dims, const gcnn_lp_append_dims* block, int32_t present, int32_t n_forced,
+                         int32_t n_forced_entries, int32_t* row_ptr, int32_t* row_col, double* row_val, double* row_lhs, double* row_rhs,
+                         const gcnn_lp_rows_set* src /* host */, const gcnn_lp_rows_set* dst /* host */,
+                         const gcnn_lp_resident* resident /* host; on dst */, const float* params, const void* host_in, void* host_out,
+                         void* arena, size_t arena_bytes, int32_t want_order, double p_max, double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
