@@ -159,6 +159,26 @@ class LpAppendLayout(C.Structure):
                 ("scratch_off", C.c_size_t), ("round", LpRoundLayout)]
 
 
+LP_ROUNDS_MAX = GROUP_MAX   # GCNN_LP_ROUNDS_MAX
+
+
+class LpRoundsMember(C.Structure):
+    _fields_ = [("dims", LpDims), ("present", C.c_int32), ("n_forced", C.c_int32), ("n_forced_entries", C.c_int32),
+                ("has_append", C.c_int32), ("block", LpAppendDims), ("row_ptr", C.c_void_p), ("row_col", C.c_void_p),
+                ("row_val", C.c_void_p), ("row_lhs", C.c_void_p), ("row_rhs", C.c_void_p), ("src", C.POINTER(LpRowsSet)),
+                ("dst", C.POINTER(LpRowsSet)), ("resident", C.POINTER(LpResident)), ("params", C.c_void_p)]
+
+
+class LpRoundsLayout(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mode", C.c_int32), ("in_bytes", C.c_size_t), ("in_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("in_size", C.c_size_t * LP_ROUNDS_MAX), ("arena_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("member_round_off", C.c_size_t * LP_ROUNDS_MAX), ("scratch_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("counts_base", C.c_size_t), ("counts_bytes", C.c_size_t), ("counts_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("out_base", C.c_size_t), ("out_bytes", C.c_size_t), ("out_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("out_size", C.c_size_t * LP_ROUNDS_MAX), ("table_off", C.c_size_t), ("table_bytes", C.c_size_t),
+                ("arena_bytes", C.c_size_t)]
+
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -242,6 +262,8 @@ SIGNATURES = {
                                       C.POINTER(LpRowsSet), _P, _Z, _P, _P]),
     "gcnn_lp_round_append": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpAppendDims), _I, _I, _I, _P, _P, _P, _P, _P, C.POINTER(LpRowsSet),
                                        C.POINTER(LpRowsSet), C.POINTER(LpResident), _P, _P, _P, _P, _Z, _I, _D, _D, _P]),
+    "gcnn_lp_rounds_layout_for": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, C.POINTER(LpRoundsLayout)]),
+    "gcnn_lp_rounds": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }
 
 _lib = None

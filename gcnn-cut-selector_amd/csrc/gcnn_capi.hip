@@ -929,7 +929,7 @@ static int infer_rank(const gcnn_dims* d, char* A, const gcnn_infer_layout& L, h
     float* out = (float*)(A + L.dev_off[6]);
     if (d->n_cuts > 0) {
         ProfScope prof("k_rank_scores", st);
-        hipLaunchKernelGGL(k_rank_scores, dim3(1), dim3(256), 0, st, out, d->n_cuts, (int*)((char*)out + L.out_off[1]));
+        GCNN_LAUNCH(k_rank_scores, dim3(1), dim3(256), 0, st, out, d->n_cuts, (int*)((char*)out + L.out_off[1]));
         LAUNCHCHK();
     }
     return 0;
@@ -1386,3 +1386,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lpres.hpp"
 // rows appended to a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_append, gcnn_lp_round_append): launch names k_lpa_*
 #include "gcnn_lpappend.hpp"
+// rounds of several resident LPs in one call (gcnn_lp_rounds)
+#include "gcnn_lprounds.hpp"

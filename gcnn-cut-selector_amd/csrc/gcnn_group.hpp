@@ -154,32 +154,19 @@ struct GroupRecScope {   // installs a recorder on this thread for one member's 
 struct GroupLaunch { GroupKernel* k; size_t off; int grid, block; size_t smem; };
 struct GroupPlan { GroupLaunch launches[GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES]; int nl; size_t bytes; };
 
-template <class Step>
-static int group_plan(int n, const gcnn_group_member* mem, void* host, Step member_step, GroupPlan* P) {
-    int rc;
-    // 1. record every regular member's step (nothing is enqueued)
-    static thread_local std::vector<GroupRecord> recs;
-    recs.resize((size_t)GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES);
-    GroupRecorder r[GCNN_GROUP_MAX];
-    int nreg = 0, nstage = 0;
-    for (int i = 0; i < n; ++i) {
-        if (group_degenerate(mem[i].dims)) continue;
-        GroupRecorder& q = r[nreg];
-        q = GroupRecorder{recs.data() + (size_t)nreg * GCNN_GROUP_MAX_STAGES, 0, GCNN_GROUP_MAX_STAGES, false};
-        {
-            GroupRecScope scope(&q);
-            rc = member_step(i);
-        }
-        if (rc) return rc;
-        if (q.bad) return GCNN_E_UNSUPPORTED;
-        for (int s = 0; s < q.n; ++s) if (!group_kernel(q.rec[s].kern)) return GCNN_E_UNSUPPORTED;
-        nstage = std::max(nstage, q.n);
-        ++nreg;
-    }
-    // 2. the launch tables, stage by stage: the members whose s-th launch runs the same kernel share one launch
-    int nl = 0;
-    size_t off = 0;
+// The launch tables of recorded steps, stage by stage, appended at *off of the staging buffer: the members whose s-th launch runs
+// the same kernel share one launch.  r[0..nreg): the members' recordings; find: the group kernel of a solo kernel.
+typedef GroupKernel* (*GroupLookup)(const void*);
+static int group_tables(int nreg, const GroupRecorder* r, void* host, GroupLookup find, GroupLaunch* launches, int cap, int* nl_io,
+                        size_t* off_io) {
+    int nl = *nl_io, nstage = 0;
+    size_t off = *off_io;
     char* h = (char*)host;
+    for (int i = 0; i < nreg; ++i) {
+        if (r[i].bad) return GCNN_E_UNSUPPORTED;
+        for (int s = 0; s < r[i].n; ++s) if (!find(r[i].rec[s].kern)) return GCNN_E_UNSUPPORTED;
+        nstage = std::max(nstage, r[i].n);
+    }
     for (int s = 0; s < nstage; ++s) {
         bool done[GCNN_GROUP_MAX] = {};
         for (int i = 0; i < nreg; ++i) {
@@ -199,10 +186,52 @@ static int group_plan(int n, const gcnn_group_member* mem, void* host, Step memb
                 ++head->n;
                 done[j] = true;
             }
-            P->launches[nl++] = GroupLaunch{group_kernel(first.kern), off, head->blk0[head->n], first.block, first.smem};
+            if (nl >= cap) return GCNN_E_UNSUPPORTED;
+            launches[nl++] = GroupLaunch{find(first.kern), off, head->blk0[head->n], first.block, first.smem};
             off = (off + sizeof(GroupHead) + (size_t)head->n * stride + 63) & ~(size_t)63;
         }
     }
+    *nl_io = nl; *off_io = off;
+    return 0;
+}
+// the launches of such tables, once they lie at `dev`
+static int group_launches(const GroupLaunch* launches, int nl, void* dev, hipStream_t st) {
+    for (int k = 0; k < nl; ++k) {
+        const GroupLaunch& L = launches[k];
+        if (L.grid <= 0) continue;
+        if (L.smem > 0 && L.k->attr.first())
+            HIPCHK(hipFuncSetAttribute(L.k->group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.smem));
+        const GroupHead* tab = (const GroupHead*)((char*)dev + L.off);
+        void* args[] = {&tab};
+        ProfScope prof(L.k->name, st);
+        HIPCHK(hipLaunchKernel(L.k->group, dim3(L.grid), dim3(L.block), args, L.smem, st));
+    }
+    return 0;
+}
+
+template <class Step>
+static int group_plan(int n, const gcnn_group_member* mem, void* host, Step member_step, GroupPlan* P) {
+    int rc;
+    // 1. record every regular member's step (nothing is enqueued)
+    static thread_local std::vector<GroupRecord> recs;
+    recs.resize((size_t)GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES);
+    GroupRecorder r[GCNN_GROUP_MAX];
+    int nreg = 0;
+    for (int i = 0; i < n; ++i) {
+        if (group_degenerate(mem[i].dims)) continue;
+        GroupRecorder& q = r[nreg];
+        q = GroupRecorder{recs.data() + (size_t)nreg * GCNN_GROUP_MAX_STAGES, 0, GCNN_GROUP_MAX_STAGES, false};
+        {
+            GroupRecScope scope(&q);
+            rc = member_step(i);
+        }
+        if (rc) return rc;
+        ++nreg;
+    }
+    // 2. the launch tables
+    int nl = 0;
+    size_t off = 0;
+    if ((rc = group_tables(nreg, r, host, group_kernel, P->launches, GCNN_GROUP_MAX * GCNN_GROUP_MAX_STAGES, &nl, &off))) return rc;
     P->nl = nl; P->bytes = off;
     return 0;
 }
@@ -212,16 +241,7 @@ template <class Step>
 static int group_issue(int n, const gcnn_group_member* mem, void* host, void* dev, const GroupPlan& P, Step member_step, hipStream_t st) {
     int rc;
     if (P.bytes) HIPCHK(hipMemcpyAsync(dev, host, P.bytes, hipMemcpyHostToDevice, st));
-    for (int k = 0; k < P.nl; ++k) {
-        const GroupLaunch& L = P.launches[k];
-        if (L.grid <= 0) continue;
-        if (L.smem > 0 && L.k->attr.first())
-            HIPCHK(hipFuncSetAttribute(L.k->group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.smem));
-        const GroupHead* tab = (const GroupHead*)((char*)dev + L.off);
-        void* args[] = {&tab};
-        ProfScope prof(L.k->name, st);
-        HIPCHK(hipLaunchKernel(L.k->group, dim3(L.grid), dim3(L.block), args, L.smem, st));
-    }
+    if ((rc = group_launches(P.launches, P.nl, dev, st))) return rc;
     for (int i = 0; i < n; ++i)
         if (group_degenerate(mem[i].dims) && (rc = member_step(i))) return rc;
     return 0;

@@ -80,10 +80,12 @@ static LpaSet lpa_set(const gcnn_lp_rows_set* s) {
 
 // Everything the append enqueues.  blk_*: where the launches read the block (the upload slot with offsets from 0, or the raw rows'
 // tail with absolute offsets: ent_base says which); raw_*: non-null in the fused call, where k_lpa_stats copies the block to.
+// counts: null, or where the caller keeps the cleared count tables (cnt + vpart, LpaScratch::clear_bytes) and has enqueued their
+// fill itself (gcnn_lprounds.hpp: one fill for all sessions).
 static int lpa_enqueue(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, const int* blk_ptr,
                        const int* blk_col, const double* blk_val, const double* blk_lhs, const double* blk_rhs, int nnz_bound, int ent_base,
                        int32_t* const raw[2], double* const rawd[3], const double* col_obj, const gcnn_lp_rows_set* src,
-                       const gcnn_lp_rows_set* dst, char* scratch, int32_t* flags_dev, hipStream_t st) {
+                       const gcnn_lp_rows_set* dst, char* scratch, int32_t* flags_dev, hipStream_t st, char* counts = nullptr) {
     const LpaScratch s = lpa_scratch(d, b);
     LpArgs a; memset(&a, 0, sizeof(a));
     a.row_ptr = blk_ptr; a.row_col = blk_col; a.row_val = blk_val; a.row_lhs = blk_lhs; a.row_rhs = blk_rhs; a.col_obj = col_obj;
@@ -98,29 +100,30 @@ static int lpa_enqueue(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, cons
     x.dR = b->n_rows; x.dN = b->row_nnz; x.dC = b->n_state_rows; x.dE = b->n_state_edges; x.dL = b->n_lhs_rows; x.dEL = b->n_lhs_edges;
     x.V = d->n_cols; x.nvc = lp_chunks(x.V); x.ent_base = ent_base;
     if (raw) { x.raw_ptr = raw[0]; x.raw_col = raw[1]; x.raw_val = rawd[0]; x.raw_lhs = rawd[1]; x.raw_rhs = rawd[2]; }
-    x.cnt = (int*)(scratch + s.cnt); x.vpart = (int*)(scratch + s.vpart); x.vsplit = (int*)(scratch + s.vsplit);
+    char* cnt = counts ? counts : scratch + s.cnt;
+    x.cnt = (int*)cnt; x.vpart = (int*)(cnt + (s.vpart - s.cnt)); x.vsplit = (int*)(scratch + s.vsplit);
     x.ent_rank = (int*)(scratch + s.ent_rank); x.tmp_row = (int*)(scratch + s.tmp_row); x.tmp_coef = (float*)(scratch + s.tmp_coef);
     x.nb_new = a.nrc; x.nb_rows = lp_chunks(x.C0); x.nb_edges = lp_chunks(x.E0); x.nb_lprows = lp_chunks(x.R0);
     x.flags_out = flags_dev;
-    HIPCHK(hipMemsetAsync(scratch + s.cnt, 0, s.clear_bytes, st));      // the count tables (no launch of the library's own)
+    if (!counts) HIPCHK(hipMemsetAsync(cnt, 0, s.clear_bytes, st));      // the count tables (no launch of the library's own)
     {
         ProfScope prof("k_lpa_stats", st);
-        hipLaunchKernelGGL(k_lpa_stats, dim3(a.nrc), dim3(LP_NT), 0, st, a, x);
+        GCNN_LAUNCH(k_lpa_stats, dim3(a.nrc), dim3(LP_NT), 0, st, a, x);
         LAUNCHCHK();
     }
     {
         ProfScope prof("k_lpa_scan", st);
-        hipLaunchKernelGGL(k_lpa_scan, dim3(lp_chunks(x.V + 1)), dim3(LP_NT), 0, st, x);
+        GCNN_LAUNCH(k_lpa_scan, dim3(lp_chunks(x.V + 1)), dim3(LP_NT), 0, st, x);
         LAUNCHCHK();
     }
     {
         ProfScope prof("k_lpa_move", st);
-        hipLaunchKernelGGL(k_lpa_move, dim3(x.nb_new + x.nb_rows + x.nb_edges + x.nb_lprows + 1), dim3(LP_NT), 0, st, a, x);
+        GCNN_LAUNCH(k_lpa_move, dim3(x.nb_new + x.nb_rows + x.nb_edges + x.nb_lprows + 1), dim3(LP_NT), 0, st, a, x);
         LAUNCHCHK();
     }
     if (x.V > 0 && x.dE > 0) {
         ProfScope prof("k_lpa_order", st);
-        hipLaunchKernelGGL(k_lpa_order, dim3((x.V + LP_NT / LP_SUB - 1) / (LP_NT / LP_SUB)), dim3(LP_NT), 0, st, x);
+        GCNN_LAUNCH(k_lpa_order, dim3((x.V + LP_NT / LP_SUB - 1) / (LP_NT / LP_SUB)), dim3(LP_NT), 0, st, x);
         LAUNCHCHK();
     }
     return 0;

@@ -98,6 +98,9 @@ extern "C" int gcnn_lp_round_layout_for(const gcnn_lp_dims* d, int32_t present, 
 // want_order: 1 ranking, 0 scores only, -1 the state only (no forward pass; the download carries the flags and cut_index)
 // lpr_check: everything a round call decides before anything is enqueued, and the layout.  lpr_run: what it enqueues; host_in null:
 // the upload already lies at dev_off[0] of the arena (gcnn_lpappend.hpp's fused call brings it up with the appended rows).
+// at (gcnn_lprounds.hpp's call of several sessions): the upload lies at at->up, the download block is at->out, the forward's flag
+// block is cleared where the download finds it, and nothing is copied: the caller brings everything up and down itself.
+struct LprAt { char* up; char* out; };
 static int lpr_check(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, const gcnn_lp_resident* res,
                      const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, int32_t want_order,
                      double p_max, double p_max_ub, size_t extra_out, gcnn_lp_round_layout* L) {
@@ -120,15 +123,15 @@ static int lpr_check(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, i
 
 static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t present, int32_t n_forced, const gcnn_lp_resident* res,
                    const float* params, const void* host_in, void* host_out, void* arena, int32_t want_order, double p_max,
-                   double p_max_ub, void* stream) {
+                   double p_max_ub, void* stream, const LprAt* at = nullptr) {
     int rc = 0;
     const gcnn_dims sd = lp_state_dims(d);
     const gcnn_graph& cg = res->cons_graph;
     hipStream_t st = (hipStream_t)stream;
     char* A = (char*)arena;
-    char* up = A + L.dev_off[0];
-    char* out = A + L.dev_off[6];
-    if (host_in) HIPCHK(hipMemcpyAsync(up, host_in, L.in_bytes, hipMemcpyHostToDevice, st));     // ONE upload: the round | forced rows
+    char* up = at ? at->up : A + L.dev_off[0];
+    char* out = at ? at->out : A + L.dev_off[6];
+    if (host_in && !at) HIPCHK(hipMemcpyAsync(up, host_in, L.in_bytes, hipMemcpyHostToDevice, st));     // ONE upload: the round | forced rows
     double* keep[4] = {res->col_lb, res->col_ub, res->col_primal, res->col_primal_avg};
     LprArgs x; memset(&x, 0, sizeof(x));
     const double* src[4];
@@ -156,7 +159,7 @@ static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t
     a.var_feats = (float*)(A + L.dev_off[1]); a.cut_feats = (float*)(A + L.dev_off[2]); a.cut_ei = (int*)(A + L.dev_off[3]);
     a.cut_ef = (float*)(A + L.dev_off[4]); a.cut_index = (int*)(out + L.out_off[5]); a.flags_out = (int*)(out + L.out_off[4]);
     int* cut_l_ptr = (int*)(A + L.dev_off[5]);
-    int* fwd_flags = (int*)(A + L.dev_off[8]);
+    int* fwd_flags = at ? (int*)(out + L.out_off[2]) : (int*)(A + L.dev_off[8]);
     x.row_dual = (const double*)(up + L.in_off[1]); x.row_basis = (const signed char*)(up + L.in_off[2]);
     x.row_place = res->row_place; x.row_scale = res->row_scale; x.cons_feats = res->cons_feats;
     x.R = d->n_rows; x.C = sd.n_cons; x.nrc = lp_chunks(x.R); x.first_row_block = a.n_stat_blocks;
@@ -165,12 +168,12 @@ static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t
     const LpEmitMore more = {nullptr, nullptr, cut_l_ptr};
     {
         ProfScope prof("k_lpr_stats", st);
-        hipLaunchKernelGGL(k_lpr_stats, dim3(std::max(1, a.n_stat_blocks + x.nrc)), dim3(LP_NT), 0, st, a, x);
+        GCNN_LAUNCH(k_lpr_stats, dim3(std::max(1, a.n_stat_blocks + x.nrc)), dim3(LP_NT), 0, st, a, x);
         LAUNCHCHK();
     }
     {
         ProfScope prof("k_lpr_emit", st);
-        hipLaunchKernelGGL(k_lpr_emit, dim3(a.nkc + 1), dim3(LP_NT), 0, st, a, more);
+        GCNN_LAUNCH(k_lpr_emit, dim3(a.nkc + 1), dim3(LP_NT), 0, st, a, more);
         LAUNCHCHK();
     }
     // the forward pass as the general path runs it (no graph plan): the resident constraint graph, the round's cut graph
@@ -181,8 +184,11 @@ static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t
                            gcnn_workspace_floats(&sd), (float*)out, 0, nullptr, 0.f, st, nullptr)))
         return rc;
     gcnn_infer_layout IL; memset(&IL, 0, sizeof(IL));
-    IL.dev_off[6] = L.dev_off[6]; IL.out_bytes = L.out_bytes;
+    IL.dev_off[6] = (size_t)(out - A); IL.out_bytes = L.out_bytes;
     for (int i = 0; i < 3; ++i) IL.out_off[i] = L.out_off[i];
+    if (at)
+        return infer_order(&sd, IL, A, kg, want_order >= 0 ? n_forced : -1, forced_rows(up, L.forced_off), A + L.dev_off[10], L.out_off[3],
+                           want_order > 0, p_max, p_max_ub, st);
     return infer_tail(&sd, IL, A, kg, fwd_flags, want_order >= 0 ? n_forced : -1, forced_rows(up, L.forced_off), A + L.dev_off[10],
                       L.out_off[3], want_order > 0, p_max, p_max_ub, host_out, st);     // ONE download
 }

@@ -15,11 +15,11 @@ static int launch_select(SelArgs& a, hipStream_t st) {
     const int n_rows = a.total_cuts + a.total_forced;
     if (n_rows > 0 && a.total_cuts > 0) {
         ProfScope prof("k_sel_pairs", st);
-        hipLaunchKernelGGL(k_sel_pairs, dim3(std::min(n_rows, 65535)), dim3(SEL_NT), 0, st, a);
+        GCNN_LAUNCH(k_sel_pairs, dim3(std::min(n_rows, 65535)), dim3(SEL_NT), 0, st, a);
         LAUNCHCHK();
     }
     ProfScope prof("k_sel_filter", st);
-    hipLaunchKernelGGL(k_sel_filter, dim3(a.n_samples), dim3(SEL_NT), 0, st, a);
+    GCNN_LAUNCH(k_sel_filter, dim3(a.n_samples), dim3(SEL_NT), 0, st, a);
     LAUNCHCHK();
     return 0;
 }
@@ -98,16 +98,22 @@ static int call_check(const float* params, const void* host_in, const void* host
 // selection (forced: the uploaded rows on the device, wherever the caller's upload put them; ws: its workspace; n_kept lands at
 // n_kept_off of the output block), else the ranking on request; then the flags go behind the outputs and ONE download brings
 // L.out_bytes home: scores | order | flags | whatever the caller's layout keeps behind them.
+// infer_order: its launches alone (the selection, or the ranking on request); infer_tail: those, the flags and the download.
+static int infer_order(const gcnn_dims* d, const gcnn_infer_layout& L, char* A, const gcnn_graph& kg, int32_t n_forced, SelRows forced,
+                       void* ws, size_t n_kept_off, int32_t want_order, double p_max, double p_max_ub, hipStream_t st) {
+    char* out = A + L.dev_off[6];
+    if (n_forced >= 0) {
+        SelArgs a = sel_args((const float*)out, SelRows{kg.l_ptr, kg.l_oth, kg.l_coef, nullptr}, forced, 1, d->n_cuts, n_forced,
+                             d->n_cuts, d->n_vars, p_max, p_max_ub, ws, (int*)(out + L.out_off[1]), (int*)(out + n_kept_off));
+        return launch_select(a, st);
+    }
+    return want_order ? infer_rank(d, A, L, st) : 0;
+}
 static int infer_tail(const gcnn_dims* d, const gcnn_infer_layout& L, char* A, const gcnn_graph& kg, const int* flags,
                       int32_t n_forced, SelRows forced, void* ws, size_t n_kept_off, int32_t want_order, double p_max, double p_max_ub,
                       void* host_out, hipStream_t st) {
     char* out = A + L.dev_off[6];
-    int rc = 0;
-    if (n_forced >= 0) {
-        SelArgs a = sel_args((const float*)out, SelRows{kg.l_ptr, kg.l_oth, kg.l_coef, nullptr}, forced, 1, d->n_cuts, n_forced,
-                             d->n_cuts, d->n_vars, p_max, p_max_ub, ws, (int*)(out + L.out_off[1]), (int*)(out + n_kept_off));
-        rc = launch_select(a, st);
-    } else if (want_order) rc = infer_rank(d, A, L, st);
+    const int rc = infer_order(d, L, A, kg, n_forced, forced, ws, n_kept_off, want_order, p_max, p_max_ub, st);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out + L.out_off[2], flags, 16, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(host_out, out, L.out_bytes, hipMemcpyDeviceToHost, st));

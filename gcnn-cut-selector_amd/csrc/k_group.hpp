@@ -20,6 +20,7 @@ static_assert(GCNN_GROUP_MAX == 8, "include/gcnn_hip.h");
 struct GroupHead { int n, stride; int blk0[GCNN_GROUP_MAX + 1]; int pad[5]; };
 static_assert(sizeof(GroupHead) == 64, "argument records start 64-B aligned");
 template <class A, class B> struct GPair { A a; B b; };
+template <class A, class B, class D> struct GTriple { A a; B b; D c; };
 
 // the member this block serves, its block index and block count within the member's share of the launch.  The table is read
 // through the constant address space: the block-uniform loads then go to scalar registers as kernel arguments do (through a
@@ -155,6 +156,12 @@ static void group_record(GroupRecorder* r, void (*k)(P...), dim3 grid, dim3 bloc
         using P2 = typename std::tuple_element<1, std::tuple<P...>>::type;
         const std::tuple<A&...> t(args...);
         ok = group_put(q, GPair<P1, P2>{P1(std::get<0>(t)), P2(std::get<1>(t))});
+    } else if constexpr (sizeof...(P) == 3) {
+        using P1 = typename std::tuple_element<0, std::tuple<P...>>::type;
+        using P2 = typename std::tuple_element<1, std::tuple<P...>>::type;
+        using P3 = typename std::tuple_element<2, std::tuple<P...>>::type;
+        const std::tuple<A&...> t(args...);
+        ok = group_put(q, GTriple<P1, P2, P3>{P1(std::get<0>(t)), P2(std::get<1>(t)), P3(std::get<2>(t))});
     } else ok = false;
     if (!ok) r->bad = true;
 }

@@ -51,8 +51,10 @@ struct LpaArgs {
 
 __device__ __forceinline__ int lpa_clamp(int x, int n) { return min(max(x, 0), n); }
 
-__global__ __launch_bounds__(LP_NT) void k_lpa_stats(LpArgs a, LpaArgs x) {
-    const int t = threadIdx.x, blk = blockIdx.x;
+// Each launch's work as a body over the block index: the solo kernels run it with blockIdx.x, a launch of several sessions' appends
+// (k_lprounds.hpp) with the member's own block index.
+__device__ __forceinline__ void lpa_stats_body(const LpArgs& a, const LpaArgs& x, const int blk) {
+    const int t = threadIdx.x;
     lp_stats_body(a, blk);
     const int g = t / LP_SUB, l = t % LP_SUB;
     for (int it = 0; it < LP_SUB; ++it) {
@@ -79,10 +81,12 @@ __global__ __launch_bounds__(LP_NT) void k_lpa_stats(LpArgs a, LpaArgs x) {
     }
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lpa_scan(LpaArgs x) {
+__global__ __launch_bounds__(LP_NT) void k_lpa_stats(LpArgs a, LpaArgs x) { lpa_stats_body(a, x, blockIdx.x); }
+
+__device__ __forceinline__ void lpa_scan_body(const LpaArgs& x, const int b) {
     __shared__ int si[4 * LP_NT];
     __shared__ int s_front;
-    const int t = threadIdx.x, b = blockIdx.x;
+    const int t = threadIdx.x;
     const int j = b * LP_NT + t;
     int n = 0;
     if (j < x.V) n = x.cnt[2 * (size_t)j] + x.cnt[2 * (size_t)j + 1];
@@ -108,6 +112,7 @@ __global__ __launch_bounds__(LP_NT) void k_lpa_scan(LpaArgs x) {
     }
     x.vsplit[j] = lo - ob;
 }
+__global__ __launch_bounds__(LP_NT) void k_lpa_scan(LpaArgs x) { lpa_scan_body(x, blockIdx.x); }
 
 // The new rows of chunk b at their final places: lp_emit_body's row half (resident form: the solve-dependent half zero) with the
 // resident counts in front, plus what gcnn_graph_build derives from it -- the by-left offsets, and the by-variable entries (staged).
@@ -194,9 +199,8 @@ __device__ __forceinline__ void lpa_emit_body(const LpArgs& a, const LpaArgs& x,
     }
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lpa_move(LpArgs a, LpaArgs x) {
+__device__ __forceinline__ void lpa_move_body(const LpArgs& a, const LpaArgs& x, int b) {
     const int t = threadIdx.x;
-    int b = blockIdx.x;
     const int C1 = x.C0 + x.dC, E1 = x.E0 + x.dE;
     if (b < x.nb_new) { lpa_emit_body(a, x, b); return; }
     b -= x.nb_new;
@@ -260,10 +264,11 @@ __global__ __launch_bounds__(LP_NT) void k_lpa_move(LpArgs a, LpaArgs x) {
     }
     if (t == 0) x.dst.l_ptr[C1] = E1;
 }
+__global__ __launch_bounds__(LP_NT) void k_lpa_move(LpArgs a, LpaArgs x) { lpa_move_body(a, x, blockIdx.x); }
 
-__global__ __launch_bounds__(LP_NT) void k_lpa_order(LpaArgs x) {
+__device__ __forceinline__ void lpa_order_body(const LpaArgs& x, const int blk) {
     const int t = threadIdx.x;
-    const int v = blockIdx.x * (LP_NT / LP_SUB) + t / LP_SUB, l = t % LP_SUB;
+    const int v = blk * (LP_NT / LP_SUB) + t / LP_SUB, l = t % LP_SUB;
     if (v >= x.V) return;
     const int nl = x.cnt[2 * (size_t)v], nr = x.cnt[2 * (size_t)v + 1];
     if (nl + nr == 0) return;
@@ -283,3 +288,4 @@ __global__ __launch_bounds__(LP_NT) void k_lpa_order(LpaArgs x) {
         }
     }
 }
+__global__ __launch_bounds__(LP_NT) void k_lpa_order(LpaArgs x) { lpa_order_body(x, blockIdx.x); }

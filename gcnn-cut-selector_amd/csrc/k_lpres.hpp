@@ -27,11 +27,13 @@ struct LprArgs {
 __global__ __launch_bounds__(LP_NT) void k_lpr_rows_stats(LpArgs a) { lp_stats_body(a, blockIdx.x); }
 __global__ __launch_bounds__(LP_NT) void k_lpr_rows_emit(LpArgs a, LpEmitMore more) { lp_emit_body(a, blockIdx.x, more); }
 
-__global__ __launch_bounds__(LP_NT) void k_lpr_stats(LpArgs a, LprArgs x) {
-    const int t = threadIdx.x, blk = blockIdx.x;
+// one block's share (block `blk` of `nblk`): the solo launch runs it with (blockIdx.x, gridDim.x), a launch of several sessions'
+// rounds (k_lprounds.hpp) with the member's solo pair, so that the clearing loops stride as the solo grid does
+__device__ __forceinline__ void lpr_stats_body(const LpArgs& a, const LprArgs& x, const int blk, const int nblk) {
+    const int t = threadIdx.x;
 #pragma unroll
     for (int q = 0; q < 3; ++q)
-        for (int i = blk * LP_NT + t; i < x.clear_words[q]; i += gridDim.x * LP_NT) x.clear[q][i] = 0;
+        for (int i = blk * LP_NT + t; i < x.clear_words[q]; i += nblk * LP_NT) x.clear[q][i] = 0;
     if (blk < x.first_row_block) {
         if (blk < a.ncc) {
             const int j = blk * LP_NT + t;
@@ -50,5 +52,6 @@ __global__ __launch_bounds__(LP_NT) void k_lpr_stats(LpArgs a, LprArgs x) {
     if (lp_in(pl, x.C)) { float* f = x.cons_feats + 4 * (size_t)pl; f[1] = bs == 0; f[3] = (float)(-dual); }
     if (lp_in(pr, x.C)) { float* f = x.cons_feats + 4 * (size_t)pr; f[1] = bs == 2; f[3] = (float)dual; }
 }
+__global__ __launch_bounds__(LP_NT) void k_lpr_stats(LpArgs a, LprArgs x) { lpr_stats_body(a, x, blockIdx.x, gridDim.x); }
 
 __global__ __launch_bounds__(LP_NT) void k_lpr_emit(LpArgs a, LpEmitMore more) { lp_emit_body(a, blockIdx.x, more); }

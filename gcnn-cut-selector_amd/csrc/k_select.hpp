@@ -44,13 +44,15 @@ __device__ __forceinline__ int wave_max_i(int x) {
     return x;
 }
 
-__global__ __launch_bounds__(SEL_NT) void k_sel_pairs(SelArgs a) {
+// block `bid` of `nblk`: the solo launch runs it with (blockIdx.x, gridDim.x), a launch of several sessions' selections
+// (k_lprounds.hpp) with the member's solo pair
+__device__ __forceinline__ void sel_pairs_body(const SelArgs& a, const int bid, const int nblk) {
     __shared__ double x[SEL_CH];
     __shared__ int red[2][SEL_NW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int k = threadIdx.x; k < SEL_CH; k += SEL_NT) x[k] = 0.0;   // kept zero between pivots: each pivot clears what it set
     const int n_rows = a.total_cuts + a.total_forced;
-    for (int g = blockIdx.x; g < n_rows; g += gridDim.x) {
+    for (int g = bid; g < n_rows; g += nblk) {
         int s = 0, hi_s = a.n_samples;   // the sample: largest s with c_off[s] + f_off[s] <= g
         while (hi_s - s > 1) {
             const int mid = (s + hi_s) >> 1;
@@ -137,6 +139,7 @@ __global__ __launch_bounds__(SEL_NT) void k_sel_pairs(SelArgs a) {
         __syncthreads();   // red[] is rewritten by the next pivot
     }
 }
+__global__ __launch_bounds__(SEL_NT) void k_sel_pairs(SelArgs a) { sel_pairs_body(a, blockIdx.x, gridDim.x); }
 
 // Stable partition of positions [0, K): those of [0, n) for which flag(p) holds move behind everything else, in position order.
 // Returns how many moved.  All threads of the block call it; thread t owns the positions [t*S, t*S+S).

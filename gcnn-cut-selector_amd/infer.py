@@ -1,7 +1,8 @@
 """Host arrays in, one C call, host arrays out: the host side of gcnn_infer, gcnn_infer_select, gcnn_infer_batch, the LP-snapshot
 calls, gcnn_lp_batch, gcnn_infer_models and gcnn_lp_models (include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
 of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers.  `LPSession`
-(`GCNN.open_lp`) is the host side of gcnn_lp_rows_build and gcnn_lp_round: an LP that stays on the device across separation rounds."""
+(`GCNN.open_lp`) is the host side of gcnn_lp_rows_build and gcnn_lp_round: an LP that stays on the device across separation rounds;
+`LPSessionGroup` is the host side of gcnn_lp_rounds: the rounds of several such sessions in one call."""
 
 from __future__ import annotations
 
@@ -268,9 +269,10 @@ class _Staging:
             return "bad_index"
         return "declined" if flags[1] or flags[2] or flags[3] else None
 
-    def _read(self, scores_off, order_off, n_kept_off, n):
-        """(scores, order | None, n_kept | None) of a state's `n` cuts, read at the given byte offsets (None: not asked for)."""
-        out = self.out_np
+    def _read(self, scores_off, order_off, n_kept_off, n, out=None):
+        """(scores, order | None, n_kept | None) of a state's `n` cuts, read at the given byte offsets (None: not asked for) of the
+        download `out` (default: the session's own)."""
+        out = self.out_np if out is None else out
         scores = out[scores_off:scores_off + 4 * n].view(np.float32).copy().view(ScoreArray)
         order = None if order_off is None else out[order_off:order_off + 4 * n].view(np.int32).copy()
         n_kept = None if n_kept_off is None else int(out[n_kept_off:n_kept_off + 4].view(np.int32)[0])
@@ -1065,58 +1067,99 @@ class LPSession(_Staging):
             return None
         return arrays, counts, self._after(counts), self._host_counts(arrays)
 
+    # A round's call in three parts, which the solo path (`_run`) and `LPSessionGroup` share: `_plan` (the host half: check,
+    # layout, the raw buffers' room and the other set of an append), `_pack` into a given staging buffer, then either `_enqueue`
+    # (the solo C call) or the group's call, and `_finish` (the verdict half: the download's flags -> raise / adopt / remember).
+    def _plan(self, rnd, forced=None, append=None):
+        """check -> layout; with `append` also the room in the raw buffers and the set of derived buffers the append writes.
+        Returns the job the other parts read; nothing of the session changes that a rejected round would have to undo."""
+        job = SimpleNamespace(forced=forced, fshape=(-1, 0) if forced is None else (forced[0].size - 1, forced[1].size))
+        job.blk = blk = self._check_block(append) if append is not None else None
+        if blk is None:
+            job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off) = self._checked(rnd, *job.fshape)
+            job.d, job.b, job.set, job.block = _lib.LpDims(**job.dims), None, None, ()
+            job.flag_words = (job.out_off[4],)
+        else:
+            _, counts, row_dims, host = blk
+            job.block = self._block_dims(counts, host)           # the block's eight counts
+            job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off, job.d, job.b) = self._checked(
+                rnd, *job.fshape, row_dims=row_dims, block=job.block)
+            with torch.cuda.device(self.model.device):
+                self._grow_raw(row_dims["n_rows"], row_dims["row_nnz"])
+                job.set = self._other_set(row_dims, host[2])
+            job.flag_words = (int(job.L.flags_off), job.out_off[4])
+        return job
+
+    @staticmethod
+    def _pack(job, buf):
+        """The job's one upload into `buf` (a staging buffer, or a member's slice of a group's): the block, the round, the forced rows."""
+        from . import lpstate
+        if job.blk is None:
+            lpstate.pack_round(buf, job.in_off, job.arrays, job.present)
+        else:
+            lpstate.pack_append(buf, job.L, job.blk[0], job.arrays, job.present)
+        if job.forced is not None:
+            for off, a in zip(job.forced_off, job.forced):
+                buf[off:off + a.nbytes] = a.view(np.uint8)
+
+    def _enqueue(self, job, want_order, p_max, p_max_ub, timings, t0):
+        """The solo call of a packed job and the wait for its download."""
+        P, extra = C.c_void_p, dict(upload_bytes=int(job.L.in_bytes))
+        if job.blk is not None:
+            _, _, dst_struct, res = job.set
+            head = (C.byref(job.d), C.byref(job.b), job.present) + job.fshape + tuple(P(t.data_ptr()) for t in self._raw) + (
+                C.byref(self._cur_struct), C.byref(dst_struct), C.byref(res))
+            self._enqueue_wait("gcnn_lp_round_append", head, (int(want_order), float(p_max), float(p_max_ub)), timings, t0, **extra)
+        elif job.forced is None:
+            self._enqueue_wait("gcnn_lp_round", (C.byref(job.d), job.present, C.byref(self._res)), (int(want_order),), timings, t0, **extra)
+        else:
+            self._enqueue_wait("gcnn_lp_round_select", (C.byref(job.d), job.present) + job.fshape + (C.byref(self._res),),
+                               (float(p_max), float(p_max_ub)), timings, t0, **extra)
+
+    def _finish(self, job, out):
+        """The verdict on a job's download block `out`: ValueError for a round or block the device flags (the session keeps the
+        rows it held; the optional arrays the round gave count as stale), else the rows are adopted and the round's optional
+        arrays remembered."""
+        from . import lpstate
+        given = {name: job.arrays[5 + q] for q, name in enumerate(lpstate.OPTIONAL) if job.present >> q & 1}
+        try:
+            for at in job.flag_words:
+                lpstate.raise_for_flags(out[at:at + 16].view(np.int32))
+        except ValueError:
+            self._stale.update(given)       # their device copies hold the rejected round's values
+            raise
+        if job.blk is not None:
+            i, dst, dst_struct, res = job.set
+            self._adopt_set(i, dst, dst_struct, job.blk[2], job.blk[3], res)
+        self._kept.update(given)
+        self._stale.difference_update(given)
+
+    def _member(self, job):
+        """The job as a member of gcnn_lp_rounds (the structs it points at live in the job and the session)."""
+        m = _lib.LpRoundsMember()
+        m.dims, m.present, (m.n_forced, m.n_forced_entries) = job.d, job.present, job.fshape
+        if job.blk is None:
+            m.resident = C.pointer(self._res)
+        else:
+            _, _, dst_struct, res = job.set
+            m.has_append, m.block = 1, job.b
+            m.row_ptr, m.row_col, m.row_val, m.row_lhs, m.row_rhs = (t.data_ptr() for t in self._raw)
+            m.src, m.dst, m.resident = C.pointer(self._cur_struct), C.pointer(dst_struct), C.pointer(res)
+        m.params = self.model._flat.data_ptr()
+        return m
+
     def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0, append=None):
         """check -> layout -> pack -> one call -> the download's LP flags checked.  Returns (the round's dims, the download's
         offsets, the arena's offsets); what the round gave of the optional column arrays is remembered once it is accepted.
         With `append` the call is gcnn_lp_round_append: the block goes up with the round, the append's launches run in front of
         the round's, and the session adopts the rows once the download shows that the device accepted the block and the round."""
-        from . import lpstate
         t0 = time.perf_counter()
-        fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
-        blk = self._check_block(append) if append is not None else None
-        if blk is None:
-            arrays, present, dims, (L, in_off, forced_off, out_off, dev_off) = self._checked(rnd, *fshape)
-            d = _lib.LpDims(**dims)
-            self._buffers(L)
-            lpstate.pack_round(self.in_np, in_off, arrays, present)
-            head = (C.byref(d), present)
-            if forced is None:
-                self._enqueue_wait("gcnn_lp_round", head + (C.byref(self._res),), (int(want_order),), timings, t0, upload_bytes=int(L.in_bytes))
-            else:
-                self._put_forced(forced_off, forced)
-                self._enqueue_wait("gcnn_lp_round_select", head + fshape + (C.byref(self._res),), (float(p_max), float(p_max_ub)), timings,
-                                   t0, upload_bytes=int(L.in_bytes))
-            flag_words = (out_off[4],)
-        else:
-            block_arrays, counts, row_dims, host = blk
-            arrays, present, dims, (L, in_off, forced_off, out_off, dev_off, d, b) = self._checked(
-                rnd, *fshape, row_dims=row_dims, block=self._block_dims(counts, host))
-            self._buffers(L)
-            lpstate.pack_append(self.in_np, L, block_arrays, arrays, present)
-            if forced is not None:
-                self._put_forced(forced_off, forced)
-            P = C.c_void_p
-            with torch.cuda.device(self.model.device):
-                self._grow_raw(row_dims["n_rows"], row_dims["row_nnz"])
-                i, dst, dst_struct, res = self._other_set(row_dims, host[2])
-            head = (C.byref(d), C.byref(b), present) + fshape + tuple(P(t.data_ptr()) for t in self._raw) + (
-                C.byref(self._cur_struct), C.byref(dst_struct), C.byref(res))
-            self._enqueue_wait("gcnn_lp_round_append", head, (int(want_order), float(p_max), float(p_max_ub)), timings, t0,
-                               upload_bytes=int(L.in_bytes))
-            flag_words = (int(L.flags_off), out_off[4])
-        given = {name: arrays[5 + q] for q, name in enumerate(lpstate.OPTIONAL) if present >> q & 1}
-        out = self.out_np
-        try:
-            for at in flag_words:
-                lpstate.raise_for_flags(out[at:at + 16].view(np.int32))
-        except ValueError:
-            self._stale.update(given)       # their device copies hold the rejected round's values
-            raise
-        if blk is not None:
-            self._adopt_set(i, dst, dst_struct, row_dims, host, res)
-        self._kept.update(given)
-        self._stale.difference_update(given)
-        return dims, out_off, dev_off
+        job = self._plan(rnd, forced, append)
+        self._buffers(job.L)
+        self._pack(job, self.in_np)
+        self._enqueue(job, want_order, p_max, p_max_ub, timings, t0)
+        self._finish(job, self.out_np)
+        return job.dims, job.out_off, job.dev_off
 
     def state(self, rnd, append=None):
         """The model's 10-tuple as host arrays and `cut_index`, as `GCNN.state_from_lp` gives them for the assembled snapshot
@@ -1134,10 +1177,12 @@ class LPSession(_Staging):
                   host(A, dev[2], (k, 6), f32), host(A, dev[3], (2, e2), i32), host(A, dev[4], (e2, 1), f32))
         return arrays + (c, v, k), self.out_np[out_off[5]:out_off[5] + 4 * k].view(np.int32).copy()
 
-    def _results(self, dims, out_off, want_order, select):
+    def _results(self, dims, out_off, want_order, select, out=None):
+        """(scores, order, n_kept, cut_index) of a round in the download block `out` (default: the session's own)."""
         n = dims["n_cuts"]
-        scores, order, n_kept = self._read(out_off[0], out_off[1] if want_order else None, out_off[3] if select else None, n)
-        return scores, order, n_kept, self.out_np[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
+        out = self.out_np if out is None else out
+        scores, order, n_kept = self._read(out_off[0], out_off[1] if want_order else None, out_off[3] if select else None, n, out)
+        return scores, order, n_kept, out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
 
     def score(self, rnd, rank=False, timings=None, append=None):
         """`GCNN.score_lp` for the assembled snapshot: a `ScoreArray` in STATE order with `.cut_index` and, with `rank`,
@@ -1171,6 +1216,216 @@ class LPSession(_Staging):
         self._col_type = self._col_obj = self._opt = None
         self._buffers_made = []
         self._kept, self._stale = {}, set()
+
+
+class LPSessionGroup:
+    """The rounds of several `LPSession`s in one call (gcnn_lp_rounds): what a scoring server does with the rounds of different
+    solver workers that wait at the same time.  One upload of all rounds and appended blocks, every stage of the members' work as
+    one launch per distinct kernel, one download; up to 8 sessions per call, more are served in several calls.  The sessions may
+    belong to different models on the group's device; a session may appear once per call.  Entry i of a result is what
+    `sessions[i].score(...)` / `.select_cuts(...)` gives with the same arguments, bit for bit, and the session is afterwards in
+    the state that solo call leaves.  Errors are per member: a round the host rejects stays out of the call, one the device
+    flags raises in its own slot (the session stays usable, as after a rejected solo round), and a member the batched call
+    declines (a ranking left to the host, a shape the recorder cannot take) goes through its solo call and comes back in place:
+    a call the library declines or refuses as a whole is halved until the member it is about stands alone, so the others still
+    share their calls, and `solo_rounds` counts every member that was answered by its own call.
+    The group owns the call's arena and pinned buffers; they grow as a session's do, and `LPSession.GUARD` applies to the arena."""
+    MAX = _lib.LP_ROUNDS_MAX
+    CAP = 256
+    GUARD = None                      # bytes of guard around the arena; None: `LPSession.GUARD`
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.pin_in = self.pin_out = self.pin_tab = self.arena = self._whole = None
+        self.in_np = self.out_np = self.tab_np = None
+        self.layouts = {}
+        self.calls = 0                    # gcnn_lp_rounds calls made
+        self.max_sessions_per_call = 0    # the most sessions one of them served
+        self.solo_rounds = 0              # members answered by their session's own call: left to it, or declined by the batched call
+
+    def guards_intact(self):
+        """True when no guard byte around the group's arena has changed (`LPSession.GUARD` set when it was allocated)."""
+        g, w = self._guard(), self._whole
+        if not g or w is None:
+            return True
+        return bool((w[:g] == LPSession.GUARD_BYTE).all()) and bool((w[w.numel() - g:] == LPSession.GUARD_BYTE).all())
+
+    def _guard(self):
+        return LPSession.GUARD if self.GUARD is None else self.GUARD
+
+    def _buffers(self, L):
+        pin = _Staging._pin
+        self.pin_in, self.in_np = pin(self.pin_in, self.in_np, L.in_bytes, 1 << 20)
+        self.pin_out, self.out_np = pin(self.pin_out, self.out_np, L.out_bytes, 1 << 16)
+        self.pin_tab, self.tab_np = pin(self.pin_tab, self.tab_np, L.table_bytes, 1 << 16)
+        if self.arena is None or self.arena.numel() < L.arena_bytes:
+            self.arena = self._whole = None
+            n, g = max(2 * L.arena_bytes, 1 << 22), self._guard()
+            if g:
+                self._whole = torch.full((n + 2 * g,), LPSession.GUARD_BYTE, dtype=torch.uint8, device=self.device)
+                self.arena = self._whole[g:g + n]
+            else:
+                self.arena = torch.empty(n, dtype=torch.uint8, device=self.device)
+
+    def _layout(self, members, n, mode):
+        L = _lib.LpRoundsLayout()
+        rc = _lib.lib().gcnn_lp_rounds_layout_for(n, members, mode, C.byref(L))
+        return False if _unsupported(rc, "gcnn_lp_rounds_layout_for") else (L, list(L.in_off), list(L.out_off))
+
+    def _call(self, sessions, jobs, mode, p_max, p_max_ub, timings=None):
+        """One gcnn_lp_rounds call over checked jobs: per job its download block (a view of the group's pinned buffer), or None
+        where the library declines the call as a whole (nothing was enqueued); any other refusal raises `GcnnError`, also before
+        anything is enqueued."""
+        t0 = time.perf_counter()
+        n = len(jobs)
+        members = (_lib.LpRoundsMember * n)(*(s._member(j) for s, j in zip(sessions, jobs)))
+        key = (mode,) + tuple(_int_key(j.dims) + (j.present,) + j.fshape + j.block for j in jobs)
+        lay = self.layouts.get(key)
+        if lay is None:
+            lay = self._layout(members, n, mode)
+            if len(self.layouts) >= self.CAP:
+                self.layouts.pop(next(iter(self.layouts)))
+            self.layouts[key] = lay
+        if lay is False:
+            return None
+        L, in_off, out_off = lay
+        self._buffers(L)
+        for j, off in zip(jobs, in_off):
+            LPSession._pack(j, self.in_np[off:])
+        t1 = time.perf_counter()
+        P = C.c_void_p
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = _lib.lib().gcnn_lp_rounds(n, members, mode, P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(self.arena.data_ptr()),
+                                           self.arena.numel(), P(self.pin_tab.data_ptr()), float(p_max), float(p_max_ub),
+                                           P(stream.cuda_stream))
+            if rc == -4:
+                return None
+            _lib.check(rc, "gcnn_lp_rounds")
+            t2 = time.perf_counter()
+            stream.synchronize()
+        if timings is not None:
+            timings.update(pack=t1 - t0, enqueue=t2 - t1, wait=time.perf_counter() - t2, upload_bytes=int(L.in_bytes))
+        self.calls += 1
+        self.max_sessions_per_call = max(self.max_sessions_per_call, n)
+        return [self.out_np[o:] for o in out_off[:n]]
+
+    def _serve(self, sessions, mode, plan, answer, solo, p_max=0.0, p_max_ub=0.0, timings=None):
+        """Results per session, each an answer or an exception.  `plan(i)`: the job of session i for the batched call (what it
+        raises belongs to that slot), None where the member goes to its solo call; `answer(i, job, out)`: the result read from
+        the member's download block; `solo(i)`: the session's own call."""
+        n = len(sessions)
+        if len({id(s) for s in sessions}) != n:
+            raise ValueError("LPSessionGroup: a session may appear once per call")
+        for s in sessions:
+            if torch.device(s.model.device) != self.device:
+                raise ValueError(f"LPSessionGroup: a session of a model on {s.model.device}, the group is on {self.device}")
+        results, jobs, solo_ids = [None] * n, {}, []
+        for i in range(n):
+            try:
+                job = plan(i)
+            except Exception as exc:  # noqa: BLE001 -- the error belongs to this member's slot
+                results[i] = exc
+                continue
+            if job is None:
+                solo_ids.append(i)
+            else:
+                jobs[i] = job
+        ids = list(jobs)
+        todo = [ids[lo:lo + self.MAX] for lo in range(0, len(ids), self.MAX)]
+        while todo:
+            part = todo.pop(0)
+            try:
+                outs = self._call([sessions[i] for i in part], [jobs[i] for i in part], mode, p_max, p_max_ub, timings)
+            except _lib.GcnnError:          # refused before anything was enqueued: as a declined call, the member's own call says why
+                outs = None
+            if outs is None:
+                if len(part) == 1:
+                    solo_ids.append(part[0])
+                else:                       # halves: the member the refusal is about ends up alone, the others keep their calls
+                    todo[:0] = [part[:len(part) // 2], part[len(part) // 2:]]
+                continue
+            for i, out in zip(part, outs):
+                try:
+                    sessions[i]._finish(jobs[i], out)
+                    results[i] = answer(i, jobs[i], out)
+                except Exception as exc:  # noqa: BLE001
+                    results[i] = exc
+        self.solo_rounds += len(solo_ids)
+        for i in sorted(solo_ids):
+            try:
+                results[i] = solo(i)
+            except Exception as exc:  # noqa: BLE001
+                results[i] = exc
+        return results
+
+    @staticmethod
+    def _finish_many(results, return_exceptions):
+        if not return_exceptions:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
+
+    @staticmethod
+    def _per_session(what, items, n):
+        items = [None] * n if items is None else list(items)
+        if len(items) != n:
+            raise ValueError(f"{what}: one entry per session expected, got {len(items)} for {n} sessions")
+        return items
+
+    def score(self, sessions, rounds, rank=False, appends=None, return_exceptions=False, timings=None):
+        """`sessions[i].score(rounds[i], rank, append=appends[i])` for every i, as a list of `ScoreArray`.  With
+        `return_exceptions` a member's exception sits in its slot; otherwise the first one is raised after every member has been
+        served."""
+        sessions, rounds = list(sessions), list(rounds)
+        appends = self._per_session("appends", appends, len(sessions))
+        self._per_session("rounds", rounds, len(sessions))
+
+        def on_device(i):
+            n = int(np.asarray(rounds[i].cut_lhs).shape[0])
+            return sessions[i].model._rank_on_device(rank, n) and n <= 4096
+
+        def plan(i):
+            if rank and not on_device(i):
+                return None                 # the host ranks this one: its solo call
+            return sessions[i]._plan(rounds[i], None, appends[i])
+
+        def answer(i, job, out):
+            scores, order, _, cut_index = sessions[i]._results(job.dims, job.out_off, bool(rank), False, out)
+            scores.cut_index = cut_index
+            if rank:
+                scores.rankings = order
+            return scores
+
+        results = self._serve(sessions, _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES, plan, answer,
+                              lambda i: sessions[i].score(rounds[i], rank, append=appends[i]), timings=timings)
+        return self._finish_many(results, return_exceptions)
+
+    def select_cuts(self, sessions, rounds, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, appends=None,
+                    return_exceptions=False, timings=None):
+        """`sessions[i].select_cuts(rounds[i], forced[i], p_max=..., p_max_ub=..., max_selected=..., append=appends[i])` for every
+        i, as a list of `SelectResult`; errors as in `score`."""
+        ops.check_thresholds(p_max, p_max_ub)
+        sessions, rounds = list(sessions), list(rounds)
+        n = len(sessions)
+        appends, forced = self._per_session("appends", appends, n), self._per_session("forced", forced, n)
+        self._per_session("rounds", rounds, n)
+
+        def plan(i):
+            s = sessions[i]
+            s.model._check_select_size("LPSession.select_cuts", "round", int(np.asarray(rounds[i].cut_lhs).shape[0]))
+            return s._plan(rounds[i], normalize_forced(forced[i], s.n_cols), appends[i])
+
+        def answer(i, job, out):
+            scores, order, n_kept, cut_index = sessions[i]._results(job.dims, job.out_off, True, True, out)
+            return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
+
+        def solo(i):
+            return sessions[i].select_cuts(rounds[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected, append=appends[i])
+
+        results = self._serve(sessions, _lib.IBATCH_SELECT, plan, answer, solo, p_max, p_max_ub, timings)
+        return self._finish_many(results, return_exceptions)
 
 
 def _int_key(dims):

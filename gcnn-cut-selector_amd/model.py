@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, LPSession, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPModelsSession, _LPSession, _ModelsSession,
+from .infer import (BAD_INDEX, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPModelsSession, _LPSession, _ModelsSession,
                     _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
 
@@ -779,6 +779,7 @@ class ModelSet:
         self._number = {k: i for i, k in enumerate(self.models)}
         self._session = None
         self._lp_session = None
+        self._lp_rounds = None            # the LPSessionGroup of `score_rounds` / `select_cuts_rounds`, built on first use
         self.calls = 0                    # gcnn_infer_models and gcnn_lp_models calls made
         self.max_models_per_call = 0      # the most models one of them served
 
@@ -888,3 +889,33 @@ class ModelSet:
 
         results = self._many(keys, snapshots, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub, lp=True)
         return GCNN._finish_many(_as_selections(results, max_selected, cut_index=True), return_exceptions)
+
+    # ---- rounds of resident LPs of several models in one call (gcnn_lp_rounds) ---------------------------------------------------
+    def _rounds(self, keys, sessions):
+        """The set's `LPSessionGroup`, once `keys` (taken for symmetry with the other methods: a session knows its model) name the
+        sessions' models."""
+        keys, sessions = list(keys), list(sessions)
+        if len(keys) != len(sessions):
+            raise ValueError(f"keys: one model key per session expected, got {len(keys)} for {len(sessions)} sessions")
+        for k, s in zip(keys, sessions):
+            if k not in self.models:
+                raise KeyError(f"no model {k!r}")
+            if s.model is not self.models[k]:
+                raise ValueError(f"the session was not opened on model {k!r}")
+        if self._lp_rounds is None:
+            self._lp_rounds = LPSessionGroup(next(iter(self.models.values())).device)
+        return self._lp_rounds, sessions
+
+    def score_rounds(self, keys, sessions, rounds, rank=False, appends=None, return_exceptions=False):
+        """`LPSessionGroup.score` over sessions opened on this set's models (`models[keys[i]].open_lp(...)`): the rounds of up to 8
+        sessions per call, whatever their models; entry i has the bits of `sessions[i].score(rounds[i], rank, append=appends[i])`."""
+        group, sessions = self._rounds(keys, sessions)
+        return group.score(sessions, rounds, rank, appends, return_exceptions)
+
+    def select_cuts_rounds(self, keys, sessions, rounds, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, appends=None,
+                           return_exceptions=False):
+        """`LPSessionGroup.select_cuts` over sessions opened on this set's models; entry i has the bits of
+        `sessions[i].select_cuts(rounds[i], forced[i], ..., append=appends[i])`."""
+        group, sessions = self._rounds(keys, sessions)
+        return group.select_cuts(sessions, rounds, forced, p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected, appends=appends,
+                                 return_exceptions=return_exceptions)

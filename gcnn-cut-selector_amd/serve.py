@@ -45,6 +45,19 @@ _LP_BASE = {KIND_LP_SCORE: KIND_SCORE, KIND_LP_RANK: KIND_RANK, KIND_LP_SELECT: 
 # cut_index (the identity) and the features [K, 3].
 KIND_HYBRID_SELECT = 6
 _HYBRID_ARRAYS = len(lpstate.CUT_FIELDS) + 1
+# An LP resident on the server's device across a worker's separation rounds (`ScoringClient.open_lp` -> `RemoteLPSession`; the
+# server holds an `infer.LPSession` per id and serves the rounds that wait together through one `infer.LPSessionGroup` call per 8):
+#   open   the seven arrays of a `lpstate.LPRows` and one float64 array of its scalars; the n_cons slot says whether the server
+#          checks the O(nnz) facts on the host too.  The reply's n_kept slot carries the session id.
+#   round  n_cons: the session id; n_vars: mode | presence mask of the four optional arrays << 8 | has a block << 12 |
+#          has_incumbent (0 None, 1 False, 2 True) << 13 | incremental << 15.  Arrays: the round's in `lpstate.ROUND_FIELDS` order
+#          without the absent optional ones, then the five arrays of an `LPRowBlock`, then the forced pair.  Mode SESSION_APPEND
+#          carries the block alone (`append_rows`).  The reply is that of the KIND_LP_* kinds, cut_index included.
+#   close  n_cons: the session id.
+KIND_LP_OPEN, KIND_LP_ROUND, KIND_LP_CLOSE = 7, 8, 9
+SESSION_SCORE, SESSION_RANK, SESSION_SELECT, SESSION_APPEND = 0, 1, 2, 3
+_SESSION_KINDS = (KIND_LP_OPEN, KIND_LP_ROUND, KIND_LP_CLOSE)
+_ROUND_BASE = len(lpstate.ROUND_FIELDS) - len(lpstate.OPTIONAL)
 _PRIMAL = (14, 15)         # positions of col_primal / col_primal_avg among lpstate.FIELDS
 MAX_MESSAGE = 1 << 30
 # request: magic, kind, n_arrays, key length, p_max, p_max_ub, max_selected (-1: none), n_forced (-1: no forced rows), n_cons, n_vars, n_cuts
@@ -155,6 +168,100 @@ def encode_hybrid_request(model_key, snapshot, forced=None, p_max=0.1, p_max_ub=
     return b"".join(parts)
 
 
+def _header(kind, n_arrays, key, p_max=0.0, p_max_ub=0.0, max_selected=None, n_forced=-1, a=0, b=0, c=0):
+    return _REQ.pack(MAGIC, kind, n_arrays, len(key), float(p_max), float(p_max_ub), -1 if max_selected is None else int(max_selected),
+                     n_forced, int(a), int(b), int(c))
+
+
+def encode_open_request(model_key, rows, deep=True):
+    """-> the message's bytes of an open request.  `rows`: a `lpstate.LPRows`, checked here as the server will check it again
+    (without the O(nnz) facts), so its ValueError is raised in the worker."""
+    arrays, dims = lpstate.check_rows(rows, deep=False)
+    arrays = list(arrays) + [np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64)]
+    key = model_key.encode("utf-8")
+    parts = [_header(KIND_LP_OPEN, len(arrays), key, a=bool(deep)), key]
+    _put_arrays(parts, arrays)
+    return b"".join(parts)
+
+
+def _round_word(mode, mask=0, has_block=False, has_incumbent=None, incremental=False):
+    inc = 0 if has_incumbent is None else 2 if has_incumbent else 1
+    return mode | mask << 8 | int(bool(has_block)) << 12 | inc << 13 | int(bool(incremental)) << 15
+
+
+def encode_round_request(model_key, session, mode, rnd=None, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None, append=None,
+                         incremental=False):
+    """-> the message's bytes of a round of session `session`.  `mode`: SESSION_SCORE / _RANK / _SELECT with `rnd` (a
+    `lpstate.LPRound`) and optionally `append` (a `lpstate.LPRowBlock`) and `forced`; SESSION_APPEND with `append` alone."""
+    arrays, mask, inc = [], 0, None
+    if mode != SESSION_APPEND:
+        inc = rnd.has_incumbent
+        for name, _ in lpstate.ROUND_FIELDS:
+            a = getattr(rnd, name)
+            if name in lpstate.OPTIONAL:
+                if a is None:
+                    continue
+                mask |= 1 << lpstate.OPTIONAL.index(name)
+            elif a is None:
+                raise ValueError(f"{name}: a round must give it")
+            arrays.append(np.asarray(a))
+    elif append is None:
+        raise ValueError("an append needs its block")
+    if append is not None:
+        arrays += [np.asarray(a) for a in append.arrays()]
+    n_forced, pair = _forced_pair(forced) if mode == SESSION_SELECT else (-1, [])
+    key = model_key.encode("utf-8")
+    parts = [_header(KIND_LP_ROUND, len(arrays) + len(pair), key, p_max, p_max_ub, max_selected, n_forced, session,
+                     _round_word(mode, mask, append is not None, inc, incremental)), key]
+    _put_arrays(parts, arrays + pair)
+    return b"".join(parts)
+
+
+def encode_close_request(model_key, session):
+    key = model_key.encode("utf-8")
+    return _header(KIND_LP_CLOSE, 0, key, a=session) + key
+
+
+def _decode_session(kind, arrays, n_forced, n_cons, n_vars):
+    """The kind-specific part of a decoded session request."""
+    if kind == KIND_LP_OPEN:
+        scalars = arrays[7]
+        if scalars.dtype != np.float64 or scalars.shape != (4,) or not np.isfinite(scalars[2]):
+            raise ProtocolError("malformed row scalars")
+        rows = lpstate.LPRows(*arrays[:7], infinity=float(scalars[0]), sum_epsilon=float(scalars[1]), n_model_vars=int(scalars[2]),
+                              obj_norm=float(scalars[3]))
+        return dict(rows=rows, deep=bool(n_cons))
+    if kind == KIND_LP_CLOSE:
+        return dict(session=n_cons)
+    mode, mask, has_block, inc = n_vars & 255, n_vars >> 8 & 15, n_vars >> 12 & 1, n_vars >> 13 & 3
+    rnd, at = None, 0
+    if mode != SESSION_APPEND:
+        fields = {}
+        for name, _ in lpstate.ROUND_FIELDS:
+            if name in lpstate.OPTIONAL and not mask >> lpstate.OPTIONAL.index(name) & 1:
+                continue
+            fields[name] = arrays[at]
+            at += 1
+        rnd = lpstate.LPRound(**fields, has_incumbent=None if inc == 0 else inc == 2)
+    block = lpstate.LPRowBlock(*arrays[at:at + 5]) if has_block else None
+    return dict(session=n_cons, mode=mode, round=rnd, block=block, incremental=bool(n_vars >> 15 & 1),
+                forced=(arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
+
+
+def _session_arrays(kind, n_forced, n_vars):
+    """How many arrays a well-formed session request of this header carries; -1 for a header that is not one."""
+    if kind == KIND_LP_OPEN:
+        return 8
+    if kind == KIND_LP_CLOSE:
+        return 0
+    mode, mask, has_block, inc = n_vars & 255, n_vars >> 8 & 15, n_vars >> 12 & 1, n_vars >> 13 & 3
+    if n_vars < 0 or n_vars >> 16 or mode > SESSION_APPEND or inc == 3 or (n_forced >= 0 and mode != SESSION_SELECT):
+        return -1
+    if mode == SESSION_APPEND:
+        return 5 if has_block and not mask else -1
+    return _ROUND_BASE + bin(mask).count("1") + 5 * has_block + (2 if n_forced >= 0 else 0)
+
+
 def _decode_hybrid(arrays, n_forced):
     scalars = arrays[_HYBRID_ARRAYS - 1]
     if scalars.dtype != np.float64 or scalars.shape != (1,):
@@ -180,8 +287,12 @@ def decode_request(buf):
     magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, n_cons, n_vars, n_cuts = _REQ.unpack_from(buf, 0)
     lp = kind in _LP_BASE
     hybrid = kind == KIND_HYBRID_SELECT
-    expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0)
-    if magic != MAGIC or kind > KIND_HYBRID_SELECT or n_arrays != expected or (lp and n_cons not in (0, 1)):
+    session = kind in _SESSION_KINDS
+    if session:
+        expected = _session_arrays(kind, n_forced, n_vars)
+    else:
+        expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0)
+    if magic != MAGIC or kind > KIND_LP_CLOSE or n_arrays != expected or (lp and n_cons not in (0, 1)):
         raise ProtocolError("not a request of this protocol")
     at = _REQ.size + key_len
     if at > len(buf):
@@ -190,6 +301,9 @@ def decode_request(buf):
     arrays, at = _get_arrays(buf, at, n_arrays)
     if at != len(buf):
         raise ProtocolError("trailing bytes")
+    if session:
+        return dict(model_key=key, kind=kind, p_max=p_max, p_max_ub=p_max_ub, max_selected=None if max_selected < 0 else max_selected,
+                    **_decode_session(kind, arrays, n_forced, n_cons, n_vars))
     if lp or hybrid:
         snap, forced = _decode_hybrid(arrays, n_forced) if hybrid else _decode_lp(arrays, n_cons, n_forced)
         return dict(model_key=key, kind=kind, snapshot=snap, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
@@ -304,6 +418,13 @@ class ScoringClient:
         res.features = arrays[3]
         return res
 
+    def open_lp(self, rows, *, deep=True):
+        """`GCNN.open_lp` behind the server: `rows` (`lpstate.LPRows`) goes over the wire once and stays on the server's device;
+        returns a `RemoteLPSession`, whose rounds send only the solve, the candidate cuts and the rows to append.  The session
+        belongs to this connection: the server closes it when the connection drops."""
+        _, sid, _ = self._call(encode_open_request(self.model_key, rows, deep))
+        return RemoteLPSession(self, sid, int(np.asarray(rows.row_lhs).shape[0]), int(np.asarray(rows.col_type).shape[0]))
+
     def get_concrete_function(self):
         """The `(state10, training) -> scores` callable `CustomCutsel(function=...)` stores (model_evaluator.py:310-314)."""
         def get_improvements(state, training=False, rank=False):
@@ -312,6 +433,58 @@ class ScoringClient:
 
     def close(self):
         self.sock.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class RemoteLPSession:
+    """An `infer.LPSession` held by a scoring server, as a worker sees it (NumPy only): `score`, `select_cuts`, `append_rows`,
+    `close`, `n_rows`, `n_cols` and use as a context manager, with `LPSession`'s signatures and results (`Scores` / `Selection`
+    with `cut_index`).  The server answers the rounds of different workers that wait at the same time with one call on the device;
+    every reply has the bits of the session's own call.  `timings` is accepted for the signature's sake and left alone."""
+
+    def __init__(self, client, session, n_rows, n_cols):
+        self.client, self.session, self._n_rows, self.n_cols, self.closed = client, session, n_rows, n_cols, False
+
+    @property
+    def n_rows(self):
+        return self._n_rows
+
+    def _round(self, mode, rnd, append, **kw):
+        if self.closed:
+            raise ServerError("the LP session is closed")
+        reply = self.client._call(encode_round_request(self.client.model_key, self.session, mode, rnd, append=append, **kw))
+        if append is not None:
+            self._n_rows += int(np.asarray(append.row_lhs).shape[0])      # (the call raised if the server did not adopt them)
+        return reply
+
+    def score(self, rnd, rank=False, timings=None, append=None):
+        arrays, _, _ = self._round(SESSION_RANK if rank else SESSION_SCORE, rnd, append)
+        scores = arrays[0].view(Scores)
+        scores.cut_index = arrays[-1]
+        if rank:
+            scores.rankings = arrays[1]
+        return scores
+
+    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None):
+        arrays, n_kept, n_selected = self._round(SESSION_SELECT, rnd, append, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
+                                                 max_selected=max_selected)
+        return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
+
+    def append_rows(self, row_ptr, row_col, row_val, row_lhs, row_rhs, incremental=False):
+        block = lpstate.LPRowBlock(row_ptr, row_col, row_val, row_lhs, row_rhs)
+        if np.asarray(row_lhs).shape[0]:
+            self._round(SESSION_APPEND, None, block, incremental=incremental)
+
+    def close(self):
+        if not self.closed:
+            self.closed = True
+            self.client._call(encode_close_request(self.client.model_key, self.session))
 
     def __enter__(self):
         return self
@@ -332,9 +505,19 @@ class ScoringServer:
     own call, which is the faster one for it (profiles/mixed_models.txt); False, or models on more than one device, groups by
     model.  `cross_model_lp`: with `cross_model`, the LP kinds share across models in the same way (`ModelSet.score_lps` /
     `select_cuts_lp_many`; profiles/lp_models.txt); False keeps them grouped by model.  `model_set`: the set to use instead of
-    `ModelSet(models)` (built on first use)."""
+    `ModelSet(models)` (built on first use).
+    Resident LPs (`ScoringClient.open_lp`): at most `max_sessions` at a time, each owned by the connection that opened it and
+    closed when that connection drops.  The rounds that wait together are grouped by mode and thresholds, across models, and each
+    group goes to `session_group` (default: an `infer.LPSessionGroup` on the first model's device, built on first use) in calls
+    of up to 8 sessions; two requests of one session are never in one call: they are served in arrival order in successive ones.
+    Opens, closes and `append_rows` are served one by one.  `stats` counts sessions_open, session_rounds (rounds served),
+    session_calls (batched calls the group made on the device: its own counter), max_sessions_per_call (the most sessions one of
+    them served) and session_solo_rounds (rounds the group answered through the session's own call: a ranking left to the host, a
+    member the batched call declined)."""
+    SESSIONS_PER_CALL = 8
 
-    def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True):
+    def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True, max_sessions=64,
+                 session_group=None):
         self.models = dict(models)
         self.address = address
         # a ModelSet needs all models on one device: models spread over several devices are served per model, as before
@@ -342,7 +525,12 @@ class ScoringServer:
         self.cross_model = bool(cross_model) and (model_set is not None or one_device)
         self.cross_model_lp = bool(cross_model_lp)
         self._model_set = model_set
-        self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0)
+        self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0, sessions_open=0,
+                          session_rounds=0, session_calls=0, session_solo_rounds=0, max_sessions_per_call=0)
+        self.max_sessions = int(max_sessions)
+        self._sessions = {}            # id -> (the connection that owns it, the LPSession)
+        self._next_session = 1
+        self._session_group = session_group
         self._listen = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
         self._listen.bind(address)
         self._listen.listen(backlog)
@@ -400,7 +588,20 @@ class ScoringServer:
         except OSError:
             self._drop(conn)
 
+    def _group(self):
+        if self._session_group is None:
+            from .infer import LPSessionGroup
+            self._session_group = LPSessionGroup(next(iter(self.models.values())).device)
+        return self._session_group
+
+    def _close_session(self, sid):
+        _, sess = self._sessions.pop(sid)
+        self.stats["sessions_open"] = len(self._sessions)
+        sess.close()
+
     def _drop(self, conn):
+        for sid in [sid for sid, (owner, _) in self._sessions.items() if owner is conn]:
+            self._close_session(sid)              # a session belongs to the connection that opened it
         if conn in self._buffers:
             del self._buffers[conn]
             try:
@@ -433,14 +634,108 @@ class ScoringServer:
             self.stats["requests"] += 1
             try:
                 req = decode_request(message)
-                if req["kind"] != KIND_HYBRID_SELECT and req["model_key"] not in self.models:
+                if req["kind"] not in (KIND_HYBRID_SELECT, KIND_LP_ROUND, KIND_LP_CLOSE) and req["model_key"] not in self.models:
                     raise KeyError(f"no model {req['model_key']!r}")
                 pending.append((conn, req))
             except Exception as exc:  # noqa: BLE001 -- a bad request gets its error; the server keeps serving
                 self.stats["errors"] += 1
                 self._reply(conn, encode_reply(error=exc))
 
+    def _fail(self, conn, exc):
+        self.stats["errors"] += 1
+        if conn in self._buffers:
+            self._reply(conn, encode_reply(error=exc))
+
+    def _owned(self, conn, req):
+        """The session a round or close request names, if `conn` owns it; else the request gets its error reply."""
+        entry = self._sessions.get(req["session"])
+        if entry is None or entry[0] is not conn:
+            self._fail(conn, KeyError(f"no LP session {req['session']} on this connection"))
+            return None
+        return entry[1]
+
+    def _serve_sessions(self, items):
+        """The session requests that are waiting, in waves: wave k holds every session's k-th request, so that a session's requests
+        are served in arrival order and never two in one call.  Within a wave opens, closes and appends are served one by one, the
+        rounds grouped by mode and thresholds and handed to the group in calls of up to SESSIONS_PER_CALL sessions."""
+        waves, seen = [], {}
+        for conn, req in items:
+            k = 0
+            if req["kind"] != KIND_LP_OPEN:
+                k = seen.get(req["session"], 0)
+                seen[req["session"]] = k + 1
+            while len(waves) <= k:
+                waves.append([])
+            waves[k].append((conn, req))
+        for wave in waves:
+            groups = {}
+            for conn, req in wave:
+                if conn not in self._buffers:
+                    continue
+                try:
+                    if req["kind"] == KIND_LP_OPEN:
+                        if len(self._sessions) >= self.max_sessions:
+                            raise RuntimeError(f"the server holds {len(self._sessions)} LP sessions already (max_sessions)")
+                        sess = self.models[req["model_key"]].open_lp(req["rows"], deep=req["deep"])
+                        sid, self._next_session = self._next_session, self._next_session + 1
+                        self._sessions[sid] = (conn, sess)
+                        self.stats["sessions_open"] = len(self._sessions)
+                        self._reply(conn, encode_reply(n_kept=sid))
+                        continue
+                    sess = self._owned(conn, req)
+                    if sess is None:
+                        continue
+                    if req["kind"] == KIND_LP_CLOSE:
+                        self._close_session(req["session"])
+                        self._reply(conn, encode_reply())
+                    elif req["mode"] == SESSION_APPEND:
+                        sess.append_rows(*req["block"].arrays(), incremental=req["incremental"])
+                        self._reply(conn, encode_reply())
+                    else:
+                        gkey = (req["mode"],) + ((req["p_max"], req["p_max_ub"]) if req["mode"] == SESSION_SELECT else ())
+                        groups.setdefault(gkey, []).append((conn, req, sess))
+                except Exception as exc:  # noqa: BLE001 -- the request gets its error; the server keeps serving
+                    self._fail(conn, exc)
+            for gkey, members in groups.items():
+                for lo in range(0, len(members), self.SESSIONS_PER_CALL):
+                    self._serve_rounds(gkey, members[lo:lo + self.SESSIONS_PER_CALL])
+
+    def _serve_rounds(self, gkey, members):
+        mode = gkey[0]
+        sessions, rounds = [m[2] for m in members], [m[1]["round"] for m in members]
+        appends = [m[1]["block"] for m in members]
+        self.stats["session_rounds"] += len(members)
+        group = self._group()
+        before = (group.calls, group.solo_rounds)
+        try:
+            if mode == SESSION_SELECT:
+                results = group.select_cuts(sessions, rounds, [m[1]["forced"] for m in members], p_max=gkey[1], p_max_ub=gkey[2],
+                                                    appends=appends, return_exceptions=True)
+            else:
+                results = group.score(sessions, rounds, rank=mode == SESSION_RANK, appends=appends, return_exceptions=True)
+        except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
+            results = [exc] * len(members)
+        # the group's own counters: a hand-off whose members the host rejects, or that goes to solo calls, makes no batched call
+        self.stats["session_calls"] += group.calls - before[0]
+        self.stats["session_solo_rounds"] += group.solo_rounds - before[1]
+        self.stats["max_sessions_per_call"] = max(self.stats["max_sessions_per_call"], group.max_sessions_per_call)
+        for (conn, req, _), res in zip(members, results):
+            if conn not in self._buffers:
+                continue
+            if isinstance(res, Exception):
+                self._fail(conn, res)
+            elif mode == SESSION_SELECT:
+                arrays = [np.asarray(res.scores), np.asarray(res.order, np.int32), np.asarray(res.cut_index, np.int32)]
+                self._reply(conn, encode_reply(arrays, res.n_kept, _n_selected(res.n_kept, req["max_selected"])))
+            else:
+                arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if mode == SESSION_RANK else [])
+                self._reply(conn, encode_reply(arrays + [np.asarray(res.cut_index, np.int32)]))
+
     def _serve(self, pending):
+        session_items = [(conn, req) for conn, req in pending if req["kind"] in _SESSION_KINDS]
+        if session_items:
+            pending = [(conn, req) for conn, req in pending if req["kind"] not in _SESSION_KINDS]
+            self._serve_sessions(session_items)
         groups = {}
         for conn, req in pending:
             selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT, KIND_HYBRID_SELECT)

@@ -815,6 +815,56 @@ int gcnn_lp_round_append(const gcnn_lp_dims* dims, const gcnn_lp_append_dims* bl
                          const gcnn_lp_resident* resident /* host; on dst */, const float* params, const void* host_in, void* host_out,
                          void* arena, size_t arena_bytes, int32_t want_order, double p_max, double p_max_ub, void* stream);
 
+/* ---- rounds of several resident LPs in one call -------------------------------------------------------------------------------------
+ * What a scoring server holds when several solver workers each keep an LP resident: one round per session, waiting at the same time.
+ * gcnn_lp_rounds serves 1..GCNN_LP_ROUNDS_MAX of them with ONE upload, ONE upload of launch tables, at most ONE fill, one launch per
+ * stage and distinct kernel, and ONE download -- the number of enqueued operations does not depend on n for same-shaped members.
+ * Member i brings what its solo call brings: dims, present, n_forced / n_forced_entries, resident, params and, with has_append, the
+ * arguments of gcnn_lp_round_append (dims then describe the LP BEFORE the append, resident points at dst).  mode (GCNN_IBATCH_SCORES /
+ * _RANK / _SELECT), p_max and p_max_ub hold for every member; n_forced is >= 0 for every member in selection mode and -1 otherwise.
+ * Each member's work is its solo call's, recorded instead of launched (gcnn_group_forward's mechanism): every launch of the solo
+ * round and append has a group twin that runs the solo body with the member's arguments and its solo (block, blocks) pair.  So the
+ * member's download block (scores | order | flags | n_kept | LP flags | cut_index | the append's flags, exactly the solo out_off /
+ * flags_off, at out_off[i] of the call's download) and everything it leaves resident (cons_feats, the optional column buffers, the
+ * raw rows and dst of an append) have the bits of gcnn_lp_round / gcnn_lp_round_select / gcnn_lp_round_append on that member alone.
+ * The appends' launches form a phase of their own in front, so that the rounds share their stages whether or not a member appends.
+ * A member whose state has no constraint rows, columns or cuts runs its round's solo launches inside the call, behind the others.
+ * The arena (the caller's; the library allocates nothing): all uploads, member after member at in_off[i] (each the solo upload: the
+ * append block, the round, the forced rows; in_size[i] = the solo in_bytes rounded up to 256) | per member at arena_off[i] the solo
+ * arena (gcnn_lp_round_layout_for, or gcnn_lp_append_layout_for's from round_off on, at member_round_off[i]; the append's scratch at
+ * scratch_off[i]) | the appends' count tables, contiguous (the one fill) | all download blocks at out_off[i] from out_base on | the
+ * launch tables at table_off.  host_staging: pinned, table_bytes.  host_in: in_bytes, laid out as the arena's front; host_out:
+ * out_bytes, as the arena from out_base on.
+ * Returned before anything is enqueued: GCNN_E_BADARG (n outside 1..GCNN_LP_ROUNDS_MAX, a missing pointer, anything a member's solo
+ * call refuses, a short or misaligned arena, thresholds that are not finite, a member's writable memory -- cons_feats, the
+ * optional column buffers, the raw rows and dst of an append -- overlapping any memory of another member, which covers one session
+ * given twice), GCNN_E_WORKSPACE (a short table) and GCNN_E_UNSUPPORTED (the solo limits; more than 4,096 cuts in an ordering mode;
+ * a member whose launches the recorder cannot take). */
+#define GCNN_LP_ROUNDS_MAX GCNN_GROUP_MAX
+typedef struct gcnn_lp_rounds_member {
+    gcnn_lp_dims dims;
+    int32_t present, n_forced, n_forced_entries;
+    int32_t has_append;
+    gcnn_lp_append_dims block;                                              /* has_append */
+    int32_t* row_ptr; int32_t* row_col; double* row_val; double* row_lhs; double* row_rhs;   /* has_append: the raw rows (device) */
+    const gcnn_lp_rows_set* src; const gcnn_lp_rows_set* dst;             /* has_append (host) */
+    const gcnn_lp_resident* resident;                                       /* host */
+    const float* params;
+} gcnn_lp_rounds_member;
+typedef struct gcnn_lp_rounds_layout {
+    int32_t n, mode;
+    size_t in_bytes, in_off[GCNN_LP_ROUNDS_MAX], in_size[GCNN_LP_ROUNDS_MAX];
+    size_t arena_off[GCNN_LP_ROUNDS_MAX], member_round_off[GCNN_LP_ROUNDS_MAX], scratch_off[GCNN_LP_ROUNDS_MAX];
+    size_t counts_base, counts_bytes, counts_off[GCNN_LP_ROUNDS_MAX];
+    size_t out_base, out_bytes, out_off[GCNN_LP_ROUNDS_MAX], out_size[GCNN_LP_ROUNDS_MAX];   /* out_off: relative to out_base */
+    size_t table_off, table_bytes;
+    size_t arena_bytes;
+} gcnn_lp_rounds_layout;
+int gcnn_lp_rounds_layout_for(int32_t n, const gcnn_lp_rounds_member* members /* host; only the sizes are read */, int32_t mode,
+                              gcnn_lp_rounds_layout* layout /* host */);
+int gcnn_lp_rounds(int32_t n, const gcnn_lp_rounds_member* members /* host */, int32_t mode, const void* host_in, void* host_out,
+                   void* arena, size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
