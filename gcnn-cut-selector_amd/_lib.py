@@ -159,6 +159,17 @@ class LpAppendLayout(C.Structure):
                 ("scratch_off", C.c_size_t), ("round", LpRoundLayout)]
 
 
+class LpRemoveDims(C.Structure):
+    _fields_ = list(LpAppendDims._fields_)     # the same eight counts, of the removed rows
+
+
+class LpRemoveLayout(C.Structure):
+    _fields_ = [("list_bytes", C.c_size_t), ("block_bytes", C.c_size_t), ("block_off", C.c_size_t * 5), ("in_bytes", C.c_size_t),
+                ("out_bytes", C.c_size_t), ("flags_off", C.c_size_t), ("append_flags_off", C.c_size_t), ("scratch_bytes", C.c_size_t),
+                ("arena_bytes", C.c_size_t), ("round_off", C.c_size_t), ("append_scratch_off", C.c_size_t), ("scratch_off", C.c_size_t),
+                ("round", LpRoundLayout)]
+
+
 LP_ROUNDS_MAX = GROUP_MAX   # GCNN_LP_ROUNDS_MAX
 
 
@@ -262,6 +273,13 @@ SIGNATURES = {
                                       C.POINTER(LpRowsSet), _P, _Z, _P, _P]),
     "gcnn_lp_round_append": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpAppendDims), _I, _I, _I, _P, _P, _P, _P, _P, C.POINTER(LpRowsSet),
                                        C.POINTER(LpRowsSet), C.POINTER(LpResident), _P, _P, _P, _P, _Z, _I, _D, _D, _P]),
+    "gcnn_lp_remove_layout_for": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpRemoveDims), C.POINTER(LpAppendDims), _I, _I, _I,
+                                            C.POINTER(LpRemoveLayout)]),
+    "gcnn_lp_rows_remove": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpRemoveDims), _P] + [_P] * 10 + [C.POINTER(LpRowsSet),
+                                      C.POINTER(LpRowsSet), _P, _Z, _P, _P]),
+    "gcnn_lp_round_remove": (C.c_int, [C.POINTER(LpDims), C.POINTER(LpRemoveDims), C.POINTER(LpAppendDims), _I, _I, _I] + [_P] * 10 + [
+                                       C.POINTER(LpRowsSet), C.POINTER(LpRowsSet), C.POINTER(LpRowsSet), C.POINTER(LpResident), _P, _P, _P,
+                                       _P, _Z, _I, _D, _D, _P]),
     "gcnn_lp_rounds_layout_for": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, C.POINTER(LpRoundsLayout)]),
     "gcnn_lp_rounds": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }

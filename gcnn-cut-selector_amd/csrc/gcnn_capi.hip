@@ -1386,5 +1386,7 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lpres.hpp"
 // rows appended to a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_append, gcnn_lp_round_append): launch names k_lpa_*
 #include "gcnn_lpappend.hpp"
+// rows removed from a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_remove, gcnn_lp_round_remove): launch names k_lpd_*
+#include "gcnn_lpremove.hpp"
 // rounds of several resident LPs in one call (gcnn_lp_rounds)
 #include "gcnn_lprounds.hpp"

@@ -39,8 +39,9 @@ static bool lpa_dims_after(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, 
     return lp_dims_ok(after);
 }
 
+// more_out: a block behind the append's flag words, for a caller that extends the call (gcnn_lpremove.hpp)
 static int lpa_layout(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, int32_t present, int32_t n_forced, int32_t n_forced_entries,
-                      gcnn_lp_append_layout* L) {
+                      gcnn_lp_append_layout* L, size_t more_out = 0) {
     gcnn_lp_dims after;
     if (!L || !lpa_dims_after(d, b, &after)) return GCNN_E_BADARG;
     memset(L, 0, sizeof(*L));
@@ -51,10 +52,10 @@ static int lpa_layout(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, int32
     L->block_off[2] = o; o += 8 * dN; L->block_off[3] = o; o += 8 * dR; L->block_off[4] = o; o += 8 * dR;
     L->block_off[0] = o; o += 4 * (dR + 1); L->block_off[1] = o; o += 4 * dN;
     L->block_bytes = (o + 255) & ~(size_t)255;
-    const int rc = lpr_round_layout(&after, present, n_forced, n_forced_entries, &L->round, 16);
+    const int rc = lpr_round_layout(&after, present, n_forced, n_forced_entries, &L->round, 16 + more_out);
     if (rc == GCNN_E_BADARG) return rc;
     L->in_bytes = L->block_bytes + L->round.in_bytes;
-    L->flags_off = L->round.out_bytes - 16;                    // the append's four flag words close the download
+    L->flags_off = L->round.out_bytes - 16 - more_out;         // the append's four flag words close the download
     L->out_bytes = L->round.out_bytes;
     L->scratch_bytes = lpa_scratch(d, b).bytes;
     L->round_off = L->block_bytes;

@@ -753,10 +753,16 @@ class LPSession(_Staging):
     orders -- is built once (gcnn_lp_rows_build + gcnn_graph_build), and a round (`lpstate.LPRound`) uploads only the solve and
     the candidate cuts (gcnn_lp_round / gcnn_lp_round_select: one upload, two state launches, the forward pass, one download).
     A round's result is by definition what `state_from_lp` / `score_lp` / `select_cuts_lp` give on
-    `lpstate.assemble(rows, round)`, bit for bit.  Rows can only be appended -- inside a round's own call (`append=` of
-    `select_cuts`, `score`, `state`: gcnn_lp_round_append derives only the new rows and copies, shifts and merges the resident
-    arrays into the session's other set of buffers) or on their own (`append_rows`); any other change of the LP -- a row
-    removed or changed, a column added, another objective -- means opening a new session.  There is no variable limit; an order
+    `lpstate.assemble(rows, round)`, bit for bit.  Rows can be appended and removed -- inside a round's own call (`append=` /
+    `remove=` of `select_cuts`, `score`, `state`: gcnn_lp_round_append derives only the new rows and copies, shifts and merges the
+    resident arrays into the session's other set of buffers; gcnn_lp_round_remove derives nothing: it compacts the resident arrays
+    and the raw rows into the other sets, with an append behind it in the same call) or on their own (`append_rows`,
+    `remove_rows`).  `remove` numbers the rows AFTER the append of the same call, in any order; the round's `row_dual` and
+    `row_basis` cover the kept rows in their order; a removal that would leave no row at all is refused (open a new session).
+    Either edit is all or nothing: if the call raises, the session holds exactly the rows and derived state it held.  Not
+    covered: a removal inside an `LPSessionGroup`'s batched call (the member takes its solo call) or through the scoring
+    server, and any other change of the LP -- a row changed, a column added, another objective -- which means opening a new
+    session.  There is no variable limit; an order
     (ranking on the device, selection) takes at most 4,096 cuts, a table at most 2^24 rows.  The session holds no parameters:
     every round reads the model's current flat parameter buffer.  After a rejected round (ValueError, GcnnError) the session
     stays usable and the next round sees nothing of the rejected one."""
@@ -781,6 +787,9 @@ class LPSession(_Staging):
         self._lhs = (0, 0)                # lhs-sided state rows and their entries: where an appended lhs row goes
         self._col_deg = np.zeros(dims["n_cols"], np.int64)      # listed entries per column, and the longest segments: kept on the host
         self._max_deg = (0, 0)
+        self._book = None                 # per resident row: entry count, side bits; a copy of row_col (`lpstate.row_book`): a removal's exact account
+        self._raw_alt, self._cap_alt = None, (0, 0)     # the second set of raw buffers: a removal compacts the raw rows into it
+        self._transit = [None]            # the third set of derived buffers: between the removal and the append of one call
         self.closed = False
         V = dims["n_cols"]
         dev = model.device
@@ -868,27 +877,32 @@ class LPSession(_Staging):
             if n:
                 dst[to:to + n].copy_(self.pin_in[off:off + n], non_blocking=True)
 
-    def _after(self, counts):
-        """The resident dims after a block of `counts`; ValueError where the sums leave int32."""
+    def _after(self, counts, old=None):
+        """The resident dims (`old`: dims to start from instead) after a block of `counts`; ValueError where the sums leave int32."""
         dR, dN, dC, dE = counts
-        old = self._dims
+        old = self._dims if old is None else old
         R, N = old["n_rows"] + dR, old["row_nnz"] + dN
         if old["n_state_edges"] + dE > 2 ** 31 - 1 or N > 2 ** 31 - 1:
             raise ValueError("the state's constraint edges do not fit int32")
         return dict(old, n_rows=R, row_nnz=N, n_state_rows=old["n_state_rows"] + dC, n_state_edges=old["n_state_edges"] + dE)
 
-    def _host_counts(self, arrays):
+    def _host_counts(self, arrays, base=None):
         """What the host keeps of the resident state once `arrays` are part of it: (lhs rows, lhs entries), the per-column
-        degrees' update and the longest segments -- exact, without a device read."""
+        degrees' update, the longest segments -- exact, without a device read -- and the arrays, for the rows' book.  `base`:
+        (col_deg, max_deg) to start from instead of the session's (a removal in front of the block)."""
         from . import lpstate
+        col_deg, max_deg = (self._col_deg, self._max_deg) if base is None else base
         dL, dEL, longest, (cols, counts) = lpstate.block_sides(arrays, self.n_cols, self._dims["infinity"])
-        v_max = max(self._max_deg[1], int((self._col_deg[cols] + counts).max())) if cols.size else self._max_deg[1]
-        return (dL, dEL), (cols, counts), (max(self._max_deg[0], longest), v_max)
+        v_max = max(max_deg[1], int((col_deg[cols] + counts).max())) if cols.size else max_deg[1]
+        return (dL, dEL), (cols, counts), (max(max_deg[0], longest), v_max), arrays
 
     def _adopt_counts(self, host):
-        (dL, dEL), (cols, counts), self._max_deg = host
+        from . import lpstate
+        (dL, dEL), (cols, counts), self._max_deg, arrays = host
         self._lhs = (self._lhs[0] + dL, self._lhs[1] + dEL)
         self._col_deg[cols] += counts
+        new = lpstate.row_book(arrays, self._dims["infinity"])
+        self._book = new if self._book is None else tuple(np.concatenate(pair) for pair in zip(self._book, new))
 
     def _append(self, arrays, counts, first):
         dims = self._after(counts)
@@ -939,11 +953,18 @@ class LPSession(_Staging):
         the device; nothing is copied, an append writes every array whole.  The two structs are made once per allocation; only
         the longest segments change from append to append."""
         i = 1 - self._cur_set if self._cur_set >= 0 else 0
+        self._sets[i] = held = self._fit_set(self._sets, i, dims)
+        res = held[3]
+        res.cons_graph.l_max_deg, res.cons_graph.v_max_deg = max_deg
+        return i, held[0], held[2], res
+
+    def _fit_set(self, slots, i, dims):
+        """`slots[i]` -- (tensors, capacities, gcnn_lp_rows_set, gcnn_lp_resident) -- with room for `dims`: as it is, or replaced."""
         need = (dims["n_rows"], dims["n_state_rows"], dims["n_state_edges"])
-        held = self._sets[i]
+        held = slots[i]
         if held is None or any(n > c for n, c in zip(need, held[1])):
             cap = tuple(2 * n if n > c else c for n, c in zip(need, held[1] if held else (0, 0, 0)))
-            self._sets[i] = held = None
+            slots[i] = held = None
             capR, capC, capE = cap
             sizes = dict(cons_feats=16 * capC, edge_row=4 * capE, edge_col=4 * capE, edge_coef=4 * capE, l_ptr=4 * (capC + 1),
                          v_ptr=4 * (dims["n_cols"] + 1), v_oth=4 * capE, v_coef=4 * capE, row_place=8 * capR, row_scale=8 * capR)
@@ -952,13 +973,11 @@ class LPSession(_Staging):
             res = _lib.LpResident(p["row_place"], p["row_scale"], p["cons_feats"], self._col_type.data_ptr(), self._col_obj.data_ptr(),
                                   *(t.data_ptr() for t in self._opt),
                                   _lib.Graph(p["l_ptr"], p["edge_col"], p["edge_coef"], p["v_ptr"], p["v_oth"], p["v_coef"], 0, 0))
-            self._sets[i] = held = (cur, cap, self._set_struct(cur), res)
-        res = held[3]
-        res.cons_graph.l_max_deg, res.cons_graph.v_max_deg = max_deg
-        return i, held[0], held[2], res
+            held = (cur, cap, self._set_struct(cur), res)
+        return held
 
-    def _block_dims(self, counts, host):
-        return counts + host[0] + self._lhs
+    def _block_dims(self, counts, host, lhs=None):
+        return counts + host[0] + (self._lhs if lhs is None else lhs)
 
     def _adopt_set(self, i, cur, struct, dims, host, res):
         self._cur, self._cur_struct, self._cur_set, self._dims, self._res = cur, struct, i, dims, res
@@ -990,6 +1009,88 @@ class LPSession(_Staging):
         lpstate.raise_for_flags(flags)
         self._adopt_set(i, dst, dst_struct, dims, host, res)
 
+    # ---- the removal -------------------------------------------------------------------------------------------------------------
+    def _raw_other(self, R, N):
+        """The second set of raw buffers with room for R rows and N entries: a removal compacts the raw rows into it (out of
+        place: the accepted rounds' raw rows are not written before the call is accepted).  Nothing is copied on growth."""
+        capR, capN = self._cap_alt
+        if self._raw_alt is None or R > capR or N > capN:
+            if self._raw_alt is None:
+                capR, capN = max(R, self._cap[0]), max(N, self._cap[1])
+            else:
+                capR, capN = max(R, 2 * capR if R > capR else capR), max(N, 2 * capN if N > capN else capN)
+            self._raw_alt = None
+            self._raw_alt = [self._alloc(4 * (capR + 1)), self._alloc(4 * capN), self._alloc(8 * capN), self._alloc(8 * capR), self._alloc(8 * capR)]
+            self._cap_alt = (capR, capN)
+        return self._raw_alt
+
+    def _removal_host(self, idx, append):
+        """The host half of removing the resident rows `idx` (ascending, checked), with `append` (a block, or None) behind it:
+        the removed rows' eight counts, the dims after the removal and after the whole edit, the checked block and its eight
+        counts, and what the host keeps of the rows once the call is accepted -- all exact, nothing of the session changes."""
+        from . import lpstate
+        six, book, col_deg, lhs, max_deg = lpstate.removal_counts(self._book, self._col_deg, self._lhs, idx)
+        old = self._dims
+        mid = dict(old, n_rows=old["n_rows"] - six[0], row_nnz=old["row_nnz"] - six[1], n_state_rows=old["n_state_rows"] - six[2],
+                   n_state_edges=old["n_state_edges"] - six[3])
+        e = SimpleNamespace(idx=idx.astype(np.int32), removed=six + self._lhs, mid=mid, final=mid, blk=None, block=None)
+        if append is not None:
+            e.blk = self._check_block(append, (mid, col_deg, max_deg))
+        if e.blk is not None:
+            arrays, counts, e.final, ((dL, dEL), (cols, add), max_deg, _) = e.blk
+            e.block = counts + (dL, dEL) + lhs
+            lhs = (lhs[0] + dL, lhs[1] + dEL)
+            col_deg[cols] += add                    # (`removal_counts` made this copy)
+            book = tuple(np.concatenate(pair) for pair in zip(book, lpstate.row_book(arrays, old["infinity"])))
+        e.host = (lhs, col_deg, max_deg, book)
+        return e
+
+    def _adopt_removal(self, job):
+        """The session after an accepted call with a removal: the destination sets become the current ones."""
+        i, cur, struct, res = job.set
+        e = job.rm
+        self._cur, self._cur_struct, self._cur_set, self._dims, self._res = cur, struct, i, e.final, res
+        self._derived = self._graph = None
+        self._lhs, self._col_deg, self._max_deg, self._book = e.host
+        self._raw, self._raw_alt, self._cap, self._cap_alt = e.raw_dst, self._raw, self._cap_alt, self._cap
+        self.layouts.clear()
+
+    def remove_rows(self, remove):
+        """Remove the resident rows at the indices `remove` (any order; ValueError for an index that is not an integer, is out
+        of range or given twice, and where no row would be left): nothing goes up but the list, nothing is derived -- the
+        resident arrays and the raw rows are compacted into the session's other sets of buffers (gcnn_lp_rows_remove), with one
+        read of the flag words.  The resident state is afterwards a fresh session's on the kept rows, bit for bit.  Removing
+        zero rows is a no-op."""
+        from . import lpstate
+        self._open()
+        idx, _ = lpstate.split_remove(remove, self.n_rows)
+        if not idx.size:
+            return
+        e = self._removal_host(idx, None)
+        P, dev = C.c_void_p, self.model.device
+        job = SimpleNamespace(rm=e)
+        with torch.cuda.device(dev):
+            e.raw_dst = self._raw_other(e.final["n_rows"], e.final["row_nnz"])
+            job.set = self._other_set(e.final, e.host[2])
+            d, m, _, L = lpstate.lp_remove_layout(self._dims, e.removed, None, 0)
+            flags_at = L.list_bytes + ((L.scratch_bytes + 255) & ~255)
+            if self.arena is None or self.arena.numel() < flags_at + 256:
+                self.arena = None
+                self.arena = self._alloc(max(2 * (flags_at + 256), 1 << 22))
+            n = 4 * e.idx.size
+            self.pin_in, self.in_np = self._pin(self.pin_in, self.in_np, n, 1 << 20)
+            self.in_np[:n] = e.idx.view(np.uint8)
+            self.arena[:n].copy_(self.pin_in[:n], non_blocking=True)
+            stream = torch.cuda.current_stream(dev)
+            at = self.arena.data_ptr()
+            _lib.check(_lib.lib().gcnn_lp_rows_remove(C.byref(d), C.byref(m), P(at), *(P(t.data_ptr()) for t in self._raw),
+                                                      *(P(t.data_ptr()) for t in e.raw_dst), C.byref(self._cur_struct), C.byref(job.set[2]),
+                                                      P(at + L.list_bytes), L.scratch_bytes, P(at + flags_at), P(stream.cuda_stream)),
+                       "gcnn_lp_rows_remove")
+            flags = self.arena[flags_at:flags_at + 16].view(torch.int32).cpu().numpy()      # the one read; waits
+        lpstate.raise_for_flags(flags)
+        self._adopt_removal(job)
+
     def resident_state(self):
         """Host copies of what the session holds of the rows, as the rounds read it: the ten derived arrays (`cons_feats` [C, 4]
         with the columns 1 and 3 as the last round left them), the longest segments and the sizes."""
@@ -1011,11 +1112,12 @@ class LPSession(_Staging):
         if self.closed:
             raise _lib.GcnnError("the LP session is closed")
 
-    def _checked(self, rnd, n_forced=-1, n_entries=0, row_dims=None, block=None):
+    def _checked(self, rnd, n_forced=-1, n_entries=0, row_dims=None, block=None, removed=None):
         """A round checked on the host -> (arrays, presence mask, dims, layout entry).  An optional array whose device copy a
         rejected round overwrote travels again from the host copy of the last accepted one.  `row_dims`, `block`: the round
         comes with an append -- the resident dims after it and the block's eight counts; the layout entry is then the fused
-        call's."""
+        call's.  `removed`: it comes with a removal -- the removed rows' eight counts (`row_dims`: after the whole edit;
+        `block`: of the append behind the removal, or None); the layout entry is gcnn_lp_remove_layout_for's."""
         from . import lpstate
         self._open()
         arrays, present, dims = lpstate.check_round(rnd, self._dims if row_dims is None else row_dims, self._kept, self.deep_check)
@@ -1024,11 +1126,13 @@ class LPSession(_Staging):
             if name in self._stale and needed and not present >> q & 1:
                 arrays[5 + q] = self._kept[name]
                 present |= 1 << q
-        key = _int_key(dims) + (present, n_forced, n_entries) + (block or ())
-        if block is None:
+        key = _int_key(dims) + (present, n_forced, n_entries) + (block or ()) + (("remove",) + removed if removed else ())
+        before = dict(self._dims, n_cuts=dims["n_cuts"], cut_nnz=dims["cut_nnz"], has_incumbent=dims["has_incumbent"])
+        if removed is not None:
+            lay = self.cached(key, self._remove_layout, before, removed, block, present, n_forced, n_entries)
+        elif block is None:
             lay = self.cached(key, self._layout, dims, present, n_forced, n_entries)
         else:
-            before = dict(self._dims, n_cuts=dims["n_cuts"], cut_nnz=dims["cut_nnz"], has_incumbent=dims["has_incumbent"])
             lay = self.cached(key, self._append_layout, before, block, present, n_forced, n_entries)
         return arrays, present, dims, lay
 
@@ -1047,33 +1151,60 @@ class LPSession(_Staging):
         return (L, [L.block_bytes + o for o in R.in_off], [L.block_bytes + o for o in R.forced_off], list(R.out_off),
                 [L.round_off + o for o in R.dev_off], d, b)
 
-    def upload_bytes(self, rnd, forced=None, append=None):
+    @staticmethod
+    def _remove_layout(before, removed, block, present, n_forced, n_entries):
+        """The layout entry of a call with a removal; the round's offsets are shifted to the whole upload and the whole arena."""
+        from . import lpstate
+        d, m, b, L = lpstate.lp_remove_layout(before, removed, block, present, n_forced, n_entries)
+        R, base = L.round, L.list_bytes + L.block_bytes
+        return (L, [base + o for o in R.in_off], [base + o for o in R.forced_off], list(R.out_off), [L.round_off + o for o in R.dev_off],
+                d, m, b)
+
+    def upload_bytes(self, rnd, forced=None, append=None, remove=None):
         """Bytes the one upload of this round would carry (with `forced`: packed forced rows of a selection; with `append`: the
-        block that goes up with it)."""
+        block that goes up with it; with `remove`: the list of removed resident rows, and the block without the rows it names)."""
+        from . import lpstate
         fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        if remove is not None:
+            self._open()
+            idx, append = lpstate.split_remove(remove, self.n_rows, append)
+            if idx.size:
+                e = self._removal_host(idx, append)
+                return int(self._checked(rnd, *fshape, row_dims=e.final, block=e.block, removed=e.removed)[3][0].in_bytes)
         if append is not None:
             blk = self._check_block(append)
             if blk is not None:
                 return int(self._checked(rnd, *fshape, row_dims=blk[2], block=self._block_dims(blk[1], blk[3]))[3][0].in_bytes)
         return int(self._checked(rnd, *fshape)[3][0].in_bytes)
 
-    def _check_block(self, block):
+    def _check_block(self, block, base=None):
         """An `LPRowBlock` checked on the host -> (arrays, counts, the resident dims after it, the host's counts); None for an
-        empty block."""
+        empty block.  `base`: (dims, col_deg, max_deg) the block lands on instead of the session's (a removal in front of it)."""
         from . import lpstate
         self._open()
         arrays, counts = lpstate.check_row_block(*block.arrays(), self.n_cols, self._dims["infinity"], self.deep_check)
         if counts[0] == 0:
             return None
-        return arrays, counts, self._after(counts), self._host_counts(arrays)
+        if base is None:
+            return arrays, counts, self._after(counts), self._host_counts(arrays)
+        return arrays, counts, self._after(counts, base[0]), self._host_counts(arrays, base[1:])
 
     # A round's call in three parts, which the solo path (`_run`) and `LPSessionGroup` share: `_plan` (the host half: check,
     # layout, the raw buffers' room and the other set of an append), `_pack` into a given staging buffer, then either `_enqueue`
     # (the solo C call) or the group's call, and `_finish` (the verdict half: the download's flags -> raise / adopt / remember).
-    def _plan(self, rnd, forced=None, append=None):
+    def _plan(self, rnd, forced=None, append=None, remove=None):
         """check -> layout; with `append` also the room in the raw buffers and the set of derived buffers the append writes.
-        Returns the job the other parts read; nothing of the session changes that a rejected round would have to undo."""
-        job = SimpleNamespace(forced=forced, fshape=(-1, 0) if forced is None else (forced[0].size - 1, forced[1].size))
+        Returns the job the other parts read; nothing of the session changes that a rejected round would have to undo.
+        `remove`: indices into the rows after the append.  Those that point into the block are resolved here -- the rows are
+        dropped from the block before it is checked -- so the device only sees removals of resident rows followed by an append of
+        the filtered block; where no resident row is removed the job is the plain or fused one, launch for launch."""
+        from . import lpstate
+        job = SimpleNamespace(forced=forced, fshape=(-1, 0) if forced is None else (forced[0].size - 1, forced[1].size), rm=None)
+        if remove is not None:
+            self._open()
+            idx, append = lpstate.split_remove(remove, self.n_rows, append)
+            if idx.size:
+                return self._plan_removal(job, rnd, idx, append)
         job.blk = blk = self._check_block(append) if append is not None else None
         if blk is None:
             job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off) = self._checked(rnd, *job.fshape)
@@ -1090,11 +1221,39 @@ class LPSession(_Staging):
             job.flag_words = (int(job.L.flags_off), job.out_off[4])
         return job
 
+    def _plan_removal(self, job, rnd, idx, append):
+        """`_plan` for a job that removes the resident rows `idx`: the removal reads the current sets and writes the second raw
+        set and the other of `_sets`; with an append behind it the removal writes a transit set (allocated on the first such
+        call, never the current one) and the append goes from there into the other of `_sets`, its rows behind the second raw
+        set's.  Nothing the accepted state's rounds read is written before the call is accepted."""
+        job.rm = e = self._removal_host(idx, append)
+        job.blk, job.block = e.blk, e.removed + (e.block or ())
+        job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off, job.d, job.m, job.b) = self._checked(
+            rnd, *job.fshape, row_dims=e.final, block=e.block, removed=e.removed)
+        with torch.cuda.device(self.model.device):
+            e.raw_dst = self._raw_other(e.final["n_rows"], e.final["row_nnz"])
+            e.transit = None
+            if e.blk is not None:
+                e.transit = self._transit[0] = self._fit_set(self._transit, 0, e.mid)
+            job.set = self._other_set(e.final, e.host[2])
+        flags = (int(job.L.flags_off),) + ((int(job.L.append_flags_off),) if e.blk is not None else ())
+        job.flag_words = flags + (job.out_off[4],)
+        return job
+
     @staticmethod
     def _pack(job, buf):
-        """The job's one upload into `buf` (a staging buffer, or a member's slice of a group's): the block, the round, the forced rows."""
+        """The job's one upload into `buf` (a staging buffer, or a member's slice of a group's): the list of removed rows, the
+        block, the round, the forced rows."""
         from . import lpstate
-        if job.blk is None:
+        if job.rm is not None:
+            n = 4 * job.rm.idx.size
+            buf[:n] = job.rm.idx.view(np.uint8)
+            if job.blk is not None:
+                for off, a in zip(job.L.block_off, job.blk[0]):
+                    if a.size:
+                        buf[off:off + a.nbytes] = a.view(np.uint8)
+            lpstate.pack_round(buf, job.in_off, job.arrays, job.present)
+        elif job.blk is None:
             lpstate.pack_round(buf, job.in_off, job.arrays, job.present)
         else:
             lpstate.pack_append(buf, job.L, job.blk[0], job.arrays, job.present)
@@ -1105,7 +1264,13 @@ class LPSession(_Staging):
     def _enqueue(self, job, want_order, p_max, p_max_ub, timings, t0):
         """The solo call of a packed job and the wait for its download."""
         P, extra = C.c_void_p, dict(upload_bytes=int(job.L.in_bytes))
-        if job.blk is not None:
+        if job.rm is not None:
+            e, (_, _, dst_struct, res) = job.rm, job.set
+            head = (C.byref(job.d), C.byref(job.m), None if job.b is None else C.byref(job.b), job.present) + job.fshape + tuple(
+                P(t.data_ptr()) for t in self._raw) + tuple(P(t.data_ptr()) for t in e.raw_dst) + (
+                C.byref(self._cur_struct), None if e.transit is None else C.byref(e.transit[2]), C.byref(dst_struct), C.byref(res))
+            self._enqueue_wait("gcnn_lp_round_remove", head, (int(want_order), float(p_max), float(p_max_ub)), timings, t0, **extra)
+        elif job.blk is not None:
             _, _, dst_struct, res = job.set
             head = (C.byref(job.d), C.byref(job.b), job.present) + job.fshape + tuple(P(t.data_ptr()) for t in self._raw) + (
                 C.byref(self._cur_struct), C.byref(dst_struct), C.byref(res))
@@ -1128,7 +1293,9 @@ class LPSession(_Staging):
         except ValueError:
             self._stale.update(given)       # their device copies hold the rejected round's values
             raise
-        if job.blk is not None:
+        if job.rm is not None:
+            self._adopt_removal(job)
+        elif job.blk is not None:
             i, dst, dst_struct, res = job.set
             self._adopt_set(i, dst, dst_struct, job.blk[2], job.blk[3], res)
         self._kept.update(given)
@@ -1148,23 +1315,25 @@ class LPSession(_Staging):
         m.params = self.model._flat.data_ptr()
         return m
 
-    def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0, append=None):
+    def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0, append=None, remove=None):
         """check -> layout -> pack -> one call -> the download's LP flags checked.  Returns (the round's dims, the download's
         offsets, the arena's offsets); what the round gave of the optional column arrays is remembered once it is accepted.
         With `append` the call is gcnn_lp_round_append: the block goes up with the round, the append's launches run in front of
-        the round's, and the session adopts the rows once the download shows that the device accepted the block and the round."""
+        the round's, and the session adopts the rows once the download shows that the device accepted the block and the round.
+        With `remove` (resident rows among the indices) the call is gcnn_lp_round_remove: the list goes up in front, the removal's
+        launches run first, then the append's, then the round's."""
         t0 = time.perf_counter()
-        job = self._plan(rnd, forced, append)
+        job = self._plan(rnd, forced, append, remove)
         self._buffers(job.L)
         self._pack(job, self.in_np)
         self._enqueue(job, want_order, p_max, p_max_ub, timings, t0)
         self._finish(job, self.out_np)
         return job.dims, job.out_off, job.dev_off
 
-    def state(self, rnd, append=None):
+    def state(self, rnd, append=None, remove=None):
         """The model's 10-tuple as host arrays and `cut_index`, as `GCNN.state_from_lp` gives them for the assembled snapshot
-        (with `append`: the rows of the block appended first, in the same call)."""
-        dims, out_off, dev = self._run(rnd, -1, append=append)
+        (with `append`: the rows of the block appended first, in the same call; with `remove`: those rows removed then)."""
+        dims, out_off, dev = self._run(rnd, -1, append=append, remove=remove)
         c, v, k, e1, e2 = dims["n_state_rows"], dims["n_cols"], dims["n_cuts"], dims["n_state_edges"], dims["cut_nnz"]
         f32, i32 = torch.float32, torch.int32
         cur, A = self._cur, self.arena
@@ -1184,35 +1353,39 @@ class LPSession(_Staging):
         scores, order, n_kept = self._read(out_off[0], out_off[1] if want_order else None, out_off[3] if select else None, n, out)
         return scores, order, n_kept, out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy()
 
-    def score(self, rnd, rank=False, timings=None, append=None):
+    def score(self, rnd, rank=False, timings=None, append=None, remove=None):
         """`GCNN.score_lp` for the assembled snapshot: a `ScoreArray` in STATE order with `.cut_index` and, with `rank`,
         `.rankings`.  `append` (an `lpstate.LPRowBlock`): rows appended in the same call, in front of the round, whose `row_dual`
-        and `row_basis` cover them; all or nothing -- if the call raises, the session holds the rows it held before."""
+        and `row_basis` cover them; all or nothing -- if the call raises, the session holds the rows it held before.  `remove`:
+        indices of rows removed in the same call, numbered AFTER the append (a just-appended row may be removed), any order; the
+        round covers the kept rows in their order: the answer is that of `lpstate.rows_without(rows_with(rows, append), remove)`."""
         n = int(np.asarray(rnd.cut_lhs).shape[0])
         on_device = self.model._rank_on_device(rank, n) and n <= 4096
-        dims, out_off, _ = self._run(rnd, int(on_device), timings, append=append)
+        dims, out_off, _ = self._run(rnd, int(on_device), timings, append=append, remove=remove)
         scores, order, _, cut_index = self._results(dims, out_off, on_device, False)
         scores.cut_index = cut_index
         if rank:
             scores.rankings = order if on_device else stable_ranking(scores)
         return scores
 
-    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None):
+    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None, remove=None):
         """`GCNN.select_cuts_lp` for the assembled snapshot: a `SelectResult` with `cut_index`.  More than 4,096 cuts raise
         `GcnnError` before anything is enqueued.  `append`: as in `score` -- the separation loop's call, which appends the cuts
-        the last selection kept and selects among the new candidates in one upload, one run of launches and one download."""
+        the last selection kept and selects among the new candidates in one upload, one run of launches and one download.
+        `remove`: as in `score` -- the rows the solver's clean-up dropped since the last round leave in the same call."""
         ops.check_thresholds(p_max, p_max_ub)
         self.model._check_select_size("LPSession.select_cuts", "round", int(np.asarray(rnd.cut_lhs).shape[0]))
         packed = normalize_forced(forced, self.n_cols)
-        dims, out_off, _ = self._run(rnd, 1, timings, packed, p_max, p_max_ub, append=append)
+        dims, out_off, _ = self._run(rnd, 1, timings, packed, p_max, p_max_ub, append=append, remove=remove)
         scores, order, n_kept, cut_index = self._results(dims, out_off, True, True)
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
     def close(self):
-        """Release the device buffers (both derived sets included); the session cannot be used afterwards."""
+        """Release the device buffers (all derived sets and both raw sets included); the session cannot be used afterwards."""
         self.closed = True
         self._raw = self._derived = self._graph = self._res = self.arena = self._cur = self._cur_struct = None
         self._sets = [None, None]
+        self._raw_alt, self._transit, self._book = None, [None], None
         self._col_type = self._col_obj = self._opt = None
         self._buffers_made = []
         self._kept, self._stale = {}, set()
@@ -1374,12 +1547,19 @@ class LPSessionGroup:
             raise ValueError(f"{what}: one entry per session expected, got {len(items)} for {n} sessions")
         return items
 
-    def score(self, sessions, rounds, rank=False, appends=None, return_exceptions=False, timings=None):
-        """`sessions[i].score(rounds[i], rank, append=appends[i])` for every i, as a list of `ScoreArray`.  With
-        `return_exceptions` a member's exception sits in its slot; otherwise the first one is raised after every member has been
-        served."""
+    @staticmethod
+    def _removes(i, removes):
+        """Whether member i comes with a removal: it is then answered through its solo call (gcnn_lp_rounds takes no removal)."""
+        return removes[i] is not None and np.asarray(removes[i]).size > 0
+
+    def score(self, sessions, rounds, rank=False, appends=None, return_exceptions=False, timings=None, removes=None):
+        """`sessions[i].score(rounds[i], rank, append=appends[i], remove=removes[i])` for every i, as a list of `ScoreArray`.
+        With `return_exceptions` a member's exception sits in its slot; otherwise the first one is raised after every member has
+        been served.  A member with a removal is answered through its solo call and comes back in place (counted in
+        `solo_rounds`); the others keep their batched call."""
         sessions, rounds = list(sessions), list(rounds)
         appends = self._per_session("appends", appends, len(sessions))
+        removes = self._per_session("removes", removes, len(sessions))
         self._per_session("rounds", rounds, len(sessions))
 
         def on_device(i):
@@ -1387,8 +1567,8 @@ class LPSessionGroup:
             return sessions[i].model._rank_on_device(rank, n) and n <= 4096
 
         def plan(i):
-            if rank and not on_device(i):
-                return None                 # the host ranks this one: its solo call
+            if (rank and not on_device(i)) or self._removes(i, removes):
+                return None                 # the host ranks this one, or it removes rows: its solo call
             return sessions[i]._plan(rounds[i], None, appends[i])
 
         def answer(i, job, out):
@@ -1399,22 +1579,25 @@ class LPSessionGroup:
             return scores
 
         results = self._serve(sessions, _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES, plan, answer,
-                              lambda i: sessions[i].score(rounds[i], rank, append=appends[i]), timings=timings)
+                              lambda i: sessions[i].score(rounds[i], rank, append=appends[i], remove=removes[i]), timings=timings)
         return self._finish_many(results, return_exceptions)
 
     def select_cuts(self, sessions, rounds, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, appends=None,
-                    return_exceptions=False, timings=None):
-        """`sessions[i].select_cuts(rounds[i], forced[i], p_max=..., p_max_ub=..., max_selected=..., append=appends[i])` for every
-        i, as a list of `SelectResult`; errors as in `score`."""
+                    return_exceptions=False, timings=None, removes=None):
+        """`sessions[i].select_cuts(rounds[i], forced[i], p_max=..., p_max_ub=..., max_selected=..., append=appends[i],
+        remove=removes[i])` for every i, as a list of `SelectResult`; errors and removals as in `score`."""
         ops.check_thresholds(p_max, p_max_ub)
         sessions, rounds = list(sessions), list(rounds)
         n = len(sessions)
         appends, forced = self._per_session("appends", appends, n), self._per_session("forced", forced, n)
+        removes = self._per_session("removes", removes, n)
         self._per_session("rounds", rounds, n)
 
         def plan(i):
             s = sessions[i]
             s.model._check_select_size("LPSession.select_cuts", "round", int(np.asarray(rounds[i].cut_lhs).shape[0]))
+            if self._removes(i, removes):
+                return None
             return s._plan(rounds[i], normalize_forced(forced[i], s.n_cols), appends[i])
 
         def answer(i, job, out):
@@ -1422,7 +1605,8 @@ class LPSessionGroup:
             return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
         def solo(i):
-            return sessions[i].select_cuts(rounds[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected, append=appends[i])
+            return sessions[i].select_cuts(rounds[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected, append=appends[i],
+                                           remove=removes[i])
 
         results = self._serve(sessions, _lib.IBATCH_SELECT, plan, answer, solo, p_max, p_max_ub, timings)
         return self._finish_many(results, return_exceptions)

@@ -304,6 +304,118 @@ def rows_with(rows: LPRows, *blocks: LPRowBlock) -> LPRows:
                   infinity=rows.infinity, sum_epsilon=rows.sum_epsilon, n_model_vars=rows.n_model_vars, obj_norm=rows.obj_norm)
 
 
+def check_remove(remove, n_rows):
+    """The row indices of a removal, checked against `n_rows` rows -> ascending int64 (empty for None or no index).  Any order is
+    accepted; ValueError for an index that is not an integer, lies outside [0, n_rows) or is given twice."""
+    if remove is None:
+        return np.zeros(0, np.int64)
+    a = np.asarray(remove)
+    if a.size == 0:
+        return np.zeros(0, np.int64)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"remove: row indices must be integers, got {a.dtype}")
+    a = np.sort(a.astype(np.int64).ravel())
+    if a[0] < 0 or a[-1] >= n_rows:
+        raise ValueError(f"remove: a row index outside [0, {n_rows})")
+    if np.any(a[1:] == a[:-1]):
+        raise ValueError("remove: a row index is given twice")
+    return a
+
+
+def _csr_without(arrays, idx):
+    """The five row arrays (row_ptr from 0) without the rows `idx` (ascending, checked); the order of the kept rows unchanged."""
+    ptr, col, val, lhs, rhs = (np.asarray(a) for a in arrays)
+    keep = np.ones(lhs.shape[0], bool)
+    keep[idx] = False
+    lens = np.diff(ptr).astype(np.int64)
+    entries = np.repeat(keep, lens)
+    new_ptr = np.concatenate([[0], np.cumsum(lens[keep])]).astype(np.int32)
+    return new_ptr, col[entries], val[entries], lhs[keep], rhs[keep]
+
+
+def rows_without(rows: LPRows, remove) -> LPRows:
+    """`rows` without the rows at the indices `remove` (any order), the order of the kept rows unchanged: what a session holds
+    after removing them."""
+    idx = check_remove(remove, np.asarray(rows.row_lhs).shape[0])
+    ptr, col, val, lhs, rhs = _csr_without((rows.row_ptr, rows.row_col, rows.row_val, rows.row_lhs, rows.row_rhs), idx)
+    return LPRows(ptr, col.astype(np.int32), val.astype(np.float64), lhs.astype(np.float64), rhs.astype(np.float64), rows.col_type,
+                  rows.col_obj, infinity=rows.infinity, sum_epsilon=rows.sum_epsilon, n_model_vars=rows.n_model_vars, obj_norm=rows.obj_norm)
+
+
+def block_without(block: LPRowBlock, idx) -> LPRowBlock:
+    """`block` without its rows `idx` (ascending indices into the block, checked)."""
+    return LPRowBlock(*_csr_without(block.arrays(), idx))
+
+
+def split_remove(remove, n_resident, block=None):
+    """A removal's indices, which number the rows AFTER the append of `block` in the same call -> (the ascending indices of
+    resident rows, the block without the rows the others name -- None where no row of it is left).  Empty indices: (empty,
+    block).  ValueError as `check_remove`, and where the removal would leave no row at all."""
+    n_block = 0 if block is None else int(np.asarray(block.row_lhs).shape[0])
+    idx = check_remove(remove, n_resident + n_block)
+    if idx.size and idx.size == n_resident + n_block:
+        raise ValueError("remove: the removal would leave no row at all; open a new session instead")
+    inside = idx[idx >= n_resident] - n_resident
+    if inside.size:
+        block = block_without(block, inside) if inside.size < n_block else None
+    return idx[idx < n_resident], block
+
+
+def row_book(arrays, infinity):
+    """What a session keeps on the host per resident row to stay exact through a removal without a device read: (entry counts
+    int64 [R], side bits int8 [R] -- 1: the lhs side is listed, 2: the rhs side --, a copy of row_col int32 [N])."""
+    row_ptr, row_col, _, row_lhs, row_rhs = arrays
+    sides = finite(row_lhs, infinity).astype(np.int8) + 2 * finite(row_rhs, infinity).astype(np.int8)
+    return np.diff(row_ptr).astype(np.int64), sides, np.array(row_col, np.int32)
+
+
+def removal_counts(book, col_deg, lhs, idx):
+    """The host's exact account of removing the resident rows `idx` (ascending) -> (the removed rows' six counts: rows, raw
+    entries, state rows, state edges, lhs state rows, lhs edges; the book without them; `col_deg` after the decrement; (lhs rows,
+    lhs entries) after; (l_max_deg, v_max_deg) after: the maximum over the kept listed rows, the maximum of the new `col_deg`)."""
+    lens, sides, cols = book
+    keep = np.ones(lens.shape[0], bool)
+    keep[idx] = False
+    has_l, has_r = (sides[idx] & 1).astype(bool), (sides[idx] & 2).astype(bool)
+    gone = lens[idx]
+    m_lhs, m_lhs_edges = int(has_l.sum()), int(gone[has_l].sum())
+    counts = (int(idx.size), int(gone.sum()), m_lhs + int(has_r.sum()), m_lhs_edges + int(gone[has_r].sum()), m_lhs, m_lhs_edges)
+    weight = np.repeat(has_l.astype(np.int64) + has_r, gone)
+    if idx.size <= 64:                                  # a few rows: slices between them, O(rows) + a copy of the entries
+        ends = np.cumsum(lens)[idx]
+        starts = ends - gone
+        hit = np.concatenate([cols[a:b] for a, b in zip(starts, ends)])
+        new_cols = np.concatenate([cols[a:b] for a, b in zip([0] + ends.tolist(), starts.tolist() + [cols.shape[0]])])
+    else:
+        entries = np.repeat(keep, lens)
+        hit, new_cols = cols[~entries], cols[entries]
+    ok = (hit >= 0) & (hit < col_deg.shape[0])
+    deg = col_deg.copy()
+    if col_deg.shape[0] <= max(8 * hit.size, 1 << 14):
+        deg -= np.bincount(hit[ok], weights=weight[ok], minlength=col_deg.shape[0]).astype(np.int64)
+    else:
+        which, inverse = np.unique(hit[ok], return_inverse=True)
+        deg[which] -= np.bincount(inverse, weights=weight[ok], minlength=which.size).astype(np.int64)
+    new_book = (lens[keep], sides[keep], new_cols)
+    listed = new_book[0][new_book[1] > 0]
+    longest = int(listed.max()) if listed.size else 0
+    return counts, new_book, deg, (lhs[0] - m_lhs, lhs[1] - m_lhs_edges), (longest, int(deg.max()) if deg.size else 0)
+
+
+def lp_remove_layout(dims, removed, block, present, n_forced=-1, n_entries=0):
+    """(LpDims, LpRemoveDims, LpAppendDims | None, LpRemoveLayout) of the library for the dims BEFORE the edit, the removed rows'
+    eight counts and, with an append behind the removal, the block's eight counts (its resident lhs counts: after the removal);
+    raises `_lib.GcnnError` where it declines the sizes."""
+    import ctypes as C
+
+    from . import _lib
+    d, m, L = _lib.LpDims(**dims), _lib.LpRemoveDims(*removed), _lib.LpRemoveLayout()
+    b = None if block is None else _lib.LpAppendDims(*block)
+    _lib.check(_lib.lib().gcnn_lp_remove_layout_for(C.byref(d), C.byref(m), None if b is None else C.byref(b), present, n_forced, n_entries,
+                                                    C.byref(L)), "gcnn_lp_remove_layout_for")
+    return d, m, b, L
+
+
 def assemble(rows: LPRows, rnd: LPRound, kept=None) -> LPSnapshot:
     """The `LPSnapshot` a round stands for: the definition of what a session answers.  `kept`: {name: array} of the optional column
     arrays as the last rounds gave them, for the ones this round leaves None."""

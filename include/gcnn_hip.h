@@ -815,6 +815,63 @@ int gcnn_lp_round_append(const gcnn_lp_dims* dims, const gcnn_lp_append_dims* bl
                          const gcnn_lp_resident* resident /* host; on dst */, const float* params, const void* host_in, void* host_out,
                          void* arena, size_t arena_bytes, int32_t want_order, double p_max, double p_max_ub, void* stream);
 
+/* ---- rows removed from a resident LP without deriving anything again -------------------------------------------------------------------
+ * Between two separation rounds a solver also cleans its LP: rows that have been slack for a while leave again.  Removal is the
+ * mirror image of the append: nothing is derived and no floating-point value is computed; every kept value is copied and every kept
+ * index renumbered by a monotone map, so both CSR orders stay stable: rows [kept lhs | kept rhs], by-left edges likewise, per
+ * variable the kept entries of its old segment in their old order, v_ptr = old v_ptr - exclusive prefix of the removed counts;
+ * row_place, row_scale, l_ptr, the 16-byte cons_feats rows and the five raw arrays (row_ptr re-based) are compacted by the same
+ * launches.  Everything goes out of place: the removal reads `src` and the raw rows and writes `dst` and a SECOND set of raw
+ * buffers (out_*), so a rejected call costs nothing to undo; no source may overlap a destination.
+ * removed: what the host counted of the removed rows -- rows, raw entries, state rows, state edges, how many of the state rows and
+ * edges are lhs sides -- and the lhs rows and entries of the resident state.  dims: the resident LP BEFORE the edit.  list: the removed
+ * LP rows, ascending, int32.
+ * gcnn_lp_rows_remove: the removal alone; list on the device; one fill of the removed counters and three launches (k_lpd_mark,
+ * k_lpd_rows, k_lpd_vars); the four flag words (word 3: the device's totals differ from the host's; any set: dst is NOT valid) go
+ * to the device address `flags`; nothing is synchronised.
+ * gcnn_lp_round_remove: the removal -- and, with `block`, an append behind it -- inside the call of the round that follows.  ONE
+ * upload of host_in (in_bytes): the list (list_bytes, a multiple of 256), then exactly gcnn_lp_round's upload, or with a block
+ * gcnn_lp_round_append's, for the dims AFTER the edit (block_off absolute, round.in_off relative to list_bytes + block_bytes).
+ * The removal's launches; with a block exactly gcnn_lp_round_append's append launches from `transit` (what the removal wrote; never
+ * src or dst) into dst, its rows copied behind the rows of out_* (whose buffers must have the room); then exactly what gcnn_lp_round /
+ * gcnn_lp_round_select enqueue on `resident`, which points at dst; ONE download of out_bytes: that call's, then the removal's four
+ * flag words at flags_off (with a block the append's at append_flags_off in front of them); no host wait in between.  block's
+ * res_lhs_* are the lhs counts after the removal.  The arena: the upload | at round_off the round's arena | the append's scratch at
+ * append_scratch_off | the removal's scratch at scratch_off.  The library allocates nothing.
+ * Returned before anything is enqueued: GCNN_E_BADARG (counts that cannot be: negative, more removed than resident, lhs counts above
+ * the totals, nothing left after the whole edit; a missing pointer; a misaligned cons_feats; a source set, raw buffer or transit set
+ * that overlaps a destination; a short or misaligned arena; thresholds that are not finite), GCNN_E_WORKSPACE (a short scratch) and
+ * GCNN_E_UNSUPPORTED (the round's limits on the dims after the edit).  Not part of gcnn_lp_rounds: a member with a removal takes
+ * this call. */
+typedef struct gcnn_lp_remove_dims {
+    int32_t n_rows, row_nnz, n_state_rows, n_state_edges;   /* the removed rows */
+    int32_t n_lhs_rows, n_lhs_edges;                          /* of them, lhs sides */
+    int32_t res_lhs_rows, res_lhs_edges;                      /* lhs sides of the resident state */
+} gcnn_lp_remove_dims;
+typedef struct gcnn_lp_remove_layout {
+    size_t list_bytes;                     /* the list opens the upload */
+    size_t block_bytes, block_off[5];      /* with a block: as gcnn_lp_append_layout's, offsets from the upload's start; else 0 */
+    size_t in_bytes, out_bytes;
+    size_t flags_off, append_flags_off;
+    size_t scratch_bytes;                  /* what gcnn_lp_rows_remove needs */
+    size_t arena_bytes, round_off, append_scratch_off, scratch_off;
+    gcnn_lp_round_layout round;            /* offsets relative to list_bytes + block_bytes (upload), 0 (download) and round_off (arena) */
+} gcnn_lp_remove_layout;
+int gcnn_lp_remove_layout_for(const gcnn_lp_dims* dims, const gcnn_lp_remove_dims* removed, const gcnn_lp_append_dims* block /* or NULL */,
+                              int32_t present, int32_t n_forced, int32_t n_forced_entries, gcnn_lp_remove_layout* layout /* host */);
+int gcnn_lp_rows_remove(const gcnn_lp_dims* dims, const gcnn_lp_remove_dims* removed, const int32_t* list /* device */,
+                        const int32_t* row_ptr, const int32_t* row_col, const double* row_val, const double* row_lhs, const double* row_rhs,
+                        int32_t* out_ptr, int32_t* out_col, double* out_val, double* out_lhs, double* out_rhs,
+                        const gcnn_lp_rows_set* src /* host */, const gcnn_lp_rows_set* dst /* host */, void* scratch, size_t scratch_bytes,
+                        int32_t* flags /* device [4] */, void* stream);
+int gcnn_lp_round_remove(const gcnn_lp_dims* dims, const gcnn_lp_remove_dims* removed, const gcnn_lp_append_dims* block /* or NULL */,
+                         int32_t present, int32_t n_forced, int32_t n_forced_entries, const int32_t* row_ptr, const int32_t* row_col,
+                         const double* row_val, const double* row_lhs, const double* row_rhs, int32_t* out_ptr, int32_t* out_col,
+                         double* out_val, double* out_lhs, double* out_rhs, const gcnn_lp_rows_set* src /* host */,
+                         const gcnn_lp_rows_set* transit /* host; with a block */, const gcnn_lp_rows_set* dst /* host */,
+                         const gcnn_lp_resident* resident /* host; on dst */, const float* params, const void* host_in, void* host_out,
+                         void* arena, size_t arena_bytes, int32_t want_order, double p_max, double p_max_ub, void* stream);
+
 /* ---- rounds of several resident LPs in one call -------------------------------------------------------------------------------------
  * What a scoring server holds when several solver workers each keep an LP resident: one round per session, waiting at the same time.
  * gcnn_lp_rounds serves 1..GCNN_LP_ROUNDS_MAX of them with ONE upload, ONE upload of launch tables, at most ONE fill, one launch per
