@@ -119,7 +119,8 @@ def fp64_moments(x):
     return mean.numpy(), ((x - mean) ** 2).mean(0).numpy()
 
 
-# ---- a training step through a NaN-filled, guarded workspace (tests/test_gpu_write_through.py, tests/test_gpu_wgrad_seams.py) ----------
+# ---- a training step through a NaN-filled, guarded workspace (tests/test_gpu_write_through.py, tests/test_gpu_wgrad_seams.py,
+# tests/test_gpu_row_seams.py: with the autograd sibling and the workspace fingerprint) -----------------------------------------------
 PATTERN = 0x7FC5A5A5           # a quiet NaN no arithmetic produces
 GUARD = 16 * 64                # 16 guard rows behind the workspace
 
@@ -140,9 +141,10 @@ def make_state(n_cons, n_vars, n_cuts, seed):
     return (f(n_cons, 4), cei, cef, f(n_vars, 14), f(n_cuts, 6), kei, kef, n_cons, n_vars, n_cuts), rng.uniform(0, 0.2, n_cuts)
 
 
-def run_step(model, state, y, ws=None, floats=0):
+def run_step(model, state, y, ws=None, floats=0, download=True):
     """One train_step (no optimizer) through a pattern-filled workspace of the library's size (or `floats`, if that is more) plus
-    the guard rows, or through `ws` as it is.  Returns (results, workspace words on the host, words the library asked for, the workspace)."""
+    the guard rows, or through `ws` as it is.  Returns (results, workspace words on the host, words the library asked for, the workspace);
+    `download=False`: None for the words (a large workspace stays on the device: `fingerprint`)."""
     import ctypes as C
     from gcnn_cut_selector_amd import _lib
     from gcnn_cut_selector_amd.trainer import TrainState, train_step
@@ -159,4 +161,49 @@ def run_step(model, state, y, ws=None, floats=0):
     torch.cuda.synchronize()
     assert model._ws_pool and model._ws_pool[-1] is ws, "the step ran through another workspace"
     res = {"loss": loss.cpu().numpy(), "scores": scores.cpu().numpy(), "grads": ts.grads.cpu().numpy()}
-    return res, ws.view(torch.int32).cpu().numpy(), need, ws
+    return res, (ws.view(torch.int32).cpu().numpy() if download else None), need, ws
+
+
+def run_autograd(model, state, y, floats=0):
+    """`run_step`'s sibling for the autograd path: the forward with gradients and the backward of the MSE loss through a pattern-filled,
+    guarded workspace.  Returns (results, words the library asked for, the workspace); the workspace stays on the device
+    (`fingerprint`)."""
+    import ctypes as C
+    from gcnn_cut_selector_amd import _lib
+    dev = model.device
+    batch = model.prepare(state)
+    need = int(_lib.lib().gcnn_workspace_floats(C.byref(batch.dims)))
+    ws = torch.empty(max(need, floats) + GUARD, dtype=torch.float32, device=dev)
+    ws.view(torch.int32).fill_(PATTERN)
+    model._ws_pool[:] = [ws]
+    yt = torch.as_tensor(y, dtype=torch.float32).to(dev)
+    pred = model(batch, True)
+    loss = ((pred - yt) ** 2).mean()
+    model.flat_parameters.grad = None
+    loss.backward()
+    torch.cuda.synchronize()
+    assert model._ws_pool and model._ws_pool[-1] is ws, "the step ran through another workspace"
+    res = {"loss": loss.detach().cpu().numpy(), "scores": pred.detach().cpu().numpy(), "grads": model.flat_parameters.grad.cpu().numpy()}
+    return res, need, ws
+
+
+FP_WORDS = 64                  # words per fingerprint: one [*, 64] row
+
+
+def fingerprint(ws, words):
+    """One fingerprint per FP_WORDS words of the first `words` words of a workspace, made on the device: the int32 words summed in
+    int64 (no overflow, and any single changed word changes its sum), and beside it how many of them still carry PATTERN.  Returns
+    (sums int64[ceil(words / 64)], pattern counts uint8[...]) on the host: 1/32 of the workspace and 1/256."""
+    w = ws.view(torch.int32)[:words]
+    pad = -words % FP_WORDS
+    if pad:
+        w = torch.cat([w, w.new_zeros(pad)])
+    sums = torch.empty(w.numel() // FP_WORDS, dtype=torch.int64, device=w.device)
+    pats = torch.empty(w.numel() // FP_WORDS, dtype=torch.uint8, device=w.device)
+    step = 1 << 20             # rows per pass: the int64 copy stays at 512 MiB
+    rows = w.view(-1, FP_WORDS)
+    for lo in range(0, rows.shape[0], step):
+        part = rows[lo:lo + step]
+        sums[lo:lo + step] = part.sum(1, dtype=torch.int64)
+        pats[lo:lo + step] = (part == PATTERN).sum(1).to(torch.uint8)
+    return sums.cpu().numpy(), pats.cpu().numpy()

@@ -249,12 +249,13 @@ def _tensor_sets():
     return out
 
 
-def strength(case, params, y_star):
+def strength(case, params, y_star, build=W.build):
     """The smallest factor over the GPU test's bound by which removing, doubling or replacing one component's share moves a targeted
     tensor: (factor, tensor, component, the largest 3 gap / (1e-4 ref) over the tensors).  Replacing: by the neighbouring (ordinary)
     cut's whole contribution, and, where another component's row lies next to this one's in some row set, by that component's share
-    in the tensors of that set's jobs -- the swap a clamping error would make."""
-    state, y, comps = W.build(case, y_star)
+    in the tensors of that set's jobs -- the swap a clamping error would make.  `build`: the builder of the case list
+    (tests/rowcases.py brings its own; a component without a constraint has c = None)."""
+    state, y, comps = build(case, y_star)
     p64 = {k: v.astype(np.float64) for k, v in params.items()}
     K = case["K"]
     p = O.to_torch(p64, torch.float64, requires_grad=True)
@@ -287,7 +288,7 @@ def strength(case, params, y_star):
                 moves.append(float(np.abs(share - 2.0 * (s[nb] - y[nb]) / K * jac(nb)[n]).max()))
             for o in comps:                                     # replaced by a planted neighbour of the tensor's row set
                 key = sets.get(n, "").lower()
-                if key and abs(o[key] - c[key]) == 1:
+                if key and c[key] is not None and abs(o[key] - c[key]) == 1:
                     moves.append(float(np.abs(share - share_of(o, n)).max()))
             f = min(moves) / allowed[n]
             if f < worst[0]:
