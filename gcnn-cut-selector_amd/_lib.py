@@ -190,6 +190,23 @@ class LpRoundsLayout(C.Structure):
                 ("arena_bytes", C.c_size_t)]
 
 
+class LpRoundsEditMember(C.Structure):      # gcnn_lp_rounds_edit_member: LpRoundsMember's fields, then the removal's
+    _fields_ = list(LpRoundsMember._fields_) + [
+        ("has_remove", C.c_int32), ("reserved", C.c_int32), ("removed", LpRemoveDims), ("out_ptr", C.c_void_p), ("out_col", C.c_void_p),
+        ("out_val", C.c_void_p), ("out_lhs", C.c_void_p), ("out_rhs", C.c_void_p), ("transit", C.POINTER(LpRowsSet))]
+
+
+class LpRoundsEditLayout(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mode", C.c_int32), ("in_bytes", C.c_size_t), ("in_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("in_size", C.c_size_t * LP_ROUNDS_MAX), ("arena_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("member_round_off", C.c_size_t * LP_ROUNDS_MAX), ("scratch_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("remove_scratch_off", C.c_size_t * LP_ROUNDS_MAX), ("counts_base", C.c_size_t), ("counts_bytes", C.c_size_t),
+                ("counts_off", C.c_size_t * LP_ROUNDS_MAX), ("remove_counts_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("out_base", C.c_size_t), ("out_bytes", C.c_size_t), ("out_off", C.c_size_t * LP_ROUNDS_MAX),
+                ("out_size", C.c_size_t * LP_ROUNDS_MAX), ("table_off", C.c_size_t), ("table_bytes", C.c_size_t),
+                ("arena_bytes", C.c_size_t)]
+
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -282,6 +299,8 @@ SIGNATURES = {
                                        _P, _Z, _I, _D, _D, _P]),
     "gcnn_lp_rounds_layout_for": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, C.POINTER(LpRoundsLayout)]),
     "gcnn_lp_rounds": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_lp_rounds_edit_layout_for": (C.c_int, [_I, C.POINTER(LpRoundsEditMember), _I, C.POINTER(LpRoundsEditLayout)]),
+    "gcnn_lp_rounds_edit": (C.c_int, [_I, C.POINTER(LpRoundsEditMember), _I, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }
 
 _lib = None

@@ -1390,3 +1390,5 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lpremove.hpp"
 // rounds of several resident LPs in one call (gcnn_lp_rounds)
 #include "gcnn_lprounds.hpp"
+// the same with an optional removal per member (gcnn_lp_rounds_edit)
+#include "gcnn_lpedits.hpp"

@@ -124,10 +124,11 @@ static int lpd_check(const gcnn_lp_dims* d, const gcnn_lp_remove_dims* m, const 
     return 0;
 }
 
-// Everything the removal enqueues: one fill, three launches.
+// Everything the removal enqueues: one fill, three launches.  counts: null, or where the caller keeps the cleared removed counters
+// (vcnt + vpart, LpdScratch::clear_bytes) and has enqueued their fill itself (gcnn_lpedits.hpp: one fill for all sessions).
 static int lpd_enqueue(const gcnn_lp_dims* d, const gcnn_lp_remove_dims* m, const gcnn_lp_dims* mid, const int32_t* list,
                        const void* const raw_src[5], void* const raw_dst[5], const gcnn_lp_rows_set* src, const gcnn_lp_rows_set* dst,
-                       char* scratch, int32_t* flags_dev, hipStream_t st) {
+                       char* scratch, int32_t* flags_dev, hipStream_t st, char* counts = nullptr) {
     const LpdScratch s = lpd_scratch(d);
     LpdArgs x; memset(&x, 0, sizeof(x));
     x.src = lpa_set(src); x.dst = lpa_set(dst);
@@ -141,24 +142,25 @@ static int lpd_enqueue(const gcnn_lp_dims* d, const gcnn_lp_remove_dims* m, cons
     x.L1 = m->res_lhs_rows - m->n_lhs_rows; x.EL1 = m->res_lhs_edges - m->n_lhs_edges;
     x.V = d->n_cols; x.nvc = lp_chunks(x.V); x.nrc = lp_chunks(x.R0);
     x.part_a = (int*)(scratch + s.part_a); x.part_b = (int*)(scratch + s.part_b);
-    x.vcnt = (int*)(scratch + s.vcnt); x.vpart = (int*)(scratch + s.vpart); x.row_map = (int*)(scratch + s.row_map);
+    char* cnt = counts ? counts : scratch + s.vcnt;
+    x.vcnt = (int*)cnt; x.vpart = (int*)(cnt + (s.vpart - s.vcnt)); x.row_map = (int*)(scratch + s.row_map);
     x.row_new = (int*)(scratch + s.row_new);
     x.nb_var = (x.V + LP_NT / LP_SUB - 1) / (LP_NT / LP_SUB); x.nb_edges = lp_chunks(x.E0); x.nb_raw = lp_chunks(x.N0);
     x.flags_out = flags_dev;
-    HIPCHK(hipMemsetAsync(scratch + s.vcnt, 0, s.clear_bytes, st));      // the removed counters (no launch of the library's own)
+    if (!counts) HIPCHK(hipMemsetAsync(cnt, 0, s.clear_bytes, st));      // the removed counters (no launch of the library's own)
     {
         ProfScope prof("k_lpd_mark", st);
-        hipLaunchKernelGGL(k_lpd_mark, dim3(x.nrc), dim3(LP_NT), 0, st, x);
+        GCNN_LAUNCH(k_lpd_mark, dim3(x.nrc), dim3(LP_NT), 0, st, x);
         LAUNCHCHK();
     }
     {
         ProfScope prof("k_lpd_rows", st);
-        hipLaunchKernelGGL(k_lpd_rows, dim3(x.nrc + 1 + lp_chunks(x.V + 1)), dim3(LP_NT), 0, st, x);
+        GCNN_LAUNCH(k_lpd_rows, dim3(x.nrc + 1 + lp_chunks(x.V + 1)), dim3(LP_NT), 0, st, x);
         LAUNCHCHK();
     }
     if (x.nb_var + x.nb_edges + x.nb_raw > 0) {
         ProfScope prof("k_lpd_vars", st);
-        hipLaunchKernelGGL(k_lpd_vars, dim3(x.nb_var + x.nb_edges + x.nb_raw), dim3(LP_NT), 0, st, x);
+        GCNN_LAUNCH(k_lpd_vars, dim3(x.nb_var + x.nb_edges + x.nb_raw), dim3(LP_NT), 0, st, x);
         LAUNCHCHK();
     }
     return 0;

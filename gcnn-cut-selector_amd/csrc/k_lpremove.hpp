@@ -28,6 +28,8 @@
 //               row plus its place in the row.  Raw blocks, a thread per old raw entry: its row by binary search over the old
 //               row_ptr, then likewise.  (These copies wait for k_lpd_rows's offsets, so they ride in the last launch; with a
 //               thread per entry a small LP with long rows still fills the device, which a block per 256 rows did not.)
+// Each kernel is its body (lpd_mark_body, lpd_rows_body, lpd_vars_body) called with blockIdx.x: none strides by its grid, so the
+// block index is all the group twins of k_lpedits.hpp need to run the same bodies for one member of a grouped call.
 // The maps cost no launch of their own (k_lpd_rows writes them where it has the row in hand); a sorted list of removed state rows
 // would need a pass to build.  Integer atomics only; every store is bounds-checked against the sizes the host computed; no scratch
 // memory, under 16 KiB of LDS.
@@ -76,9 +78,9 @@ __device__ __forceinline__ LpdRow lpd_row(const LpdArgs& x, int r) {
     return w;
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lpd_mark(LpdArgs x) {
+__device__ __forceinline__ void lpd_mark_body(const LpdArgs& x, const int blk) {
     __shared__ int s_cnt[8];
-    const int t = threadIdx.x, blk = blockIdx.x;
+    const int t = threadIdx.x;
     if (t < 8) s_cnt[t] = 0;
     __syncthreads();
     const int r = blk * LP_NT + t;
@@ -111,10 +113,12 @@ __global__ __launch_bounds__(LP_NT) void k_lpd_mark(LpdArgs x) {
     }
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lpd_rows(LpdArgs x) {
+__global__ __launch_bounds__(LP_NT) void k_lpd_mark(LpdArgs x) { lpd_mark_body(x, blockIdx.x); }
+
+__device__ __forceinline__ void lpd_rows_body(const LpdArgs& x, const int blk) {
     __shared__ int si[4 * LP_NT];
     __shared__ int s_front;
-    const int t = threadIdx.x, blk = blockIdx.x;
+    const int t = threadIdx.x;
     if (blk > x.nrc) {                                         // ---- variable blocks: the new v_ptr
         const int b = blk - x.nrc - 1;
         const int j = b * LP_NT + t;
@@ -180,9 +184,10 @@ __global__ __launch_bounds__(LP_NT) void k_lpd_rows(LpdArgs x) {
     }
 }
 
-__global__ __launch_bounds__(LP_NT) void k_lpd_vars(LpdArgs x) {
+__global__ __launch_bounds__(LP_NT) void k_lpd_rows(LpdArgs x) { lpd_rows_body(x, blockIdx.x); }
+
+__device__ __forceinline__ void lpd_vars_body(const LpdArgs& x, int b) {
     const int t = threadIdx.x;
-    int b = blockIdx.x;
     if (b < x.nb_var) {                                        // ---- variables: LP_SUB lanes each, the segment compacted in order
         const int v = b * (LP_NT / LP_SUB) + t / LP_SUB, l = t % LP_SUB;
         if (v >= x.V) return;
@@ -231,3 +236,4 @@ __global__ __launch_bounds__(LP_NT) void k_lpd_vars(LpdArgs x) {
     const int k = e - x.raw_ptr[r], to = x.out_ptr[q] + k;
     if (k >= 0 && lp_in(to, x.N1)) { x.out_col[to] = x.raw_col[e]; x.out_val[to] = x.raw_val[e]; }
 }
+__global__ __launch_bounds__(LP_NT) void k_lpd_vars(LpdArgs x) { lpd_vars_body(x, blockIdx.x); }

@@ -760,8 +760,7 @@ class LPSession(_Staging):
     `remove_rows`).  `remove` numbers the rows AFTER the append of the same call, in any order; the round's `row_dual` and
     `row_basis` cover the kept rows in their order; a removal that would leave no row at all is refused (open a new session).
     Either edit is all or nothing: if the call raises, the session holds exactly the rows and derived state it held.  Not
-    covered: a removal inside an `LPSessionGroup`'s batched call (the member takes its solo call) or through the scoring
-    server, and any other change of the LP -- a row changed, a column added, another objective -- which means opening a new
+    covered: any other change of the LP -- a row changed, a column added, another objective -- which means opening a new
     session.  There is no variable limit; an order
     (ranking on the device, selection) takes at most 4,096 cuts, a table at most 2^24 rows.  The session holds no parameters:
     every round reads the model's current flat parameter buffer.  After a rejected round (ValueError, GcnnError) the session
@@ -1301,11 +1300,20 @@ class LPSession(_Staging):
         self._kept.update(given)
         self._stale.difference_update(given)
 
-    def _member(self, job):
-        """The job as a member of gcnn_lp_rounds (the structs it points at live in the job and the session)."""
-        m = _lib.LpRoundsMember()
+    def _member(self, job, edit=False):
+        """The job as a member of gcnn_lp_rounds, or with `edit` of gcnn_lp_rounds_edit, which also takes a job with a removal
+        (the structs it points at live in the job and the session)."""
+        m = _lib.LpRoundsEditMember() if edit else _lib.LpRoundsMember()
         m.dims, m.present, (m.n_forced, m.n_forced_entries) = job.d, job.present, job.fshape
-        if job.blk is None:
+        if job.rm is not None:
+            e, (_, _, dst_struct, res) = job.rm, job.set
+            m.has_remove, m.removed = 1, job.m
+            if job.b is not None:
+                m.has_append, m.block, m.transit = 1, job.b, C.pointer(e.transit[2])
+            m.row_ptr, m.row_col, m.row_val, m.row_lhs, m.row_rhs = (t.data_ptr() for t in self._raw)
+            m.out_ptr, m.out_col, m.out_val, m.out_lhs, m.out_rhs = (t.data_ptr() for t in e.raw_dst)
+            m.src, m.dst, m.resident = C.pointer(self._cur_struct), C.pointer(dst_struct), C.pointer(res)
+        elif job.blk is None:
             m.resident = C.pointer(self._res)
         else:
             _, _, dst_struct, res = job.set
@@ -1399,7 +1407,9 @@ class LPSessionGroup:
     `sessions[i].score(...)` / `.select_cuts(...)` gives with the same arguments, bit for bit, and the session is afterwards in
     the state that solo call leaves.  Errors are per member: a round the host rejects stays out of the call, one the device
     flags raises in its own slot (the session stays usable, as after a rejected solo round), and a member the batched call
-    declines (a ranking left to the host, a shape the recorder cannot take) goes through its solo call and comes back in place:
+    declines (a ranking left to the host, a shape the recorder cannot take, and -- unless the group was made with
+    `batch_removes=True`, which sends a chunk with such a member through gcnn_lp_rounds_edit -- a member that removes rows) goes
+    through its solo call and comes back in place:
     a call the library declines or refuses as a whole is halved until the member it is about stands alone, so the others still
     share their calls, and `solo_rounds` counts every member that was answered by its own call.
     The group owns the call's arena and pinned buffers; they grow as a session's do, and `LPSession.GUARD` applies to the arena."""
@@ -1407,12 +1417,13 @@ class LPSessionGroup:
     CAP = 256
     GUARD = None                      # bytes of guard around the arena; None: `LPSession.GUARD`
 
-    def __init__(self, device):
+    def __init__(self, device, batch_removes=False):
         self.device = torch.device(device)
+        self.batch_removes = bool(batch_removes)      # a member with a removal: inside the batched call (gcnn_lp_rounds_edit), or solo
         self.pin_in = self.pin_out = self.pin_tab = self.arena = self._whole = None
         self.in_np = self.out_np = self.tab_np = None
         self.layouts = {}
-        self.calls = 0                    # gcnn_lp_rounds calls made
+        self.calls = 0                    # gcnn_lp_rounds / gcnn_lp_rounds_edit calls made
         self.max_sessions_per_call = 0    # the most sessions one of them served
         self.solo_rounds = 0              # members answered by their session's own call: left to it, or declined by the batched call
 
@@ -1440,22 +1451,26 @@ class LPSessionGroup:
             else:
                 self.arena = torch.empty(n, dtype=torch.uint8, device=self.device)
 
-    def _layout(self, members, n, mode):
-        L = _lib.LpRoundsLayout()
-        rc = _lib.lib().gcnn_lp_rounds_layout_for(n, members, mode, C.byref(L))
-        return False if _unsupported(rc, "gcnn_lp_rounds_layout_for") else (L, list(L.in_off), list(L.out_off))
+    def _layout(self, members, n, mode, edit=False):
+        name = "gcnn_lp_rounds_edit_layout_for" if edit else "gcnn_lp_rounds_layout_for"
+        L = _lib.LpRoundsEditLayout() if edit else _lib.LpRoundsLayout()
+        rc = getattr(_lib.lib(), name)(n, members, mode, C.byref(L))
+        return False if _unsupported(rc, name) else (L, list(L.in_off), list(L.out_off))
 
     def _call(self, sessions, jobs, mode, p_max, p_max_ub, timings=None):
-        """One gcnn_lp_rounds call over checked jobs: per job its download block (a view of the group's pinned buffer), or None
-        where the library declines the call as a whole (nothing was enqueued); any other refusal raises `GcnnError`, also before
-        anything is enqueued."""
+        """One gcnn_lp_rounds call over checked jobs -- gcnn_lp_rounds_edit where one of them removes rows: per job its download
+        block (a view of the group's pinned buffer), or None where the library declines the call as a whole (nothing was
+        enqueued); any other refusal raises `GcnnError`, also before anything is enqueued."""
         t0 = time.perf_counter()
         n = len(jobs)
-        members = (_lib.LpRoundsMember * n)(*(s._member(j) for s, j in zip(sessions, jobs)))
-        key = (mode,) + tuple(_int_key(j.dims) + (j.present,) + j.fshape + j.block for j in jobs)
+        edit = any(j.rm is not None for j in jobs)
+        name = "gcnn_lp_rounds_edit" if edit else "gcnn_lp_rounds"
+        kind = _lib.LpRoundsEditMember if edit else _lib.LpRoundsMember
+        members = (kind * n)(*(s._member(j, edit) for s, j in zip(sessions, jobs)))
+        key = (mode, edit) + tuple(_int_key(j.dims) + (j.present, j.rm is not None) + j.fshape + j.block for j in jobs)
         lay = self.layouts.get(key)
         if lay is None:
-            lay = self._layout(members, n, mode)
+            lay = self._layout(members, n, mode, edit)
             if len(self.layouts) >= self.CAP:
                 self.layouts.pop(next(iter(self.layouts)))
             self.layouts[key] = lay
@@ -1469,12 +1484,12 @@ class LPSessionGroup:
         P = C.c_void_p
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            rc = _lib.lib().gcnn_lp_rounds(n, members, mode, P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(self.arena.data_ptr()),
+            rc = getattr(_lib.lib(), name)(n, members, mode, P(self.pin_in.data_ptr()), P(self.pin_out.data_ptr()), P(self.arena.data_ptr()),
                                            self.arena.numel(), P(self.pin_tab.data_ptr()), float(p_max), float(p_max_ub),
                                            P(stream.cuda_stream))
             if rc == -4:
                 return None
-            _lib.check(rc, "gcnn_lp_rounds")
+            _lib.check(rc, name)
             t2 = time.perf_counter()
             stream.synchronize()
         if timings is not None:
@@ -1547,16 +1562,16 @@ class LPSessionGroup:
             raise ValueError(f"{what}: one entry per session expected, got {len(items)} for {n} sessions")
         return items
 
-    @staticmethod
-    def _removes(i, removes):
-        """Whether member i comes with a removal: it is then answered through its solo call (gcnn_lp_rounds takes no removal)."""
-        return removes[i] is not None and np.asarray(removes[i]).size > 0
+    def _removes(self, i, removes):
+        """Whether member i comes with a removal that its solo call answers: every removal unless the group was made with
+        `batch_removes` (gcnn_lp_rounds takes none; gcnn_lp_rounds_edit does)."""
+        return not self.batch_removes and removes[i] is not None and np.asarray(removes[i]).size > 0
 
     def score(self, sessions, rounds, rank=False, appends=None, return_exceptions=False, timings=None, removes=None):
         """`sessions[i].score(rounds[i], rank, append=appends[i], remove=removes[i])` for every i, as a list of `ScoreArray`.
         With `return_exceptions` a member's exception sits in its slot; otherwise the first one is raised after every member has
         been served.  A member with a removal is answered through its solo call and comes back in place (counted in
-        `solo_rounds`); the others keep their batched call."""
+        `solo_rounds`) while the others keep their batched call; with `batch_removes` it is a member of the batched call."""
         sessions, rounds = list(sessions), list(rounds)
         appends = self._per_session("appends", appends, len(sessions))
         removes = self._per_session("removes", removes, len(sessions))
@@ -1569,7 +1584,7 @@ class LPSessionGroup:
         def plan(i):
             if (rank and not on_device(i)) or self._removes(i, removes):
                 return None                 # the host ranks this one, or it removes rows: its solo call
-            return sessions[i]._plan(rounds[i], None, appends[i])
+            return sessions[i]._plan(rounds[i], None, appends[i], removes[i] if self.batch_removes else None)
 
         def answer(i, job, out):
             scores, order, _, cut_index = sessions[i]._results(job.dims, job.out_off, bool(rank), False, out)
@@ -1598,7 +1613,7 @@ class LPSessionGroup:
             s.model._check_select_size("LPSession.select_cuts", "round", int(np.asarray(rounds[i].cut_lhs).shape[0]))
             if self._removes(i, removes):
                 return None
-            return s._plan(rounds[i], normalize_forced(forced[i], s.n_cols), appends[i])
+            return s._plan(rounds[i], normalize_forced(forced[i], s.n_cols), appends[i], removes[i] if self.batch_removes else None)
 
         def answer(i, job, out):
             scores, order, n_kept, cut_index = sessions[i]._results(job.dims, job.out_off, True, True, out)

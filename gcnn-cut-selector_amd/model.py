@@ -891,9 +891,9 @@ class ModelSet:
         return GCNN._finish_many(_as_selections(results, max_selected, cut_index=True), return_exceptions)
 
     # ---- rounds of resident LPs of several models in one call (gcnn_lp_rounds) ---------------------------------------------------
-    def _rounds(self, keys, sessions):
+    def _rounds(self, keys, sessions, batch_removes=False):
         """The set's `LPSessionGroup`, once `keys` (taken for symmetry with the other methods: a session knows its model) name the
-        sessions' models."""
+        sessions' models.  `batch_removes`: how this call's members with a removal are served (`LPSessionGroup`)."""
         keys, sessions = list(keys), list(sessions)
         if len(keys) != len(sessions):
             raise ValueError(f"keys: one model key per session expected, got {len(keys)} for {len(sessions)} sessions")
@@ -904,18 +904,20 @@ class ModelSet:
                 raise ValueError(f"the session was not opened on model {k!r}")
         if self._lp_rounds is None:
             self._lp_rounds = LPSessionGroup(next(iter(self.models.values())).device)
+        self._lp_rounds.batch_removes = bool(batch_removes)
         return self._lp_rounds, sessions
 
-    def score_rounds(self, keys, sessions, rounds, rank=False, appends=None, return_exceptions=False):
+    def score_rounds(self, keys, sessions, rounds, rank=False, appends=None, return_exceptions=False, removes=None, batch_removes=False):
         """`LPSessionGroup.score` over sessions opened on this set's models (`models[keys[i]].open_lp(...)`): the rounds of up to 8
-        sessions per call, whatever their models; entry i has the bits of `sessions[i].score(rounds[i], rank, append=appends[i])`."""
-        group, sessions = self._rounds(keys, sessions)
-        return group.score(sessions, rounds, rank, appends, return_exceptions)
+        sessions per call, whatever their models; entry i has the bits of `sessions[i].score(rounds[i], rank, append=appends[i],
+        remove=removes[i])`.  A member with a removal takes its solo call unless `batch_removes` (gcnn_lp_rounds_edit)."""
+        group, sessions = self._rounds(keys, sessions, batch_removes)
+        return group.score(sessions, rounds, rank, appends, return_exceptions, removes=removes)
 
     def select_cuts_rounds(self, keys, sessions, rounds, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, appends=None,
-                           return_exceptions=False):
+                           return_exceptions=False, removes=None, batch_removes=False):
         """`LPSessionGroup.select_cuts` over sessions opened on this set's models; entry i has the bits of
-        `sessions[i].select_cuts(rounds[i], forced[i], ..., append=appends[i])`."""
-        group, sessions = self._rounds(keys, sessions)
+        `sessions[i].select_cuts(rounds[i], forced[i], ..., append=appends[i], remove=removes[i])`; removals as in `score_rounds`."""
+        group, sessions = self._rounds(keys, sessions, batch_removes)
         return group.select_cuts(sessions, rounds, forced, p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected, appends=appends,
-                                 return_exceptions=return_exceptions)
+                                 return_exceptions=return_exceptions, removes=removes)

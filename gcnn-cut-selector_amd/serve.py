@@ -51,8 +51,11 @@ _HYBRID_ARRAYS = len(lpstate.CUT_FIELDS) + 1
 #          checks the O(nnz) facts on the host too.  The reply's n_kept slot carries the session id.
 #   round  n_cons: the session id; n_vars: mode | presence mask of the four optional arrays << 8 | has a block << 12 |
 #          has_incumbent (0 None, 1 False, 2 True) << 13 | incremental << 15.  Arrays: the round's in `lpstate.ROUND_FIELDS` order
-#          without the absent optional ones, then the five arrays of an `LPRowBlock`, then the forced pair.  Mode SESSION_APPEND
-#          carries the block alone (`append_rows`).  The reply is that of the KIND_LP_* kinds, cut_index included.
+#          without the absent optional ones, then the five arrays of an `LPRowBlock`, then the forced pair.  n_cuts (the
+#          header's last word, 0 in every other session request): 1 when the round removes rows; it then carries one more array,
+#          the removed rows' indices (int32, one dimension, numbered after the block's append), behind the block's arrays and in
+#          front of the forced pair.  Mode SESSION_APPEND is an edit alone: a block (`append_rows`), a list (`remove_rows`) or
+#          both, but at least one.  The reply is that of the KIND_LP_* kinds, cut_index included.
 #   close  n_cons: the session id.
 KIND_LP_OPEN, KIND_LP_ROUND, KIND_LP_CLOSE = 7, 8, 9
 SESSION_SCORE, SESSION_RANK, SESSION_SELECT, SESSION_APPEND = 0, 1, 2, 3
@@ -190,9 +193,10 @@ def _round_word(mode, mask=0, has_block=False, has_incumbent=None, incremental=F
 
 
 def encode_round_request(model_key, session, mode, rnd=None, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None, append=None,
-                         incremental=False):
+                         incremental=False, remove=None):
     """-> the message's bytes of a round of session `session`.  `mode`: SESSION_SCORE / _RANK / _SELECT with `rnd` (a
-    `lpstate.LPRound`) and optionally `append` (a `lpstate.LPRowBlock`) and `forced`; SESSION_APPEND with `append` alone."""
+    `lpstate.LPRound`) and optionally `append` (a `lpstate.LPRowBlock`), `remove` (row indices, numbered after the append) and
+    `forced`; SESSION_APPEND with `append`, `remove` or both alone.  A request without a removal has the bytes it always had."""
     arrays, mask, inc = [], 0, None
     if mode != SESSION_APPEND:
         inc = rnd.has_incumbent
@@ -205,14 +209,16 @@ def encode_round_request(model_key, session, mode, rnd=None, forced=None, p_max=
             elif a is None:
                 raise ValueError(f"{name}: a round must give it")
             arrays.append(np.asarray(a))
-    elif append is None:
-        raise ValueError("an append needs its block")
+    elif append is None and remove is None:
+        raise ValueError("an edit needs a block to append or rows to remove")
     if append is not None:
         arrays += [np.asarray(a) for a in append.arrays()]
+    if remove is not None:
+        arrays.append(np.ascontiguousarray(np.asarray(remove).ravel(), dtype=np.int32))
     n_forced, pair = _forced_pair(forced) if mode == SESSION_SELECT else (-1, [])
     key = model_key.encode("utf-8")
     parts = [_header(KIND_LP_ROUND, len(arrays) + len(pair), key, p_max, p_max_ub, max_selected, n_forced, session,
-                     _round_word(mode, mask, append is not None, inc, incremental)), key]
+                     _round_word(mode, mask, append is not None, inc, incremental), int(remove is not None)), key]
     _put_arrays(parts, arrays + pair)
     return b"".join(parts)
 
@@ -222,7 +228,7 @@ def encode_close_request(model_key, session):
     return _header(KIND_LP_CLOSE, 0, key, a=session) + key
 
 
-def _decode_session(kind, arrays, n_forced, n_cons, n_vars):
+def _decode_session(kind, arrays, n_forced, n_cons, n_vars, n_cuts=0):
     """The kind-specific part of a decoded session request."""
     if kind == KIND_LP_OPEN:
         scalars = arrays[7]
@@ -244,22 +250,29 @@ def _decode_session(kind, arrays, n_forced, n_cons, n_vars):
             at += 1
         rnd = lpstate.LPRound(**fields, has_incumbent=None if inc == 0 else inc == 2)
     block = lpstate.LPRowBlock(*arrays[at:at + 5]) if has_block else None
-    return dict(session=n_cons, mode=mode, round=rnd, block=block, incremental=bool(n_vars >> 15 & 1),
+    remove = None
+    if n_cuts:
+        remove = arrays[at + 5 * has_block]
+        if remove.dtype != np.int32 or remove.ndim != 1:
+            raise ProtocolError("malformed list of removed rows")
+    return dict(session=n_cons, mode=mode, round=rnd, block=block, remove=remove, incremental=bool(n_vars >> 15 & 1),
                 forced=(arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
 
 
-def _session_arrays(kind, n_forced, n_vars):
+def _session_arrays(kind, n_forced, n_vars, n_cuts=0):
     """How many arrays a well-formed session request of this header carries; -1 for a header that is not one."""
     if kind == KIND_LP_OPEN:
         return 8
     if kind == KIND_LP_CLOSE:
         return 0
+    if n_cuts not in (0, 1):
+        return -1
     mode, mask, has_block, inc = n_vars & 255, n_vars >> 8 & 15, n_vars >> 12 & 1, n_vars >> 13 & 3
     if n_vars < 0 or n_vars >> 16 or mode > SESSION_APPEND or inc == 3 or (n_forced >= 0 and mode != SESSION_SELECT):
         return -1
     if mode == SESSION_APPEND:
-        return 5 if has_block and not mask else -1
-    return _ROUND_BASE + bin(mask).count("1") + 5 * has_block + (2 if n_forced >= 0 else 0)
+        return 5 * has_block + n_cuts if (has_block or n_cuts) and not mask else -1
+    return _ROUND_BASE + bin(mask).count("1") + 5 * has_block + n_cuts + (2 if n_forced >= 0 else 0)
 
 
 def _decode_hybrid(arrays, n_forced):
@@ -289,7 +302,7 @@ def decode_request(buf):
     hybrid = kind == KIND_HYBRID_SELECT
     session = kind in _SESSION_KINDS
     if session:
-        expected = _session_arrays(kind, n_forced, n_vars)
+        expected = _session_arrays(kind, n_forced, n_vars, n_cuts)
     else:
         expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0)
     if magic != MAGIC or kind > KIND_LP_CLOSE or n_arrays != expected or (lp and n_cons not in (0, 1)):
@@ -303,7 +316,7 @@ def decode_request(buf):
         raise ProtocolError("trailing bytes")
     if session:
         return dict(model_key=key, kind=kind, p_max=p_max, p_max_ub=p_max_ub, max_selected=None if max_selected < 0 else max_selected,
-                    **_decode_session(kind, arrays, n_forced, n_cons, n_vars))
+                    **_decode_session(kind, arrays, n_forced, n_cons, n_vars, n_cuts))
     if lp or hybrid:
         snap, forced = _decode_hybrid(arrays, n_forced) if hybrid else _decode_lp(arrays, n_cons, n_forced)
         return dict(model_key=key, kind=kind, snapshot=snap, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
@@ -443,10 +456,11 @@ class ScoringClient:
 
 
 class RemoteLPSession:
-    """An `infer.LPSession` held by a scoring server, as a worker sees it (NumPy only): `score`, `select_cuts`, `append_rows`,
-    `close`, `n_rows`, `n_cols` and use as a context manager, with `LPSession`'s signatures and results (`Scores` / `Selection`
-    with `cut_index`).  The server answers the rounds of different workers that wait at the same time with one call on the device;
-    every reply has the bits of the session's own call.  `timings` is accepted for the signature's sake and left alone."""
+    """An `infer.LPSession` held by a scoring server, as a worker sees it (NumPy only): `score`, `select_cuts` (with `append=` and
+    `remove=`), `append_rows`, `remove_rows`, `close`, `n_rows`, `n_cols` and use as a context manager, with `LPSession`'s
+    signatures and results (`Scores` / `Selection` with `cut_index`); `n_rows` follows the edits the server accepted.  The
+    server answers the rounds of different workers that wait at the same time with one call on the device; every reply has the
+    bits of the session's own call.  `timings` is accepted for the signature's sake and left alone."""
 
     def __init__(self, client, session, n_rows, n_cols):
         self.client, self.session, self._n_rows, self.n_cols, self.closed = client, session, n_rows, n_cols, False
@@ -455,24 +469,28 @@ class RemoteLPSession:
     def n_rows(self):
         return self._n_rows
 
-    def _round(self, mode, rnd, append, **kw):
+    def _round(self, mode, rnd, append, remove=None, **kw):
         if self.closed:
             raise ServerError("the LP session is closed")
-        reply = self.client._call(encode_round_request(self.client.model_key, self.session, mode, rnd, append=append, **kw))
-        if append is not None:
-            self._n_rows += int(np.asarray(append.row_lhs).shape[0])      # (the call raised if the server did not adopt them)
+        n_block = 0 if append is None else int(np.asarray(append.row_lhs).shape[0])
+        idx = lpstate.check_remove(remove, self._n_rows + n_block)      # (a bad index raises here, in the worker)
+        if idx.size and idx.size == self._n_rows + n_block:
+            raise ValueError("remove: the removal would leave no row at all; open a new session instead")
+        reply = self.client._call(encode_round_request(self.client.model_key, self.session, mode, rnd, append=append,
+                                                       remove=idx if idx.size else None, **kw))
+        self._n_rows += n_block - int(idx.size)                           # (the call raised if the server did not adopt the edits)
         return reply
 
-    def score(self, rnd, rank=False, timings=None, append=None):
-        arrays, _, _ = self._round(SESSION_RANK if rank else SESSION_SCORE, rnd, append)
+    def score(self, rnd, rank=False, timings=None, append=None, remove=None):
+        arrays, _, _ = self._round(SESSION_RANK if rank else SESSION_SCORE, rnd, append, remove)
         scores = arrays[0].view(Scores)
         scores.cut_index = arrays[-1]
         if rank:
             scores.rankings = arrays[1]
         return scores
 
-    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None):
-        arrays, n_kept, n_selected = self._round(SESSION_SELECT, rnd, append, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
+    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None, remove=None):
+        arrays, n_kept, n_selected = self._round(SESSION_SELECT, rnd, append, remove, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
                                                  max_selected=max_selected)
         return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
 
@@ -480,6 +498,11 @@ class RemoteLPSession:
         block = lpstate.LPRowBlock(row_ptr, row_col, row_val, row_lhs, row_rhs)
         if np.asarray(row_lhs).shape[0]:
             self._round(SESSION_APPEND, None, block, incremental=incremental)
+
+    def remove_rows(self, remove):
+        """`LPSession.remove_rows` behind the server: only the indices go over the wire.  Removing zero rows is a no-op."""
+        if remove is not None and np.asarray(remove).size:
+            self._round(SESSION_APPEND, None, None, remove)
 
     def close(self):
         if not self.closed:
@@ -510,7 +533,9 @@ class ScoringServer:
     closed when that connection drops.  The rounds that wait together are grouped by mode and thresholds, across models, and each
     group goes to `session_group` (default: an `infer.LPSessionGroup` on the first model's device, built on first use) in calls
     of up to 8 sessions; two requests of one session are never in one call: they are served in arrival order in successive ones.
-    Opens, closes and `append_rows` are served one by one.  `stats` counts sessions_open, session_rounds (rounds served),
+    Rounds with and without a removal share their calls: the default group is made with `batch_removes=True`
+    (gcnn_lp_rounds_edit), and `removes=` is handed to the group only in a call where a member removes rows.
+    Opens, closes, `append_rows` and `remove_rows` are served one by one.  `stats` counts sessions_open, session_rounds (rounds served),
     session_calls (batched calls the group made on the device: its own counter), max_sessions_per_call (the most sessions one of
     them served) and session_solo_rounds (rounds the group answered through the session's own call: a ranking left to the host, a
     member the batched call declined)."""
@@ -591,7 +616,7 @@ class ScoringServer:
     def _group(self):
         if self._session_group is None:
             from .infer import LPSessionGroup
-            self._session_group = LPSessionGroup(next(iter(self.models.values())).device)
+            self._session_group = LPSessionGroup(next(iter(self.models.values())).device, batch_removes=True)
         return self._session_group
 
     def _close_session(self, sid):
@@ -689,7 +714,7 @@ class ScoringServer:
                         self._close_session(req["session"])
                         self._reply(conn, encode_reply())
                     elif req["mode"] == SESSION_APPEND:
-                        sess.append_rows(*req["block"].arrays(), incremental=req["incremental"])
+                        self._edit_alone(sess, req)
                         self._reply(conn, encode_reply())
                     else:
                         gkey = (req["mode"],) + ((req["p_max"], req["p_max_ub"]) if req["mode"] == SESSION_SELECT else ())
@@ -700,19 +725,35 @@ class ScoringServer:
                 for lo in range(0, len(members), self.SESSIONS_PER_CALL):
                     self._serve_rounds(gkey, members[lo:lo + self.SESSIONS_PER_CALL])
 
+    @staticmethod
+    def _edit_alone(sess, req):
+        """An edit without a round: the block appended, then the rows removed that the list names (numbered after the append;
+        those that point into the block never reach the device).  Everything the host can refuse is refused before either."""
+        block, remove = req["block"], req.get("remove")
+        if remove is None:
+            sess.append_rows(*block.arrays(), incremental=req["incremental"])
+            return
+        idx, block = lpstate.split_remove(remove, sess.n_rows, block)
+        if block is not None:
+            sess.append_rows(*block.arrays(), incremental=req["incremental"])
+        if idx.size:
+            sess.remove_rows(idx)
+
     def _serve_rounds(self, gkey, members):
         mode = gkey[0]
         sessions, rounds = [m[2] for m in members], [m[1]["round"] for m in members]
         appends = [m[1]["block"] for m in members]
+        removes = [m[1].get("remove") for m in members]
+        more = dict(removes=removes) if any(r is not None for r in removes) else {}      # (a group without the keyword keeps working)
         self.stats["session_rounds"] += len(members)
         group = self._group()
         before = (group.calls, group.solo_rounds)
         try:
             if mode == SESSION_SELECT:
                 results = group.select_cuts(sessions, rounds, [m[1]["forced"] for m in members], p_max=gkey[1], p_max_ub=gkey[2],
-                                                    appends=appends, return_exceptions=True)
+                                                    appends=appends, return_exceptions=True, **more)
             else:
-                results = group.score(sessions, rounds, rank=mode == SESSION_RANK, appends=appends, return_exceptions=True)
+                results = group.score(sessions, rounds, rank=mode == SESSION_RANK, appends=appends, return_exceptions=True, **more)
         except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
             results = [exc] * len(members)
         # the group's own counters: a hand-off whose members the host rejects, or that goes to solo calls, makes no batched call

@@ -841,8 +841,8 @@ int gcnn_lp_round_append(const gcnn_lp_dims* dims, const gcnn_lp_append_dims* bl
  * Returned before anything is enqueued: GCNN_E_BADARG (counts that cannot be: negative, more removed than resident, lhs counts above
  * the totals, nothing left after the whole edit; a missing pointer; a misaligned cons_feats; a source set, raw buffer or transit set
  * that overlaps a destination; a short or misaligned arena; thresholds that are not finite), GCNN_E_WORKSPACE (a short scratch) and
- * GCNN_E_UNSUPPORTED (the round's limits on the dims after the edit).  Not part of gcnn_lp_rounds: a member with a removal takes
- * this call. */
+ * GCNN_E_UNSUPPORTED (the round's limits on the dims after the edit).  Not part of gcnn_lp_rounds; gcnn_lp_rounds_edit (below) takes a
+ * member with a removal and gives it what this call gives. */
 typedef struct gcnn_lp_remove_dims {
     int32_t n_rows, row_nnz, n_state_rows, n_state_edges;   /* the removed rows */
     int32_t n_lhs_rows, n_lhs_edges;                          /* of them, lhs sides */
@@ -921,6 +921,63 @@ int gcnn_lp_rounds_layout_for(int32_t n, const gcnn_lp_rounds_member* members /*
                               gcnn_lp_rounds_layout* layout /* host */);
 int gcnn_lp_rounds(int32_t n, const gcnn_lp_rounds_member* members /* host */, int32_t mode, const void* host_in, void* host_out,
                    void* arena, size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
+
+/* ---- rounds of several resident LPs in one call, with removals ------------------------------------------------------------------------
+ * gcnn_lp_rounds with an optional removal per member: what the server holds when the workers' solvers clean their LPs between rounds.
+ * A member holds what gcnn_lp_rounds_member holds, in the same order; with has_remove it adds the remaining arguments of
+ * gcnn_lp_round_remove: `removed`, the five out_* raw buffers and, needed only with has_append, `transit`.  dims then describe the LP
+ * BEFORE any edit, row_* are the raw SOURCE (read), src is read by the removal, resident points at dst, and block's res_lhs_* are the
+ * counts after the removal, exactly as in the solo call.  A member with has_remove = 0 means what it means in gcnn_lp_rounds.
+ * The contract is gcnn_lp_rounds', extended: every member's download block (the solo call's, the append's flag words at the solo
+ * append_flags_off / flags_off, the removal's four at the solo flags_off) and everything the member leaves resident (cons_feats, the
+ * optional column buffers, the out_* raw rows, dst, the transit set) have the bits of the member's solo call on that member alone --
+ * gcnn_lp_round / _select, gcnn_lp_round_append or gcnn_lp_round_remove, as its edits require.  The removal's three launches have group
+ * twins like every other launch (k_lpes_mark, k_lpes_rows, k_lpes_vars run the bodies of k_lpd_mark, k_lpd_rows, k_lpd_vars with the
+ * member's arguments and its solo block index).
+ * Three phases, each recorded and planned on its own: the removals (at most 3 stages), the appends (at most 4) reading what the
+ * removals wrote, the rounds -- so the members' round launches share their stages whatever edits a member carries.  For n same-shaped
+ * members the launches are those of one solo call of the same kind whatever n is: 11 plain, 14 with a removal, 15 with an append, 18
+ * with both.  Enqueued: ONE upload of all members' uploads, ONE of the launch tables, at most ONE fill (the removals' counters and the
+ * appends' count tables lie side by side: counts_base, counts_bytes), the launches, ONE download; no host wait, no device-to-device
+ * copy.  A member whose state after the edits has no constraint rows, columns or cuts: its edits ride in the edit phases, its
+ * round's solo launches run inside the call, behind the others.
+ * The arena: all uploads, member after member at in_off[i] (each the solo upload -- the list, the block, the round, the forced rows, as
+ * gcnn_lp_remove_layout_for / gcnn_lp_append_layout_for / gcnn_lp_round_layout_for lay it out; in_size[i] = the solo in_bytes rounded up
+ * to 256) | per member at arena_off[i] the solo arena (the round's at member_round_off[i], the append's scratch at scratch_off[i], the
+ * removal's at remove_scratch_off[i]; its counters are not used there) | the fill region: per member the removal's counters at
+ * remove_counts_off[i], then the append's count tables at counts_off[i] | all download blocks at out_off[i] from out_base on | the
+ * launch tables at table_off (sized for 3 + 4 + 16 stages a member).  host_staging: pinned, table_bytes.
+ * Returned before anything is enqueued: what gcnn_lp_rounds returns, on the dims each check applies to; what gcnn_lp_round_remove
+ * refuses of a member (its counts, a missing out_* or transit, a transit set equal to src or dst, out_* over the raw source); across
+ * members the overlap rule extended by what a removing member writes (out_*, the transit set, dst) and reads (src, the raw source). */
+typedef struct gcnn_lp_rounds_edit_member {
+    gcnn_lp_dims dims;
+    int32_t present, n_forced, n_forced_entries;
+    int32_t has_append;
+    gcnn_lp_append_dims block;                                              /* has_append */
+    int32_t* row_ptr; int32_t* row_col; double* row_val; double* row_lhs; double* row_rhs;   /* an edit: the raw rows (device) */
+    const gcnn_lp_rows_set* src; const gcnn_lp_rows_set* dst;             /* an edit (host) */
+    const gcnn_lp_resident* resident;                                       /* host */
+    const float* params;
+    int32_t has_remove, reserved;
+    gcnn_lp_remove_dims removed;                                            /* has_remove */
+    int32_t* out_ptr; int32_t* out_col; double* out_val; double* out_lhs; double* out_rhs;   /* has_remove: the second raw set (device) */
+    const gcnn_lp_rows_set* transit;                                        /* has_remove and has_append (host) */
+} gcnn_lp_rounds_edit_member;
+typedef struct gcnn_lp_rounds_edit_layout {
+    int32_t n, mode;
+    size_t in_bytes, in_off[GCNN_LP_ROUNDS_MAX], in_size[GCNN_LP_ROUNDS_MAX];
+    size_t arena_off[GCNN_LP_ROUNDS_MAX], member_round_off[GCNN_LP_ROUNDS_MAX], scratch_off[GCNN_LP_ROUNDS_MAX];
+    size_t remove_scratch_off[GCNN_LP_ROUNDS_MAX];
+    size_t counts_base, counts_bytes, counts_off[GCNN_LP_ROUNDS_MAX], remove_counts_off[GCNN_LP_ROUNDS_MAX];
+    size_t out_base, out_bytes, out_off[GCNN_LP_ROUNDS_MAX], out_size[GCNN_LP_ROUNDS_MAX];   /* out_off: relative to out_base */
+    size_t table_off, table_bytes;
+    size_t arena_bytes;
+} gcnn_lp_rounds_edit_layout;
+int gcnn_lp_rounds_edit_layout_for(int32_t n, const gcnn_lp_rounds_edit_member* members /* host; only the sizes are read */, int32_t mode,
+                                   gcnn_lp_rounds_edit_layout* layout /* host */);
+int gcnn_lp_rounds_edit(int32_t n, const gcnn_lp_rounds_edit_member* members /* host */, int32_t mode, const void* host_in, void* host_out,
+                        void* arena, size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
 
 #ifdef __cplusplus
 }
