@@ -855,6 +855,7 @@ extern "C" int gcnn_forward(const gcnn_dims* d, const float* p, const float* con
 }
 // ---- single-state inference: the SCIP cut selector's call (model_evaluator.py:82-111) as ONE entry point --------------------
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // Byte carver of the call layouts (this one, gcnn_select.hpp, gcnn_lpstate.hpp, gcnn_ibatch.hpp): take() hands out the running offset
 // and moves it on by `bytes` rounded up to `align` -- 16 inside an upload or a scratch block, 256 for a block of the device arena.
 struct Carver {
@@ -1384,11 +1385,12 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lpmodels.hpp"
 // an LP resident on the device across separation rounds (include/gcnn_hip.h: gcnn_lp_rows_build, gcnn_lp_round): launch names k_lpr_*
 #include "gcnn_lpres.hpp"
-// rows appended to a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_append, gcnn_lp_round_append): launch names k_lpa_*
+// rows appended to a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_append): launch names k_lpa_*
 #include "gcnn_lpappend.hpp"
-// rows removed from a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_remove, gcnn_lp_round_remove): launch names k_lpd_*
+// rows removed from a resident LP without a rebuild (include/gcnn_hip.h: gcnn_lp_rows_remove): launch names k_lpd_*; and the round with
+// edits, solo: one description, plan, check and enqueue of "removal, append, round" (gcnn_lp_round_append, gcnn_lp_round_remove)
 #include "gcnn_lpremove.hpp"
-// rounds of several resident LPs in one call (gcnn_lp_rounds)
+// the twins of the appends' and rounds' launches for calls of several resident LPs: launch names k_lprs_*
 #include "gcnn_lprounds.hpp"
-// the same with an optional removal per member (gcnn_lp_rounds_edit)
+// rounds of several resident LPs in one call, on the same edit plan (gcnn_lp_rounds, gcnn_lp_rounds_edit): launch names k_lpes_*
 #include "gcnn_lpedits.hpp"

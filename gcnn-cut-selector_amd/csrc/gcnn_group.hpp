@@ -64,9 +64,10 @@ static GroupKernel* group_kernel(const void* solo) {
 }
 
 // every launch of the step: a head and at least one record (each padded to 64 B at most); GCNN_GROUP_MAX_STAGES launches per
-// member at most.  (What a step uploads is what it uses: records at their own size, about 40 KB per setcov member.)
-static inline size_t group_table_bytes(int n) {
-    return (size_t)n * GCNN_GROUP_MAX_STAGES * (sizeof(GroupHead) + ((al16(GROUP_REC_BYTES) + 63) & ~(size_t)63));
+// member at most (stages: of a call that records more phases, gcnn_lpedits.hpp).  (What a step uploads is what it uses: records at
+// their own size, about 40 KB per setcov member.)
+static inline size_t group_table_bytes(int n, int stages = GCNN_GROUP_MAX_STAGES) {
+    return (size_t)n * stages * (sizeof(GroupHead) + ((al16(GROUP_REC_BYTES) + 63) & ~(size_t)63));
 }
 
 extern "C" int gcnn_group_table_bytes(int32_t n_members, size_t* bytes) {

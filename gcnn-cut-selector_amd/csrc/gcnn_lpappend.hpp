@@ -1,7 +1,8 @@
-// gcnn_lpappend.hpp -- host side of the incremental append to a resident LP (k_lpappend.hpp): gcnn_lp_rows_append, the append alone,
-// and gcnn_lp_round_append, the append inside the call of the round that follows it.  Included at the end of gcnn_capi.hip behind
-// gcnn_lpres.hpp (it shares that file's lpr_check / lpr_run and layout, and everything they share), kept apart so that its launch
-// names form their own inventory (tests/test_lpappend_build.py).
+// gcnn_lpappend.hpp -- host side of the incremental append to a resident LP (k_lpappend.hpp): its layout, check and launches
+// (lpa_layout, lpa_check, lpa_enqueue) and gcnn_lp_rows_append, the append alone.  The append inside the call of the round that
+// follows it (gcnn_lp_round_append) is one case of the round with edits, gcnn_lpremove.hpp.  Included at the end of gcnn_capi.hip
+// behind gcnn_lpres.hpp (it shares that file's layout and everything they share), kept apart so that its launch names form their
+// own inventory (tests/test_lpappend_build.py).
 #include "k_lpappend.hpp"
 
 // scratch carving: row_stat | row_part | blk_flags | cnt + vpart (one cleared block) | vsplit | ent_rank | tmp_row | tmp_coef
@@ -82,7 +83,7 @@ static LpaSet lpa_set(const gcnn_lp_rows_set* s) {
 // Everything the append enqueues.  blk_*: where the launches read the block (the upload slot with offsets from 0, or the raw rows'
 // tail with absolute offsets: ent_base says which); raw_*: non-null in the fused call, where k_lpa_stats copies the block to.
 // counts: null, or where the caller keeps the cleared count tables (cnt + vpart, LpaScratch::clear_bytes) and has enqueued their
-// fill itself (gcnn_lprounds.hpp: one fill for all sessions).
+// fill itself (gcnn_lpedits.hpp: one fill for all sessions).
 static int lpa_enqueue(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, const int* blk_ptr,
                        const int* blk_col, const double* blk_val, const double* blk_lhs, const double* blk_rhs, int nnz_bound, int ent_base,
                        int32_t* const raw[2], double* const rawd[3], const double* col_obj, const gcnn_lp_rows_set* src,
@@ -153,33 +154,4 @@ extern "C" int gcnn_lp_rows_append(const gcnn_lp_dims* d, const gcnn_lp_append_d
     if (scratch_bytes < lpa_scratch(d, b).bytes) return GCNN_E_WORKSPACE;
     return lpa_enqueue(d, b, row_ptr + d->n_rows, row_col, row_val, row_lhs + d->n_rows, row_rhs + d->n_rows, after.row_nnz,
                        d->row_nnz, nullptr, nullptr, col_obj, src, dst, (char*)scratch, flags, (hipStream_t)stream);
-}
-
-extern "C" int gcnn_lp_round_append(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, int32_t present, int32_t n_forced,
-                                    int32_t n_forced_entries, int32_t* row_ptr, int32_t* row_col, double* row_val, double* row_lhs,
-                                    double* row_rhs, const gcnn_lp_rows_set* src, const gcnn_lp_rows_set* dst,
-                                    const gcnn_lp_resident* resident, const float* params, const void* host_in, void* host_out,
-                                    void* arena, size_t arena_bytes, int32_t want_order, double p_max, double p_max_ub, void* stream) {
-    gcnn_lp_append_layout L;
-    int rc = lpa_layout(d, b, present, n_forced, n_forced_entries, &L);
-    if (rc) return rc;
-    gcnn_lp_dims after;
-    if ((rc = lpa_check(d, b, &after, row_ptr, row_col, row_val, row_lhs, row_rhs, resident ? resident->col_obj : nullptr, src, dst))) return rc;
-    if (!arena || ((uintptr_t)arena & 255) || arena_bytes < L.arena_bytes) return GCNN_E_BADARG;
-    char* A = (char*)arena;
-    gcnn_lp_round_layout RL;
-    if ((rc = lpr_check(&after, present, n_forced, n_forced_entries, resident, params, host_in, host_out, A + L.round_off, L.round.arena_bytes,
-                        n_forced >= 0 ? 1 : want_order, p_max, p_max_ub, 16, &RL)))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(A, host_in, L.in_bytes, hipMemcpyHostToDevice, st));          // ONE upload: the block | the round | forced rows
-    int32_t* const raw[2] = {row_ptr, row_col};
-    double* const rawd[3] = {row_val, row_lhs, row_rhs};
-    char* out = A + L.round_off + RL.dev_off[6];
-    if ((rc = lpa_enqueue(d, b, (const int*)(A + L.block_off[0]), (const int*)(A + L.block_off[1]), (const double*)(A + L.block_off[2]),
-                          (const double*)(A + L.block_off[3]), (const double*)(A + L.block_off[4]), b->row_nnz, 0, raw, rawd,
-                          resident->col_obj, src, dst, A + L.scratch_off, (int32_t*)(out + L.flags_off), st)))
-        return rc;
-    return lpr_run(&after, RL, present, n_forced, resident, params, nullptr, host_out, A + L.round_off, n_forced >= 0 ? 1 : want_order, p_max,
-                   p_max_ub, stream);                                                   // ONE download, the append's flags in it
 }

@@ -97,8 +97,8 @@ extern "C" int gcnn_lp_round_layout_for(const gcnn_lp_dims* d, int32_t present, 
 
 // want_order: 1 ranking, 0 scores only, -1 the state only (no forward pass; the download carries the flags and cut_index)
 // lpr_check: everything a round call decides before anything is enqueued, and the layout.  lpr_run: what it enqueues; host_in null:
-// the upload already lies at dev_off[0] of the arena (gcnn_lpappend.hpp's fused call brings it up with the appended rows).
-// at (gcnn_lprounds.hpp's call of several sessions): the upload lies at at->up, the download block is at->out, the forward's flag
+// the upload already lies at dev_off[0] of the arena (gcnn_lpremove.hpp's round with edits brings it up with the list and the block).
+// at (gcnn_lpedits.hpp's calls of several sessions): the upload lies at at->up, the download block is at->out, the forward's flag
 // block is cleared where the download finds it, and nothing is copied: the caller brings everything up and down itself.
 struct LprAt { char* up; char* out; };
 static int lpr_check(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, const gcnn_lp_resident* res,

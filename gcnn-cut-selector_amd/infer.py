@@ -1111,14 +1111,18 @@ class LPSession(_Staging):
         if self.closed:
             raise _lib.GcnnError("the LP session is closed")
 
-    def _checked(self, rnd, n_forced=-1, n_entries=0, row_dims=None, block=None, removed=None):
-        """A round checked on the host -> (arrays, presence mask, dims, layout entry).  An optional array whose device copy a
-        rejected round overwrote travels again from the host copy of the last accepted one.  `row_dims`, `block`: the round
-        comes with an append -- the resident dims after it and the block's eight counts; the layout entry is then the fused
-        call's.  `removed`: it comes with a removal -- the removed rows' eight counts (`row_dims`: after the whole edit;
-        `block`: of the append behind the removal, or None); the layout entry is gcnn_lp_remove_layout_for's."""
+    def _checked(self, rnd, n_forced=-1, n_entries=0, rm=None, blk=None):
+        """A round checked on the host -> (arrays, presence mask, dims, layout record, the edits' counts).  An optional array whose
+        device copy a rejected round overwrote travels again from the host copy of the last accepted one.  `rm`, `blk`: the
+        round's edits (`_edit_host`); the round then covers the rows after them, and the layout is that of the call which
+        carries them.  The counts: the removed rows' eight and the block's eight, each only where there is one."""
         from . import lpstate
         self._open()
+        row_dims = block = removed = None
+        if rm is not None:
+            row_dims, block, removed = rm.final, rm.block, rm.removed
+        elif blk is not None:
+            row_dims, block = blk[2], self._block_dims(blk[1], blk[3])
         arrays, present, dims = lpstate.check_round(rnd, self._dims if row_dims is None else row_dims, self._kept, self.deep_check)
         for q, name in enumerate(lpstate.OPTIONAL):
             needed = not name.startswith("col_primal") or dims["has_incumbent"]
@@ -1127,54 +1131,51 @@ class LPSession(_Staging):
                 present |= 1 << q
         key = _int_key(dims) + (present, n_forced, n_entries) + (block or ()) + (("remove",) + removed if removed else ())
         before = dict(self._dims, n_cuts=dims["n_cuts"], cut_nnz=dims["cut_nnz"], has_incumbent=dims["has_incumbent"])
+        lay = self.cached(key, self._edit_layout, before, removed, block, present, n_forced, n_entries)
+        return arrays, present, dims, lay, (removed or ()) + (block or ())
+
+    @staticmethod
+    def _edit_layout(before, removed, block, present, n_forced, n_entries):
+        """The layout record of a round with its edits, whichever library layout applies (gcnn_lp_remove_layout_for,
+        gcnn_lp_append_layout_for, gcnn_lp_round_layout_for) for the dims BEFORE the edits: `L`, that layout (in_bytes, out_bytes,
+        arena_bytes); the round's `in_off`, `forced_off` and `dev_off`, shifted to the whole upload and the whole arena, and its
+        `out_off`; `block_off`, absolute; `flag_words`, where the download carries the flags of the removal, of the append and of
+        the round, in that order; `d`, `m`, `b`, the ctypes dims of the call (`m`, `b`: None without that edit)."""
+        from . import lpstate
+        m = b = None
         if removed is not None:
-            lay = self.cached(key, self._remove_layout, before, removed, block, present, n_forced, n_entries)
-        elif block is None:
-            lay = self.cached(key, self._layout, dims, present, n_forced, n_entries)
+            d, m, b, L = lpstate.lp_remove_layout(before, removed, block, present, n_forced, n_entries)
+            R, up, arena = L.round, L.list_bytes + L.block_bytes, L.round_off
+            flags = (int(L.flags_off),) + (() if b is None else (int(L.append_flags_off),))
+        elif block is not None:
+            d, b, L = lpstate.lp_append_layout(before, block, present, n_forced, n_entries)
+            R, up, arena, flags = L.round, L.block_bytes, L.round_off, (int(L.flags_off),)
         else:
-            lay = self.cached(key, self._append_layout, before, block, present, n_forced, n_entries)
-        return arrays, present, dims, lay
+            d, L = lpstate.lp_round_layout(before, present, n_forced, n_entries)
+            R, up, arena, flags = L, 0, 0, ()
+        return SimpleNamespace(L=L, in_off=[up + o for o in R.in_off], forced_off=[up + o for o in R.forced_off], out_off=list(R.out_off),
+                               dev_off=[arena + o for o in R.dev_off], block_off=() if b is None else tuple(L.block_off),
+                               flag_words=flags + (R.out_off[4],), d=d, m=m, b=b)
 
-    @staticmethod
-    def _layout(dims, present, n_forced, n_entries):
+    def _edit_host(self, append, remove):
+        """The host half of a round's edits -> (rm, blk): `_removal_host`'s record where resident rows leave, or None; the checked
+        block (`_check_block`), or None.  `remove` numbers the rows after the append: indices that point into the block are
+        resolved here -- the rows are dropped from the block before it is checked -- so the device only sees removals of resident
+        rows followed by an append of the filtered block.  Nothing of the session changes."""
         from . import lpstate
-        _, L = lpstate.lp_round_layout(dims, present, n_forced, n_entries)
-        return L, list(L.in_off), list(L.forced_off), list(L.out_off), list(L.dev_off)
-
-    @staticmethod
-    def _append_layout(before, block, present, n_forced, n_entries):
-        """The fused call's layout entry; the round's offsets are shifted to the whole upload and the whole arena."""
-        from . import lpstate
-        d, b, L = lpstate.lp_append_layout(before, block, present, n_forced, n_entries)
-        R = L.round
-        return (L, [L.block_bytes + o for o in R.in_off], [L.block_bytes + o for o in R.forced_off], list(R.out_off),
-                [L.round_off + o for o in R.dev_off], d, b)
-
-    @staticmethod
-    def _remove_layout(before, removed, block, present, n_forced, n_entries):
-        """The layout entry of a call with a removal; the round's offsets are shifted to the whole upload and the whole arena."""
-        from . import lpstate
-        d, m, b, L = lpstate.lp_remove_layout(before, removed, block, present, n_forced, n_entries)
-        R, base = L.round, L.list_bytes + L.block_bytes
-        return (L, [base + o for o in R.in_off], [base + o for o in R.forced_off], list(R.out_off), [L.round_off + o for o in R.dev_off],
-                d, m, b)
-
-    def upload_bytes(self, rnd, forced=None, append=None, remove=None):
-        """Bytes the one upload of this round would carry (with `forced`: packed forced rows of a selection; with `append`: the
-        block that goes up with it; with `remove`: the list of removed resident rows, and the block without the rows it names)."""
-        from . import lpstate
-        fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
         if remove is not None:
             self._open()
             idx, append = lpstate.split_remove(remove, self.n_rows, append)
             if idx.size:
-                e = self._removal_host(idx, append)
-                return int(self._checked(rnd, *fshape, row_dims=e.final, block=e.block, removed=e.removed)[3][0].in_bytes)
-        if append is not None:
-            blk = self._check_block(append)
-            if blk is not None:
-                return int(self._checked(rnd, *fshape, row_dims=blk[2], block=self._block_dims(blk[1], blk[3]))[3][0].in_bytes)
-        return int(self._checked(rnd, *fshape)[3][0].in_bytes)
+                rm = self._removal_host(idx, append)
+                return rm, rm.blk
+        return None, self._check_block(append) if append is not None else None
+
+    def upload_bytes(self, rnd, forced=None, append=None, remove=None):
+        """Bytes the one upload of this round would carry (with `forced`: packed forced rows of a selection; with `append`: the
+        block that goes up with it; with `remove`: the list of removed resident rows, and the block without the rows it names)."""
+        fshape = (-1, 0) if forced is None else (forced[0].size - 1, forced[1].size)
+        return int(self._checked(rnd, *fshape, *self._edit_host(append, remove))[3].L.in_bytes)
 
     def _check_block(self, block, base=None):
         """An `LPRowBlock` checked on the host -> (arrays, counts, the resident dims after it, the host's counts); None for an
@@ -1189,54 +1190,34 @@ class LPSession(_Staging):
         return arrays, counts, self._after(counts, base[0]), self._host_counts(arrays, base[1:])
 
     # A round's call in three parts, which the solo path (`_run`) and `LPSessionGroup` share: `_plan` (the host half: check,
-    # layout, the raw buffers' room and the other set of an append), `_pack` into a given staging buffer, then either `_enqueue`
-    # (the solo C call) or the group's call, and `_finish` (the verdict half: the download's flags -> raise / adopt / remember).
+    # layout, the buffers the edits write), `_pack` into a given staging buffer, then either `_enqueue` (the solo C call) or the
+    # group's call, and `_finish` (the verdict half: the download's flags -> raise / adopt / remember).  A job has one shape: its
+    # two optional edits `rm` (a removal of resident rows) and `blk` (a block appended behind it), each possibly None, and the round.
     def _plan(self, rnd, forced=None, append=None, remove=None):
-        """check -> layout; with `append` also the room in the raw buffers and the set of derived buffers the append writes.
-        Returns the job the other parts read; nothing of the session changes that a rejected round would have to undo.
-        `remove`: indices into the rows after the append.  Those that point into the block are resolved here -- the rows are
-        dropped from the block before it is checked -- so the device only sees removals of resident rows followed by an append of
-        the filtered block; where no resident row is removed the job is the plain or fused one, launch for launch."""
-        from . import lpstate
-        job = SimpleNamespace(forced=forced, fshape=(-1, 0) if forced is None else (forced[0].size - 1, forced[1].size), rm=None)
-        if remove is not None:
-            self._open()
-            idx, append = lpstate.split_remove(remove, self.n_rows, append)
-            if idx.size:
-                return self._plan_removal(job, rnd, idx, append)
-        job.blk = blk = self._check_block(append) if append is not None else None
-        if blk is None:
-            job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off) = self._checked(rnd, *job.fshape)
-            job.d, job.b, job.set, job.block = _lib.LpDims(**job.dims), None, None, ()
-            job.flag_words = (job.out_off[4],)
-        else:
-            _, counts, row_dims, host = blk
-            job.block = self._block_dims(counts, host)           # the block's eight counts
-            job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off, job.d, job.b) = self._checked(
-                rnd, *job.fshape, row_dims=row_dims, block=job.block)
-            with torch.cuda.device(self.model.device):
-                self._grow_raw(row_dims["n_rows"], row_dims["row_nnz"])
-                job.set = self._other_set(row_dims, host[2])
-            job.flag_words = (int(job.L.flags_off), job.out_off[4])
-        return job
-
-    def _plan_removal(self, job, rnd, idx, append):
-        """`_plan` for a job that removes the resident rows `idx`: the removal reads the current sets and writes the second raw
-        set and the other of `_sets`; with an append behind it the removal writes a transit set (allocated on the first such
-        call, never the current one) and the append goes from there into the other of `_sets`, its rows behind the second raw
-        set's.  Nothing the accepted state's rounds read is written before the call is accepted."""
-        job.rm = e = self._removal_host(idx, append)
-        job.blk, job.block = e.blk, e.removed + (e.block or ())
-        job.arrays, job.present, job.dims, (job.L, job.in_off, job.forced_off, job.out_off, job.dev_off, job.d, job.m, job.b) = self._checked(
-            rnd, *job.fshape, row_dims=e.final, block=e.block, removed=e.removed)
+        """check -> layout -> the buffers the edits write.  Returns the job the other parts read: `rm`, `blk`, the checked round,
+        the fields of its layout record (`_edit_layout`), `block` (the edits' counts: what the layout depends on besides the
+        dims) and `set` (the set of derived buffers the edits leave, or None).  Nothing of the session changes that a rejected
+        round would have to undo: an append extends the raw rows behind the resident ones and writes the other of `_sets`; a
+        removal reads the current sets and writes the second raw set and the other of `_sets`; with an append behind it the
+        removal writes a transit set (allocated on the first such call, never the current one) and the append goes from there
+        into the other of `_sets`, its rows behind the second raw set's.  Where no resident row is removed the job is the plain
+        or the appending one, launch for launch."""
+        job = SimpleNamespace(forced=forced, fshape=(-1, 0) if forced is None else (forced[0].size - 1, forced[1].size), set=None)
+        job.rm, job.blk = rm, blk = self._edit_host(append, remove)
+        job.arrays, job.present, job.dims, lay, job.block = self._checked(rnd, *job.fshape, rm, blk)
+        vars(job).update(vars(lay))           # L, in_off, forced_off, out_off, dev_off, block_off, flag_words, d, m, b
+        if rm is None and blk is None:
+            return job
+        final, max_deg = (blk[2], blk[3][2]) if rm is None else (rm.final, rm.host[2])
         with torch.cuda.device(self.model.device):
-            e.raw_dst = self._raw_other(e.final["n_rows"], e.final["row_nnz"])
-            e.transit = None
-            if e.blk is not None:
-                e.transit = self._transit[0] = self._fit_set(self._transit, 0, e.mid)
-            job.set = self._other_set(e.final, e.host[2])
-        flags = (int(job.L.flags_off),) + ((int(job.L.append_flags_off),) if e.blk is not None else ())
-        job.flag_words = flags + (job.out_off[4],)
+            if rm is None:
+                self._grow_raw(final["n_rows"], final["row_nnz"])
+            else:
+                rm.raw_dst = self._raw_other(final["n_rows"], final["row_nnz"])
+                rm.transit = None
+                if blk is not None:
+                    rm.transit = self._transit[0] = self._fit_set(self._transit, 0, rm.mid)
+            job.set = self._other_set(final, max_deg)
         return job
 
     @staticmethod
@@ -1245,40 +1226,34 @@ class LPSession(_Staging):
         block, the round, the forced rows."""
         from . import lpstate
         if job.rm is not None:
-            n = 4 * job.rm.idx.size
-            buf[:n] = job.rm.idx.view(np.uint8)
-            if job.blk is not None:
-                for off, a in zip(job.L.block_off, job.blk[0]):
-                    if a.size:
-                        buf[off:off + a.nbytes] = a.view(np.uint8)
-            lpstate.pack_round(buf, job.in_off, job.arrays, job.present)
-        elif job.blk is None:
-            lpstate.pack_round(buf, job.in_off, job.arrays, job.present)
-        else:
-            lpstate.pack_append(buf, job.L, job.blk[0], job.arrays, job.present)
+            buf[:4 * job.rm.idx.size] = job.rm.idx.view(np.uint8)
+        if job.blk is not None:
+            for off, a in zip(job.block_off, job.blk[0]):
+                if a.size:
+                    buf[off:off + a.nbytes] = a.view(np.uint8)
+        lpstate.pack_round(buf, job.in_off, job.arrays, job.present)
         if job.forced is not None:
             for off, a in zip(job.forced_off, job.forced):
                 buf[off:off + a.nbytes] = a.view(np.uint8)
 
     def _enqueue(self, job, want_order, p_max, p_max_ub, timings, t0):
-        """The solo call of a packed job and the wait for its download."""
-        P, extra = C.c_void_p, dict(upload_bytes=int(job.L.in_bytes))
-        if job.rm is not None:
-            e, (_, _, dst_struct, res) = job.rm, job.set
-            head = (C.byref(job.d), C.byref(job.m), None if job.b is None else C.byref(job.b), job.present) + job.fshape + tuple(
-                P(t.data_ptr()) for t in self._raw) + tuple(P(t.data_ptr()) for t in e.raw_dst) + (
-                C.byref(self._cur_struct), None if e.transit is None else C.byref(e.transit[2]), C.byref(dst_struct), C.byref(res))
-            self._enqueue_wait("gcnn_lp_round_remove", head, (int(want_order), float(p_max), float(p_max_ub)), timings, t0, **extra)
-        elif job.blk is not None:
+        """The solo call of a packed job and the wait for its download: of the four entry points the one the job's edits ask for."""
+        P, e, d = C.c_void_p, job.rm, C.byref(job.d)
+        tail = (int(want_order), float(p_max), float(p_max_ub))
+        if e is not None or job.blk is not None:      # an edit: from the current sets into `set`, the round on what it leaves
             _, _, dst_struct, res = job.set
-            head = (C.byref(job.d), C.byref(job.b), job.present) + job.fshape + tuple(P(t.data_ptr()) for t in self._raw) + (
-                C.byref(self._cur_struct), C.byref(dst_struct), C.byref(res))
-            self._enqueue_wait("gcnn_lp_round_append", head, (int(want_order), float(p_max), float(p_max_ub)), timings, t0, **extra)
-        elif job.forced is None:
-            self._enqueue_wait("gcnn_lp_round", (C.byref(job.d), job.present, C.byref(self._res)), (int(want_order),), timings, t0, **extra)
+            raw, src, dst = tuple(P(t.data_ptr()) for t in self._raw), C.byref(self._cur_struct), (C.byref(dst_struct), C.byref(res))
+        if e is not None:
+            name = "gcnn_lp_round_remove"
+            head = (d, C.byref(job.m), None if job.b is None else C.byref(job.b), job.present) + job.fshape + raw + tuple(
+                P(t.data_ptr()) for t in e.raw_dst) + (src, None if e.transit is None else C.byref(e.transit[2])) + dst
+        elif job.blk is not None:
+            name, head = "gcnn_lp_round_append", (d, C.byref(job.b), job.present) + job.fshape + raw + (src,) + dst
+        elif job.forced is not None:
+            name, head, tail = "gcnn_lp_round_select", (d, job.present) + job.fshape + (C.byref(self._res),), tail[1:]
         else:
-            self._enqueue_wait("gcnn_lp_round_select", (C.byref(job.d), job.present) + job.fshape + (C.byref(self._res),),
-                               (float(p_max), float(p_max_ub)), timings, t0, **extra)
+            name, head, tail = "gcnn_lp_round", (d, job.present, C.byref(self._res)), tail[:1]
+        self._enqueue_wait(name, head, tail, timings, t0, upload_bytes=int(job.L.in_bytes))
 
     def _finish(self, job, out):
         """The verdict on a job's download block `out`: ValueError for a round or block the device flags (the session keeps the
@@ -1305,22 +1280,18 @@ class LPSession(_Staging):
         (the structs it points at live in the job and the session)."""
         m = _lib.LpRoundsEditMember() if edit else _lib.LpRoundsMember()
         m.dims, m.present, (m.n_forced, m.n_forced_entries) = job.d, job.present, job.fshape
-        if job.rm is not None:
-            e, (_, _, dst_struct, res) = job.rm, job.set
-            m.has_remove, m.removed = 1, job.m
-            if job.b is not None:
-                m.has_append, m.block, m.transit = 1, job.b, C.pointer(e.transit[2])
-            m.row_ptr, m.row_col, m.row_val, m.row_lhs, m.row_rhs = (t.data_ptr() for t in self._raw)
-            m.out_ptr, m.out_col, m.out_val, m.out_lhs, m.out_rhs = (t.data_ptr() for t in e.raw_dst)
-            m.src, m.dst, m.resident = C.pointer(self._cur_struct), C.pointer(dst_struct), C.pointer(res)
-        elif job.blk is None:
-            m.resident = C.pointer(self._res)
-        else:
+        m.resident, m.params = C.pointer(self._res), self.model._flat.data_ptr()
+        if job.set is not None:             # an edit: it reads the current sets and leaves `set`
             _, _, dst_struct, res = job.set
-            m.has_append, m.block = 1, job.b
             m.row_ptr, m.row_col, m.row_val, m.row_lhs, m.row_rhs = (t.data_ptr() for t in self._raw)
             m.src, m.dst, m.resident = C.pointer(self._cur_struct), C.pointer(dst_struct), C.pointer(res)
-        m.params = self.model._flat.data_ptr()
+        if job.b is not None:
+            m.has_append, m.block = 1, job.b
+        if job.rm is not None:
+            m.has_remove, m.removed = 1, job.m
+            m.out_ptr, m.out_col, m.out_val, m.out_lhs, m.out_rhs = (t.data_ptr() for t in job.rm.raw_dst)
+            if job.rm.transit is not None:
+                m.transit = C.pointer(job.rm.transit[2])
         return m
 
     def _run(self, rnd, want_order, timings=None, forced=None, p_max=0.0, p_max_ub=0.0, append=None, remove=None):
