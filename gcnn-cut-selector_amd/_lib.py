@@ -106,6 +106,17 @@ class HybridLayout(C.Structure):
                 ("scratch_base", C.c_size_t * IBATCH_MAX)]
 
 
+LP_COLLECT_OUTPUTS = 14   # GCNN_LP_COLLECT_OUTPUTS
+
+
+class LpCollectLayout(C.Structure):
+    _fields_ = [("in_bytes", C.c_size_t), ("snap_off", C.c_size_t * LP_ARRAYS), ("quality_off", C.c_size_t),
+                ("forced_off", C.c_size_t * 3), ("table_off", C.c_size_t), ("table_bytes", C.c_size_t), ("out_bytes", C.c_size_t),
+                ("out_off", C.c_size_t * LP_COLLECT_OUTPUTS), ("arena_bytes", C.c_size_t), ("out_dev_off", C.c_size_t),
+                ("rows_off", C.c_size_t * 3), ("ws_off", C.c_size_t), ("lp_scratch_off", C.c_size_t),
+                ("hyb_scratch_off", C.c_size_t), ("entry_snap", C.c_size_t * HYBRID_ARRAYS)]
+
+
 GROUP_MAX = 8   # GCNN_GROUP_MAX
 MBATCH_HEAD = 16                                                              # model words in front of the states' models
 MBATCH_TABLE_WORDS = IBATCH_TABLE_COLS * IBATCH_TABLE_STRIDE + MBATCH_HEAD + IBATCH_MAX   # GCNN_MBATCH_TABLE_WORDS
@@ -274,6 +285,8 @@ SIGNATURES = {
     "gcnn_hybrid_layout_for": (C.c_int, [_I, _P, _P, _P, _I, C.POINTER(HybridLayout)]),
     "gcnn_hybrid_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P]),
     "gcnn_hybrid_select": (C.c_int, [_I, _P, _P, _P, _I, _P, _P, _P, _Z, _D, _D, _P]),
+    "gcnn_lp_collect_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, C.POINTER(LpCollectLayout)]),
+    "gcnn_lp_collect": (C.c_int, [C.POINTER(LpDims), _I, _I, _P, _P, _P, _Z, _D, _D, _P]),
     "gcnn_infer_models_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, C.POINTER(MbatchLayout)]),
     "gcnn_infer_models_fill_table": (C.c_int, [_I, _P, _P, _P, _I, _P, _P]),
     "gcnn_infer_models": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),

@@ -1379,6 +1379,8 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lpbatch.hpp"
 // hybrid cut selection from the cut rows of many snapshots (include/gcnn_hip.h: gcnn_hybrid_select): launch names k_hyb_*
 #include "gcnn_hybrid.hpp"
+// the data collector's expert round: state and selection over the caller's quality (include/gcnn_hip.h: gcnn_lp_collect): launch names k_collect_*
+#include "gcnn_collect.hpp"
 // host states of several models in one call (include/gcnn_hip.h: gcnn_infer_models): launch names k_mb_*
 #include "gcnn_mbatch.hpp"
 // raw LP snapshots of several models in one call (include/gcnn_hip.h: gcnn_lp_models): launch names k_lpm_*

@@ -643,3 +643,38 @@ def lp_layout(dims, n_forced=-1, n_entries=0):
     d, L = _lib.LpDims(**dims), _lib.LpLayout()
     _lib.check(_lib.lib().gcnn_lp_layout_for(C.byref(d), n_forced, n_entries, C.byref(L)), "gcnn_lp_layout_for")
     return d, L
+
+
+# ---- the data collector's expert round (collect.py, csrc/gcnn_collect.hpp): what both the in-process call and the server's client use ----
+class CollectResult:
+    """What `collect_lp` answers for an expert round of data_collector.SamplingAgent.cutselselect (data_collector.py:101-195).
+    `state`: the 10-tuple of host arrays `GCNN.state_from_lp(snapshot)` returns; `cut_index` [K] int32: state position -> input
+    cut; `improvements` = quality[cut_index], float64: the labels ALIGNED with `state` -- what a sample writer stores
+    (`utils.save_sample(path, utils.inputs_to_state(res.state), res.improvements)`).
+    `order` [K] int32 (kept cuts first, best first, then the removed ones), `n_kept`, `n_selected` = min(n_kept, max_selected):
+    the plugin's ranking and parallelism filter over `quality`, in INPUT cut indices.
+    `hybrid_quality` [K] float64 and `features` [K, 3] float64 (efficacy, integer support, objective parallelism), input cut
+    order: the plugin's fallback ranking (data_collector.py:145-148) without a second call."""
+
+    def __init__(self, state, cut_index, improvements, order, n_kept, n_selected, hybrid_quality, features):
+        self.state, self.cut_index, self.improvements = state, cut_index, improvements
+        self.order, self.n_kept, self.n_selected = order, n_kept, n_selected
+        self.hybrid_quality, self.features = hybrid_quality, features
+
+    def __repr__(self):
+        return f"CollectResult(n_cuts={self.order.shape[0]}, n_kept={self.n_kept}, n_selected={self.n_selected})"
+
+
+def check_quality(quality, n_cuts):
+    """The expert's quality of an expert round -> a contiguous float64 vector of `n_cuts` finite values, or ValueError.  Integer and
+    float arrays are accepted (cast to float64); anything else, a wrong length or a value that is not finite is refused: the
+    reference records a sample only when every dive solved (data_collector.py:119-133), so -inf and NaN never belong to one."""
+    q = np.asarray(quality)
+    if q.dtype.kind not in "fiu":
+        raise ValueError(f"quality must be a float64 vector, got dtype {q.dtype}")
+    if q.ndim != 1 or q.shape[0] != n_cuts:
+        raise ValueError(f"quality must hold one value per cut ({n_cuts}), got shape {tuple(q.shape)}")
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if not np.isfinite(q).all():
+        raise ValueError("quality: every value must be finite (a round with an unsolved dive is not recorded)")
+    return q

@@ -646,6 +646,15 @@ class GCNN:
             cut_index = cut_index.cpu().numpy()
         return SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
 
+    def collect_lp(self, snapshot, quality, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        """An expert round of the data collector (data_collector.py:101-195): `collect.Collector.collect_lp` on this model's
+        device -- the sample's state and the plugin's selection over the expert's float64 `quality`, in one call.  No parameter
+        of the model is read: a process without a model uses a `Collector` directly."""
+        if getattr(self, "_collector", None) is None:
+            from .collect import Collector
+            self._collector = Collector(self.device)
+        return self._collector.collect_lp(snapshot, quality, forced, p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
+
     def open_lp(self, rows, *, deep=True):
         """Keep an LP on the device across the separation rounds of one node: `rows` (`lpstate.LPRows`) goes up once, every
         `lpstate.LPRound` then uploads only the solve and the candidate cuts.  Returns an `LPSession` (infer.py): `state`, `score`,

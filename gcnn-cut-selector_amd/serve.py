@@ -14,7 +14,8 @@ requests of all models one `ModelSet.score_lps` / `ModelSet.select_cuts_lp_many`
 `GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP kinds one
 `GCNN.score_lps` / `GCNN.select_cuts_lp_many` call -- and goes back for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
 hybrid quality from the cut rows, `client.select_cuts_hybrid`) need no model: those that are waiting are grouped by thresholds and
-answered with one `HybridSelector.select_cuts_many`.
+answered with one `HybridSelector.select_cuts_many`.  The data collector's expert rounds (`client.collect_lp`: the sample's state and
+the selection over the expert's quality, `collect.Collector`) need no model either and are answered one by one.
 
 Wire format (AF_UNIX stream; little-endian; no pickle -- nothing a peer sends is ever executed): a message is a uint32 byte count
 followed by that many bytes: a fixed header, the model key, then arrays, each a 24-byte descriptor (dtype code, ndim, two
@@ -62,6 +63,11 @@ SESSION_SCORE, SESSION_RANK, SESSION_SELECT, SESSION_APPEND = 0, 1, 2, 3
 _SESSION_KINDS = (KIND_LP_OPEN, KIND_LP_ROUND, KIND_LP_CLOSE)
 _ROUND_BASE = len(lpstate.ROUND_FIELDS) - len(lpstate.OPTIONAL)
 _PRIMAL = (14, 15)         # positions of col_primal / col_primal_avg among lpstate.FIELDS
+# An expert round of the data collector (collect.Collector.collect_lp; no model: the model key is ignored): KIND_LP_SELECT's arrays,
+# then one float64 array [K] with the expert's quality in input cut order, in front of the optional forced pair.  The reply carries
+# the seven state arrays, cut_index, improvements, order, the hybrid quality and the features; n_kept and n_selected in its header.
+# Kind 10 stays unknown.  There is no session mode: a collector has no use for a resident LP.
+KIND_COLLECT = 11
 MAX_MESSAGE = 1 << 30
 # request: magic, kind, n_arrays, key length, p_max, p_max_ub, max_selected (-1: none), n_forced (-1: no forced rows), n_cons, n_vars, n_cuts
 _REQ = struct.Struct("<4sBBHddiiiii")
@@ -167,6 +173,22 @@ def encode_hybrid_request(model_key, snapshot, forced=None, p_max=0.1, p_max_ub=
     key = model_key.encode("utf-8")
     parts = [_REQ.pack(MAGIC, KIND_HYBRID_SELECT, len(arrays) + len(pair), len(key), float(p_max), float(p_max_ub),
                        -1 if max_selected is None else int(max_selected), n_forced, 0, 0, 0), key]
+    _put_arrays(parts, arrays + pair)
+    return b"".join(parts)
+
+
+def encode_collect_request(model_key, snapshot, quality, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
+    """-> the message's bytes of an expert round.  The snapshot and the quality are checked here as the server will check them
+    again (`lpstate.check_snapshot` without the O(nnz) facts, `lpstate.check_quality`), so their ValueError is raised in the worker."""
+    arrays, dims = lpstate.check_snapshot(snapshot, deep=False)
+    q = lpstate.check_quality(quality, dims["n_cuts"])
+    inc = dims["has_incumbent"]
+    arrays = [a for i, a in enumerate(arrays) if inc or i not in _PRIMAL]
+    arrays.append(np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64))
+    arrays.append(q)
+    n_forced, pair = _forced_pair(forced)
+    key = model_key.encode("utf-8")
+    parts = [_header(KIND_COLLECT, len(arrays) + len(pair), key, p_max, p_max_ub, max_selected, n_forced, inc), key]
     _put_arrays(parts, arrays + pair)
     return b"".join(parts)
 
@@ -298,14 +320,15 @@ def decode_request(buf):
     if len(buf) < _REQ.size:
         raise ProtocolError("truncated header")
     magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, n_cons, n_vars, n_cuts = _REQ.unpack_from(buf, 0)
-    lp = kind in _LP_BASE
+    collect = kind == KIND_COLLECT
+    lp = kind in _LP_BASE or collect
     hybrid = kind == KIND_HYBRID_SELECT
     session = kind in _SESSION_KINDS
     if session:
         expected = _session_arrays(kind, n_forced, n_vars, n_cuts)
     else:
-        expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0)
-    if magic != MAGIC or kind > KIND_LP_CLOSE or n_arrays != expected or (lp and n_cons not in (0, 1)):
+        expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0) + collect
+    if magic != MAGIC or (kind > KIND_LP_CLOSE and not collect) or n_arrays != expected or (lp and n_cons not in (0, 1)):
         raise ProtocolError("not a request of this protocol")
     at = _REQ.size + key_len
     if at > len(buf):
@@ -319,6 +342,12 @@ def decode_request(buf):
                     **_decode_session(kind, arrays, n_forced, n_cons, n_vars, n_cuts))
     if lp or hybrid:
         snap, forced = _decode_hybrid(arrays, n_forced) if hybrid else _decode_lp(arrays, n_cons, n_forced)
+        if collect:
+            quality = arrays[-3 if n_forced >= 0 else -1]
+            if quality.dtype != np.float64 or quality.ndim != 1:
+                raise ProtocolError("malformed quality")
+            return dict(model_key=key, kind=kind, snapshot=snap, quality=quality, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
+                        max_selected=None if max_selected < 0 else max_selected)
         return dict(model_key=key, kind=kind, snapshot=snap, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
                     max_selected=None if max_selected < 0 else max_selected)
     return dict(model_key=key, kind=kind, state=tuple(arrays[:7]) + (n_cons, n_vars, n_cuts),
@@ -431,6 +460,15 @@ class ScoringClient:
         res.features = arrays[3]
         return res
 
+    def collect_lp(self, snapshot, quality, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
+        """`collect.Collector.collect_lp` behind the server: an expert round of the data collector -- the sample's state and the
+        plugin's selection over the expert's float64 `quality` (input cut order) -- as a `lpstate.CollectResult`.  A quality of
+        the wrong length or dtype kind, or with a value that is not finite, is refused here, in the worker."""
+        arrays, n_kept, n_selected = self._call(encode_collect_request(self.model_key, snapshot, quality, forced, p_max, p_max_ub,
+                                                                       max_selected))
+        state = tuple(arrays[:7]) + (arrays[0].shape[0], arrays[3].shape[0], arrays[4].shape[0])
+        return lpstate.CollectResult(state, arrays[7], arrays[8], arrays[9], n_kept, n_selected, arrays[10], arrays[11])
+
     def open_lp(self, rows, *, deep=True):
         """`GCNN.open_lp` behind the server: `rows` (`lpstate.LPRows`) goes over the wire once and stays on the server's device;
         returns a `RemoteLPSession`, whose rounds send only the solve, the candidate cuts and the rows to append.  The session
@@ -538,7 +576,9 @@ class ScoringServer:
     Opens, closes, `append_rows` and `remove_rows` are served one by one.  `stats` counts sessions_open, session_rounds (rounds served),
     session_calls (batched calls the group made on the device: its own counter), max_sessions_per_call (the most sessions one of
     them served) and session_solo_rounds (rounds the group answered through the session's own call: a ranking left to the host, a
-    member the batched call declined)."""
+    member the batched call declined).
+    Expert rounds of a data collector (`ScoringClient.collect_lp`) are served one by one by one `collect.Collector`, built on first
+    use; `stats["collect_calls"]` counts them.  They and the hybrid kind need no model: `models` may be empty."""
     SESSIONS_PER_CALL = 8
 
     def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True, max_sessions=64,
@@ -551,7 +591,7 @@ class ScoringServer:
         self.cross_model_lp = bool(cross_model_lp)
         self._model_set = model_set
         self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0, sessions_open=0,
-                          session_rounds=0, session_calls=0, session_solo_rounds=0, max_sessions_per_call=0)
+                          session_rounds=0, session_calls=0, session_solo_rounds=0, max_sessions_per_call=0, collect_calls=0)
         self.max_sessions = int(max_sessions)
         self._sessions = {}            # id -> (the connection that owns it, the LPSession)
         self._next_session = 1
@@ -564,12 +604,35 @@ class ScoringServer:
         self._thread = None
         self._buffers = {}
         self._hybrid = None            # the HybridSelector, built on first use on the device of the first model
+        self._collector = None         # the Collector of the expert rounds, built on first use on the same device
+
+    def _device(self):
+        """The device of the first model; None (the current device) for a server that holds no model: the kinds without one."""
+        first = next(iter(self.models.values()), None)
+        return None if first is None else first.device
 
     def _hybrid_selector(self):
         if self._hybrid is None:
             from .hybrid import HybridSelector
-            self._hybrid = HybridSelector(next(iter(self.models.values())).device)
+            self._hybrid = HybridSelector(self._device())
         return self._hybrid
+
+    def _collect_one(self, conn, req):
+        """An expert round (KIND_COLLECT), answered on its own: they are 5 % of a collector's rounds and rarely wait together."""
+        self.stats["collect_calls"] += 1
+        try:
+            if self._collector is None:
+                from .collect import Collector
+                self._collector = Collector(self._device())
+            res = self._collector.collect_lp(req["snapshot"], req["quality"], req["forced"], p_max=req["p_max"],
+                                             p_max_ub=req["p_max_ub"], max_selected=req["max_selected"])
+        except Exception as exc:  # noqa: BLE001 -- the request gets its error; the others are served
+            self._fail(conn, exc)
+            return
+        arrays = list(res.state[:7]) + [np.asarray(res.cut_index, np.int32), np.asarray(res.improvements, np.float64),
+                                        np.asarray(res.order, np.int32), np.asarray(res.hybrid_quality, np.float64),
+                                        np.asarray(res.features, np.float64)]
+        self._reply(conn, encode_reply(arrays, res.n_kept, res.n_selected))
 
     def _set(self):
         if self._model_set is None:
@@ -659,7 +722,7 @@ class ScoringServer:
             self.stats["requests"] += 1
             try:
                 req = decode_request(message)
-                if req["kind"] not in (KIND_HYBRID_SELECT, KIND_LP_ROUND, KIND_LP_CLOSE) and req["model_key"] not in self.models:
+                if req["kind"] not in (KIND_HYBRID_SELECT, KIND_LP_ROUND, KIND_LP_CLOSE, KIND_COLLECT) and req["model_key"] not in self.models:
                     raise KeyError(f"no model {req['model_key']!r}")
                 pending.append((conn, req))
             except Exception as exc:  # noqa: BLE001 -- a bad request gets its error; the server keeps serving
@@ -779,6 +842,10 @@ class ScoringServer:
             self._serve_sessions(session_items)
         groups = {}
         for conn, req in pending:
+            if req["kind"] == KIND_COLLECT:
+                if conn in self._buffers:
+                    self._collect_one(conn, req)
+                continue
             selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT, KIND_HYBRID_SELECT)
             hybrid = req["kind"] == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
             # one ModelSet call for all models: host states with `cross_model`, LP snapshots with `cross_model_lp` as well

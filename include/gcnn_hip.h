@@ -628,6 +628,51 @@ int gcnn_hybrid_select(int32_t n, const gcnn_hybrid_dims* dims, const int32_t* n
                        int32_t mode, const void* host_in, void* host_out, void* arena, size_t arena_bytes, double p_max,
                        double p_max_ub, void* stream);
 
+/* ---- the data collector's expert round: the sample's state and the selection over the caller's quality, in one call ---------------
+ * data_collector.SamplingAgent.cutselselect (data_collector.py:86-195) in a round that queries the expert: SCIP's dives give a
+ * float64 quality per cut (data_collector.py:104-131); the plugin then needs get_state(model, cuts) for the sample
+ * (data_collector.py:135-136) and its ranking and parallelism filter over that quality (data_collector.py:150-195).  gcnn_lp_collect
+ * replaces both: ONE host->device copy, at most six launches, ONE device->host copy; nothing is synchronised, nothing allocated.
+ *   the state      gcnn_lp_state's two launches write the seven arrays, cut_index and the four LP flags into the download block;
+ *   the rows       gcnn_hybrid_select's two row-building launches, on a one-entry table whose eight array positions point into
+ *                  the uploaded LP snapshot (cut_ptr, cut_col, cut_val, cut_lhs, cut_rhs, col_type, col_obj, col_lp; `infinity`
+ *                  from dims): cut_val / norm in fp32, INPUT cut order -- and with them the hybrid quality and features of
+ *                  gcnn_hybrid_select, the plugin's fallback ranking (data_collector.py:145-148), for free;
+ *   the selection  gcnn_select_cuts' pair launch on those rows and the forced rows, then gcnn_hybrid_select's fp64 filter with the
+ *                  UPLOADED quality as its key: order = sorted(range(K), key=lambda x: quality[x], reverse=True) over INPUT cut
+ *                  indices (ties in input order), low[p] = quality[order[p]] < 0.9 * quality[order[0]] in fp64, forced phase,
+ *                  main phase.  order and n_kept are in input cut indices; the state is in get_state's order (lhs-side cuts
+ *                  first), so the sample's labels are quality[cut_index[p]] for state position p.
+ * quality must be finite (the reference records a sample only when every dive solved: the caller checks; NaN ranks as -inf here).
+ * n_forced >= 0 (0: none), forced rows as gcnn_infer_select takes them.
+ * host_in (pinned, 16-byte aligned, in_bytes; WRITTEN: the call puts its table at table_off before the copy): the LP snapshot packed
+ *   at snap_off as gcnn_lp_layout_for says | quality_off: quality [K] f64 | forced_off[0..2]: forced_ptr | forced_col | forced_val |
+ *   table_off.  in_bytes = gcnn_lp_layout_for(dims, n_forced, n_forced_entries).in_bytes + 8 * K rounded up to 16 + table_bytes.
+ * host_out (pinned, out_bytes), at out_off[GCNN_LP_COLLECT_*]: cons_feats [C,4] | cons_edge_inds [2,E1] | cons_edge_feats [E1] |
+ *   var_feats [V,14] | cut_feats [K,6] | cut_edge_inds [2,E2] | cut_edge_feats [E2] | cut_index [K] int32 | LP flags [4] |
+ *   hybrid quality [K] f64 | features [K][3] f64 | order [K] int32 | n_kept int32 | hybrid flags [4] (words 0-2 as the LP flags').
+ *   Any flag set => nothing else is valid.
+ * entry_snap: the eight positions the table's entry holds, = snap_off of the corresponding LP arrays (the upload lies at the arena's
+ *   start).  The scratch of both families is carved out of the arena, so GCNN_E_WORKSPACE does not arise.
+ * Returned before anything is enqueued: GCNN_E_BADARG for dims gcnn_lp_layout_for refuses, negative forced sizes or entries without
+ * a row, a missing or misaligned buffer, an arena shorter than arena_bytes or not 256-byte aligned, a threshold that is not finite;
+ * GCNN_E_UNSUPPORTED for more than 4,096 cuts, or more than 2^24 state rows, columns or forced rows. */
+#define GCNN_LP_COLLECT_OUTPUTS 14
+enum { GCNN_LP_COLLECT_CONS_FEATS = 0, GCNN_LP_COLLECT_CONS_EDGE_INDS, GCNN_LP_COLLECT_CONS_EDGE_FEATS, GCNN_LP_COLLECT_VAR_FEATS,
+       GCNN_LP_COLLECT_CUT_FEATS, GCNN_LP_COLLECT_CUT_EDGE_INDS, GCNN_LP_COLLECT_CUT_EDGE_FEATS, GCNN_LP_COLLECT_CUT_INDEX,
+       GCNN_LP_COLLECT_LP_FLAGS, GCNN_LP_COLLECT_HYBRID_QUALITY, GCNN_LP_COLLECT_FEATURES, GCNN_LP_COLLECT_ORDER,
+       GCNN_LP_COLLECT_N_KEPT, GCNN_LP_COLLECT_HYBRID_FLAGS };
+typedef struct gcnn_lp_collect_layout {
+    size_t in_bytes, snap_off[GCNN_LP_ARRAYS], quality_off, forced_off[3], table_off, table_bytes;
+    size_t out_bytes, out_off[GCNN_LP_COLLECT_OUTPUTS];
+    size_t arena_bytes, out_dev_off, rows_off[3], ws_off, lp_scratch_off, hyb_scratch_off;   /* internal carving of the arena (the upload lies at 0) */
+    size_t entry_snap[GCNN_HYBRID_ARRAYS];
+} gcnn_lp_collect_layout;
+int gcnn_lp_collect_layout_for(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries,
+                               gcnn_lp_collect_layout* layout /* host */);
+int gcnn_lp_collect(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries, void* host_in, void* host_out, void* arena,
+                    size_t arena_bytes, double p_max, double p_max_ub, void* stream);
+
 /* ---- host states of several models in one call: the task farm as the reference fills it (model_evaluator.py:211-219) --------------
  * The evaluators' queue runs `seed` innermost, so the states that wait at a scoring server belong to DIFFERENT models.
  * gcnn_infer_models is gcnn_infer_batch's contract for 1..GCNN_IBATCH_MAX states of 1..GCNN_GROUP_MAX models: model_of_state[s] in
