@@ -6,16 +6,21 @@ worker, one selector call per separation round) share ONE process that owns the 
     CustomCutsel(function=client.get_concrete_function(), ...)                            # model_evaluator.py:310-314
     client.select_cuts_lp(lpstate.LPSnapshot(...), max_selected=10)                       # or: the raw LP, get_state left to the GPU
 
-The server takes every request that is waiting and groups them by kind: the host-state requests of ALL models share one
-`ModelSet.score_states` / `ModelSet.select_cuts_many` call (a group of one model's requests takes that model's own call) (the farm's queue runs `seed` innermost, model_evaluator.py:211-219, so
-the workers that wait hold different models; one upload, the models' forward passes as a group, one download), and the LP
-requests of all models one `ModelSet.score_lps` / `ModelSet.select_cuts_lp_many` call, which also builds the states on the device
-(`cross_model_lp`).  With `cross_model=False` it groups by model and kind and answers each group with one `GCNN.score_states` /
-`GCNN.select_cuts_many` call (one forward pass over the disjoint union of the group's states) -- for the LP kinds one
-`GCNN.score_lps` / `GCNN.select_cuts_lp_many` call -- and goes back for whatever queued up meanwhile.  It never waits for a batch to fill: a lone request is served at once.  Hybrid requests (SCIP's
-hybrid quality from the cut rows, `client.select_cuts_hybrid`) need no model: those that are waiting are grouped by thresholds and
-answered with one `HybridSelector.select_cuts_many`.  The data collector's expert rounds (`client.collect_lp`: the sample's state and
-the selection over the expert's quality, `collect.Collector`) need no model either and are answered one by one.
+The server takes every request that is waiting and groups them by kind.  The host-state requests of ALL models share one
+`ModelSet.score_states` / `ModelSet.select_cuts_many` call: the farm's queue runs `seed` innermost (model_evaluator.py:211-219), so
+the workers that wait hold different models -- one upload, the models' forward passes as a group, one download.  A group that
+holds one model's requests takes that model's own call.  The LP requests of all models share one `ModelSet.score_lps` /
+`ModelSet.select_cuts_lp_many` call, which also builds the states on the device (`cross_model_lp`).  With `cross_model=False` the
+server groups by model and kind and answers each group with one `GCNN.score_states` / `GCNN.select_cuts_many` call (one forward
+pass over the disjoint union of the group's states), for the LP kinds one `GCNN.score_lps` / `GCNN.select_cuts_lp_many` call.
+Then it goes back for whatever queued up meanwhile; it never waits for a batch to fill: a lone request is served at once.  Hybrid
+requests (SCIP's hybrid quality from the cut rows, `client.select_cuts_hybrid`) need no model: those that are waiting are grouped
+by thresholds and answered with one `HybridSelector.select_cuts_many`.  The data collector's expert rounds (`client.collect_lp`:
+the sample's state and the selection over the expert's quality, `collect.Collector`) need no model either; each is answered alone.
+
+What the codec and the server's reader know about a request kind stands in its row of `_KINDS`.  A new kind is a number, a row, an
+`encode_*_request` over `_message` and, unless it answers with one of the two shapes there are (`_scores_reply`, `_selection_reply`
+and their readers), a function that makes its reply; the server answers it through `_answer_group`.
 
 Wire format (AF_UNIX stream; little-endian; no pickle -- nothing a peer sends is ever executed): a message is a uint32 byte count
 followed by that many bytes: a fixed header, the model key, then arrays, each a 24-byte descriptor (dtype code, ndim, two
@@ -132,81 +137,77 @@ def encode_request(model_key, kind, state, forced=None, p_max=0.1, p_max_ub=0.5,
     through `encode_lp_request`); `forced`: None or (edge_inds [2,E], values [E][, n_forced]) as `GCNN.select_cuts` takes it."""
     if len(state) != 10:
         raise ValueError(f"expected the 10-tuple state, got {len(state)} items")
+    return _message(kind, model_key, state[:7], forced, p_max, p_max_ub, max_selected, *state[7:])
+
+
+def _message(kind, model_key, arrays=(), forced=None, p_max=0.0, p_max_ub=0.0, max_selected=None, a=0, b=0, c=0):
+    """Every request's bytes: the header with the kind's three words `a, b, c`, the key, the kind's arrays and, behind them, the
+    forced rows as `GCNN.select_cuts` takes them (the header then says how many)."""
+    n_forced = -1
+    if forced is not None:
+        fi = np.asarray(forced[0])
+        n_forced = int(forced[2]) if len(forced) > 2 else (int(fi[0].max()) + 1 if fi.size else 0)
+        arrays = list(arrays) + [fi, np.asarray(forced[1])]
     key = model_key.encode("utf-8")
-    n_forced, pair = _forced_pair(forced)
-    arrays = list(state[:7]) + pair
     parts = [_REQ.pack(MAGIC, kind, len(arrays), len(key), float(p_max), float(p_max_ub), -1 if max_selected is None else int(max_selected),
-                       n_forced, int(state[7]), int(state[8]), int(state[9])), key]
+                       n_forced, int(a), int(b), int(c)), key]
     _put_arrays(parts, arrays)
     return b"".join(parts)
 
 
-def _forced_pair(forced):
-    """Forced rows as `GCNN.select_cuts` takes them -> (n_forced or -1, the arrays to send)."""
-    if forced is None:
-        return -1, []
-    fi = np.asarray(forced[0])
-    return int(forced[2]) if len(forced) > 2 else (int(fi[0].max()) + 1 if fi.size else 0), [fi, np.asarray(forced[1])]
+def _scalars(dims):
+    return np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64)
+
+
+def _take_scalars(a, what):          # the four scalars behind a snapshot's or an open's arrays -> keywords of `LPSnapshot` / `LPRows`
+    if a.dtype != np.float64 or a.shape != (4,) or not np.isfinite(a[2]):
+        raise ProtocolError(f"malformed {what} scalars")
+    return dict(infinity=float(a[0]), sum_epsilon=float(a[1]), n_model_vars=int(a[2]), obj_norm=float(a[3]))
+
+
+# the LP payload: the snapshot's arrays in lpstate.FIELDS order, without the primal pair when there is no incumbent, then the scalars
+_LP_FIELDS = {inc: [(i, n) for i, (n, _) in enumerate(lpstate.FIELDS) if inc or i not in _PRIMAL] for inc in (0, 1)}
+
+
+def _lp_payload(snapshot):
+    """-> (the arrays an LP message carries, dims); the snapshot is checked as the server will check it, so it raises in the worker."""
+    arrays, dims = lpstate.check_snapshot(snapshot, deep=False)
+    return [arrays[i] for i, _ in _LP_FIELDS[dims["has_incumbent"]]] + [_scalars(dims)], dims
+
+
+def _lp_snapshot(inc, arrays):       # the inverse of `_lp_payload`; the arrays behind the payload are not looked at
+    fields = _LP_FIELDS[inc]
+    return lpstate.LPSnapshot(**{n: a for (_, n), a in zip(fields, arrays)}, **_take_scalars(arrays[len(fields)], "snapshot"),
+                              has_incumbent=bool(inc))
 
 
 def encode_lp_request(model_key, kind, snapshot, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
-    """-> the message's bytes of an LP request (kind KIND_LP_*).  The snapshot is checked here as the server will check it again
-    (`lpstate.check_snapshot` without the O(nnz) facts), so its ValueError is raised in the worker."""
-    arrays, dims = lpstate.check_snapshot(snapshot, deep=False)
-    inc = dims["has_incumbent"]
-    arrays = [a for i, a in enumerate(arrays) if inc or i not in _PRIMAL]
-    arrays.append(np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64))
-    n_forced, pair = _forced_pair(forced)
-    key = model_key.encode("utf-8")
-    parts = [_REQ.pack(MAGIC, kind, len(arrays) + len(pair), len(key), float(p_max), float(p_max_ub),
-                       -1 if max_selected is None else int(max_selected), n_forced, inc, 0, 0), key]
-    _put_arrays(parts, arrays + pair)
-    return b"".join(parts)
+    """-> the message's bytes of an LP request (kind KIND_LP_*); a snapshot `lpstate.check_snapshot` refuses raises here."""
+    arrays, dims = _lp_payload(snapshot)
+    return _message(kind, model_key, arrays, forced, p_max, p_max_ub, max_selected, dims["has_incumbent"])
 
 
 def encode_hybrid_request(model_key, snapshot, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
     """-> the message's bytes of a hybrid selection request.  `snapshot`: a `lpstate.CutSnapshot` or `LPSnapshot`, checked here as
     the server will check it again (without the O(nnz) facts), so its ValueError is raised in the worker."""
     arrays, dims = lpstate.check_cut_snapshot(snapshot, deep=False)
-    arrays = list(arrays) + [np.array([dims["infinity"]], np.float64)]
-    n_forced, pair = _forced_pair(forced)
-    key = model_key.encode("utf-8")
-    parts = [_REQ.pack(MAGIC, KIND_HYBRID_SELECT, len(arrays) + len(pair), len(key), float(p_max), float(p_max_ub),
-                       -1 if max_selected is None else int(max_selected), n_forced, 0, 0, 0), key]
-    _put_arrays(parts, arrays + pair)
-    return b"".join(parts)
+    return _message(KIND_HYBRID_SELECT, model_key, list(arrays) + [np.array([dims["infinity"]], np.float64)], forced, p_max, p_max_ub,
+                    max_selected)
 
 
 def encode_collect_request(model_key, snapshot, quality, forced=None, p_max=0.1, p_max_ub=0.5, max_selected=None):
     """-> the message's bytes of an expert round.  The snapshot and the quality are checked here as the server will check them
     again (`lpstate.check_snapshot` without the O(nnz) facts, `lpstate.check_quality`), so their ValueError is raised in the worker."""
-    arrays, dims = lpstate.check_snapshot(snapshot, deep=False)
-    q = lpstate.check_quality(quality, dims["n_cuts"])
-    inc = dims["has_incumbent"]
-    arrays = [a for i, a in enumerate(arrays) if inc or i not in _PRIMAL]
-    arrays.append(np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64))
-    arrays.append(q)
-    n_forced, pair = _forced_pair(forced)
-    key = model_key.encode("utf-8")
-    parts = [_header(KIND_COLLECT, len(arrays) + len(pair), key, p_max, p_max_ub, max_selected, n_forced, inc), key]
-    _put_arrays(parts, arrays + pair)
-    return b"".join(parts)
-
-
-def _header(kind, n_arrays, key, p_max=0.0, p_max_ub=0.0, max_selected=None, n_forced=-1, a=0, b=0, c=0):
-    return _REQ.pack(MAGIC, kind, n_arrays, len(key), float(p_max), float(p_max_ub), -1 if max_selected is None else int(max_selected),
-                     n_forced, int(a), int(b), int(c))
+    arrays, dims = _lp_payload(snapshot)
+    arrays.append(lpstate.check_quality(quality, dims["n_cuts"]))
+    return _message(KIND_COLLECT, model_key, arrays, forced, p_max, p_max_ub, max_selected, dims["has_incumbent"])
 
 
 def encode_open_request(model_key, rows, deep=True):
     """-> the message's bytes of an open request.  `rows`: a `lpstate.LPRows`, checked here as the server will check it again
     (without the O(nnz) facts), so its ValueError is raised in the worker."""
     arrays, dims = lpstate.check_rows(rows, deep=False)
-    arrays = list(arrays) + [np.array([dims["infinity"], dims["sum_epsilon"], dims["n_model_vars"], dims["obj_norm"]], np.float64)]
-    key = model_key.encode("utf-8")
-    parts = [_header(KIND_LP_OPEN, len(arrays), key, a=bool(deep)), key]
-    _put_arrays(parts, arrays)
-    return b"".join(parts)
+    return _message(KIND_LP_OPEN, model_key, list(arrays) + [_scalars(dims)], a=bool(deep))
 
 
 def _round_word(mode, mask=0, has_block=False, has_incumbent=None, incremental=False):
@@ -237,31 +238,51 @@ def encode_round_request(model_key, session, mode, rnd=None, forced=None, p_max=
         arrays += [np.asarray(a) for a in append.arrays()]
     if remove is not None:
         arrays.append(np.ascontiguousarray(np.asarray(remove).ravel(), dtype=np.int32))
-    n_forced, pair = _forced_pair(forced) if mode == SESSION_SELECT else (-1, [])
-    key = model_key.encode("utf-8")
-    parts = [_header(KIND_LP_ROUND, len(arrays) + len(pair), key, p_max, p_max_ub, max_selected, n_forced, session,
-                     _round_word(mode, mask, append is not None, inc, incremental), int(remove is not None)), key]
-    _put_arrays(parts, arrays + pair)
-    return b"".join(parts)
+    return _message(KIND_LP_ROUND, model_key, arrays, forced if mode == SESSION_SELECT else None, p_max, p_max_ub, max_selected, session,
+                    _round_word(mode, mask, append is not None, inc, incremental), remove is not None)
 
 
 def encode_close_request(model_key, session):
-    key = model_key.encode("utf-8")
-    return _header(KIND_LP_CLOSE, 0, key, a=session) + key
+    return _message(KIND_LP_CLOSE, model_key, a=session)
 
 
-def _decode_session(kind, arrays, n_forced, n_cons, n_vars, n_cuts=0):
-    """The kind-specific part of a decoded session request."""
-    if kind == KIND_LP_OPEN:
-        scalars = arrays[7]
-        if scalars.dtype != np.float64 or scalars.shape != (4,) or not np.isfinite(scalars[2]):
-            raise ProtocolError("malformed row scalars")
-        rows = lpstate.LPRows(*arrays[:7], infinity=float(scalars[0]), sum_epsilon=float(scalars[1]), n_model_vars=int(scalars[2]),
-                              obj_norm=float(scalars[3]))
-        return dict(rows=rows, deep=bool(n_cons))
-    if kind == KIND_LP_CLOSE:
-        return dict(session=n_cons)
-    mode, mask, has_block, inc = n_vars & 255, n_vars >> 8 & 15, n_vars >> 12 & 1, n_vars >> 13 & 3
+# ---- the request kinds, decoded: (the header's three words, the arrays in front of the forced pair) -> the kind's fields -------------
+def _lp_arrays(inc, behind=1):       # how many arrays an LP payload of this n_cons slot has, the scalars (and the quality) included
+    return len(_LP_FIELDS[inc]) + behind if inc in _LP_FIELDS else -1
+
+
+def _decode_collect(words, arrays):
+    snap, quality = _lp_snapshot(words[0], arrays), arrays[_lp_arrays(words[0])]
+    if quality.dtype != np.float64 or quality.ndim != 1:
+        raise ProtocolError("malformed quality")
+    return dict(snapshot=snap, quality=quality)
+
+
+def _decode_hybrid(words, arrays):
+    scalars = arrays[_HYBRID_ARRAYS - 1]
+    if scalars.dtype != np.float64 or scalars.shape != (1,):
+        raise ProtocolError("malformed snapshot scalars")
+    return dict(snapshot=lpstate.CutSnapshot(**dict(zip((n for n, _ in lpstate.CUT_FIELDS), arrays)), infinity=float(scalars[0])))
+
+
+def _round_bits(word):
+    """The inverse of `_round_word`: (mode, presence mask, has a block, has_incumbent's code, incremental)."""
+    return word & 255, word >> 8 & 15, word >> 12 & 1, word >> 13 & 3, word >> 15 & 1
+
+
+def _round_arrays(session, word, removes):
+    """How many arrays a well-formed round of these words carries in front of the forced pair; -1 for words that are none."""
+    mode, mask, has_block, inc, _ = _round_bits(word)
+    if removes not in (0, 1) or word < 0 or word >> 16 or mode > SESSION_APPEND or inc == 3:
+        return -1
+    if mode == SESSION_APPEND:
+        return 5 * has_block + removes if (has_block or removes) and not mask else -1
+    return _ROUND_BASE + bin(mask).count("1") + 5 * has_block + removes
+
+
+def _decode_round(words, arrays):
+    session, word, removes = words
+    mode, mask, has_block, inc, incremental = _round_bits(word)
     rnd, at = None, 0
     if mode != SESSION_APPEND:
         fields = {}
@@ -273,62 +294,45 @@ def _decode_session(kind, arrays, n_forced, n_cons, n_vars, n_cuts=0):
         rnd = lpstate.LPRound(**fields, has_incumbent=None if inc == 0 else inc == 2)
     block = lpstate.LPRowBlock(*arrays[at:at + 5]) if has_block else None
     remove = None
-    if n_cuts:
+    if removes:
         remove = arrays[at + 5 * has_block]
         if remove.dtype != np.int32 or remove.ndim != 1:
             raise ProtocolError("malformed list of removed rows")
-    return dict(session=n_cons, mode=mode, round=rnd, block=block, remove=remove, incremental=bool(n_vars >> 15 & 1),
-                forced=(arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
+    return dict(session=session, mode=mode, round=rnd, block=block, remove=remove, incremental=bool(incremental))
 
 
-def _session_arrays(kind, n_forced, n_vars, n_cuts=0):
-    """How many arrays a well-formed session request of this header carries; -1 for a header that is not one."""
-    if kind == KIND_LP_OPEN:
-        return 8
-    if kind == KIND_LP_CLOSE:
-        return 0
-    if n_cuts not in (0, 1):
-        return -1
-    mode, mask, has_block, inc = n_vars & 255, n_vars >> 8 & 15, n_vars >> 12 & 1, n_vars >> 13 & 3
-    if n_vars < 0 or n_vars >> 16 or mode > SESSION_APPEND or inc == 3 or (n_forced >= 0 and mode != SESSION_SELECT):
-        return -1
-    if mode == SESSION_APPEND:
-        return 5 * has_block + n_cuts if (has_block or n_cuts) and not mask else -1
-    return _ROUND_BASE + bin(mask).count("1") + 5 * has_block + n_cuts + (2 if n_forced >= 0 else 0)
+def _kind(decode, arrays, model=False, forced=lambda a, b, c: True):
+    return dict(decode=decode, arrays=arrays, model=model, forced=forced)
 
 
-def _decode_hybrid(arrays, n_forced):
-    scalars = arrays[_HYBRID_ARRAYS - 1]
-    if scalars.dtype != np.float64 or scalars.shape != (1,):
-        raise ProtocolError("malformed snapshot scalars")
-    snap = lpstate.CutSnapshot(**dict(zip((n for n, _ in lpstate.CUT_FIELDS), arrays)), infinity=float(scalars[0]))
-    return snap, ((arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
-
-
-def _decode_lp(arrays, inc, n_forced):
-    names = [n for i, (n, _) in enumerate(lpstate.FIELDS) if inc or i not in _PRIMAL]
-    scalars = arrays[len(names)]
-    if scalars.dtype != np.float64 or scalars.shape != (4,) or not np.isfinite(scalars[2]):
-        raise ProtocolError("malformed snapshot scalars")
-    snap = lpstate.LPSnapshot(**dict(zip(names, arrays)), infinity=float(scalars[0]), sum_epsilon=float(scalars[1]),
-                              n_model_vars=int(scalars[2]), obj_norm=float(scalars[3]), has_incumbent=bool(inc))
-    return snap, ((arrays[-2], arrays[-1], n_forced) if n_forced >= 0 else None)
+# One row per request kind -- all that the codec and the server's reader know about it; a kind without a row is unknown (10 is).
+#   decode  (the three words, the arrays) -> the kind's fields of the decoded dict
+#   arrays  (the three words) -> how many arrays a well-formed request carries in front of the forced pair, -1 for words it refuses
+#   model   the request names a model that the server must hold
+#   forced  (the three words) -> whether forced rows may follow (the dict then has `forced`); None: the header's slot is not looked at
+_STATE = _kind(lambda words, arrays: dict(state=tuple(arrays[:7]) + tuple(words)), lambda a, b, c: 7, model=True)
+_LP = _kind(lambda words, arrays: dict(snapshot=_lp_snapshot(words[0], arrays)), lambda a, b, c: _lp_arrays(a), model=True)
+_KINDS = {
+    KIND_SCORE: _STATE, KIND_RANK: _STATE, KIND_SELECT: _STATE,
+    KIND_LP_SCORE: _LP, KIND_LP_RANK: _LP, KIND_LP_SELECT: _LP,
+    KIND_HYBRID_SELECT: _kind(_decode_hybrid, lambda a, b, c: _HYBRID_ARRAYS),
+    KIND_LP_OPEN: _kind(lambda words, arrays: dict(rows=lpstate.LPRows(*arrays[:7], **_take_scalars(arrays[7], "row")), deep=bool(words[0])),
+                        lambda a, b, c: 8, model=True, forced=None),
+    KIND_LP_ROUND: _kind(_decode_round, _round_arrays, forced=lambda a, b, c: b & 255 == SESSION_SELECT),
+    KIND_LP_CLOSE: _kind(lambda words, arrays: dict(session=words[0]), lambda a, b, c: 0, forced=None),
+    KIND_COLLECT: _kind(_decode_collect, lambda a, b, c: _lp_arrays(a, 2)),
+}
+_NO_KIND = _kind(None, lambda a, b, c: -1, forced=None)      # what an unknown kind number looks up: refused with the count check
 
 
 def decode_request(buf):
-    """-> dict(model_key, kind, state | snapshot, forced, p_max, p_max_ub, max_selected); raises ProtocolError on anything malformed."""
+    """-> dict(model_key, kind, p_max, p_max_ub, max_selected and the kind's fields); raises ProtocolError on anything malformed."""
     if len(buf) < _REQ.size:
         raise ProtocolError("truncated header")
-    magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, n_cons, n_vars, n_cuts = _REQ.unpack_from(buf, 0)
-    collect = kind == KIND_COLLECT
-    lp = kind in _LP_BASE or collect
-    hybrid = kind == KIND_HYBRID_SELECT
-    session = kind in _SESSION_KINDS
-    if session:
-        expected = _session_arrays(kind, n_forced, n_vars, n_cuts)
-    else:
-        expected = ((len(lpstate.FIELDS) if n_cons else len(lpstate.FIELDS) - 2) + 1 if lp else _HYBRID_ARRAYS if hybrid else 7) + (2 if n_forced >= 0 else 0) + collect
-    if magic != MAGIC or (kind > KIND_LP_CLOSE and not collect) or n_arrays != expected or (lp and n_cons not in (0, 1)):
+    magic, kind, n_arrays, key_len, p_max, p_max_ub, max_selected, n_forced, *words = _REQ.unpack_from(buf, 0)
+    row = _KINDS.get(kind, _NO_KIND)
+    expected, has_forced = row["arrays"](*words), row["forced"] is not None and n_forced >= 0
+    if magic != MAGIC or expected < 0 or (has_forced and not row["forced"](*words)) or n_arrays != expected + 2 * has_forced:
         raise ProtocolError("not a request of this protocol")
     at = _REQ.size + key_len
     if at > len(buf):
@@ -337,30 +341,18 @@ def decode_request(buf):
     arrays, at = _get_arrays(buf, at, n_arrays)
     if at != len(buf):
         raise ProtocolError("trailing bytes")
-    if session:
-        return dict(model_key=key, kind=kind, p_max=p_max, p_max_ub=p_max_ub, max_selected=None if max_selected < 0 else max_selected,
-                    **_decode_session(kind, arrays, n_forced, n_cons, n_vars, n_cuts))
-    if lp or hybrid:
-        snap, forced = _decode_hybrid(arrays, n_forced) if hybrid else _decode_lp(arrays, n_cons, n_forced)
-        if collect:
-            quality = arrays[-3 if n_forced >= 0 else -1]
-            if quality.dtype != np.float64 or quality.ndim != 1:
-                raise ProtocolError("malformed quality")
-            return dict(model_key=key, kind=kind, snapshot=snap, quality=quality, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
-                        max_selected=None if max_selected < 0 else max_selected)
-        return dict(model_key=key, kind=kind, snapshot=snap, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
-                    max_selected=None if max_selected < 0 else max_selected)
-    return dict(model_key=key, kind=kind, state=tuple(arrays[:7]) + (n_cons, n_vars, n_cuts),
-                forced=(arrays[7], arrays[8], n_forced) if n_forced >= 0 else None, p_max=p_max, p_max_ub=p_max_ub,
-                max_selected=None if max_selected < 0 else max_selected)
+    req = row["decode"](words, arrays)
+    req.update(model_key=key, kind=kind, p_max=p_max, p_max_ub=p_max_ub, max_selected=None if max_selected < 0 else max_selected)
+    if row["forced"] is not None:
+        req["forced"] = (arrays[-2], arrays[-1], n_forced) if has_forced else None
+    return req
 
 
 def encode_reply(arrays=(), n_kept=-1, n_selected=-1, error=None):
+    status = 0
     if error is not None:
         status = ERR_VALUE if isinstance(error, ValueError) else ERR_GCNN if type(error).__name__ == "GcnnError" else ERR_OTHER
         arrays = [np.frombuffer(f"{type(error).__name__}: {error}".encode("utf-8", "replace"), np.uint8)]
-    else:
-        status = 0
     parts = [_REP.pack(MAGIC, status, len(arrays), 0, n_kept, n_selected)]
     _put_arrays(parts, arrays)
     return b"".join(parts)
@@ -415,7 +407,50 @@ class Selection:
         self.order, self.n_kept, self.n_selected, self.scores, self.cut_index = order, n_kept, n_selected, scores, cut_index
 
 
-class ScoringClient:
+# The two reply shapes, each as the server makes it from a result -- `encode_reply`'s (arrays, n_kept, n_selected) -- and as the client
+# reads it from what `decode_reply` returns.  `lp`: the result comes from an LP and carries cut_index.
+def _scores_reply(res, rank, lp):
+    """[scores, rankings?, cut_index?]"""
+    arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if rank else [])
+    return arrays + ([np.asarray(res.cut_index, np.int32)] if lp else []), -1, -1
+
+
+def _scores_of(reply, rank, lp):
+    scores = reply[0][0].view(Scores)
+    scores.rankings, scores.cut_index = reply[0][1] if rank else None, reply[0][-1] if lp else None
+    return scores
+
+
+def _selection_reply(res, max_selected, lp, features=False):
+    """[scores, order, cut_index?, features?], n_kept and n_selected in the header"""
+    arrays = [np.asarray(res.scores), np.asarray(res.order, np.int32)] + ([np.asarray(res.cut_index, np.int32)] if lp else [])
+    return arrays + ([np.asarray(res.features, np.float64)] if features else []), res.n_kept, _n_selected(res.n_kept, max_selected)
+
+
+def _selection_of(reply, lp, features=False):
+    arrays, n_kept, n_selected = reply
+    res = Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2] if lp else None)
+    res.features = arrays[3] if features else None
+    return res
+
+
+def _reply_of(base, lp, features=False):
+    """(request, result) -> `encode_reply`'s arguments; `base`: KIND_ or, the same numbers, SESSION_SCORE / _RANK / _SELECT."""
+    if base == KIND_SELECT:
+        return lambda req, res: _selection_reply(res, req["max_selected"], lp, features)
+    return lambda req, res: _scores_reply(res, base == KIND_RANK, lp)
+
+
+class _Closing:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class ScoringClient(_Closing):
     def __init__(self, address, model_key, timeout=None):
         self.model_key = model_key
         self.sock = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
@@ -428,37 +463,22 @@ class ScoringClient:
         return decode_reply(_recv_exact(self.sock, n))
 
     def score_state(self, state, rank=False):
-        arrays, _, _ = self._call(encode_request(self.model_key, KIND_RANK if rank else KIND_SCORE, state))
-        scores = arrays[0].view(Scores)
-        if rank:
-            scores.rankings = arrays[1]
-        return scores
+        return _scores_of(self._call(encode_request(self.model_key, KIND_RANK if rank else KIND_SCORE, state)), rank, False)
 
     def select_cuts(self, state, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
-        arrays, n_kept, n_selected = self._call(encode_request(self.model_key, KIND_SELECT, state, forced, p_max, p_max_ub, max_selected))
-        return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores))
+        return _selection_of(self._call(encode_request(self.model_key, KIND_SELECT, state, forced, p_max, p_max_ub, max_selected)), False)
 
     def score_lp(self, snapshot, rank=False):
         """`GCNN.score_lp` behind the server: the raw LP goes over the wire, get_state's arithmetic runs on the GPU."""
-        arrays, _, _ = self._call(encode_lp_request(self.model_key, KIND_LP_RANK if rank else KIND_LP_SCORE, snapshot))
-        scores = arrays[0].view(Scores)
-        scores.cut_index = arrays[-1]
-        if rank:
-            scores.rankings = arrays[1]
-        return scores
+        return _scores_of(self._call(encode_lp_request(self.model_key, KIND_LP_RANK if rank else KIND_LP_SCORE, snapshot)), rank, True)
 
     def select_cuts_lp(self, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
-        arrays, n_kept, n_selected = self._call(encode_lp_request(self.model_key, KIND_LP_SELECT, snapshot, forced, p_max, p_max_ub,
-                                                                  max_selected))
-        return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
+        return _selection_of(self._call(encode_lp_request(self.model_key, KIND_LP_SELECT, snapshot, forced, p_max, p_max_ub, max_selected)), True)
 
     def select_cuts_hybrid(self, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
         """`HybridSelector.select_cuts` behind the server: SCIP's hybrid quality (float64, input cut order) and the parallelism
         filter from a `lpstate.CutSnapshot` or `LPSnapshot`.  The `Selection` also carries `.features` [K, 3]."""
-        arrays, n_kept, n_selected = self._call(encode_hybrid_request(self.model_key, snapshot, forced, p_max, p_max_ub, max_selected))
-        res = Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
-        res.features = arrays[3]
-        return res
+        return _selection_of(self._call(encode_hybrid_request(self.model_key, snapshot, forced, p_max, p_max_ub, max_selected)), True, True)
 
     def collect_lp(self, snapshot, quality, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None):
         """`collect.Collector.collect_lp` behind the server: an expert round of the data collector -- the sample's state and the
@@ -485,15 +505,9 @@ class ScoringClient:
     def close(self):
         self.sock.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
-class RemoteLPSession:
+class RemoteLPSession(_Closing):
     """An `infer.LPSession` held by a scoring server, as a worker sees it (NumPy only): `score`, `select_cuts` (with `append=` and
     `remove=`), `append_rows`, `remove_rows`, `close`, `n_rows`, `n_cols` and use as a context manager, with `LPSession`'s
     signatures and results (`Scores` / `Selection` with `cut_index`); `n_rows` follows the edits the server accepted.  The
@@ -520,17 +534,11 @@ class RemoteLPSession:
         return reply
 
     def score(self, rnd, rank=False, timings=None, append=None, remove=None):
-        arrays, _, _ = self._round(SESSION_RANK if rank else SESSION_SCORE, rnd, append, remove)
-        scores = arrays[0].view(Scores)
-        scores.cut_index = arrays[-1]
-        if rank:
-            scores.rankings = arrays[1]
-        return scores
+        return _scores_of(self._round(SESSION_RANK if rank else SESSION_SCORE, rnd, append, remove), rank, True)
 
     def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None, remove=None):
-        arrays, n_kept, n_selected = self._round(SESSION_SELECT, rnd, append, remove, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
-                                                 max_selected=max_selected)
-        return Selection(arrays[1], n_kept, n_selected, arrays[0].view(Scores), arrays[2])
+        return _selection_of(self._round(SESSION_SELECT, rnd, append, remove, forced=forced, p_max=p_max, p_max_ub=p_max_ub,
+                                         max_selected=max_selected), True)
 
     def append_rows(self, row_ptr, row_col, row_val, row_lhs, row_rhs, incremental=False):
         block = lpstate.LPRowBlock(row_ptr, row_col, row_val, row_lhs, row_rhs)
@@ -547,12 +555,6 @@ class RemoteLPSession:
             self.closed = True
             self.client._call(encode_close_request(self.client.model_key, self.session))
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 # ---- server ------------------------------------------------------------------------------------------------------------------------
@@ -620,19 +622,20 @@ class ScoringServer:
     def _collect_one(self, conn, req):
         """An expert round (KIND_COLLECT), answered on its own: they are 5 % of a collector's rounds and rarely wait together."""
         self.stats["collect_calls"] += 1
-        try:
+
+        def call():
             if self._collector is None:
                 from .collect import Collector
                 self._collector = Collector(self._device())
-            res = self._collector.collect_lp(req["snapshot"], req["quality"], req["forced"], p_max=req["p_max"],
-                                             p_max_ub=req["p_max_ub"], max_selected=req["max_selected"])
-        except Exception as exc:  # noqa: BLE001 -- the request gets its error; the others are served
-            self._fail(conn, exc)
-            return
-        arrays = list(res.state[:7]) + [np.asarray(res.cut_index, np.int32), np.asarray(res.improvements, np.float64),
-                                        np.asarray(res.order, np.int32), np.asarray(res.hybrid_quality, np.float64),
-                                        np.asarray(res.features, np.float64)]
-        self._reply(conn, encode_reply(arrays, res.n_kept, res.n_selected))
+            return [self._collector.collect_lp(req["snapshot"], req["quality"], req["forced"], p_max=req["p_max"],
+                                               p_max_ub=req["p_max_ub"], max_selected=req["max_selected"])]
+
+        def reply_of(req, res):
+            arrays = list(res.state[:7]) + [np.asarray(res.cut_index, np.int32), np.asarray(res.improvements, np.float64),
+                                            np.asarray(res.order, np.int32), np.asarray(res.hybrid_quality, np.float64),
+                                            np.asarray(res.features, np.float64)]
+            return arrays, res.n_kept, res.n_selected
+        self._answer_group([(conn, req)], call, reply_of)
 
     def _set(self):
         if self._model_set is None:
@@ -722,7 +725,7 @@ class ScoringServer:
             self.stats["requests"] += 1
             try:
                 req = decode_request(message)
-                if req["kind"] not in (KIND_HYBRID_SELECT, KIND_LP_ROUND, KIND_LP_CLOSE, KIND_COLLECT) and req["model_key"] not in self.models:
+                if _KINDS[req["kind"]]["model"] and req["model_key"] not in self.models:
                     raise KeyError(f"no model {req['model_key']!r}")
                 pending.append((conn, req))
             except Exception as exc:  # noqa: BLE001 -- a bad request gets its error; the server keeps serving
@@ -805,97 +808,95 @@ class ScoringServer:
     def _serve_rounds(self, gkey, members):
         mode = gkey[0]
         sessions, rounds = [m[2] for m in members], [m[1]["round"] for m in members]
-        appends = [m[1]["block"] for m in members]
-        removes = [m[1].get("remove") for m in members]
+        appends, removes = [m[1]["block"] for m in members], [m[1].get("remove") for m in members]
         more = dict(removes=removes) if any(r is not None for r in removes) else {}      # (a group without the keyword keeps working)
         self.stats["session_rounds"] += len(members)
         group = self._group()
-        before = (group.calls, group.solo_rounds)
+
+        def call():
+            before = (group.calls, group.solo_rounds)
+            try:
+                if mode == SESSION_SELECT:
+                    return group.select_cuts(sessions, rounds, [m[1]["forced"] for m in members], p_max=gkey[1], p_max_ub=gkey[2],
+                                             appends=appends, return_exceptions=True, **more)
+                return group.score(sessions, rounds, rank=mode == SESSION_RANK, appends=appends, return_exceptions=True, **more)
+            finally:
+                # the group's own counters: a hand-off whose members the host rejects, or that goes to solo calls, makes no batched call
+                self.stats["session_calls"] += group.calls - before[0]
+                self.stats["session_solo_rounds"] += group.solo_rounds - before[1]
+                self.stats["max_sessions_per_call"] = max(self.stats["max_sessions_per_call"], group.max_sessions_per_call)
+        self._answer_group(members, call, _reply_of(mode, True))
+
+    def _answer_group(self, members, call, reply_of):
+        """One call for `members` ([(connection, request, ...)]): `call()` returns a result or an exception per member, and one that
+        it raises is every member's; a member whose connection dropped meanwhile is skipped."""
         try:
-            if mode == SESSION_SELECT:
-                results = group.select_cuts(sessions, rounds, [m[1]["forced"] for m in members], p_max=gkey[1], p_max_ub=gkey[2],
-                                                    appends=appends, return_exceptions=True, **more)
-            else:
-                results = group.score(sessions, rounds, rank=mode == SESSION_RANK, appends=appends, return_exceptions=True, **more)
+            results = call()
         except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
             results = [exc] * len(members)
-        # the group's own counters: a hand-off whose members the host rejects, or that goes to solo calls, makes no batched call
-        self.stats["session_calls"] += group.calls - before[0]
-        self.stats["session_solo_rounds"] += group.solo_rounds - before[1]
-        self.stats["max_sessions_per_call"] = max(self.stats["max_sessions_per_call"], group.max_sessions_per_call)
-        for (conn, req, _), res in zip(members, results):
+        for (conn, req, *_), res in zip(members, results):
             if conn not in self._buffers:
                 continue
             if isinstance(res, Exception):
                 self._fail(conn, res)
-            elif mode == SESSION_SELECT:
-                arrays = [np.asarray(res.scores), np.asarray(res.order, np.int32), np.asarray(res.cut_index, np.int32)]
-                self._reply(conn, encode_reply(arrays, res.n_kept, _n_selected(res.n_kept, req["max_selected"])))
             else:
-                arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if mode == SESSION_RANK else [])
-                self._reply(conn, encode_reply(arrays + [np.asarray(res.cut_index, np.int32)]))
+                self._reply(conn, encode_reply(*reply_of(req, res)))
 
-    def _serve(self, pending):
-        session_items = [(conn, req) for conn, req in pending if req["kind"] in _SESSION_KINDS]
-        if session_items:
-            pending = [(conn, req) for conn, req in pending if req["kind"] not in _SESSION_KINDS]
-            self._serve_sessions(session_items)
+    def _grouped(self, pending):
+        """The requests of the kinds 0-6, which can share a call -> {(model key or None, kind[, p_max, p_max_ub]): [(conn, request)]}."""
         groups = {}
         for conn, req in pending:
-            if req["kind"] == KIND_COLLECT:
-                if conn in self._buffers:
-                    self._collect_one(conn, req)
+            kind = req["kind"]
+            if kind in _SESSION_KINDS or kind == KIND_COLLECT:
                 continue
-            selects = req["kind"] in (KIND_SELECT, KIND_LP_SELECT, KIND_HYBRID_SELECT)
-            hybrid = req["kind"] == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
+            hybrid = kind == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
+            selects = hybrid or _LP_BASE.get(kind, kind) == KIND_SELECT
             # one ModelSet call for all models: host states with `cross_model`, LP snapshots with `cross_model_lp` as well
-            shared = hybrid or (self.cross_model and (self.cross_model_lp or req["kind"] not in _LP_BASE))
-            gkey = (None if shared else req["model_key"], req["kind"]) + ((req["p_max"], req["p_max_ub"]) if selects else ())
+            shared = hybrid or (self.cross_model and (self.cross_model_lp or kind not in _LP_BASE))
+            gkey = (None if shared else req["model_key"], kind) + ((req["p_max"], req["p_max_ub"]) if selects else ())
             groups.setdefault(gkey, []).append((conn, req))
-        for gkey, items in groups.items():
+        return groups
+
+    def _callables(self, gkey, mkeys, lp):       # -> (score_many, select_many, the `ModelSet` behind them or None)
+        if gkey[1] == KIND_HYBRID_SELECT:
+            return None, self._hybrid_selector().select_cuts_many, None
+        if gkey[0] is None and len(set(mkeys)) > 1:
+            mset = self._set()
+            score_many, select_many = (mset.score_lps, mset.select_cuts_lp_many) if lp else (mset.score_states, mset.select_cuts_many)
+            return partial(score_many, mkeys), partial(select_many, mkeys), mset
+        model = self.models[mkeys[0]]
+        return ((model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)) + (None,)
+
+    def _serve(self, pending):
+        self._serve_sessions([(conn, req) for conn, req in pending if req["kind"] in _SESSION_KINDS])
+        for conn, req in pending:
+            if req["kind"] == KIND_COLLECT and conn in self._buffers:
+                self._collect_one(conn, req)
+        for gkey, items in self._grouped(pending).items():
             hybrid = gkey[1] == KIND_HYBRID_SELECT
             lp = gkey[1] in _LP_BASE or hybrid
-            kind = KIND_SELECT if hybrid else _LP_BASE.get(gkey[1], gkey[1])
-            states = [r["snapshot" if lp else "state"] for _, r in items]
+            base = KIND_SELECT if hybrid else _LP_BASE.get(gkey[1], gkey[1])
             self.stats["calls"] += 1
             self.stats["batched_calls"] += len(items) > 1
             self.stats["max_batch"] = max(self.stats["max_batch"], len(items))
-            mkeys = [r["model_key"] for _, r in items]
-            mset = None
-            try:
-                if hybrid:
-                    score_many, select_many = None, self._hybrid_selector().select_cuts_many
-                elif gkey[0] is None and len(set(mkeys)) > 1:
-                    mset = self._set()
-                    score_many, select_many = (mset.score_lps, mset.select_cuts_lp_many) if lp else (mset.score_states, mset.select_cuts_many)
-                    score_many, select_many = partial(score_many, mkeys), partial(select_many, mkeys)
-                else:
-                    model = self.models[mkeys[0]]
-                    score_many, select_many = (model.score_lps, model.select_cuts_lp_many) if lp else (model.score_states, model.select_cuts_many)
-                if kind == KIND_SELECT:
-                    results = select_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3], return_exceptions=True)
-                else:
-                    results = score_many(states, rank=kind == KIND_RANK, return_exceptions=True)
-            except Exception as exc:  # noqa: BLE001 -- e.g. thresholds that are not finite: the whole group shares them
-                results = [exc] * len(items)
-            if not hybrid:
-                served = 1 if mset is None else getattr(mset, "max_models_per_call", len(set(mkeys)))
-                self.stats["max_models_per_call"] = max(self.stats["max_models_per_call"], served)
-            for (conn, req), res in zip(items, results):
-                if conn not in self._buffers:
-                    continue
-                if isinstance(res, Exception):
-                    self.stats["errors"] += 1
-                    self._reply(conn, encode_reply(error=res))
-                elif kind == KIND_SELECT:
-                    arrays = [np.asarray(res.scores), np.asarray(res.order, np.int32)]
-                    arrays += [np.asarray(res.cut_index, np.int32)] if lp else []
-                    arrays += [np.asarray(res.features, np.float64)] if hybrid else []
-                    self._reply(conn, encode_reply(arrays, res.n_kept, _n_selected(res.n_kept, req["max_selected"])))
-                else:
-                    arrays = [np.asarray(res)] + ([np.asarray(res.rankings, np.int32)] if kind == KIND_RANK else [])
-                    arrays += [np.asarray(res.cut_index, np.int32)] if lp else []
-                    self._reply(conn, encode_reply(arrays))
+
+            def call():
+                states, mkeys, mset = [r["snapshot" if lp else "state"] for _, r in items], [r["model_key"] for _, r in items], None
+                try:
+                    score_many, select_many, mset = self._callables(gkey, mkeys, lp)
+                    if base == KIND_SELECT:
+                        return select_many(states, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3], return_exceptions=True)
+                    return score_many(states, rank=base == KIND_RANK, return_exceptions=True)
+                finally:
+                    if not hybrid:
+                        served = 1 if mset is None else getattr(mset, "max_models_per_call", len(set(mkeys)))
+                        self.stats["max_models_per_call"] = max(self.stats["max_models_per_call"], served)
+            self._answer_group(items, call, _reply_of(base, lp, hybrid))
+
+    def _accept(self):               # a worker has connected: its connection joins those the loop reads
+        conn, _ = self._listen.accept()
+        self._buffers[conn] = bytearray()
+        self._sel.register(conn, selectors.EVENT_READ)
 
     def serve_forever(self):
         self._sel = sel = selectors.DefaultSelector()
@@ -909,9 +910,7 @@ class ScoringServer:
                 for key, _ in events:
                     s = key.fileobj
                     if s is self._listen:
-                        conn, _ = s.accept()
-                        self._buffers[conn] = bytearray()
-                        sel.register(conn, selectors.EVENT_READ)
+                        self._accept()
                     elif s is self._wake_r:
                         s.recv(16)
                     else:

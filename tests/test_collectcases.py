@@ -3,9 +3,7 @@ tests/collectcases.py against its three planted defects, each caught by a named 
 makes before anything is enqueued; improvements == quality[cut_index]; the wire round trip of kind 11, the bytes of the kinds 3-6
 before and after, kind 10 still refused; the server's bookkeeping with a stub collector; the client's local refusals."""
 import hashlib
-import selectors
 import socket
-import struct
 import subprocess
 import sys
 import os
@@ -17,7 +15,9 @@ import collectcases as CC
 import hybrid_restate as H
 import hybridcases as X
 from gcnn_cut_selector_amd import lpstate, serve
-from test_lprounds_host import BEFORE, FORCED, _snap
+from servecommon import FORCED, Peer, server_fixture, stub_server
+from servecommon import pump as _pump, snap as _snap
+from test_lprounds_host import BEFORE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -238,37 +238,7 @@ class StubCollector:
                                      n_kept if max_selected is None else min(n_kept, max_selected), quality + 1.0, np.ones((k, 3)))
 
 
-class Peer:
-    def __init__(self, server):
-        self.sock, self.conn = socket.socketpair()
-        self.sock.settimeout(5)
-        server._buffers[self.conn] = bytearray()
-        server._sel.register(self.conn, selectors.EVENT_READ)
-
-    def send(self, message):
-        self.sock.sendall(struct.pack("<I", len(message)) + message)
-
-    def reply(self):
-        (n,) = struct.unpack("<I", serve._recv_exact(self.sock, 4))
-        return serve.decode_reply(serve._recv_exact(self.sock, n))
-
-
-@pytest.fixture
-def server(tmp_path):
-    s = serve.ScoringServer({}, str(tmp_path / "sock"))           # no model at all
-    s._collector = StubCollector()
-    s._sel = selectors.DefaultSelector()
-    yield s
-    s._sel.close()
-    s._shutdown()
-
-
-def _pump(server, peers):
-    pending, ready = [], {key.fileobj for key, _ in server._sel.select(0)}
-    for p in peers:
-        if p.conn in ready and p.conn in server._buffers:
-            server._read(p.conn, pending)
-    server._serve(pending)
+server = server_fixture(lambda tmp_path: stub_server(tmp_path, {}, StubCollector()))           # no model at all
 
 
 def test_server_answers_expert_rounds_one_by_one(server):

@@ -36,9 +36,7 @@ def _lock_step(server, procs, deadline):
         for key, _ in sel.select(1.0):
             s = key.fileobj
             if s is server._listen:
-                conn, _ = s.accept()
-                server._buffers[conn] = bytearray()
-                sel.register(conn, selectors.EVENT_READ)
+                server._accept()
                 connected += 1
             else:
                 server._read(s, pending)

@@ -2,39 +2,18 @@
 `remove=` and `remove_rows`): the wire round trip of rounds with a removal, with a block and a removal, and of the edit-alone
 forms; requests without a removal against bytes assembled by hand from the documented header; the malformed cases; and the
 server's bookkeeping with stub models, sessions and stub groups, driven through `_read` and `_serve` without torch."""
-import selectors
-import socket
-import struct
 import types
 
 import numpy as np
 import pytest
 
 from gcnn_cut_selector_amd import lpstate, serve
+from servecommon import BLOCK, FORCED, Peer, StubModel, server_fixture, shut, stub_server
+from servecommon import by_hand as _by_hand, open_session as _open, pump as _pump, same_fields as _same_fields, snap as _snap
 
 
-def _snap():
-    return lpstate.LPSnapshot(
-        row_ptr=np.array([0, 2, 3], np.int32), row_col=np.array([0, 2, 1], np.int32), row_val=np.array([1.0, -2.0, 0.5]),
-        row_lhs=np.array([-1e20, 0.5]), row_rhs=np.array([3.0, 1e20]), row_dual=np.array([0.25, 0.0]), row_basis=np.array([0, 2], np.int8),
-        col_type=np.array([0, 1, 3], np.int8), col_obj=np.array([1.0, 0.0, 2.0]), col_lb=np.zeros(3), col_ub=np.array([1.0, 1.0, 1e20]),
-        col_basis=np.array([1, 0, 2], np.int8), col_lp=np.array([0.5, 1.0, 0.0]), col_redcost=np.array([0.0, 0.5, 0.0]),
-        cut_ptr=np.array([0, 2, 3], np.int32), cut_col=np.array([0, 1, 2], np.int32), cut_val=np.array([1.0, 1.0, -1.0]),
-        cut_lhs=np.array([-1e20, 0.25]), cut_rhs=np.array([1.5, 1e20]), col_primal=np.array([1.0, 0.0, 0.5]),
-        col_primal_avg=np.array([0.5, 0.5, 0.5]))
-
-
-FORCED = (np.array([[0, 0], [0, 2]], np.int32), np.array([1.0, -1.0], np.float32), 1)
 ROUND_NAMES = [n for n, _ in lpstate.ROUND_FIELDS]
 BLOCK_NAMES = ("row_ptr", "row_col", "row_val", "row_lhs", "row_rhs")
-BLOCK = lpstate.LPRowBlock(np.array([0, 1, 3], np.int32), np.array([2, 0, 1], np.int32), np.array([1.5, -1.0, 2.0]),
-                           np.array([-1e20, 0.0]), np.array([2.0, 1e20]))
-
-
-def _same_fields(a, b, names):
-    for n in names:
-        x, y = getattr(a, n), getattr(b, n)
-        assert (x is None and y is None) or np.array_equal(np.asarray(x), np.asarray(y)), n
 
 
 def test_wire_round_trip_with_removals():
@@ -65,19 +44,6 @@ def test_wire_round_trip_with_removals():
         serve.encode_round_request("m", 9, serve.SESSION_APPEND)
     # a request without a removal decodes with none
     assert serve.decode_request(serve.encode_round_request("m", 7, serve.SESSION_SCORE, rnd))["remove"] is None
-
-
-def _by_hand(kind, key, arrays, p_max=0.0, p_max_ub=0.0, max_selected=-1, n_forced=-1, a=0, b=0, c=0):
-    """A request assembled from the documented layout alone: the header `<4sBBHddiiiii` (magic, kind, n_arrays, key length, p_max,
-    p_max_ub, max_selected, n_forced and three words), the key, then per array a 24-byte descriptor `<BBHIIQ4x` (dtype code, rank,
-    pad, two dimensions, byte count) and its raw buffer."""
-    codes = {"float32": 0, "float64": 1, "int32": 2, "int64": 3, "uint8": 4, "int8": 5}
-    out = [struct.pack("<4sBBHddiiiii", b"GCS1", kind, len(arrays), len(key), p_max, p_max_ub, max_selected, n_forced, a, b, c), key]
-    for x in arrays:
-        x = np.ascontiguousarray(x)
-        shape = tuple(x.shape) + (0,) * (2 - x.ndim)
-        out += [struct.pack("<BBHIIQ4x", codes[x.dtype.name], x.ndim, 0, shape[0], shape[1], x.nbytes), x.tobytes()]
-    return b"".join(out)
 
 
 def test_requests_without_a_removal_keep_their_bytes():
@@ -143,17 +109,6 @@ class StubSession:
         self.closed = True
 
 
-class StubModel:
-    device = "stub"
-
-    def __init__(self, name):
-        self.name, self.opened = name, []
-
-    def open_lp(self, rows, *, deep=True):
-        self.opened.append(StubSession(self, rows, deep))
-        return self.opened[-1]
-
-
 class OldStubGroup:
     """A group from before removals: its calls take no `removes`.  Answers a member with its round's cut count."""
 
@@ -193,58 +148,11 @@ class StubGroup(OldStubGroup):
         return self._serve("select", sessions, rounds, self._selection, appends=list(appends), **more)
 
 
-class Peer:
-    """A worker's end of a connection to the server under test, usable as the `client` of a `RemoteLPSession`: `_call` sends
-    a framed message, lets the server take one turn and reads the framed reply."""
-    model_key = "a"
-
-    def __init__(self, server):
-        self.server = server
-        self.sock, self.conn = socket.socketpair()
-        self.sock.settimeout(5)              # a reply that does not come fails the test instead of blocking it
-        server._buffers[self.conn] = bytearray()
-        server._sel.register(self.conn, selectors.EVENT_READ)
-
-    def send(self, message):
-        self.sock.sendall(struct.pack("<I", len(message)) + message)
-
-    def reply(self):
-        (n,) = struct.unpack("<I", serve._recv_exact(self.sock, 4))
-        return serve.decode_reply(serve._recv_exact(self.sock, n))
-
-    def _call(self, message):
-        self.send(message)
-        _pump(self.server, [self])
-        return self.reply()
-
-
 def _server(tmp_path, group):
-    s = serve.ScoringServer({"a": StubModel("a"), "b": StubModel("b")}, str(tmp_path / "sock"), session_group=group)
-    s._sel = selectors.DefaultSelector()
-    return s
+    return stub_server(tmp_path, {"a": StubModel("a", StubSession), "b": StubModel("b", StubSession)}, session_group=group)
 
 
-@pytest.fixture
-def server(tmp_path):
-    s = _server(tmp_path, StubGroup())
-    yield s
-    s._sel.close()
-    s._shutdown()
-
-
-def _pump(server, peers):
-    """What one turn of `serve_forever` does with what the peers have sent: read every connection, then serve."""
-    pending, ready = [], {key.fileobj for key, _ in server._sel.select(0)}
-    for p in peers:
-        if p.conn in ready and p.conn in server._buffers:
-            server._read(p.conn, pending)
-    server._serve(pending)
-
-
-def _open(server, peer, key="a"):
-    peer.send(serve.encode_open_request(key, lpstate.LPRows.from_snapshot(_snap())))
-    _pump(server, [peer])
-    return peer.reply()[1]
+server = server_fixture(lambda tmp_path: _server(tmp_path, StubGroup()))
 
 
 def _round(k=2):
@@ -305,8 +213,7 @@ def test_a_group_without_the_keyword_serves_removal_free_traffic(tmp_path):
             peers[0].reply()
         assert peers[1].reply()[0][0].shape == (2,)
     finally:
-        server._sel.close()
-        server._shutdown()
+        shut(server)
 
 
 def test_edits_alone_reach_the_session_and_the_client_counts_rows(server):

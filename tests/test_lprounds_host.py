@@ -4,8 +4,6 @@ server's bookkeeping with stub models, sessions and a stub group, driven through
 connection, close on drop, the `max_sessions` error, a foreign id, two requests of one session in successive calls, 11 waiting
 rounds as calls of 8 and 3, grouping by mode and thresholds."""
 import hashlib
-import selectors
-import socket
 import struct
 import types
 
@@ -13,6 +11,8 @@ import numpy as np
 import pytest
 
 from gcnn_cut_selector_amd import lpstate, serve
+from servecommon import BLOCK, FORCED, Peer, StubModel, server_fixture, stub_server
+from servecommon import open_session as _open, pump as _pump, same_fields as _same_fields, snap as _snap
 
 
 def _state():
@@ -22,18 +22,6 @@ def _state():
     return (f(2, 4), cei, f(3, 1), f(3, 14), f(2, 6), kei, f(2, 1), 2, 3, 2)
 
 
-def _snap():
-    return lpstate.LPSnapshot(
-        row_ptr=np.array([0, 2, 3], np.int32), row_col=np.array([0, 2, 1], np.int32), row_val=np.array([1.0, -2.0, 0.5]),
-        row_lhs=np.array([-1e20, 0.5]), row_rhs=np.array([3.0, 1e20]), row_dual=np.array([0.25, 0.0]), row_basis=np.array([0, 2], np.int8),
-        col_type=np.array([0, 1, 3], np.int8), col_obj=np.array([1.0, 0.0, 2.0]), col_lb=np.zeros(3), col_ub=np.array([1.0, 1.0, 1e20]),
-        col_basis=np.array([1, 0, 2], np.int8), col_lp=np.array([0.5, 1.0, 0.0]), col_redcost=np.array([0.0, 0.5, 0.0]),
-        cut_ptr=np.array([0, 2, 3], np.int32), cut_col=np.array([0, 1, 2], np.int32), cut_val=np.array([1.0, 1.0, -1.0]),
-        cut_lhs=np.array([-1e20, 0.25]), cut_rhs=np.array([1.5, 1e20]), col_primal=np.array([1.0, 0.0, 0.5]),
-        col_primal_avg=np.array([0.5, 0.5, 0.5]))
-
-
-FORCED = (np.array([[0, 0], [0, 2]], np.int32), np.array([1.0, -1.0], np.float32), 1)
 # (length, sha256) of the messages the encoders of the kinds 0-6 gave for the inputs above before the session kinds existed
 BEFORE = {
     0: (521, "21b250555236ffecddc979d3a696c50de432d452120308a8decf12ca2e8cd742"),
@@ -58,15 +46,7 @@ def test_kinds_0_to_6_keep_their_bytes():
             serve.KIND_HYBRID_SELECT, serve.KIND_LP_OPEN, serve.KIND_LP_ROUND, serve.KIND_LP_CLOSE) == tuple(range(10))
 
 
-def _same_fields(a, b, names):
-    for n in names:
-        x, y = getattr(a, n), getattr(b, n)
-        assert (x is None and y is None) or np.array_equal(np.asarray(x), np.asarray(y)), n
-
-
 ROUND_NAMES = [n for n, _ in lpstate.ROUND_FIELDS]
-BLOCK = lpstate.LPRowBlock(np.array([0, 1, 3], np.int32), np.array([2, 0, 1], np.int32), np.array([1.5, -1.0, 2.0]),
-                           np.array([-1e20, 0.0]), np.array([2.0, 1e20]))
 
 
 def test_wire_round_trip_of_the_session_kinds():
@@ -123,17 +103,6 @@ class StubSession:
         self.closed = True
 
 
-class StubModel:
-    device = "stub"
-
-    def __init__(self, name):
-        self.name, self.opened = name, []
-
-    def open_lp(self, rows, *, deep=True):
-        self.opened.append(StubSession(self, rows, deep))
-        return self.opened[-1]
-
-
 class StubGroup:
     """Answers a member with its round's cut count; a round whose row_dual[0] is negative gets a ValueError in its slot.  Keeps
     `LPSessionGroup`'s counters: a selection or a scoring is one batched call, a ranking is left to the sessions' own calls."""
@@ -168,45 +137,8 @@ class StubGroup:
                                                                      cut_index=np.arange(k, dtype=np.int32)[::-1], n_kept=k))
 
 
-class Peer:
-    """A worker's end of a connection to the server under test: sends framed messages, reads framed replies."""
-
-    def __init__(self, server):
-        self.sock, self.conn = socket.socketpair()
-        self.sock.settimeout(5)              # a reply that does not come fails the test instead of blocking it
-        server._buffers[self.conn] = bytearray()
-        server._sel.register(self.conn, selectors.EVENT_READ)
-
-    def send(self, message):
-        self.sock.sendall(struct.pack("<I", len(message)) + message)
-
-    def reply(self):
-        (n,) = struct.unpack("<I", serve._recv_exact(self.sock, 4))
-        return serve.decode_reply(serve._recv_exact(self.sock, n))
-
-
-@pytest.fixture
-def server(tmp_path):
-    s = serve.ScoringServer({"a": StubModel("a"), "b": StubModel("b")}, str(tmp_path / "sock"), max_sessions=3, session_group=StubGroup())
-    s._sel = selectors.DefaultSelector()
-    yield s
-    s._sel.close()
-    s._shutdown()
-
-
-def _pump(server, peers):
-    """What one turn of `serve_forever` does with what the peers have sent: read every connection, then serve."""
-    pending, ready = [], {key.fileobj for key, _ in server._sel.select(0)}
-    for p in peers:
-        if p.conn in ready and p.conn in server._buffers:
-            server._read(p.conn, pending)
-    server._serve(pending)
-
-
-def _open(server, peer, key="a"):
-    peer.send(serve.encode_open_request(key, lpstate.LPRows.from_snapshot(_snap())))
-    _pump(server, [peer])
-    return peer.reply()[1]
+server = server_fixture(lambda tmp_path: stub_server(tmp_path, {"a": StubModel("a", StubSession), "b": StubModel("b", StubSession)},
+                                                     max_sessions=3, session_group=StubGroup()))
 
 
 def _round(k=2, dual=0.25):
