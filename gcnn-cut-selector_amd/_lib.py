@@ -132,6 +132,16 @@ class LpModelsLayout(C.Structure):
     _fields_ = [("models", MbatchLayout), ("lp", LpBatchLayout)]   # lp.state == models.u
 
 
+class EnsembleLayout(C.Structure):
+    _fields_ = [("u", IbatchLayout), ("n_models", C.c_int32), ("reserved", C.c_int32), ("member_off", C.c_size_t),
+                ("member_stride", C.c_size_t), ("ws_off", C.c_size_t * GROUP_MAX), ("table_off", C.c_size_t),
+                ("table_bytes", C.c_size_t)]
+
+
+class LpEnsembleLayout(C.Structure):
+    _fields_ = [("ens", EnsembleLayout), ("lp", LpBatchLayout)]   # lp.state == ens.u
+
+
 LPR_LB, LPR_UB, LPR_PRIMAL, LPR_PRIMAL_AVG = 1, 2, 4, 8      # GCNN_LPR_*: the optional column arrays a round carries
 LPR_DERIVED, LPR_ARRAYS, LPR_BLOCKS = 7, 15, 11             # GCNN_LPR_DERIVED, GCNN_LPR_ARRAYS, GCNN_LPR_BLOCKS
 
@@ -314,6 +324,11 @@ SIGNATURES = {
     "gcnn_lp_rounds": (C.c_int, [_I, C.POINTER(LpRoundsMember), _I, _P, _P, _P, _Z, _P, _D, _D, _P]),
     "gcnn_lp_rounds_edit_layout_for": (C.c_int, [_I, C.POINTER(LpRoundsEditMember), _I, C.POINTER(LpRoundsEditLayout)]),
     "gcnn_lp_rounds_edit": (C.c_int, [_I, C.POINTER(LpRoundsEditMember), _I, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_ensemble_mean": (C.c_int, [_P, _I, _I, _P, _P]),
+    "gcnn_infer_ensemble_layout_for": (C.c_int, [_DP, _I, _I, _I, _I, C.POINTER(EnsembleLayout)]),
+    "gcnn_infer_ensemble": (C.c_int, [_DP, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_lp_ensemble_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, _I, C.POINTER(LpEnsembleLayout)]),
+    "gcnn_lp_ensemble": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }
 
 _lib = None

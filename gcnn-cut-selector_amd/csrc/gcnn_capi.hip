@@ -1396,3 +1396,6 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 #include "gcnn_lprounds.hpp"
 // rounds of several resident LPs in one call, on the same edit plan (gcnn_lp_rounds, gcnn_lp_rounds_edit): launch names k_lpes_*
 #include "gcnn_lpedits.hpp"
+// one state scored by an ensemble of models, their mean ranked or selected (include/gcnn_hip.h: gcnn_ensemble_mean,
+// gcnn_infer_ensemble, gcnn_lp_ensemble): launch names k_ens_*
+#include "gcnn_ensemble.hpp"

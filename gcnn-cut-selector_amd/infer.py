@@ -2,7 +2,9 @@
 calls, gcnn_lp_batch, gcnn_infer_models and gcnn_lp_models (include/gcnn_hip.h).  What `GCNN.score_state`, `select_cuts` and their many-state forms (model.py) are composed of: the checks
 of a host state, the one packer of the upload, the forced rows, and the two sessions that own the staging buffers.  `LPSession`
 (`GCNN.open_lp`) is the host side of gcnn_lp_rows_build and gcnn_lp_round: an LP that stays on the device across separation rounds;
-`LPSessionGroup` is the host side of gcnn_lp_rounds: the rounds of several such sessions in one call."""
+`LPSessionGroup` is the host side of gcnn_lp_rounds: the rounds of several such sessions in one call.  `_EnsembleSession` and
+`_LPEnsembleSession` are the host side of gcnn_infer_ensemble and gcnn_lp_ensemble: ONE state scored by several models, their mean
+ranked or selected (`ModelSet.score_ensemble` and its siblings)."""
 
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ class ScoreArray(np.ndarray):
     order, equal scores in index order -- `sorted(range(n), key=lambda x: quality[x], reverse=True)` of model_evaluator.py:110."""
     rankings = None
     cut_index = None      # calls that start from an LP snapshot: state position -> input cut (scores are in STATE order)
+    members = None        # `ModelSet.score_ensemble`: float32 [M, K], every member's own scores (the array itself is their mean)
 
     def numpy(self):
         return np.asarray(self)
@@ -35,6 +38,7 @@ class SelectResult:
     removed ones), `n_selected` = min(n_kept, max_selected) -- the reference's 'nselectedcuts' --, `n_kept` and the `scores`."""
 
     features = None       # `HybridSelector` (hybrid.py): [K, 3] float64 efficacy, integer support, objective parallelism
+    members = None        # `ModelSet.select_cuts_ensemble`: float32 [M, K], every member's own scores (`scores` is their mean)
 
     def __init__(self, order, n_kept, n_selected, scores, cut_index=None):
         self.order, self.n_kept, self.n_selected, self.scores = order, n_kept, n_selected, scores
@@ -745,6 +749,119 @@ class _LPModelsSession(_ModelsSession):
     def last_states(self):
         """The seven arrays of every state the last call built in the arena (`_LPBatchSession.last_states`)."""
         return self.base.last_states()
+
+
+class _EnsembleSession:
+    """Host side of gcnn_infer_ensemble: one C call for ONE host state scored by up to 8 models -- the state goes up once, whatever
+    the number of models.  It packs with a `_BatchSession`'s packer into that session's pinned buffers and arena (`base`: the batch
+    session of one of the models; every model of the call lives on its device) and adds the pinned staging buffer of the grouped
+    forward passes' launch tables.  `calls`: C calls made; `upload_bytes`: bytes of state uploads they made (the launch tables,
+    the call's second copy, are not counted) -- tests and tools read both."""
+    MAX_MODELS = _lib.GROUP_MAX
+    CAP = _BatchSession.CAP
+    cached = _Staging.cached          # the same bounded cache of layouts
+
+    def __init__(self, base):
+        self.base = base
+        self.layouts = {}
+        self.staging = None
+        self.calls = 0
+        self.upload_bytes = 0
+
+    @staticmethod
+    def _counts(fshape, mode):
+        return (int(fshape[0]), int(fshape[1])) if mode == _lib.IBATCH_SELECT else (0, 0)
+
+    def _layout(self, key, fshape, mode, n_models):
+        dims = (_lib.Dims * 1)(_lib.Dims(*key))
+        f, fe = self._counts(fshape, mode)
+        EL = _lib.EnsembleLayout()
+        if _unsupported(_lib.lib().gcnn_infer_ensemble_layout_for(dims, f, fe, mode, n_models, C.byref(EL)), "gcnn_infer_ensemble_layout_for"):
+            return False
+        nf, nfe = forced_counts(((f, fe),))
+        table = np.zeros(_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE, np.int32)
+        _lib.check(_lib.lib().gcnn_infer_batch_fill_table(1, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
+        cols = table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :2].tolist()
+        return _BatchSession._entry(dims, nf, nfe, EL.u, table, cols, EL=EL, counts=(f, fe), n_cuts=key[2])
+
+    def _call(self, name, lay, head, mode, models, p_max, p_max_ub, timings, t0):
+        """The C call `name` on what lies packed in the base session's buffers; True where the library declines it."""
+        base = self.base
+        self.staging, _ = base._pin(self.staging, None, lay.EL.table_bytes, 1 << 16)
+        params = (C.c_void_p * len(models))(*(m._flat.data_ptr() for m in models))
+        nbytes = int(lay.L.in_bytes)
+        if base._enqueue_wait(name, (*head, *lay.counts, mode, len(models)), (C.c_void_p(self.staging.data_ptr()), float(p_max), float(p_max_ub)),
+                              timings, t0, params=params, may_decline=True, upload_bytes=nbytes):
+            return True
+        self.calls += 1
+        self.upload_bytes += nbytes
+        base.last = None              # the arena no longer holds that session's own plan
+        return False
+
+    def _answer(self, lay, mode, n_models):
+        """(mean, order | None, n_kept | None, members [M, K]) of the download; the flag policy as exceptions."""
+        base, out_off, n = self.base, lay.out_off, lay.n_cuts
+        verdict = base._verdict(out_off[3])
+        if verdict == "bad_index":
+            raise ValueError(BAD_INDEX)
+        if verdict:
+            raise _UseGeneralPath()
+        mean, order, n_kept = base._read(out_off[0], out_off[1] if mode else None, out_off[2] if mode == _lib.IBATCH_SELECT else None, n)
+        at, stride = int(lay.EL.member_off), int(lay.EL.member_stride)
+        members = np.stack([base.out_np[at + m * stride:at + m * stride + 4 * n].view(np.float32) for m in range(n_models)])
+        return mean, order, n_kept, members
+
+    def run(self, inputs, forced, mode, models, p_max=0.0, p_max_ub=0.0, timings=None):
+        """inputs: the model's 10-tuple of host arrays; forced: packed (ptr, col, val), read in selection mode only; models: the
+        `GCNN`s in the ensemble's order.  Returns (mean, order | None, n_kept | None, members); raises _UseGeneralPath for what
+        the call declines and ValueError for an index out of range."""
+        t0 = time.perf_counter()
+        arrays, key = check_state(inputs)
+        if edges_without_nodes(key):
+            raise ValueError(BAD_INDEX)
+        fshape = (forced[0].size - 1, forced[1].size) if mode == _lib.IBATCH_SELECT else (0, 0)
+        lay = self.cached((mode, key, fshape, len(models)), self._layout, key, fshape, mode, len(models))
+        if lay is False:
+            raise _UseGeneralPath()
+        self.base._pack(lay, [(arrays, key)], [forced] if mode == _lib.IBATCH_SELECT else None)
+        if self._call("gcnn_infer_ensemble", lay, (lay.dims,), mode, models, p_max, p_max_ub, timings, t0):
+            raise _UseGeneralPath()
+        return self._answer(lay, mode, len(models))
+
+
+class _LPEnsembleSession(_EnsembleSession):
+    """Host side of gcnn_lp_ensemble: `_EnsembleSession` over an `_LPBatchSession` (`base`) -- one upload of the packed snapshot,
+    the state built once in the arena.  The library writes the call's tables into the pinned upload itself."""
+
+    def _layout(self, dims, fshape, mode, n_models):
+        f, fe = self._counts(fshape, mode)
+        L = _lib.LpEnsembleLayout()
+        if _unsupported(_lib.lib().gcnn_lp_ensemble_layout_for(C.byref(_lib.LpDims(**dims)), f, fe, mode, n_models, C.byref(L)),
+                        "gcnn_lp_ensemble_layout_for"):
+            return False
+        return self.base._entry([dims], ((f, fe),), None, None, L.lp, EL=L.ens, counts=(f, fe), n_cuts=dims["n_cuts"])
+
+    def run(self, snap, forced, mode, models, p_max=0.0, p_max_ub=0.0, timings=None):
+        """`_EnsembleSession.run` from an `LPSnapshot`: (mean, order | None, n_kept | None, members, cut_index), in STATE order."""
+        from . import lpstate
+        t0 = time.perf_counter()
+        base = self.base
+        arrays, dims = base.check(snap)
+        select = mode == _lib.IBATCH_SELECT
+        fshape = (forced[0].size - 1, forced[1].size) if select else (0, 0)
+        lay = self.cached((mode, _int_key(dims), fshape, len(models)), self._layout, dims, fshape, mode, len(models))
+        if lay is False:
+            raise _UseGeneralPath()
+        base._buffers(lay.L)
+        lpstate.pack_snapshot(base.in_np, lay.snap_at[0], arrays)
+        base._put_forced_stacked(lay.forced_off, lay.f_off, lay.fe_off, [forced] if select else None)
+        d = _lib.LpDims(**dims)
+        if self._call("gcnn_lp_ensemble", lay, (C.byref(d),), mode, models, p_max, p_max_ub, timings, t0):
+            raise _UseGeneralPath()
+        base.last = (lay.L, lay.keys)      # the arena holds this call's state, at the places `base.last_states` reads
+        out, out_off, n = base.out_np, lay.out_off, lay.n_cuts
+        lpstate.raise_for_flags(out[out_off[4]:out_off[4] + 16].view(np.int32))
+        return self._answer(lay, mode, len(models)) + (out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy(),)
 
 
 class LPSession(_Staging):

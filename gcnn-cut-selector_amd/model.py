@@ -21,7 +21,8 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _InferenceSession, _LPBatchSession, _LPModelsSession, _LPSession, _ModelsSession,
+from .infer import (BAD_INDEX, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _EnsembleSession, _InferenceSession, _LPBatchSession, _LPEnsembleSession, _LPModelsSession, _LPSession,
+                    _ModelsSession,
                     _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
 
@@ -774,8 +775,9 @@ class ModelSet:
     per 8 models / 64 states: one upload, one index pass and one by-variable stage, the models' forward passes as a group, one
     download.  Every state's result has the bits of its own model's `GCNN.score_states` / `select_cuts_many` on that model's
     states alone.  `score_lps` and `select_cuts_lp_many` are the same for raw `LPSnapshot`s (gcnn_lp_models: the states are built
-    on the device in front of the same work), with the bits of `GCNN.score_lps` / `select_cuts_lp_many`.  All models live on one
-    device."""
+    on the device in front of the same work), with the bits of `GCNN.score_lps` / `select_cuts_lp_many`.  `score_ensemble`,
+    `select_cuts_ensemble` and their LP forms let up to 8 of the models score ONE state and rank or select by the mean of their
+    scores, in one call (gcnn_infer_ensemble / gcnn_lp_ensemble).  All models live on one device."""
     MAX_MODELS = _ModelsSession.MAX_MODELS
 
     def __init__(self, models):
@@ -788,6 +790,8 @@ class ModelSet:
         self._number = {k: i for i, k in enumerate(self.models)}
         self._session = None
         self._lp_session = None
+        self._ensemble = None             # the sessions of the `*_ensemble` methods, built on first use
+        self._lp_ensemble = None
         self._lp_rounds = None            # the LPSessionGroup of `score_rounds` / `select_cuts_rounds`, built on first use
         self.calls = 0                    # gcnn_infer_models and gcnn_lp_models calls made
         self.max_models_per_call = 0      # the most models one of them served
@@ -930,3 +934,154 @@ class ModelSet:
         group, sessions = self._rounds(keys, sessions, batch_removes)
         return group.select_cuts(sessions, rounds, forced, p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected, appends=appends,
                                  return_exceptions=return_exceptions, removes=removes)
+
+    # ---- ensembles: ONE state scored by several of the set's models, the mean ranked or selected once ----------------------------
+    def ensemble_session(self, lp=False):
+        """The session behind the `*_ensemble` methods (`_EnsembleSession`; with `lp`, `_LPEnsembleSession`): its `calls` and
+        `upload_bytes` count the one-call path's C calls and state uploads."""
+        first = next(iter(self.models.values()))
+        if lp:
+            if self._lp_ensemble is None:
+                self._lp_ensemble = _LPEnsembleSession(first._sess("_lp_batch_session", _LPBatchSession))
+            return self._lp_ensemble
+        if self._ensemble is None:
+            self._ensemble = _EnsembleSession(first._sess("_batch_session", _BatchSession))
+        return self._ensemble
+
+    def _ensemble_models(self, keys):
+        """The models of an ensemble in the caller's order; ValueError before any device work for zero or more than 8 keys, a
+        duplicate key and an unknown key."""
+        keys = list(keys)
+        if not 1 <= len(keys) <= self.MAX_MODELS:
+            raise ValueError(f"an ensemble holds 1..{self.MAX_MODELS} models, got {len(keys)}")
+        if len(set(keys)) != len(keys):
+            raise ValueError(f"an ensemble names every model once, got {keys!r}")
+        for k in keys:
+            if k not in self.models:
+                raise ValueError(f"no model {k!r}")
+        return [self.models[k] for k in keys]
+
+    @staticmethod
+    def _ensemble_general(models, state, packed, p_max, p_max_ub, n_cuts):
+        """The general path of an ensemble -- `prepare` once, `trainer.forward_group` over the models with that one batch,
+        `ops.ensemble_mean`, and with `packed` forced rows gcnn_select_cuts over the mean: (mean, order | None, n_kept | None,
+        members) as host values, with the bits of the one-call path."""
+        from . import trainer
+        first = models[0]
+        with torch.no_grad():
+            batch = first.prepare(state)
+            rows = trainer.forward_group(models, [batch] * len(models))
+            mean = ops.ensemble_mean(rows)
+            order = n_kept = None
+            if packed is not None:
+                forced_dev = tuple(torch.from_numpy(a).to(first.device) for a in packed)
+                order, n_kept = ops.select_cuts(mean, batch.cut_graph, None, forced_dev, p_max=p_max, p_max_ub=p_max_ub, max_cuts=n_cuts)
+                order, n_kept = order.cpu().numpy(), int(n_kept.cpu()[0])
+            members = torch.stack(rows).cpu().numpy() if rows else np.zeros((0, n_cuts), np.float32)
+            return mean.cpu().numpy().view(ScoreArray), order, n_kept, members
+
+    @staticmethod
+    def _empty_ensemble(n_models, select, max_selected=None, cut_index=None):
+        """The answer for a state without cuts."""
+        scores = np.zeros(0, np.float32).view(ScoreArray)
+        members = np.zeros((n_models, 0), np.float32)
+        if select:
+            res = SelectResult(np.zeros(0, np.int32), 0, n_selected(0, max_selected), scores, cut_index)
+            res.members = members
+            return res
+        scores.members, scores.cut_index = members, cut_index
+        return scores
+
+    def _score_ensemble(self, models, state, rank, lp, timings=None):
+        first = models[0]
+        if lp:
+            n_cuts = int(np.asarray(state.cut_lhs).shape[0])
+        else:
+            n_cuts = state.dims.n_cuts if isinstance(state, Batch) else int(state[4].shape[0])
+        on_device = first._rank_on_device(rank, n_cuts) and n_cuts <= ops.SELECT_MAX_CUTS
+        cut_index = None
+        if n_cuts == 0:
+            if lp:
+                self.ensemble_session(True).base.check(state)
+            scores = self._empty_ensemble(len(models), False, cut_index=np.zeros(0, np.int32) if lp else None)
+            if rank:
+                scores.rankings = np.zeros(0, np.int32)
+            return scores
+        got = None
+        if lp or is_host_state(state):
+            try:
+                got = self.ensemble_session(lp).run(state, None, _lib.IBATCH_RANK if on_device else _lib.IBATCH_SCORES, models,
+                                                    timings=timings)
+            except _UseGeneralPath:
+                pass
+        if got is None:
+            on_device = False
+            if lp:
+                state, cut_index = first._lp().build_state(state)
+                cut_index = cut_index.cpu().numpy()
+            got = self._ensemble_general(models, state, None, 0.0, 0.0, n_cuts)
+        elif lp:
+            cut_index = got[4]
+        scores, order, _, members = got[:4]
+        scores.members, scores.cut_index = members, cut_index
+        if rank:
+            scores.rankings = order if on_device else stable_ranking(scores)
+        return scores
+
+    def _select_ensemble(self, models, state, forced, p_max, p_max_ub, max_selected, lp, timings=None):
+        ops.check_thresholds(p_max, p_max_ub)
+        first = models[0]
+        if lp:
+            n_cuts, n_vars = int(np.asarray(state.cut_lhs).shape[0]), _snapshot_vars(state)
+        else:
+            n_cuts = state.dims.n_cuts if isinstance(state, Batch) else int(state[4].shape[0])
+            n_vars = state.dims.n_vars if isinstance(state, Batch) else int(state[3].shape[0])
+        first._check_select_size("select_cuts_lp_ensemble" if lp else "select_cuts_ensemble", "snapshot" if lp else "state", n_cuts)
+        packed = normalize_forced(forced, n_vars)
+        cut_index = None
+        if n_cuts == 0:
+            if lp:
+                self.ensemble_session(True).base.check(state)
+            return self._empty_ensemble(len(models), True, max_selected, np.zeros(0, np.int32) if lp else None)
+        got = None
+        if lp or is_host_state(state):
+            try:
+                got = self.ensemble_session(lp).run(state, packed, _lib.IBATCH_SELECT, models, p_max, p_max_ub, timings=timings)
+            except _UseGeneralPath:
+                pass
+        if got is None:
+            if lp:
+                state, cut_index = first._lp().build_state(state)
+                cut_index = cut_index.cpu().numpy()
+            got = self._ensemble_general(models, state, packed, p_max, p_max_ub, n_cuts)
+        elif lp:
+            cut_index = got[4]
+        scores, order, n_kept, members = got[:4]
+        result = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
+        result.members = members
+        return result
+
+    def score_ensemble(self, keys, state, rank=False, timings=None):
+        """ONE state scored by the models `keys` (1..8, each once, in this order) and averaged: the reference trains five seeds per
+        problem (model_trainer.py:38-49) and this lets all of them score the same round.  Returns a `ScoreArray` holding the mean
+        -- acc = member[0], acc += member[m] in the order of `keys`, acc / float32(M), all in fp32 --, with `.members` (float32
+        [M, K]: row m has the bits of `score_states(keys, [state] * M)[m]`) and, with `rank`, `.rankings` of the mean as
+        `GCNN.score_state` gives them.  A host state takes ONE gcnn_infer_ensemble call: one upload of the state, one graph plan,
+        the M forward passes as one group, one download.  States that call declines, device tensors and prepared `Batch`es take
+        `prepare` once + `trainer.forward_group` + `ops.ensemble_mean`; the bits are the same."""
+        return self._score_ensemble(self._ensemble_models(keys), state, rank, False, timings)
+
+    def select_cuts_ensemble(self, keys, state, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None):
+        """`GCNN.select_cuts` over the mean of the models `keys` (as `score_ensemble` defines it): the plugin's ranking and
+        parallelism filter (model_evaluator.py:109-154) run once, on the device, in the same call as the M forward passes.  Returns
+        a `SelectResult` whose `scores` are the mean, with `.members`."""
+        return self._select_ensemble(self._ensemble_models(keys), state, forced, p_max, p_max_ub, max_selected, False, timings)
+
+    def score_lp_ensemble(self, keys, snapshot, rank=False, timings=None):
+        """`score_ensemble` from an `LPSnapshot` (gcnn_lp_ensemble: one upload of the packed snapshot, the state built once on the
+        device).  Results are in STATE order and carry `.cut_index`."""
+        return self._score_ensemble(self._ensemble_models(keys), snapshot, rank, True, timings)
+
+    def select_cuts_lp_ensemble(self, keys, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None):
+        """`select_cuts_ensemble` from an `LPSnapshot`; `order` is in STATE order and the result carries `.cut_index`."""
+        return self._select_ensemble(self._ensemble_models(keys), snapshot, forced, p_max, p_max_ub, max_selected, True, timings)

@@ -217,3 +217,31 @@ def select_cuts(quality, cut_graph: BipartiteGraph, cut_offsets=None, forced=Non
                                         float(p_max), float(p_max_ub), _ptr(order), _ptr(n_kept), _ptr(ws), ws_bytes,
                                         _stream(dev)), "gcnn_select_cuts")
     return order, n_kept
+
+
+# ---- ensembles (gcnn_ensemble_mean): the mean of several models' scores of one state, model_trainer.py:38-49's five seeds --------
+ENSEMBLE_MAX = _lib.GROUP_MAX
+
+
+def ensemble_mean(member_scores):
+    """Mean of 1..8 score rows on the device (k_ens_mean); nothing is synchronised.  member_scores: a list of 1-D fp32 device
+    tensors of one length, in the ensemble's order.  acc = row[0], acc = acc + row[m] in that order, acc / float(M): fp32,
+    round-to-nearest, nothing contracted, so a float32 loop on the host gives the same bits; one row comes back as its copy."""
+    rows = list(member_scores)
+    if not 1 <= len(rows) <= ENSEMBLE_MAX:
+        raise ValueError(f"ensemble_mean: 1..{ENSEMBLE_MAX} score rows expected, got {len(rows)}")
+    first = rows[0]
+    for r in rows:
+        if not isinstance(r, torch.Tensor) or not r.is_cuda or r.dtype != torch.float32 or r.dim() != 1:
+            raise ValueError("ensemble_mean: every row must be a 1-D fp32 device tensor")
+        if r.device != first.device or r.numel() != first.numel():
+            raise ValueError("ensemble_mean: the rows must have one length and live on one device")
+    rows = [r.contiguous() for r in rows]
+    n = first.numel()
+    if n >= 2 ** 31:
+        raise ValueError("ensemble_mean: at most 2^31 - 1 scores per row")
+    mean = torch.empty(n, dtype=torch.float32, device=first.device)
+    ptrs = (C.c_void_p * len(rows))(*(r.data_ptr() for r in rows))
+    with torch.cuda.device(first.device):
+        _lib.check(_lib.lib().gcnn_ensemble_mean(ptrs, len(rows), n, _ptr(mean), _stream(first.device)), "gcnn_ensemble_mean")
+    return mean

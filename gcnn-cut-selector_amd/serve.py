@@ -46,6 +46,7 @@ KIND_SCORE, KIND_RANK, KIND_SELECT = 0, 1, 2
 # there is an incumbent.  Replies carry cut_index as one more array.
 KIND_LP_SCORE, KIND_LP_RANK, KIND_LP_SELECT = 3, 4, 5
 _LP_BASE = {KIND_LP_SCORE: KIND_SCORE, KIND_LP_RANK: KIND_RANK, KIND_LP_SELECT: KIND_SELECT}
+_ENSEMBLE_KINDS = (KIND_SCORE, KIND_RANK, KIND_SELECT, KIND_LP_SCORE, KIND_LP_RANK, KIND_LP_SELECT)   # what an ensemble's name may ask for
 # SCIP's hybrid selection from the cut rows alone (hybrid.HybridSelector; no model: the model key is ignored): the eight arrays of a
 # lpstate.CutSnapshot, one float64 array with `infinity`, then the optional forced pair.  Replies carry the float64 quality, order,
 # cut_index (the identity) and the features [K, 3].
@@ -580,20 +581,28 @@ class ScoringServer:
     them served) and session_solo_rounds (rounds the group answered through the session's own call: a ranking left to the host, a
     member the batched call declined).
     Expert rounds of a data collector (`ScoringClient.collect_lp`) are served one by one by one `collect.Collector`, built on first
-    use; `stats["collect_calls"]` counts them.  They and the hybrid kind need no model: `models` may be empty."""
+    use; `stats["collect_calls"]` counts them.  They and the hybrid kind need no model: `models` may be empty.
+    `ensembles`: {name: [model keys]} -- a client opened with an ensemble's name uses the kinds 0-5 as they are and is answered with
+    the MEAN of those models' scores, its ranking or the selection over it (`ModelSet.score_ensemble`, `select_cuts_ensemble` and
+    their LP forms; the members' own scores stay on the server).  A name must not be a model key; its 1..8 keys must be loaded
+    models, each named once, all on one device.  Every ensemble request is answered with its own call, never grouped with other
+    requests; `stats["ensemble_calls"]` counts them.  Every other kind under an ensemble's name gets the error reply of an unknown
+    model."""
     SESSIONS_PER_CALL = 8
 
     def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True, max_sessions=64,
-                 session_group=None):
+                 session_group=None, ensembles=None):
         self.models = dict(models)
         self.address = address
+        self.ensembles = self._checked_ensembles(ensembles, model_set)
         # a ModelSet needs all models on one device: models spread over several devices are served per model, as before
         one_device = len({str(getattr(m, "device", None)) for m in self.models.values()}) <= 1
         self.cross_model = bool(cross_model) and (model_set is not None or one_device)
         self.cross_model_lp = bool(cross_model_lp)
         self._model_set = model_set
         self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0, sessions_open=0,
-                          session_rounds=0, session_calls=0, session_solo_rounds=0, max_sessions_per_call=0, collect_calls=0)
+                          session_rounds=0, session_calls=0, session_solo_rounds=0, max_sessions_per_call=0, collect_calls=0,
+                          ensemble_calls=0)
         self.max_sessions = int(max_sessions)
         self._sessions = {}            # id -> (the connection that owns it, the LPSession)
         self._next_session = 1
@@ -607,6 +616,39 @@ class ScoringServer:
         self._buffers = {}
         self._hybrid = None            # the HybridSelector, built on first use on the device of the first model
         self._collector = None         # the Collector of the expert rounds, built on first use on the same device
+
+    def _checked_ensembles(self, ensembles, model_set):
+        """{name: [keys]} as the server keeps it; ValueError for a name that is a model key, for keys that are not loaded models or
+        named twice, for fewer than 1 or more than 8 of them, and for models on more than one device."""
+        out = {}
+        for name, keys in dict(ensembles or {}).items():
+            keys = list(keys)
+            if name in self.models:
+                raise ValueError(f"ensemble {name!r}: the name is a model key")
+            if not 1 <= len(keys) <= 8 or len(set(keys)) != len(keys):
+                raise ValueError(f"ensemble {name!r}: 1..8 model keys, each once, expected, got {keys!r}")
+            missing = [k for k in keys if k not in self.models]
+            if missing:
+                raise ValueError(f"ensemble {name!r}: no model {missing[0]!r}")
+            out[name] = keys
+        if out and model_set is None and len({str(getattr(m, "device", None)) for m in self.models.values()}) > 1:
+            raise ValueError("ensembles need all models of the server on one device")
+        return out
+
+    def _ensemble_one(self, conn, req):
+        """A request of the kinds 0-5 under an ensemble's name, answered with its own `ModelSet.*_ensemble` call."""
+        kind = req["kind"]
+        lp, base, keys = kind in _LP_BASE, _LP_BASE.get(kind, kind), self.ensembles[req["model_key"]]
+        self.stats["calls"] += 1
+        self.stats["ensemble_calls"] += 1
+
+        def call():
+            mset, arg = self._set(), req["snapshot" if lp else "state"]
+            if base == KIND_SELECT:
+                select = mset.select_cuts_lp_ensemble if lp else mset.select_cuts_ensemble
+                return [select(keys, arg, req["forced"], p_max=req["p_max"], p_max_ub=req["p_max_ub"], max_selected=req["max_selected"])]
+            return [(mset.score_lp_ensemble if lp else mset.score_ensemble)(keys, arg, rank=base == KIND_RANK)]
+        self._answer_group([(conn, req)], call, _reply_of(base, lp))
 
     def _device(self):
         """The device of the first model; None (the current device) for a server that holds no model: the kinds without one."""
@@ -725,7 +767,10 @@ class ScoringServer:
             self.stats["requests"] += 1
             try:
                 req = decode_request(message)
-                if _KINDS[req["kind"]]["model"] and req["model_key"] not in self.models:
+                if req["model_key"] in self.ensembles:
+                    if req["kind"] not in _ENSEMBLE_KINDS:       # sessions, hybrid and collector rounds know no ensemble
+                        raise KeyError(f"no model {req['model_key']!r}")
+                elif _KINDS[req["kind"]]["model"] and req["model_key"] not in self.models:
                     raise KeyError(f"no model {req['model_key']!r}")
                 pending.append((conn, req))
             except Exception as exc:  # noqa: BLE001 -- a bad request gets its error; the server keeps serving
@@ -847,7 +892,7 @@ class ScoringServer:
         groups = {}
         for conn, req in pending:
             kind = req["kind"]
-            if kind in _SESSION_KINDS or kind == KIND_COLLECT:
+            if kind in _SESSION_KINDS or kind == KIND_COLLECT or req["model_key"] in self.ensembles:
                 continue
             hybrid = kind == KIND_HYBRID_SELECT       # no model: requests of every model key share a group
             selects = hybrid or _LP_BASE.get(kind, kind) == KIND_SELECT
@@ -872,6 +917,8 @@ class ScoringServer:
         for conn, req in pending:
             if req["kind"] == KIND_COLLECT and conn in self._buffers:
                 self._collect_one(conn, req)
+            elif req["model_key"] in self.ensembles and req["kind"] in _ENSEMBLE_KINDS:
+                self._ensemble_one(conn, req)
         for gkey, items in self._grouped(pending).items():
             hybrid = gkey[1] == KIND_HYBRID_SELECT
             lp = gkey[1] in _LP_BASE or hybrid

@@ -1024,6 +1024,68 @@ int gcnn_lp_rounds_edit_layout_for(int32_t n, const gcnn_lp_rounds_edit_member* 
 int gcnn_lp_rounds_edit(int32_t n, const gcnn_lp_rounds_edit_member* members /* host */, int32_t mode, const void* host_in, void* host_out,
                         void* arena, size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
 
+/* ---- ensembles: ONE state scored by several models, their mean ranked or selected once -----------------------------------------------
+ * The reference trains five seeds per problem (train_models, model_trainer.py:38-49); its selector plugin ranks and filters by ONE
+ * quality vector (model_evaluator.py:82-154).  These entry points let 1..GCNN_GROUP_MAX models score the same round and hand the
+ * plugin the mean of their predicted bound improvements.  For members m = 0..M-1 in the caller's order and a state with K cuts:
+ *   member[m][k]  model m's score of cut k: the bits gcnn_infer_models gives for that state and that model;
+ *   mean[k]       acc = member[0][k]; acc = acc + member[m][k] for m = 1..M-1 in that order; acc / float(M) -- every step fp32,
+ *                 rounded to nearest, nothing contracted: a float32 loop on the host gives the same bits.  M == 1: mean ==
+ *                 member[0] bit for bit.  A NaN in any member gives a NaN mean.
+ * gcnn_ensemble_mean is that combination alone (model_evaluator.py:82-154 reads its result, model_trainer.py:38-49 supplies its
+ * inputs): member_scores is a HOST array of n_models DEVICE pointers to [n] floats, mean [n] is device memory; one launch on
+ * `stream`, none for n == 0.  GCNN_E_BADARG for n_models outside 1..GCNN_GROUP_MAX, n < 0, or a null pointer with n > 0. */
+int gcnn_ensemble_mean(const float* const* member_scores /* host [n_models] of device pointers */, int32_t n_models, int32_t n,
+                       float* mean /* device [n] */, void* stream);
+/* gcnn_infer_ensemble (model_evaluator.py:82-154 for the models of model_trainer.py:38-49): gcnn_infer_batch's contract for ONE host
+ * state and n_models models.  mode: GCNN_IBATCH_SCORES / _RANK / _SELECT.  host_in (pinned): gcnn_infer_batch's upload of one state
+ * at layout.u.in_off (the table written by gcnn_infer_batch_fill_table(1, ...), the zero block, the seven arrays with STATE-LOCAL
+ * ids, the forced rows in selection mode) -- the state goes up ONCE, whatever n_models is.  params: host array of n_models device
+ * pointers, all different.  host_staging: pinned, 16-byte aligned, layout.table_bytes bytes (the launch tables of the grouped
+ * forward passes; the second host->device copy).
+ * Device work: the index pass and the by-variable sort of the one state (ONE graph plan), the n_models forward passes as one group
+ * (one launch per distinct kernel and stage; every member reads the same feature arrays and the same two graphs and has its own
+ * parameters, workspace and score row), the mean, then gcnn_infer_batch's ranking of, or gcnn_select_cuts' filter over, the mean.
+ * host_out (pinned, layout.u.out_bytes), ONE device->host copy: u.out_off[0] mean [K], u.out_off[1] order [K] int32 (RANK: the
+ * descending stable ranking of the mean, NaN as -inf; SELECT: as gcnn_select_cuts), u.out_off[2] n_kept int32 (SELECT), u.out_off[3]
+ * the four flags of gcnn_infer_batch, and at member_off + m * member_stride member[m] [K].  A flag set => nothing else is valid.
+ * The arena holds n_models forward workspaces.  Returned before anything is enqueued: GCNN_E_BADARG for n_models outside
+ * 1..GCNN_GROUP_MAX, a negative size, an unknown mode, a missing buffer, a short or misaligned arena, a threshold that is not
+ * finite; GCNN_E_UNSUPPORTED for more than 32,768 variables, for more than 4,096 cuts in RANK / SELECT, for edges with nothing to
+ * point at and for a forward pass the group recorder cannot take: the caller takes the general path (gcnn_graph_build,
+ * gcnn_group_forward, gcnn_ensemble_mean, gcnn_select_cuts), which gives the same bits. */
+typedef struct gcnn_ensemble_layout {
+    gcnn_ibatch_layout u;                          /* the one state's union: upload, download, arena (dev_off: internal) */
+    int32_t n_models, reserved;
+    size_t member_off, member_stride;              /* host_out: member m's scores at member_off + m * member_stride */
+    size_t ws_off[GCNN_GROUP_MAX], table_off;      /* internal: the members' forward workspaces and the launch tables in the arena */
+    size_t table_bytes;                            /* host_staging holds this much */
+} gcnn_ensemble_layout;
+int gcnn_infer_ensemble_layout_for(const gcnn_dims* dims, int32_t n_forced, int32_t n_forced_entries, int32_t mode, int32_t n_models,
+                                   gcnn_ensemble_layout* layout /* host */);
+int gcnn_infer_ensemble(const gcnn_dims* dims, int32_t n_forced, int32_t n_forced_entries, int32_t mode, int32_t n_models,
+                        const float* const* params /* host [n_models] */, const void* host_in, void* host_out, void* arena,
+                        size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
+/* gcnn_lp_ensemble (model_evaluator.py:82-154 for the models of model_trainer.py:38-49): the same from ONE raw LP snapshot --
+ * gcnn_lp_batch's contract for one snapshot and n_models models.  ONE upload of the packed snapshot (+ forced rows), gcnn_lp_batch's
+ * two builder launches build the state ONCE where gcnn_infer_ensemble's upload would have put it, then that call's device work.
+ * layout.ens: gcnn_infer_ensemble's layout for the built state's sizes (nothing of it is uploaded); layout.lp: as in
+ * gcnn_lp_batch_layout with lp.state == ens.u.  host_in (pinned, lp.in_bytes, WRITABLE): the call itself writes the tables into
+ * [0, lp.table_bytes); the caller packs the snapshot at lp.snap_base[0] + gcnn_lp_layout.snap_off[i] and the forced rows at
+ * lp.forced_off.  host_out (pinned, lp.out_bytes): gcnn_infer_ensemble's block (mean, order, n_kept, flags, members at
+ * ens.member_off), then lp.out_off[4] the four LP flags and lp.out_off[5] cut_index [K].  Everything is in STATE order.
+ * Returned before anything is enqueued: what gcnn_infer_ensemble returns for the built state's sizes, and GCNN_E_BADARG for a
+ * gcnn_lp_dims gcnn_lp_layout_for refuses. */
+typedef struct gcnn_lp_ensemble_layout {
+    gcnn_ensemble_layout ens;
+    gcnn_lp_batch_layout lp;
+} gcnn_lp_ensemble_layout;
+int gcnn_lp_ensemble_layout_for(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries, int32_t mode, int32_t n_models,
+                                gcnn_lp_ensemble_layout* layout /* host */);
+int gcnn_lp_ensemble(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries, int32_t mode, int32_t n_models,
+                     const float* const* params /* host [n_models] */, void* host_in, void* host_out, void* arena, size_t arena_bytes,
+                     void* host_staging, double p_max, double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
