@@ -228,6 +228,14 @@ class LpRoundsEditLayout(C.Structure):
                 ("arena_bytes", C.c_size_t)]
 
 
+class LpRoundEnsembleLayout(C.Structure):   # gcnn_lp_round_ensemble_layout: the solo round's layout, then where the ensemble's pieces lie
+    _fields_ = [("round", LpRoundLayout), ("n_models", C.c_int32), ("reserved", C.c_int32), ("in_bytes", C.c_size_t),
+                ("out_bytes", C.c_size_t), ("solo_out_bytes", C.c_size_t), ("flags_off", C.c_size_t), ("append_flags_off", C.c_size_t),
+                ("member_off", C.c_size_t), ("member_stride", C.c_size_t), ("arena_bytes", C.c_size_t), ("solo_arena_bytes", C.c_size_t),
+                ("round_off", C.c_size_t), ("out_base", C.c_size_t), ("ws_off", C.c_size_t * GROUP_MAX), ("table_off", C.c_size_t),
+                ("table_bytes", C.c_size_t)]
+
+
 # gcnn_prenorm_merge's state: fp32 count at byte 0, mean [units] and var [units] at these byte offsets
 PRENORM_STATE_BYTES, PRENORM_STATE_MEAN, PRENORM_STATE_VAR = 272, 16, 80   # GCNN_PRENORM_STATE_*
 
@@ -329,6 +337,8 @@ SIGNATURES = {
     "gcnn_infer_ensemble": (C.c_int, [_DP, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
     "gcnn_lp_ensemble_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, _I, C.POINTER(LpEnsembleLayout)]),
     "gcnn_lp_ensemble": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_lp_round_ensemble_layout_for": (C.c_int, [C.POINTER(LpRoundsEditMember), _I, _I, C.POINTER(LpRoundEnsembleLayout)]),
+    "gcnn_lp_round_ensemble": (C.c_int, [C.POINTER(LpRoundsEditMember), _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }
 
 _lib = None

@@ -100,7 +100,10 @@ extern "C" int gcnn_lp_round_layout_for(const gcnn_lp_dims* d, int32_t present, 
 // the upload already lies at dev_off[0] of the arena (gcnn_lpremove.hpp's round with edits brings it up with the list and the block).
 // at (gcnn_lpedits.hpp's calls of several sessions): the upload lies at at->up, the download block is at->out, the forward's flag
 // block is cleared where the download finds it, and nothing is copied: the caller brings everything up and down itself.
+// fwd (gcnn_lpens.hpp's round of an ensemble): what is enqueued in place of the one forward pass, on the same condition; it leaves
+// the scores where the forward pass leaves them, at the head of the download block.
 struct LprAt { char* up; char* out; };
+struct LprForward { int (*run)(void* self, hipStream_t st); void* self; };
 static int lpr_check(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries, const gcnn_lp_resident* res,
                      const float* params, const void* host_in, void* host_out, void* arena, size_t arena_bytes, int32_t want_order,
                      double p_max, double p_max_ub, size_t extra_out, gcnn_lp_round_layout* L) {
@@ -123,7 +126,7 @@ static int lpr_check(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, i
 
 static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t present, int32_t n_forced, const gcnn_lp_resident* res,
                    const float* params, const void* host_in, void* host_out, void* arena, int32_t want_order, double p_max,
-                   double p_max_ub, void* stream, const LprAt* at = nullptr) {
+                   double p_max_ub, void* stream, const LprAt* at = nullptr, const LprForward* fwd = nullptr) {
     int rc = 0;
     const gcnn_dims sd = lp_state_dims(d);
     const gcnn_graph& cg = res->cons_graph;
@@ -180,8 +183,9 @@ static int lpr_run(const gcnn_lp_dims* d, const gcnn_lp_round_layout& L, int32_t
     gcnn_graph kg; memset(&kg, 0, sizeof(kg));
     kg.l_ptr = cut_l_ptr; kg.l_oth = a.cut_ei + a.nnz_k; kg.l_coef = a.cut_ef; kg.v_ptr = cg.v_ptr;    // (v_*: never read, as in infer_run)
     if (want_order >= 0 && sd.n_cuts > 0 &&           // (a round without cuts has nothing to score: it only refreshes the resident columns)
-        (rc = forward_impl(&sd, params, res->cons_feats, a.var_feats, a.cut_feats, &cg, &kg, (float*)(A + L.dev_off[7]),
-                           gcnn_workspace_floats(&sd), (float*)out, 0, nullptr, 0.f, st, nullptr)))
+        (rc = fwd ? fwd->run(fwd->self, st)
+                  : forward_impl(&sd, params, res->cons_feats, a.var_feats, a.cut_feats, &cg, &kg, (float*)(A + L.dev_off[7]),
+                                 gcnn_workspace_floats(&sd), (float*)out, 0, nullptr, 0.f, st, nullptr)))
         return rc;
     gcnn_infer_layout IL; memset(&IL, 0, sizeof(IL));
     IL.dev_off[6] = (size_t)(out - A); IL.out_bytes = L.out_bytes;

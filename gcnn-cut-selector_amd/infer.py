@@ -1487,6 +1487,95 @@ class LPSession(_Staging):
         self._kept, self._stale = {}, set()
 
 
+class LPEnsembleSession(LPSession):
+    """An `LPSession` whose rounds are scored by an ensemble of 1..8 models (`ModelSet.open_lp_ensemble`): the reference trains
+    five seeds per problem (model_trainer.py:38-49) and its selector plugin ranks and filters by one quality vector
+    (model_evaluator.py:82-154), here the fp32 mean of the members' scores.  Nothing in a resident LP belongs to a model, so the
+    session is the plain one -- rows, edits, `state`, guards and `upload_bytes` are inherited unchanged -- and only the round's
+    call differs: gcnn_lp_round_ensemble uploads what the plain round uploads, whatever the number of models, runs the edits and
+    the round's two state launches once, the M forward passes as one group over that one state, the mean, and the ranking or the
+    selection over the mean, and brings the mean and the members' rows home in one download.
+    A round's result is by definition what `ModelSet.score_lp_ensemble` / `select_cuts_lp_ensemble` give for the same keys on
+    `lpstate.assemble(rows after the call's edits, round)`, bit for bit, field for field: the mean, `.members` (float32 [M, K];
+    row m is what `models[m].open_lp(rows).score(round)` returns), `.rankings` or `order`, `n_kept`, `n_selected`, `.cut_index`.
+    The session holds no parameters: every round reads each model's current flat parameter buffer.  It takes its device from the
+    first model.  An `LPSessionGroup` refuses it: one ensemble of five fills a grouped call's eight forward passes.
+    `calls`: gcnn_lp_round_ensemble calls made."""
+
+    def __init__(self, models, rows, deep=True):
+        self.models = list(models)
+        if not 1 <= len(self.models) <= _lib.GROUP_MAX:
+            raise ValueError(f"an ensemble holds 1..{_lib.GROUP_MAX} models, got {len(self.models)}")
+        if len({str(m.device) for m in self.models}) != 1:
+            raise ValueError("LPEnsembleSession: all models must be on one device")
+        self.pin_tab = None
+        self.calls = 0
+        self._ens = None                  # the layout of the last ensemble call: where its download keeps the members' rows
+        super().__init__(self.models[0], rows, deep)
+
+    def _buffers(self, L):
+        """The plain session's buffers for `L`; for the layout of an ensemble call (it has `table_bytes`) also the pinned staging
+        buffer of the group's launch tables."""
+        super()._buffers(L)
+        if hasattr(L, "table_bytes"):
+            self.pin_tab, _ = self._pin(self.pin_tab, None, L.table_bytes, 1 << 16)
+
+    def _enqueue(self, job, want_order, p_max, p_max_ub, timings, t0):
+        """The one C call of a packed job and the wait for its download: gcnn_lp_round_ensemble for scores, ranking or selection,
+        whatever edits the job carries; the state alone (`want_order` < 0) needs no model and takes the plain session's call."""
+        if want_order < 0:
+            return super()._enqueue(job, want_order, p_max, p_max_ub, timings, t0)
+        mode = _lib.IBATCH_SELECT if job.forced is not None else (_lib.IBATCH_RANK if want_order else _lib.IBATCH_SCORES)
+        member, n = self._member(job, edit=True), len(self.models)
+        EL = _lib.LpRoundEnsembleLayout()
+        _lib.check(_lib.lib().gcnn_lp_round_ensemble_layout_for(C.byref(member), mode, n, C.byref(EL)), "gcnn_lp_round_ensemble_layout_for")
+        if EL.in_bytes != job.L.in_bytes:         # the plain round's upload, which `_pack` has already written
+            raise _lib.GcnnError("gcnn_lp_round_ensemble_layout_for: the upload is not the plain round's")
+        self._buffers(EL)
+        params = (C.c_void_p * n)(*(m._flat.data_ptr() for m in self.models))
+        self._enqueue_wait("gcnn_lp_round_ensemble", (C.byref(member), mode, n), (C.c_void_p(self.pin_tab.data_ptr()), float(p_max), float(p_max_ub)),
+                           timings, t0, params=params, upload_bytes=int(EL.in_bytes))
+        self._ens = EL
+        self.calls += 1
+
+    def _results(self, dims, out_off, want_order, select, out=None):
+        """(mean, order, n_kept, cut_index, members [M, K]) of a round in the session's download."""
+        n, EL = dims["n_cuts"], self._ens
+        at, stride = int(EL.member_off), int(EL.member_stride)
+        members = np.stack([self.out_np[at + m * stride:at + m * stride + 4 * n].view(np.float32).copy() for m in range(len(self.models))])
+        return super()._results(dims, out_off, want_order, select, out) + (members,)
+
+    def score(self, rnd, rank=False, timings=None, append=None, remove=None):
+        """`ModelSet.score_lp_ensemble` for the assembled snapshot: a `ScoreArray` of the mean in STATE order with `.cut_index`,
+        `.members` and, with `rank`, `.rankings` (on the host up to `HOST_RANK_MAX` cuts, on the device up to 4,096, on the host
+        beyond).  `append`, `remove`: as in `LPSession.score`."""
+        n = int(np.asarray(rnd.cut_lhs).shape[0])
+        on_device = self.model._rank_on_device(rank, n) and n <= 4096
+        dims, out_off, _ = self._run(rnd, int(on_device), timings, append=append, remove=remove)
+        scores, order, _, cut_index, members = self._results(dims, out_off, on_device, False)
+        scores.cut_index, scores.members = cut_index, members
+        if rank:
+            scores.rankings = order if on_device else stable_ranking(scores)
+        return scores
+
+    def select_cuts(self, rnd, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None, append=None, remove=None):
+        """`ModelSet.select_cuts_lp_ensemble` for the assembled snapshot: a `SelectResult` over the mean with `.cut_index` and
+        `.members`.  More than 4,096 cuts raise `GcnnError` before anything is enqueued, and the session stays usable.
+        `append`, `remove`: as in `LPSession.select_cuts`."""
+        ops.check_thresholds(p_max, p_max_ub)
+        self.model._check_select_size("LPEnsembleSession.select_cuts", "round", int(np.asarray(rnd.cut_lhs).shape[0]))
+        packed = normalize_forced(forced, self.n_cols)
+        dims, out_off, _ = self._run(rnd, 1, timings, packed, p_max, p_max_ub, append=append, remove=remove)
+        scores, order, n_kept, cut_index, members = self._results(dims, out_off, True, True)
+        result = SelectResult(order, n_kept, n_selected(n_kept, max_selected), scores, cut_index)
+        result.members = members
+        return result
+
+    def close(self):
+        super().close()
+        self._ens = None
+
+
 class LPSessionGroup:
     """The rounds of several `LPSession`s in one call (gcnn_lp_rounds): what a scoring server does with the rounds of different
     solver workers that wait at the same time.  One upload of all rounds and appended blocks, every stage of the members' work as
@@ -1591,6 +1680,8 @@ class LPSessionGroup:
         raises belongs to that slot), None where the member goes to its solo call; `answer(i, job, out)`: the result read from
         the member's download block; `solo(i)`: the session's own call."""
         n = len(sessions)
+        if any(isinstance(s, LPEnsembleSession) for s in sessions):       # (its M forward passes would fill the grouped call alone)
+            raise ValueError("LPSessionGroup: an ensemble session's rounds take its own call; grouping them is not supported")
         if len({id(s) for s in sessions}) != n:
             raise ValueError("LPSessionGroup: a session may appear once per call")
         for s in sessions:

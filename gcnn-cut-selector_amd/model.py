@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _EnsembleSession, _InferenceSession, _LPBatchSession, _LPEnsembleSession, _LPModelsSession, _LPSession,
+from .infer import (BAD_INDEX, LPEnsembleSession, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _EnsembleSession, _InferenceSession, _LPBatchSession, _LPEnsembleSession, _LPModelsSession, _LPSession,
                     _ModelsSession,
                     _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
@@ -777,7 +777,8 @@ class ModelSet:
     states alone.  `score_lps` and `select_cuts_lp_many` are the same for raw `LPSnapshot`s (gcnn_lp_models: the states are built
     on the device in front of the same work), with the bits of `GCNN.score_lps` / `select_cuts_lp_many`.  `score_ensemble`,
     `select_cuts_ensemble` and their LP forms let up to 8 of the models score ONE state and rank or select by the mean of their
-    scores, in one call (gcnn_infer_ensemble / gcnn_lp_ensemble).  All models live on one device."""
+    scores, in one call (gcnn_infer_ensemble / gcnn_lp_ensemble); `open_lp_ensemble` keeps an LP resident for such an ensemble
+    (gcnn_lp_round_ensemble).  All models live on one device."""
     MAX_MODELS = _ModelsSession.MAX_MODELS
 
     def __init__(self, models):
@@ -910,6 +911,8 @@ class ModelSet:
         keys, sessions = list(keys), list(sessions)
         if len(keys) != len(sessions):
             raise ValueError(f"keys: one model key per session expected, got {len(keys)} for {len(sessions)} sessions")
+        if any(isinstance(s, LPEnsembleSession) for s in sessions):
+            raise ValueError("an ensemble session's rounds take its own call; grouping them is not supported")
         for k, s in zip(keys, sessions):
             if k not in self.models:
                 raise KeyError(f"no model {k!r}")
@@ -960,6 +963,16 @@ class ModelSet:
             if k not in self.models:
                 raise ValueError(f"no model {k!r}")
         return [self.models[k] for k in keys]
+
+    def open_lp_ensemble(self, keys, rows, *, deep=True):
+        """`GCNN.open_lp` for an ensemble: keep `rows` (`lpstate.LPRows`) on the device across the separation rounds of one node
+        and let the models `keys` (1..8, each once, in this order) score every round together.  Returns an `LPEnsembleSession`
+        (infer.py): `score` and `select_cuts` give what `score_lp_ensemble` / `select_cuts_lp_ensemble` give for `keys` on
+        `lpstate.assemble(rows, round)`, bit for bit, from the plain session's upload of the round (gcnn_lp_round_ensemble);
+        rows are appended and removed as in an `LPSession`.  ValueError before any device work for zero or more than 8 keys, a
+        duplicate or unknown key and models on different devices.  The session takes its device from the first model and
+        reads each model's current parameters every round."""
+        return LPEnsembleSession(self._ensemble_models(keys), rows, deep)
 
     @staticmethod
     def _ensemble_general(models, state, packed, p_max, p_max_ub, n_cuts):

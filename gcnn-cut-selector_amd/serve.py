@@ -587,14 +587,19 @@ class ScoringServer:
     their LP forms; the members' own scores stay on the server).  A name must not be a model key; its 1..8 keys must be loaded
     models, each named once, all on one device.  Every ensemble request is answered with its own call, never grouped with other
     requests; `stats["ensemble_calls"]` counts them.  Every other kind under an ensemble's name gets the error reply of an unknown
-    model."""
+    model -- unless the server was made with `ensemble_sessions=True`: then a client opened with an ensemble's name can keep an LP
+    resident as under a model key (kinds 7-9, the same wire bytes).  The open gives `ModelSet.open_lp_ensemble` and counts against
+    `max_sessions`; each of the session's rounds is answered by its own call (gcnn_lp_round_ensemble), never through the session
+    group, in the wave order of the other sessions' rounds, with the mean as the scores; `stats["ensemble_calls"]` and
+    `stats["session_rounds"]` count them.  The hybrid and the collector's kinds stay refused."""
     SESSIONS_PER_CALL = 8
 
     def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True, max_sessions=64,
-                 session_group=None, ensembles=None):
+                 session_group=None, ensembles=None, ensemble_sessions=False):
         self.models = dict(models)
         self.address = address
         self.ensembles = self._checked_ensembles(ensembles, model_set)
+        self.ensemble_sessions = bool(ensemble_sessions)
         # a ModelSet needs all models on one device: models spread over several devices are served per model, as before
         one_device = len({str(getattr(m, "device", None)) for m in self.models.values()}) <= 1
         self.cross_model = bool(cross_model) and (model_set is not None or one_device)
@@ -605,6 +610,7 @@ class ScoringServer:
                           ensemble_calls=0)
         self.max_sessions = int(max_sessions)
         self._sessions = {}            # id -> (the connection that owns it, the LPSession)
+        self._ensemble_sids = set()    # the ids among them whose session an ensemble scores (`ensemble_sessions`)
         self._next_session = 1
         self._session_group = session_group
         self._listen = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
@@ -729,6 +735,7 @@ class ScoringServer:
 
     def _close_session(self, sid):
         _, sess = self._sessions.pop(sid)
+        self._ensemble_sids.discard(sid)
         self.stats["sessions_open"] = len(self._sessions)
         sess.close()
 
@@ -768,7 +775,8 @@ class ScoringServer:
             try:
                 req = decode_request(message)
                 if req["model_key"] in self.ensembles:
-                    if req["kind"] not in _ENSEMBLE_KINDS:       # sessions, hybrid and collector rounds know no ensemble
+                    # hybrid and collector rounds know no ensemble; sessions only where the server was made with `ensemble_sessions`
+                    if req["kind"] not in _ENSEMBLE_KINDS and not (self.ensemble_sessions and req["kind"] in _SESSION_KINDS):
                         raise KeyError(f"no model {req['model_key']!r}")
                 elif _KINDS[req["kind"]]["model"] and req["model_key"] not in self.models:
                     raise KeyError(f"no model {req['model_key']!r}")
@@ -812,9 +820,15 @@ class ScoringServer:
                     if req["kind"] == KIND_LP_OPEN:
                         if len(self._sessions) >= self.max_sessions:
                             raise RuntimeError(f"the server holds {len(self._sessions)} LP sessions already (max_sessions)")
-                        sess = self.models[req["model_key"]].open_lp(req["rows"], deep=req["deep"])
+                        keys = self.ensembles.get(req["model_key"])
+                        if keys is None:
+                            sess = self.models[req["model_key"]].open_lp(req["rows"], deep=req["deep"])
+                        else:
+                            sess = self._set().open_lp_ensemble(keys, req["rows"], deep=req["deep"])
                         sid, self._next_session = self._next_session, self._next_session + 1
                         self._sessions[sid] = (conn, sess)
+                        if keys is not None:
+                            self._ensemble_sids.add(sid)
                         self.stats["sessions_open"] = len(self._sessions)
                         self._reply(conn, encode_reply(n_kept=sid))
                         continue
@@ -827,6 +841,8 @@ class ScoringServer:
                     elif req["mode"] == SESSION_APPEND:
                         self._edit_alone(sess, req)
                         self._reply(conn, encode_reply())
+                    elif req["session"] in self._ensemble_sids:
+                        self._ensemble_round(conn, req, sess)
                     else:
                         gkey = (req["mode"],) + ((req["p_max"], req["p_max_ub"]) if req["mode"] == SESSION_SELECT else ())
                         groups.setdefault(gkey, []).append((conn, req, sess))
@@ -835,6 +851,20 @@ class ScoringServer:
             for gkey, members in groups.items():
                 for lo in range(0, len(members), self.SESSIONS_PER_CALL):
                     self._serve_rounds(gkey, members[lo:lo + self.SESSIONS_PER_CALL])
+
+    def _ensemble_round(self, conn, req, sess):
+        """A round of a session that an ensemble scores, answered with the session's own call: a plain round's reply, the mean as
+        the scores."""
+        mode = req["mode"]
+        self.stats["session_rounds"] += 1
+        self.stats["ensemble_calls"] += 1
+
+        def call():
+            if mode == SESSION_SELECT:
+                return [sess.select_cuts(req["round"], req["forced"], p_max=req["p_max"], p_max_ub=req["p_max_ub"],
+                                         max_selected=req["max_selected"], append=req["block"], remove=req.get("remove"))]
+            return [sess.score(req["round"], rank=mode == SESSION_RANK, append=req["block"], remove=req.get("remove"))]
+        self._answer_group([(conn, req, sess)], call, _reply_of(mode, True))
 
     @staticmethod
     def _edit_alone(sess, req):

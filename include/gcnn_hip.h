@@ -1086,6 +1086,50 @@ int gcnn_lp_ensemble(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_force
                      const float* const* params /* host [n_models] */, void* host_in, void* host_out, void* arena, size_t arena_bytes,
                      void* host_staging, double p_max, double p_max_ub, void* stream);
 
+/* ---- a round of ONE resident LP scored by an ensemble -------------------------------------------------------------------------------
+ * gcnn_lp_round_ensemble (model_evaluator.py:82-154 for the models of model_trainer.py:38-49): what gcnn_lp_ensemble gives for the
+ * snapshot assembled from the resident rows and this round, without uploading or deriving the rows again.  Nothing in a resident LP
+ * belongs to a model.  `round` is the description of one round of one resident LP that gcnn_lp_rounds_edit takes, with its optional
+ * removal and optional append (its `params` field is not read); mode: GCNN_IBATCH_SCORES / _RANK / _SELECT, n_forced >= 0 in
+ * selection mode and -1 otherwise.  params: host array of n_models device pointers, all different.  host_staging: pinned, 16-byte
+ * aligned, table_bytes bytes.
+ * Enqueued, in this order: ONE upload of host_in (in_bytes) -- byte for byte the solo call's of this round and these edits
+ * (gcnn_lp_round_layout_for / gcnn_lp_append_layout_for / gcnn_lp_remove_layout_for: the list | the block | the round | the forced
+ * rows), so it does not depend on n_models; the edits' launches; the round's two state launches, ONCE; the launch tables of the
+ * group (the second host->device copy) and the n_models forward passes as one group, one launch per distinct kernel and stage --
+ * every member reads the same feature arrays, the resident constraint graph and the round's cut graph, and has its own parameters,
+ * forward workspace and score row; the mean (gcnn_ensemble_mean's definition); the solo round's ranking or selection over the mean;
+ * ONE download of out_bytes.  No kernel is this call's own.
+ * host_out: the solo call's download block with the mean where the scores were -- round.out_off[0] mean [K], [1] order, [3] n_kept,
+ * [4] the four LP flags, [5] cut_index, the edits' flag words at append_flags_off / flags_off as in the solo layouts -- then at
+ * member_off + m * member_stride member[m] [K]: the bits gcnn_lp_round gives for model m.  Everything the call leaves resident has
+ * the bits the solo call of the same round and edits leaves.  A state without constraint rows or columns runs the members' solo
+ * launches inside the call; a round without cuts scores nothing and only refreshes the resident columns.
+ * The arena: the solo call's arena (solo_arena_bytes; the round's part at round_off, round.dev_off relative to it) | at out_base the
+ * download block and the members' rows | the forward workspaces at ws_off[m] | the launch tables at table_off.
+ * Returned before anything is enqueued: GCNN_E_BADARG for n_models outside 1..GCNN_GROUP_MAX, a null or repeated entry of params, a
+ * missing or misaligned host_staging, an unknown mode, n_forced < 0 in selection mode or >= 0 otherwise, a short or misaligned
+ * arena, and everything the solo call of the round refuses; GCNN_E_WORKSPACE for a short table; GCNN_E_UNSUPPORTED for the solo
+ * limits (2^24 rows per table, more than 4,096 cuts in RANK / SELECT) and a forward pass the group recorder cannot take.  There is
+ * no variable limit. */
+typedef struct gcnn_lp_round_ensemble_layout {
+    gcnn_lp_round_layout round;            /* the solo round's: upload offsets relative to its place in the upload, download offsets
+                                              relative to the download block, dev_off relative to round_off */
+    int32_t n_models, reserved;
+    size_t in_bytes;                       /* the solo call's upload */
+    size_t out_bytes, solo_out_bytes;      /* host_out: the download, which reaches over the members' rows; the solo block in front */
+    size_t flags_off, append_flags_off;    /* the edits' flag words in the download, as in the solo layouts (0: no such edit) */
+    size_t member_off, member_stride;      /* host_out: member m's scores at member_off + m * member_stride */
+    size_t arena_bytes, solo_arena_bytes, round_off, out_base;
+    size_t ws_off[GCNN_GROUP_MAX], table_off;      /* internal: the members' forward workspaces and the launch tables in the arena */
+    size_t table_bytes;                    /* host_staging holds this much */
+} gcnn_lp_round_ensemble_layout;
+int gcnn_lp_round_ensemble_layout_for(const gcnn_lp_rounds_edit_member* round /* host; only the sizes are read */, int32_t mode,
+                                      int32_t n_models, gcnn_lp_round_ensemble_layout* layout /* host */);
+int gcnn_lp_round_ensemble(const gcnn_lp_rounds_edit_member* round /* host */, int32_t mode, int32_t n_models,
+                           const float* const* params /* host [n_models] */, const void* host_in, void* host_out, void* arena,
+                           size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
