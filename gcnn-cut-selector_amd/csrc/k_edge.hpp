@@ -26,6 +26,17 @@
 #ifndef EDGE_UB
 #define EDGE_UB 2   // ... sender-ordered backward pass (two gathers per edge).  4 needs 100 VGPRs (four waves per SIMD): 23.7 vs 22.3 us per 800 k-edge pass
 #endif
+// The forms without the long-row body are compiled register-lean (LEAN, see edge_own_row): k_edge_bwd_send<1> 80 -> 64 VGPRs and
+// k_edge_fwd<2, count> 68 -> 62, eight waves per SIMD; k_edge_bwd_send<2> / <4> 76 / 74 -> 70 / 68, seven.  Measured against the
+// plain forms on setcov-500 x 32: 0.2397 -> 0.2367 ms per step with every form lean (profiles/README.md, "Edge passes at eight
+// waves per SIMD"; pinning any form to eight waves with amdgpu_waves_per_eu on top of it was level or slower and is not done).
+// EDGE_LEAN picks the forms for an A/B build: 1 / 2 / 4 k_edge_bwd_send<4 / 2 / 1>, 32 / 8 / 16 k_edge_fwd<4 / 2 / 1, count>,
+// 64 k_edge_fwd<*> without counts.
+#ifndef EDGE_LEAN
+#define EDGE_LEAN 0x7f
+#endif
+__host__ __device__ constexpr bool edge_fwd_lean(int slots, bool count) { return EDGE_LEAN & (!count ? 64 : slots == 4 ? 32 : slots == 2 ? 8 : 16); }
+__host__ __device__ constexpr bool edge_send_lean(int slots) { return EDGE_LEAN & (slots == 4 ? 1 : slots == 2 ? 2 : 4); }
 struct EdgeArgs {
     const int* seg_ptr; const int* oth; const float* coef;
     const float* p_own; const float* p_oth;       // projected table of the segment owner [n_own,64] / of the other side (gathered)
@@ -76,6 +87,14 @@ struct EdgeSum { float4 acc, cnt; };   // per lane group, after the slot reducti
 __device__ __forceinline__ float4 edge_row(const float* __restrict__ tab, unsigned byte_off) {
     return *(const float4*)((const char*)tab + byte_off);
 }
+// The owner's own rows (P_own[r] read, S / N / dP_send[r] written).  LEAN: addressed like the gathered rows, uniform base + 32-bit
+// byte offset (2^24 rows at most, as there) -- as 64-bit pointers their per-lane column part is hoisted out of the work-item loop,
+// two live registers per table: 5-8 VGPRs of a kernel.  The forms with the long-row body, the block-per-segment pass and k_infer_s2
+// keep the pointers (LEAN = false: their code and registers are what they were; not re-measured).
+template <bool LEAN, class T>
+__device__ __forceinline__ T* edge_own_row(T* tab, const int r, const int ch) {
+    return LEAN ? (T*)((char*)tab + (((unsigned)r << 8) + 4u * (unsigned)ch)) : tab + (size_t)r * EMB + ch;
+}
 template <bool COUNT, bool NEG>
 __device__ __forceinline__ void edge_fwd_term(const float c, const float4 p, const float4 w, const float4 pown, float4& acc, unsigned (&n)[4]) {
     float h0 = fmaf(c, w.x, p.x) + pown.x, h1 = fmaf(c, w.y, p.y) + pown.y;
@@ -87,12 +106,12 @@ __device__ __forceinline__ void edge_fwd_term(const float c, const float4 p, con
         n[0] += h0 != 0.f; n[1] += h1 != 0.f; n[2] += h2 != 0.f; n[3] += h3 != 0.f;
     }
 }
-template <int SLOTS, bool COUNT, bool NEG>
+template <int SLOTS, bool COUNT, bool NEG, bool LEAN = false>
 __device__ __forceinline__ EdgeSum edge_fwd_partial(const EdgeArgs& a, const EdgeLane<SLOTS>& L, const float4 w, const float esh,
                                                     const float esc, const int r, const int beg, const int end) {
     constexpr int G = 16 * SLOTS, STEP = EDGE_U * SLOTS;
     const int gl = L.gl, slot = L.slot, ch = L.ch;
-    const float4 pown = *(const float4*)(a.p_own + (size_t)r * EMB + ch);
+    const float4 pown = *(const float4*)edge_own_row<LEAN>(a.p_own, r, ch);
     const unsigned chb = 4u * ch;                       // this lane's column, in bytes
     const int src0 = (L.gbase + slot) << 2;             // ds_bpermute address of the lane holding edge `slot` of the chunk
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -143,17 +162,17 @@ __device__ __forceinline__ EdgeSum edge_fwd_partial(const EdgeArgs& a, const Edg
     out.cnt = COUNT ? slot_reduce<SLOTS>(make_float4((float)n[0], (float)n[1], (float)n[2], (float)n[3])) : make_float4(0.f, 0.f, 0.f, 0.f);
     return out;
 }
-template <int SLOTS, bool COUNT, bool NEG>
+template <int SLOTS, bool COUNT, bool NEG, bool LEAN>
 __device__ __forceinline__ void edge_fwd_segment(const EdgeArgs& a, const float s1, const EdgeLane<SLOTS>& L, const float4 w,
                                                  const float esh, const float esc, const int r, const int beg, const int end) {
-    const EdgeSum t = edge_fwd_partial<SLOTS, COUNT, NEG>(a, L, w, esh, esc, r, beg, end);
+    const EdgeSum t = edge_fwd_partial<SLOTS, COUNT, NEG, LEAN>(a, L, w, esh, esc, r, beg, end);
     if (L.slot == 0) {
-        store16<GCNN_ST_EDGE>(a.out + (size_t)r * EMB + L.ch, s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
-        if (COUNT) store16<GCNN_ST_EDGE>(a.cnt_rows + (size_t)r * EMB + L.ch, t.cnt.x, t.cnt.y, t.cnt.z, t.cnt.w);
+        store16<GCNN_ST_EDGE>(edge_own_row<LEAN>(a.out, r, L.ch), s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
+        if (COUNT) store16<GCNN_ST_EDGE>(edge_own_row<LEAN>(a.cnt_rows, r, L.ch), t.cnt.x, t.cnt.y, t.cnt.z, t.cnt.w);
     }
 }
 
-template <int SLOTS, bool COUNT, bool NEG>
+template <int SLOTS, bool COUNT, bool NEG, bool LEAN = false>
 __device__ __forceinline__ void edge_fwd_impl(const EdgeArgs& a, const float s1, const int bid, const int nblk) {
     constexpr int G = 16 * SLOTS, RPW = 64 / G;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -165,7 +184,7 @@ __device__ __forceinline__ void edge_fwd_impl(const EdgeArgs& a, const float s1,
         const int r = item * RPW + lane / G;
         if (r < a.n_own) {
             const int beg = a.seg_ptr[r], end = a.seg_ptr[r + 1];
-            if (end - beg <= edge_long_threshold(SLOTS)) edge_fwd_segment<SLOTS, COUNT, NEG>(a, s1, L, w, esh, esc, r, beg, end);
+            if (end - beg <= edge_long_threshold(SLOTS)) edge_fwd_segment<SLOTS, COUNT, NEG, LEAN>(a, s1, L, w, esh, esc, r, beg, end);
         }
     }
 }
@@ -181,8 +200,9 @@ __device__ __forceinline__ void edge_fwd_body(const EdgeArgs& a, const int long_
     if (LONG && bx < long_blocks) { edge_fwd_long_body<SLOTS, COUNT>(a, long_blocks, bx, edge_long_threshold(SLOTS)); return; }
     const float s1 = *a.s1;
     const int bid = bx - (LONG ? long_blocks : 0), nblk = gx - (LONG ? long_blocks : 0);
-    if (s1 < 0.f) edge_fwd_impl<SLOTS, COUNT, true>(a, s1, bid, nblk);
-    else edge_fwd_impl<SLOTS, COUNT, false>(a, s1, bid, nblk);
+    constexpr bool LEAN = !LONG && edge_fwd_lean(SLOTS, COUNT);
+    if (s1 < 0.f) edge_fwd_impl<SLOTS, COUNT, true, LEAN>(a, s1, bid, nblk);
+    else edge_fwd_impl<SLOTS, COUNT, false, LEAN>(a, s1, bid, nblk);
 }
 template <int SLOTS, bool COUNT, bool LONG = false>
 __global__ __launch_bounds__(256) void k_edge_fwd(EdgeArgs a, int long_blocks) { edge_fwd_body<SLOTS, COUNT, LONG>(a, long_blocks, blockIdx.x, gridDim.x); }
@@ -305,12 +325,12 @@ __device__ __forceinline__ void edge_bwd_term(const float c, const float4 d, con
     dw.x = fmaf(c, t0, dw.x); dw.y = fmaf(c, t1, dw.y); dw.z = fmaf(c, t2, dw.z); dw.w = fmaf(c, t3, dw.w);
 }
 struct BwdSum { float4 acc, dw; };   // per lane group, after the slot reduction: sum_e t_e and sum_e c_e*t_e (both before the s1 factor)
-template <int SLOTS, bool NEG>
+template <int SLOTS, bool NEG, bool LEAN = false>
 __device__ __forceinline__ BwdSum edge_bwd_send_partial(const EdgeArgs& a, const EdgeLane<SLOTS>& L, const float4 w,
                                                         const float esh, const float esc, const int u, const int beg, const int end) {
     constexpr int G = 16 * SLOTS, STEP = EDGE_UB * SLOTS;
     const int gl = L.gl, slot = L.slot, ch = L.ch;
-    const float4 psend = *(const float4*)(a.p_own + (size_t)u * EMB + ch);
+    const float4 psend = *(const float4*)edge_own_row<LEAN>(a.p_own, u, ch);
     const unsigned chb = 4u * ch;
     const int src0 = (L.gbase + slot) << 2;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), dw = acc;
@@ -333,7 +353,16 @@ __device__ __forceinline__ BwdSum edge_bwd_send_partial(const EdgeArgs& a, const
 #pragma unroll
             for (int v = 0; v < EDGE_UB; ++v) edge_bwd_term<NEG>(ci[v], d[v], q[v], w, psend, acc, dw);
         }
-        if (i0 < cnt) {
+        if (LEAN && SLOTS == 1) {   // the 1 .. EDGE_UB-1 edges left are the same for every lane of the group: a gather pair and a term each, no masks or rows kept across them (-8 VGPRs)
+#pragma unroll
+            for (int v = 0; v < EDGE_UB - 1; ++v) {
+                const bool ok = i0 + v < cnt;
+                const int src = ok ? src0 + ((i0 + v) << 2) : (L.gbase << 2);   // by every lane, as below
+                const unsigned o = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)ob) + chb;
+                const float cv = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, c)));
+                if (ok) edge_bwd_term<NEG>(cv, edge_row(a.d_s, o), edge_row(a.p_oth, o), w, psend, acc, dw);
+            }
+        } else if (i0 < cnt) {
             unsigned oi[EDGE_UB]; float ci[EDGE_UB]; bool ok[EDGE_UB]; float4 d[EDGE_UB], q[EDGE_UB];
 #pragma unroll
             for (int v = 0; v < EDGE_UB; ++v) {
@@ -356,11 +385,11 @@ __device__ __forceinline__ BwdSum edge_bwd_send_partial(const EdgeArgs& a, const
     return out;
 }
 // ... of a whole segment by one lane group: stores dP_send[u], returns the segment's share of d w_edge
-template <int SLOTS, bool NEG>
+template <int SLOTS, bool NEG, bool LEAN>
 __device__ __forceinline__ float4 edge_bwd_send_segment(const EdgeArgs& a, const float s1, const EdgeLane<SLOTS>& L, const float4 w,
                                                         const float esh, const float esc, const int u, const int beg, const int end) {
-    const BwdSum t = edge_bwd_send_partial<SLOTS, NEG>(a, L, w, esh, esc, u, beg, end);
-    if (L.slot == 0) store16<GCNN_ST_EDGE>(a.out + (size_t)u * EMB + L.ch, s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
+    const BwdSum t = edge_bwd_send_partial<SLOTS, NEG, LEAN>(a, L, w, esh, esc, u, beg, end);
+    if (L.slot == 0) store16<GCNN_ST_EDGE>(edge_own_row<LEAN>(a.out, u, L.ch), s1 * t.acc.x, s1 * t.acc.y, s1 * t.acc.z, s1 * t.acc.w);
     return t.dw;
 }
 // d w_edge = s1 * sum over ALL edges of c_e * t_e.  Every lane group adds up the shares of the segments it serves (a fixed
@@ -382,7 +411,7 @@ __device__ __forceinline__ void edge_dw_block_store(float4 dw, const float s1, f
         *(float4*)(dst + ch) = make_float4(s1 * p.x, s1 * p.y, s1 * p.z, s1 * p.w);
     }
 }
-template <int SLOTS, bool NEG>
+template <int SLOTS, bool NEG, bool LEAN>
 __device__ __forceinline__ void edge_bwd_send_impl(const EdgeArgs& a, const float s1, const int bid, const int nblk) {
     constexpr int G = 16 * SLOTS, RPW = 64 / G;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -396,7 +425,7 @@ __device__ __forceinline__ void edge_bwd_send_impl(const EdgeArgs& a, const floa
         if (u < a.n_own) {
             const int beg = a.seg_ptr[u], end = a.seg_ptr[u + 1];
             if (end - beg <= edge_long_threshold(SLOTS)) {
-                const float4 dw = edge_bwd_send_segment<SLOTS, NEG>(a, s1, L, w, esh, esc, u, beg, end);
+                const float4 dw = edge_bwd_send_segment<SLOTS, NEG, LEAN>(a, s1, L, w, esh, esc, u, beg, end);
                 dwsum.x += dw.x; dwsum.y += dw.y; dwsum.z += dw.z; dwsum.w += dw.w;
             }
         }
@@ -443,7 +472,8 @@ __device__ __forceinline__ void edge_bwd_send_body(const EdgeArgs& a, const int 
     }
     const float s1 = *a.s1;
     const int bid = bx - (LONG ? long_blocks : 0);
-    if (s1 < 0.f) edge_bwd_send_impl<SLOTS, true>(a, s1, bid, nblk); else edge_bwd_send_impl<SLOTS, false>(a, s1, bid, nblk);
+    constexpr bool LEAN = !LONG && edge_send_lean(SLOTS);
+    if (s1 < 0.f) edge_bwd_send_impl<SLOTS, true, LEAN>(a, s1, bid, nblk); else edge_bwd_send_impl<SLOTS, false, LEAN>(a, s1, bid, nblk);
 }
 template <int SLOTS, bool LONG = false>
 __global__ __launch_bounds__(256) void k_edge_bwd_send(EdgeArgs a, int long_blocks) { edge_bwd_send_body<SLOTS, LONG>(a, long_blocks, blockIdx.x, gridDim.x); }
