@@ -337,6 +337,10 @@ SIGNATURES = {
     "gcnn_infer_ensemble": (C.c_int, [_DP, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
     "gcnn_lp_ensemble_layout_for": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, _I, C.POINTER(LpEnsembleLayout)]),
     "gcnn_lp_ensemble": (C.c_int, [C.POINTER(LpDims), _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_infer_ensemble_batch_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, C.POINTER(EnsembleLayout)]),
+    "gcnn_infer_ensemble_batch": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
+    "gcnn_lp_ensemble_batch_layout_for": (C.c_int, [_I, _P, _P, _P, _I, _I, C.POINTER(LpEnsembleLayout)]),
+    "gcnn_lp_ensemble_batch": (C.c_int, [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
     "gcnn_lp_round_ensemble_layout_for": (C.c_int, [C.POINTER(LpRoundsEditMember), _I, _I, C.POINTER(LpRoundEnsembleLayout)]),
     "gcnn_lp_round_ensemble": (C.c_int, [C.POINTER(LpRoundsEditMember), _I, _I, _P, _P, _P, _P, _Z, _P, _D, _D, _P]),
 }

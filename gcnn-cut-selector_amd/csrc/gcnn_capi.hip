@@ -1399,5 +1399,8 @@ extern "C" int gcnn_ranking_metric(const float* pred, const float* truth, const 
 // one state scored by an ensemble of models, their mean ranked or selected (include/gcnn_hip.h: gcnn_ensemble_mean,
 // gcnn_infer_ensemble, gcnn_lp_ensemble): launch names k_ens_*
 #include "gcnn_ensemble.hpp"
+// many states, or LP snapshots, scored by one ensemble in one call (include/gcnn_hip.h: gcnn_infer_ensemble_batch,
+// gcnn_lp_ensemble_batch): gcnn_ensemble.hpp's call over a union of 1..64 states; its own launch name k_eb_mean_rank
+#include "gcnn_ensbatch.hpp"
 // a round of one resident LP scored by an ensemble (include/gcnn_hip.h: gcnn_lp_round_ensemble): composition, no launch name of its own
 #include "gcnn_lpens.hpp"

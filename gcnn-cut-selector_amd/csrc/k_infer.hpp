@@ -156,15 +156,11 @@ __global__ __launch_bounds__(256) void k_iplan_order(IplanArgs a) { iplan_order_
 // n <= RK_MAX; leaves the sorted keys (NaN as -inf) in v and the cut indices in ix, ix[0] = the best cut.  Shared by
 // k_rank_scores, the cut selection's filter (k_select.hpp) and the test-set ranking (k_rank.hpp, which also sorts fp64 keys: T is
 // the key type, compared as it is -- an fp64 key is never narrowed).
+// rank_desc_network is the network alone, on m = 2^j >= n keys that already lie in v (NaN as -inf, -inf from n on) with their indices
+// in ix (0x7fffffff from n on), behind a barrier: a kernel that has just computed its keys sorts them without reading them back
+// (k_ensbatch.hpp).
 template <int NT, typename T>
-__device__ __forceinline__ void rank_desc_lds(const T* __restrict__ scores, int n, T* v, int* ix) {
-    int m = 1;
-    while (m < n) m <<= 1;
-    for (int i = threadIdx.x; i < m; i += NT) {
-        const T x = i < n ? scores[i] : (T)-INFINITY;
-        v[i] = x != x ? (T)-INFINITY : x; ix[i] = i < n ? i : 0x7fffffff;
-    }
-    __syncthreads();
+__device__ __forceinline__ void rank_desc_network(int m, T* v, int* ix) {
     for (int k = 2; k <= m; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = threadIdx.x; i < m; i += NT) {
@@ -180,6 +176,17 @@ __device__ __forceinline__ void rank_desc_lds(const T* __restrict__ scores, int 
             }
             __syncthreads();
         }
+}
+template <int NT, typename T>
+__device__ __forceinline__ void rank_desc_lds(const T* __restrict__ scores, int n, T* v, int* ix) {
+    int m = 1;
+    while (m < n) m <<= 1;
+    for (int i = threadIdx.x; i < m; i += NT) {
+        const T x = i < n ? scores[i] : (T)-INFINITY;
+        v[i] = x != x ? (T)-INFINITY : x; ix[i] = i < n ? i : 0x7fffffff;
+    }
+    __syncthreads();
+    rank_desc_network<NT>(m, v, ix);
 }
 // One block, n <= RK_MAX.
 __global__ __launch_bounds__(256) void k_rank_scores(const float* __restrict__ scores, int n, int* __restrict__ order) {

@@ -4,7 +4,9 @@ of a host state, the one packer of the upload, the forced rows, and the two sess
 (`GCNN.open_lp`) is the host side of gcnn_lp_rows_build and gcnn_lp_round: an LP that stays on the device across separation rounds;
 `LPSessionGroup` is the host side of gcnn_lp_rounds: the rounds of several such sessions in one call.  `_EnsembleSession` and
 `_LPEnsembleSession` are the host side of gcnn_infer_ensemble and gcnn_lp_ensemble: ONE state scored by several models, their mean
-ranked or selected (`ModelSet.score_ensemble` and its siblings)."""
+ranked or selected (`ModelSet.score_ensemble` and its siblings); `_EnsembleBatchSession` and `_LPEnsembleBatchSession` are the host
+side of gcnn_infer_ensemble_batch and gcnn_lp_ensemble_batch: up to 64 states scored by one ensemble in one call
+(`ModelSet.score_ensemble_many` and its siblings)."""
 
 from __future__ import annotations
 
@@ -862,6 +864,93 @@ class _LPEnsembleSession(_EnsembleSession):
         out, out_off, n = base.out_np, lay.out_off, lay.n_cuts
         lpstate.raise_for_flags(out[out_off[4]:out_off[4] + 16].view(np.int32))
         return self._answer(lay, mode, len(models)) + (out[out_off[5]:out_off[5] + 4 * n].view(np.int32).copy(),)
+
+
+class _EnsembleBatchSession(_EnsembleSession):
+    """Host side of gcnn_infer_ensemble_batch: one C call for up to 64 host states scored by ONE ensemble of up to 8 models -- the
+    states go up once as gcnn_infer_batch's union, whatever the number of models.  `_EnsembleSession` over the same `_BatchSession`
+    (`base`: its packer, pinned buffers and arena).  `run` answers per state as `_BatchSession.run` does, an "ok" answer carrying the
+    mean as its scores and the members' rows [M, K_s] last.  `calls`, `upload_bytes`: as `_EnsembleSession`; `max_states_per_call`:
+    the most states one call served."""
+    MAX = _lib.IBATCH_MAX
+    ENTRY = "gcnn_infer_ensemble_batch"
+
+    def __init__(self, base):
+        super().__init__(base)
+        self.max_states_per_call = 0
+
+    def _layout(self, keys, fshapes, mode, n_models):
+        n = len(keys)
+        dims = (_lib.Dims * n)(*(_lib.Dims(*k) for k in keys))
+        nf, nfe = forced_counts(fshapes)
+        EL = _lib.EnsembleLayout()
+        if _unsupported(_lib.lib().gcnn_infer_ensemble_batch_layout_for(n, dims, nf, nfe, mode, n_models, C.byref(EL)),
+                        "gcnn_infer_ensemble_batch_layout_for"):
+            return False
+        table = np.zeros(_lib.IBATCH_TABLE_COLS * _lib.IBATCH_TABLE_STRIDE, np.int32)
+        _lib.check(_lib.lib().gcnn_infer_batch_fill_table(n, dims, nf, nfe, table.ctypes.data), "gcnn_infer_batch_fill_table")
+        cols = table.reshape(_lib.IBATCH_TABLE_COLS, _lib.IBATCH_TABLE_STRIDE)[:, :n + 1].tolist()
+        return _BatchSession._entry(dims, nf, nfe, EL.u, table, cols, EL=EL, counts=(), k_off=cols[2])
+
+    def _finish(self, got, lay, n, n_models):
+        """The call's answers with every "ok" state's member rows [M, K_s] appended, read from the same download."""
+        at, stride, out = int(lay.EL.member_off), int(lay.EL.member_stride), self.base.out_np
+        for s, r in enumerate(got):
+            if r[0] == "ok":
+                lo, hi = at + 4 * lay.k_off[s], at + 4 * lay.k_off[s + 1]
+                got[s] = r + (np.stack([out[lo + m * stride:hi + m * stride].view(np.float32) for m in range(n_models)]),)
+        self.max_states_per_call = max(self.max_states_per_call, n)
+        return got
+
+    def run(self, checked, forced, mode, models, p_max=0.0, p_max_ub=0.0):
+        """checked, forced: as `_BatchSession.run` takes them; models: the `GCNN`s in the ensemble's order.  Returns per state
+        ("ok", mean, order, n_kept, members), ("bad_index",) or ("declined",); every state ("declined",) where the library declines
+        the call as a whole; None where it declines the union's sizes (the caller splits it)."""
+        n = len(checked)
+        keys = tuple(k for _, k in checked)
+        fshapes = forced_shapes(forced) if mode == _lib.IBATCH_SELECT else ()
+        lay = self.cached((mode, keys, fshapes, len(models)), self._layout, keys, fshapes, mode, len(models))
+        if lay is False:
+            return None
+        self.base._pack(lay, checked, forced if mode == _lib.IBATCH_SELECT else None)
+        if self._call(self.ENTRY, lay, (n, lay.dims, lay.nf, lay.nfe), mode, models, p_max, p_max_ub, None, 0.0):
+            return [("declined",)] * n
+        return self._finish(self.base._collect(lay.out_off, lay.k_off, n, mode), lay, n, len(models))
+
+
+class _LPEnsembleBatchSession(_EnsembleBatchSession):
+    """Host side of gcnn_lp_ensemble_batch: `_EnsembleBatchSession` over an `_LPBatchSession` (`base`) -- one upload of the packed
+    snapshots, every state built once in the arena.  The library writes the call's tables into the pinned upload itself.  An "ok"
+    answer is ("ok", mean, order, n_kept, cut_index, members), in STATE order."""
+    ENTRY = "gcnn_lp_ensemble_batch"
+
+    def _layout(self, dims, fshapes, mode, n_models):
+        nf, nfe = forced_counts(fshapes)
+        L = _lib.LpEnsembleLayout()
+        if _unsupported(_lib.lib().gcnn_lp_ensemble_batch_layout_for(len(dims), self.base._dims_array(dims), nf, nfe, mode, n_models,
+                                                                     C.byref(L)), "gcnn_lp_ensemble_batch_layout_for"):
+            return False
+        return self.base._entry(dims, fshapes, nf, nfe, L.lp, EL=L.ens, counts=())
+
+    def run(self, checked, forced, mode, models, p_max=0.0, p_max_ub=0.0):
+        """checked: [(arrays, dims)] as `_LPBatchSession.check` returns them; otherwise as `_EnsembleBatchSession.run`, with
+        ("error", ValueError) for what the device flags in a snapshot itself."""
+        from . import lpstate
+        base, n = self.base, len(checked)
+        dims = [d for _, d in checked]
+        select = mode == _lib.IBATCH_SELECT
+        fshapes = forced_shapes(forced) if select else ()
+        lay = self.cached((mode, tuple(_int_key(d) for d in dims), fshapes, len(models)), self._layout, dims, fshapes, mode, len(models))
+        if lay is False:
+            return None
+        base._buffers(lay.L)
+        for (arrays, _), at in zip(checked, lay.snap_at):
+            lpstate.pack_snapshot(base.in_np, at, arrays)
+        base._put_forced_stacked(lay.forced_off, lay.f_off, lay.fe_off, forced if select else None)
+        if self._call(self.ENTRY, lay, (n, base._dims_array(dims), lay.nf, lay.nfe), mode, models, p_max, p_max_ub, None, 0.0):
+            return [("declined",)] * n
+        base.last = (lay.L, lay.keys)      # the arena holds this call's states, at the places `base.last_states` reads
+        return self._finish(base._answers(lay, n, mode), lay, n, len(models))
 
 
 class LPSession(_Staging):

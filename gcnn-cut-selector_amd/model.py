@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _safe_pickle, ops
 from .graph import BipartiteGraph, _ptr, _stream
-from .infer import (BAD_INDEX, LPEnsembleSession, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _EnsembleSession, _InferenceSession, _LPBatchSession, _LPEnsembleSession, _LPModelsSession, _LPSession,
+from .infer import (BAD_INDEX, LPEnsembleSession, LPSession, LPSessionGroup, ScoreArray, SelectResult, _BatchSession, _EnsembleBatchSession, _EnsembleSession, _InferenceSession, _LPBatchSession, _LPEnsembleBatchSession, _LPEnsembleSession, _LPModelsSession, _LPSession,
                     _ModelsSession,
                     _UseGeneralPath,
                     check_feature_shapes, check_state, edges_without_nodes, is_host_state, n_selected, normalize_forced, stable_ranking)
@@ -181,7 +181,10 @@ def _serve_many(n, admit, split, run, solo):
 
 
 def _state_vars(state):
-    return state.dims.n_vars if isinstance(state, Batch) else int(np.asarray(state[3]).shape[0])
+    if isinstance(state, Batch):
+        return state.dims.n_vars
+    v = state[3]                  # (a device tensor has a shape too, and NumPy cannot read it)
+    return int(v.shape[0]) if hasattr(v, "shape") else int(np.asarray(v).shape[0])
 
 
 def _snapshot_vars(snapshot):
@@ -778,7 +781,8 @@ class ModelSet:
     on the device in front of the same work), with the bits of `GCNN.score_lps` / `select_cuts_lp_many`.  `score_ensemble`,
     `select_cuts_ensemble` and their LP forms let up to 8 of the models score ONE state and rank or select by the mean of their
     scores, in one call (gcnn_infer_ensemble / gcnn_lp_ensemble); `open_lp_ensemble` keeps an LP resident for such an ensemble
-    (gcnn_lp_round_ensemble).  All models live on one device."""
+    (gcnn_lp_round_ensemble); `score_ensemble_many`, `select_cuts_ensemble_many` and their LP forms answer up to 64 states per call
+    with one such ensemble (gcnn_infer_ensemble_batch / gcnn_lp_ensemble_batch).  All models live on one device."""
     MAX_MODELS = _ModelsSession.MAX_MODELS
 
     def __init__(self, models):
@@ -793,6 +797,8 @@ class ModelSet:
         self._lp_session = None
         self._ensemble = None             # the sessions of the `*_ensemble` methods, built on first use
         self._lp_ensemble = None
+        self._ensemble_batch = None       # the sessions of the `*_ensemble_many` methods, built on first use
+        self._lp_ensemble_batch = None
         self._lp_rounds = None            # the LPSessionGroup of `score_rounds` / `select_cuts_rounds`, built on first use
         self.calls = 0                    # gcnn_infer_models and gcnn_lp_models calls made
         self.max_models_per_call = 0      # the most models one of them served
@@ -1098,3 +1104,100 @@ class ModelSet:
     def select_cuts_lp_ensemble(self, keys, snapshot, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, timings=None):
         """`select_cuts_ensemble` from an `LPSnapshot`; `order` is in STATE order and the result carries `.cut_index`."""
         return self._select_ensemble(self._ensemble_models(keys), snapshot, forced, p_max, p_max_ub, max_selected, True, timings)
+
+    # ---- ensembles over many states: what waits at a farm's scoring server, scored by ONE ensemble in one call --------------------
+    def ensemble_batch_session(self, lp=False):
+        """The session behind the `*_ensemble_many` methods (`_EnsembleBatchSession`; with `lp`, `_LPEnsembleBatchSession`): its
+        `calls`, `upload_bytes` and `max_states_per_call` count the one-call path's C calls, state uploads and widest call."""
+        first = next(iter(self.models.values()))
+        if lp:
+            if self._lp_ensemble_batch is None:
+                self._lp_ensemble_batch = _LPEnsembleBatchSession(first._sess("_lp_batch_session", _LPBatchSession))
+            return self._lp_ensemble_batch
+        if self._ensemble_batch is None:
+            self._ensemble_batch = _EnsembleBatchSession(first._sess("_batch_session", _BatchSession))
+        return self._ensemble_batch
+
+    def _ensemble_many(self, models, states, mode, solo, forced=None, p_max=0.0, p_max_ub=0.0, lp=False):
+        """`GCNN._many` for one ensemble: results per state -- ("ok", mean, order, n_kept[, cut_index], members), whatever `solo(i)`
+        returned for a state the batched call declines, or an exception."""
+        session = self.ensemble_batch_session(lp)
+
+        def admit(i):
+            if forced is not None and isinstance(forced[i], Exception):
+                raise forced[i]
+            if not lp:
+                return GCNN._admit_state(states[i], mode)
+            entry = session.base.check(states[i])
+            n_cuts = entry[1]["n_cuts"]
+            return None if n_cuts == 0 or (mode != _lib.IBATCH_SCORES and n_cuts > 4096) else entry
+
+        def run(ids, checked):
+            return session.run([checked[i] for i in ids], None if forced is None else [forced[i] for i in ids], mode, models, p_max,
+                               p_max_ub)
+
+        return _serve_many(len(states), admit, lambda ids: [ids[j:j + session.MAX] for j in range(0, len(ids), session.MAX)], run, solo)
+
+    def _score_ensemble_many(self, keys, states, rank, return_exceptions, lp):
+        keys = list(keys)
+        models, states = self._ensemble_models(keys), list(states)
+        mode = _lib.IBATCH_RANK if rank else _lib.IBATCH_SCORES
+        one = self.score_lp_ensemble if lp else self.score_ensemble
+        results = self._ensemble_many(models, states, mode, lambda i: one(keys, states[i], rank), lp=lp)
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                scores = r[1]
+                scores.members = r[-1]
+                if lp:
+                    scores.cut_index = r[4]
+                if rank:
+                    scores.rankings = r[2]
+                results[i] = scores
+        return GCNN._finish_many(results, return_exceptions)
+
+    def _select_ensemble_many(self, keys, states, forced, p_max, p_max_ub, max_selected, return_exceptions, lp):
+        keys = list(keys)
+        models, states = self._ensemble_models(keys), list(states)
+        ops.check_thresholds(p_max, p_max_ub)
+        forced, packed = _packed_forced(states, forced, _snapshot_vars if lp else _state_vars, "snapshot" if lp else "state")
+        one = self.select_cuts_lp_ensemble if lp else self.select_cuts_ensemble
+
+        def solo(i):
+            return one(keys, states[i], forced[i], p_max=p_max, p_max_ub=p_max_ub, max_selected=max_selected)
+
+        results = self._ensemble_many(models, states, _lib.IBATCH_SELECT, solo, packed, p_max, p_max_ub, lp=lp)
+        for i, r in enumerate(results):
+            if isinstance(r, tuple):
+                results[i] = SelectResult(r[2], r[3], n_selected(r[3], max_selected), r[1], r[4] if lp else None)
+                results[i].members = r[-1]
+        return GCNN._finish_many(results, return_exceptions)
+
+    def score_ensemble_many(self, keys, states, rank=False, return_exceptions=False):
+        """`score_ensemble` for many host states at once -- what waits at the scoring server of an evaluator farm
+        (model_evaluator.py:157-241) that deploys the five seeds of a problem (model_trainer.py:38-49) as one ensemble.  `keys`: as
+        `score_ensemble` takes them (1..8, each once, order kept; ValueError before any device work otherwise).  Up to 64 states
+        per gcnn_infer_ensemble_batch call, more in several: one upload of the states as gcnn_infer_batch's union, one graph plan,
+        the M forward passes over the union as one group, the mean, one download.  Returns a list of `ScoreArray` in the caller's
+        order, each the mean over its state's cuts with `.members` (float32 [M, K_i]) and, with `rank`, `.rankings`.  For the
+        states s_0..s_{S-1} one call admits, `.members[m]` of state i has the bits of `models[keys[m]].score_states([s_0..])[i]`;
+        the mean and the ranking are `score_ensemble`'s definitions on them, so one state alone gives `score_ensemble`'s bits.
+        Errors are per state as in `GCNN.score_states`.  States the call declines (no cuts, more than 4,096 cuts when ranking,
+        device tensors, prepared `Batch`es) go through `score_ensemble` and come back in place."""
+        return self._score_ensemble_many(keys, states, rank, return_exceptions, False)
+
+    def select_cuts_ensemble_many(self, keys, states, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None, return_exceptions=False):
+        """`select_cuts_ensemble` for many host states at once (gcnn_infer_ensemble_batch in selection mode).  `forced`: None, or one
+        entry per state in the forms `select_cuts` accepts.  Returns a list of `SelectResult` whose `scores` are the mean, with
+        `.members`; the selection of every state is `ops.select_cuts` over the union's mean with that state's forced rows."""
+        return self._select_ensemble_many(keys, states, forced, p_max, p_max_ub, max_selected, return_exceptions, False)
+
+    def score_lp_ensemble_many(self, keys, snapshots, rank=False, return_exceptions=False):
+        """`score_ensemble_many` from `LPSnapshot`s (gcnn_lp_ensemble_batch: one upload of the packed snapshots, every state built
+        once on the device; no variable limit).  Results are in STATE order and carry `.cut_index`; `.members[m]` has the bits of
+        `models[keys[m]].score_lps(...)` on the snapshots one call admits.  A snapshot the device flags holds its own ValueError."""
+        return self._score_ensemble_many(keys, snapshots, rank, return_exceptions, True)
+
+    def select_cuts_lp_ensemble_many(self, keys, snapshots, forced=None, *, p_max=0.1, p_max_ub=0.5, max_selected=None,
+                                     return_exceptions=False):
+        """`select_cuts_ensemble_many` from `LPSnapshot`s; every `order` is in STATE order and the results carry `.cut_index`."""
+        return self._select_ensemble_many(keys, snapshots, forced, p_max, p_max_ub, max_selected, return_exceptions, True)

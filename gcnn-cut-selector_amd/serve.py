@@ -585,8 +585,13 @@ class ScoringServer:
     `ensembles`: {name: [model keys]} -- a client opened with an ensemble's name uses the kinds 0-5 as they are and is answered with
     the MEAN of those models' scores, its ranking or the selection over it (`ModelSet.score_ensemble`, `select_cuts_ensemble` and
     their LP forms; the members' own scores stay on the server).  A name must not be a model key; its 1..8 keys must be loaded
-    models, each named once, all on one device.  Every ensemble request is answered with its own call, never grouped with other
-    requests; `stats["ensemble_calls"]` counts them.  Every other kind under an ensemble's name gets the error reply of an unknown
+    models, each named once, all on one device.  Every ensemble request is answered with its own call and `stats["ensemble_calls"]`
+    counts them -- unless the server was made with `ensemble_batching=True`: then the requests of the kinds 0-5 under ensemble names
+    that wait together are grouped by ensemble name, kind and, for selections, thresholds, and each group is answered with one
+    `ModelSet.*_ensemble_many` call (gcnn_infer_ensemble_batch / gcnn_lp_ensemble_batch: up to 64 states per C call); the wire
+    bytes are the same either way.  `stats["ensemble_calls"]` then counts those calls, `ensemble_batched_calls` the ones that served
+    more than one request and `max_ensemble_batch` the most requests one of them served.  Requests of different ensembles never
+    share a call.  Every other kind under an ensemble's name gets the error reply of an unknown
     model -- unless the server was made with `ensemble_sessions=True`: then a client opened with an ensemble's name can keep an LP
     resident as under a model key (kinds 7-9, the same wire bytes).  The open gives `ModelSet.open_lp_ensemble` and counts against
     `max_sessions`; each of the session's rounds is answered by its own call (gcnn_lp_round_ensemble), never through the session
@@ -595,11 +600,12 @@ class ScoringServer:
     SESSIONS_PER_CALL = 8
 
     def __init__(self, models, address, backlog=128, cross_model=True, model_set=None, cross_model_lp=True, max_sessions=64,
-                 session_group=None, ensembles=None, ensemble_sessions=False):
+                 session_group=None, ensembles=None, ensemble_sessions=False, ensemble_batching=False):
         self.models = dict(models)
         self.address = address
         self.ensembles = self._checked_ensembles(ensembles, model_set)
         self.ensemble_sessions = bool(ensemble_sessions)
+        self.ensemble_batching = bool(ensemble_batching)
         # a ModelSet needs all models on one device: models spread over several devices are served per model, as before
         one_device = len({str(getattr(m, "device", None)) for m in self.models.values()}) <= 1
         self.cross_model = bool(cross_model) and (model_set is not None or one_device)
@@ -607,7 +613,7 @@ class ScoringServer:
         self._model_set = model_set
         self.stats = dict(requests=0, calls=0, batched_calls=0, max_batch=0, errors=0, max_models_per_call=0, sessions_open=0,
                           session_rounds=0, session_calls=0, session_solo_rounds=0, max_sessions_per_call=0, collect_calls=0,
-                          ensemble_calls=0)
+                          ensemble_calls=0, ensemble_batched_calls=0, max_ensemble_batch=0)
         self.max_sessions = int(max_sessions)
         self._sessions = {}            # id -> (the connection that owns it, the LPSession)
         self._ensemble_sids = set()    # the ids among them whose session an ensemble scores (`ensemble_sessions`)
@@ -655,6 +661,37 @@ class ScoringServer:
                 return [select(keys, arg, req["forced"], p_max=req["p_max"], p_max_ub=req["p_max_ub"], max_selected=req["max_selected"])]
             return [(mset.score_lp_ensemble if lp else mset.score_ensemble)(keys, arg, rank=base == KIND_RANK)]
         self._answer_group([(conn, req)], call, _reply_of(base, lp))
+
+    def _ensemble_groups(self, pending):
+        """The requests of the kinds 0-5 under ensemble names -> {(ensemble name, kind[, p_max, p_max_ub]): [(conn, request)]}, groups
+        and members in arrival order (`ensemble_batching`)."""
+        groups = {}
+        for conn, req in pending:
+            kind = req["kind"]
+            if req["model_key"] in self.ensembles and kind in _ENSEMBLE_KINDS:
+                selects = _LP_BASE.get(kind, kind) == KIND_SELECT
+                gkey = (req["model_key"], kind) + ((req["p_max"], req["p_max_ub"]) if selects else ())
+                groups.setdefault(gkey, []).append((conn, req))
+        return groups
+
+    def _ensemble_many(self, gkey, items):
+        """A group of `_ensemble_groups`, answered with one `ModelSet.*_ensemble_many` call: every member gets the reply
+        `_ensemble_one` gives for the same result, or its own error."""
+        kind = gkey[1]
+        lp, base, keys = kind in _LP_BASE, _LP_BASE.get(kind, kind), self.ensembles[gkey[0]]
+        self.stats["calls"] += 1
+        self.stats["ensemble_calls"] += 1
+        self.stats["ensemble_batched_calls"] += len(items) > 1
+        self.stats["max_ensemble_batch"] = max(self.stats["max_ensemble_batch"], len(items))
+
+        def call():
+            mset, args = self._set(), [r["snapshot" if lp else "state"] for _, r in items]
+            if base == KIND_SELECT:
+                select = mset.select_cuts_lp_ensemble_many if lp else mset.select_cuts_ensemble_many
+                return select(keys, args, [r["forced"] for _, r in items], p_max=gkey[2], p_max_ub=gkey[3], return_exceptions=True)
+            return (mset.score_lp_ensemble_many if lp else mset.score_ensemble_many)(keys, args, rank=base == KIND_RANK,
+                                                                                     return_exceptions=True)
+        self._answer_group(items, call, _reply_of(base, lp))
 
     def _device(self):
         """The device of the first model; None (the current device) for a server that holds no model: the kinds without one."""
@@ -947,8 +984,11 @@ class ScoringServer:
         for conn, req in pending:
             if req["kind"] == KIND_COLLECT and conn in self._buffers:
                 self._collect_one(conn, req)
-            elif req["model_key"] in self.ensembles and req["kind"] in _ENSEMBLE_KINDS:
+            elif req["model_key"] in self.ensembles and req["kind"] in _ENSEMBLE_KINDS and not self.ensemble_batching:
                 self._ensemble_one(conn, req)
+        if self.ensemble_batching:
+            for gkey, items in self._ensemble_groups(pending).items():
+                self._ensemble_many(gkey, items)
         for gkey, items in self._grouped(pending).items():
             hybrid = gkey[1] == KIND_HYBRID_SELECT
             lp = gkey[1] in _LP_BASE or hybrid

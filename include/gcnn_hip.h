@@ -1086,6 +1086,51 @@ int gcnn_lp_ensemble(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_force
                      const float* const* params /* host [n_models] */, void* host_in, void* host_out, void* arena, size_t arena_bytes,
                      void* host_staging, double p_max, double p_max_ub, void* stream);
 
+/* ---- ensembles over many states: what waits at a farm's scoring server, scored by ONE ensemble in one call ----------------------------
+ * gcnn_infer_ensemble_batch (the evaluators' farm of SCIP workers, model_evaluator.py:157-241, each deploying the five seeds of
+ * model_trainer.py:38-49 as an ensemble): gcnn_infer_ensemble for 1..GCNN_IBATCH_MAX host states at once.  dims, n_forced,
+ * n_forced_entries, mode, host_in: exactly gcnn_infer_batch's (layout.u is that call's layout for these states: in_bytes, in_off and
+ * out_off are the same, byte for byte, whatever n_models is; the table is written by gcnn_infer_batch_fill_table).  params,
+ * host_staging: as gcnn_infer_ensemble takes them.  The call writes nothing into host_in.
+ * Enqueued, in this order: ONE upload of the states; the index pass; the by-variable stage of the union, ONCE; the launch tables of
+ * the group (the second host->device copy); the n_models forward passes over the union as ONE group (the members of an ensemble
+ * over a union are still the members of one group, so n_models <= GCNN_GROUP_MAX is the only bound); the mean (gcnn_ensemble_mean's
+ * definition); the per-state tail -- RANK: mean and ranking of every state's segment in one launch of its own, SELECT:
+ * gcnn_infer_batch's selection over all states, each with its own forced rows; ONE download.
+ * host_out (pinned, layout.u.out_bytes): gcnn_infer_batch's block with the mean where the scores were -- u.out_off[0] mean [K_total]
+ * (state s at k_off[s]), u.out_off[1] order [K_total] (state-local cut indices), u.out_off[2] n_kept [n_states], u.out_off[3] flags
+ * [n_states][4] -- and behind it, at member_off + m * member_stride, member[m] [K_total]: member_stride = the 16-byte multiple that
+ * holds 4 * K_total bytes.  member[m]'s bits are those of gcnn_infer_batch for model m on the same states in the same order.  A
+ * state with a flag set has no valid results and changes no other state's (gcnn_infer_batch).
+ * Returned before anything is enqueued: what gcnn_infer_batch returns for these sizes (n_states outside 1..GCNN_IBATCH_MAX, a negative
+ * size, an unknown mode, a union past 2^24 rows or 2^30 edges, edges with nothing to point at, thresholds that are not finite,
+ * missing buffers, a short or misaligned arena); GCNN_E_BADARG for n_models outside 1..GCNN_GROUP_MAX, a null params entry and a
+ * missing host_staging; GCNN_E_UNSUPPORTED for a state of more than 4,096 cuts in RANK / SELECT and for a forward pass the group
+ * recorder cannot take (the caller serves the states one by one).  There is no variable limit. */
+int gcnn_infer_ensemble_batch_layout_for(int32_t n_states, const gcnn_dims* dims /* host [n_states] */, const int32_t* n_forced,
+                                         const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
+                                         gcnn_ensemble_layout* layout /* host */);
+int gcnn_infer_ensemble_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
+                              int32_t mode, int32_t n_models, const float* const* params /* host [n_models] */, const void* host_in,
+                              void* host_out, void* arena, size_t arena_bytes, void* host_staging, double p_max, double p_max_ub,
+                              void* stream);
+/* gcnn_lp_ensemble_batch (the evaluators' farm, model_evaluator.py:157-241, with the five seeds of model_trainer.py:38-49 as one
+ * ensemble): the same from 1..GCNN_IBATCH_MAX raw LP snapshots -- gcnn_lp_batch's contract for n snapshots and n_models models.
+ * ONE upload (tables | packed snapshots | forced rows), gcnn_lp_batch's two builder launches build every state ONCE where
+ * gcnn_infer_ensemble_batch's upload would have put it, then that call's device work.  layout.ens: gcnn_infer_ensemble_batch's
+ * layout for the built states' sizes; layout.lp: as in gcnn_lp_batch_layout with lp.state == ens.u.  host_in (pinned, lp.in_bytes,
+ * WRITABLE): the call itself writes the tables into [0, lp.table_bytes), as gcnn_lp_ensemble does; the caller packs snapshot s at
+ * lp.snap_base[s] + gcnn_lp_layout.snap_off[i] and the stacked forced rows at lp.forced_off.  host_out (pinned, lp.out_bytes):
+ * gcnn_infer_ensemble_batch's block (members at ens.member_off), then lp.out_off[4] the LP flags [n][4] and lp.out_off[5] cut_index
+ * [K_total], as gcnn_lp_batch lays them out.  Everything is in STATE order.  Returned before anything is enqueued: what
+ * gcnn_infer_ensemble_batch returns for the built states' sizes and what gcnn_lp_batch returns for these snapshots. */
+int gcnn_lp_ensemble_batch_layout_for(int32_t n, const gcnn_lp_dims* dims /* host [n] */, const int32_t* n_forced,
+                                      const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
+                                      gcnn_lp_ensemble_layout* layout /* host */);
+int gcnn_lp_ensemble_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries, int32_t mode,
+                           int32_t n_models, const float* const* params /* host [n_models] */, void* host_in, void* host_out,
+                           void* arena, size_t arena_bytes, void* host_staging, double p_max, double p_max_ub, void* stream);
+
 /* ---- a round of ONE resident LP scored by an ensemble -------------------------------------------------------------------------------
  * gcnn_lp_round_ensemble (model_evaluator.py:82-154 for the models of model_trainer.py:38-49): what gcnn_lp_ensemble gives for the
  * snapshot assembled from the resident rows and this round, without uploading or deriving the rows again.  Nothing in a resident LP
