@@ -331,9 +331,17 @@ def forward_group(models, batches, out=None):
 
 def ranking_fraction(pred: np.ndarray, true: np.ndarray) -> float:
     """model_trainer.py:288-301: length of the ranking prefix on which prediction and truth agree, over #cuts.
-    Python's `sorted(..., reverse=True)` is stable, i.e. ties keep index order: a stable argsort of the negated key."""
-    pr = np.argsort(-np.asarray(pred), kind="stable")
-    tr = np.argsort(-np.asarray(true), kind="stable")
+    Python's `sorted(..., reverse=True)` is stable, i.e. ties keep index order: a stable argsort of the negated key.
+    The device metric's rule (k_ranking) holds here too, so that a sample is credited the same whichever path its batch takes:
+    NaN ranks as -inf, and a sample without cuts has fraction 0."""
+    def order(key):
+        key = np.array(key, dtype=np.float64)
+        key[np.isnan(key)] = -np.inf
+        return np.argsort(-key, kind="stable")
+
+    pr, tr = order(pred), order(true)
+    if len(pr) == 0:
+        return 0.0
     diff = pr != tr
     return (int(np.argmax(diff)) if diff.any() else len(pr)) / len(pr)
 
