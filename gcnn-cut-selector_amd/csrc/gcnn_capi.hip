@@ -295,8 +295,9 @@ static void carve(const gcnn_dims* d, float* base, Work* w) {
     }
     w->stats = (double*)take(2 * (size_t)(ST_MAX_BLOCKS * ST_MAX_UNITS + 2 * ST_MAX_UNITS));
     w->stat_ids = (int*)take((size_t)std::max(d->n_cons_edges, d->n_cut_edges));
-    w->score_nblk = cdiv(d->n_cuts, SB_ROWS);
-    w->score_partial = take((size_t)cdiv(d->n_cuts, 16) * HEAD_SLAB);   // per 64-cut block (k_score_bwd) or per tile (CF_LOSS)
+    // (in size_t: a size query reaches this with any n_cuts >= 0, and cdiv(int, int) is for launch grids, whose rows check_common bounds)
+    w->score_nblk = (int)((K + SB_ROWS - 1) / SB_ROWS);
+    w->score_partial = take((K + 15) / 16 * HEAD_SLAB);   // per 64-cut block (k_score_bwd) or per tile (CF_LOSS)
     w->total = off;
 }
 
@@ -342,7 +343,7 @@ int gcnn_param_info(int index, int* offset, int* rows, int* cols, int* trainable
 }
 
 size_t gcnn_workspace_floats(const gcnn_dims* dims) {
-    if (!dims) return 0;
+    if (!dims || dims->n_cons < 0 || dims->n_vars < 0 || dims->n_cuts < 0 || dims->n_cons_edges < 0 || dims->n_cut_edges < 0) return 0;
     Work w; carve(dims, nullptr, &w);
     return w.total;
 }
@@ -862,6 +863,16 @@ struct Carver {
     size_t off;
     size_t take(size_t bytes, size_t align) { const size_t o = off; off += (bytes + align - 1) & ~(align - 1); return o; }
 };
+// How every exported *_layout_for hands its layout out: built in a copy of the caller's struct and copied back only when the sizes
+// are accepted, so a refused query leaves the caller's struct as it was (the calls themselves build theirs in a local, directly).
+template <class L, class F> static int layout_out(L* out, F build) {
+    if (!out) return build((L*)nullptr);
+    L tmp;
+    memcpy(&tmp, out, sizeof(L));
+    const int rc = build(&tmp);
+    if (rc == 0) memcpy(out, &tmp, sizeof(L));
+    return rc;
+}
 // the forced rows as every selecting call uploads them: forced_ptr [F+1] int32 | forced_col [EF] int32 | forced_val [EF] f32
 static void forced_block(Carver& c, size_t F, size_t EF, size_t out[3]) {
     out[0] = c.take(4 * (F + 1), 16); out[1] = c.take(4 * EF, 16); out[2] = c.take(4 * EF, 16);
@@ -892,7 +903,9 @@ static int infer_layout(const gcnn_dims* d, size_t extra_in, size_t extra_out, g
     L->arena_bytes = dev.off;
     return 0;
 }
-extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) { return infer_layout(d, 0, 0, L); }
+extern "C" int gcnn_infer_layout_for(const gcnn_dims* d, gcnn_infer_layout* L) {
+    return layout_out(L, [&](gcnn_infer_layout* l) { return infer_layout(d, 0, 0, l); });
+}
 // Edges with nothing to point at: every id of such a list is out of range, and there is no row of its own to park it on -- the
 // plan's substitute id 0 would send the forward to row 0 of an empty table (k_infer.hpp).  The calls that upload a host state
 // refuse such a state before anything is enqueued (state_call, gcnn_select.hpp; ibatch_sums, gcnn_ibatch.hpp).
@@ -940,7 +953,8 @@ static int infer_rank(const gcnn_dims* d, char* A, const gcnn_infer_layout& L, h
 extern "C" int gcnn_host_sort_edges_by_row(const int32_t* rows, const int32_t* cols, const float* vals, int32_t n_edges, int32_t n_left,
                                            int32_t* out_inds, float* out_vals, int32_t* scratch) {
     if (n_edges < 0 || n_left < 0 || (n_edges > 0 && (!rows || !cols || !vals || !out_inds || !out_vals || !scratch))) return GCNN_E_BADARG;
-    for (int i = 0; i <= n_left; ++i) scratch[i] = 0;
+    if (n_edges == 0) return 0;   // nothing to place, and the pointers may be null
+    for (size_t i = 0; i <= (size_t)n_left; ++i) scratch[i] = 0;
     for (int e = 0; e < n_edges; ++e) {
         const int r = rows[e];
         if (r < 0 || r >= n_left) return GCNN_E_BADARG;
@@ -959,6 +973,7 @@ extern "C" int gcnn_host_sort_edges_by_row(const int32_t* rows, const int32_t* c
 extern "C" int gcnn_host_pack_edges(const int32_t* rows, const int32_t* cols, const float* vals, int32_t n_edges, int32_t n_left,
                                     int32_t* out_inds, float* out_vals, int32_t* scratch) {
     if (n_edges < 0 || n_left < 0 || (n_edges > 0 && (!rows || !cols || !vals || !out_inds || !out_vals || !scratch))) return GCNN_E_BADARG;
+    if (n_edges == 0) return 0;   // nothing to copy, and the pointers may be null
     int unsorted = 0;
     for (int e = 1; e < n_edges; ++e) unsorted |= rows[e] < rows[e - 1];
     if (unsorted && gcnn_host_sort_edges_by_row(rows, cols, vals, n_edges, n_left, out_inds, out_vals, scratch) == 0) return 1;

@@ -60,7 +60,7 @@ static int collect_layout(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_for
 }
 
 extern "C" int gcnn_lp_collect_layout_for(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_entries, gcnn_lp_collect_layout* L) {
-    return collect_layout(d, n_forced, n_forced_entries, L);
+    return layout_out(L, [&](gcnn_lp_collect_layout* l) { return collect_layout(d, n_forced, n_forced_entries, l); });
 }
 
 // the one-entry table of k_hyb_stats / k_hyb_emit: the snapshot's arrays where the LP upload put them, the outputs in the download block

@@ -30,7 +30,7 @@ static int eb_rank_tail(const EnsCall& c, const gcnn_ibatch_layout& L, const IbA
 extern "C" int gcnn_infer_ensemble_batch_layout_for(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
                                                     const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
                                                     gcnn_ensemble_layout* layout) {
-    return ens_layout(n_states, dims, n_forced, n_forced_entries, mode, n_models, false, layout);
+    return layout_out(layout, [&](gcnn_ensemble_layout* l) { return ens_layout(n_states, dims, n_forced, n_forced_entries, mode, n_models, false, l); });
 }
 
 extern "C" int gcnn_infer_ensemble_batch(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
@@ -43,7 +43,7 @@ extern "C" int gcnn_infer_ensemble_batch(int32_t n_states, const gcnn_dims* dims
 extern "C" int gcnn_lp_ensemble_batch_layout_for(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced,
                                                  const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
                                                  gcnn_lp_ensemble_layout* layout) {
-    return lpens_layout(n, dims, n_forced, n_forced_entries, mode, n_models, false, layout, nullptr);
+    return layout_out(layout, [&](gcnn_lp_ensemble_layout* l) { return lpens_layout(n, dims, n_forced, n_forced_entries, mode, n_models, false, l, nullptr); });
 }
 
 extern "C" int gcnn_lp_ensemble_batch(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,

@@ -72,7 +72,7 @@ static int ens_layout(int n_states, const gcnn_dims* d, const int32_t* n_forced,
 
 extern "C" int gcnn_infer_ensemble_layout_for(const gcnn_dims* dims, int32_t n_forced, int32_t n_forced_entries, int32_t mode,
                                               int32_t n_models, gcnn_ensemble_layout* layout) {
-    return ens_layout(1, dims, &n_forced, &n_forced_entries, mode, n_models, true, layout);
+    return layout_out(layout, [&](gcnn_ensemble_layout* l) { return ens_layout(1, dims, &n_forced, &n_forced_entries, mode, n_models, true, l); });
 }
 
 // What a call holds between its host half and its device half: the index pass's arguments, the members and their recorded launches.
@@ -203,7 +203,7 @@ static int lpens_layout(int n, const gcnn_lp_dims* d, const int32_t* n_forced, c
 
 extern "C" int gcnn_lp_ensemble_layout_for(const gcnn_lp_dims* dims, int32_t n_forced, int32_t n_forced_entries, int32_t mode,
                                            int32_t n_models, gcnn_lp_ensemble_layout* layout) {
-    return lpens_layout(1, dims, &n_forced, &n_forced_entries, mode, n_models, true, layout, nullptr);
+    return layout_out(layout, [&](gcnn_lp_ensemble_layout* l) { return lpens_layout(1, dims, &n_forced, &n_forced_entries, mode, n_models, true, l, nullptr); });
 }
 
 // lpens_call: the whole call on LP snapshots -- gcnn_lp_ensemble with one, gcnn_lp_ensemble_batch (gcnn_ensbatch.hpp) with 1..64.

@@ -76,7 +76,7 @@ static int hyb_layout(int n, const gcnn_hybrid_dims* dims, const int32_t* n_forc
 
 extern "C" int gcnn_hybrid_layout_for(int32_t n, const gcnn_hybrid_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
                                       int32_t mode, gcnn_hybrid_layout* L) {
-    return hyb_layout(n, dims, n_forced, n_forced_entries, mode, L);
+    return layout_out(L, [&](gcnn_hybrid_layout* l) { return hyb_layout(n, dims, n_forced, n_forced_entries, mode, l); });
 }
 
 extern "C" int gcnn_hybrid_fill_table(int32_t n, const gcnn_hybrid_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,

@@ -96,14 +96,16 @@ static int ibatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_f
 
 extern "C" int gcnn_infer_batch_layout_for(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
                                            const int32_t* n_forced_entries, int32_t mode, gcnn_ibatch_layout* L) {
-    return ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, L);
+    return layout_out(L, [&](gcnn_ibatch_layout* l) { return ibatch_layout(n_states, dims, n_forced, n_forced_entries, mode, l); });
 }
 
 extern "C" int gcnn_infer_batch_fill_table(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
                                            const int32_t* n_forced_entries, int32_t* table) {
     if (!table) return GCNN_E_BADARG;
-    // (forced rows are counted whenever they are given: a table filled for SELECT serves the other modes too)
-    return ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, table);
+    // (forced rows are counted whenever they are given: a table filled for SELECT serves the other modes too; checked in full before
+    // the first word is written: a refused call leaves the table as it was)
+    const int rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, nullptr);
+    return rc ? rc : ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, table);
 }
 
 // Where a union lies in device memory: the table, the zero block, the seven stacked arrays, the forced rows and the output block.

@@ -66,7 +66,7 @@ static int lpa_layout(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, int32
 }
 extern "C" int gcnn_lp_append_layout_for(const gcnn_lp_dims* d, const gcnn_lp_append_dims* b, int32_t present, int32_t n_forced,
                                          int32_t n_forced_entries, gcnn_lp_append_layout* L) {
-    return lpa_layout(d, b, present, n_forced, n_forced_entries, L);
+    return layout_out(L, [&](gcnn_lp_append_layout* l) { return lpa_layout(d, b, present, n_forced, n_forced_entries, l); });
 }
 
 static bool lpa_set_ok(const gcnn_lp_rows_set* s, int R, int C, int E) {

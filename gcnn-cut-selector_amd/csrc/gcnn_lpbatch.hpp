@@ -66,7 +66,7 @@ static int lpbatch_layout(int n, const gcnn_lp_dims* dims, const int32_t* n_forc
 
 extern "C" int gcnn_lp_batch_layout_for(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
                                         int32_t mode, gcnn_lp_batch_layout* L) {
-    return lpbatch_layout(n, dims, n_forced, n_forced_entries, mode, L, nullptr);
+    return layout_out(L, [&](gcnn_lp_batch_layout* l) { return lpbatch_layout(n, dims, n_forced, n_forced_entries, mode, l, nullptr); });
 }
 
 static void lpset_blocks(const gcnn_lp_dims& d, int* stats, int* emit) {

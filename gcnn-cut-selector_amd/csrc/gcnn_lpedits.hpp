@@ -88,12 +88,12 @@ static int lpes_layout(int n, const Member* mem, int mode, int stages, Layout* L
 
 extern "C" int gcnn_lp_rounds_layout_for(int32_t n, const gcnn_lp_rounds_member* members, int32_t mode, gcnn_lp_rounds_layout* layout) {
     LpEdit E[GCNN_LP_ROUNDS_MAX]; LpePlan P[GCNN_LP_ROUNDS_MAX];
-    return lpes_layout(n, members, mode, LPRS_STAGES, layout, E, P);
+    return layout_out(layout, [&](gcnn_lp_rounds_layout* l) { return lpes_layout(n, members, mode, LPRS_STAGES, l, E, P); });
 }
 extern "C" int gcnn_lp_rounds_edit_layout_for(int32_t n, const gcnn_lp_rounds_edit_member* members, int32_t mode,
                                               gcnn_lp_rounds_edit_layout* layout) {
     LpEdit E[GCNN_LP_ROUNDS_MAX]; LpePlan P[GCNN_LP_ROUNDS_MAX];
-    return lpes_layout(n, members, mode, LPES_STAGES, layout, E, P);
+    return layout_out(layout, [&](gcnn_lp_rounds_edit_layout* l) { return lpes_layout(n, members, mode, LPES_STAGES, l, E, P); });
 }
 
 // group_check's rule on resident LPs: what a member's launches write must not overlap anything another member's launches touch.

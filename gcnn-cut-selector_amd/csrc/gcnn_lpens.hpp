@@ -55,7 +55,7 @@ static int lpens_layout(const gcnn_lp_rounds_edit_member* m, int mode, int n_mod
 extern "C" int gcnn_lp_round_ensemble_layout_for(const gcnn_lp_rounds_edit_member* round, int32_t mode, int32_t n_models,
                                                  gcnn_lp_round_ensemble_layout* layout) {
     LpEdit e; LpePlan P;
-    return lpens_layout(round, mode, n_models, &e, &P, layout);
+    return layout_out(layout, [&](gcnn_lp_round_ensemble_layout* l) { return lpens_layout(round, mode, n_models, &e, &P, l); });
 }
 
 // The host half behind the checks: the members over the state this round will build (the places lpr_run gives the round's feature

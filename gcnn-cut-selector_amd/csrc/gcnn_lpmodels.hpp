@@ -25,7 +25,7 @@ static int lpm_layout(int n, const gcnn_lp_dims* dims, const int32_t* n_forced, 
 
 extern "C" int gcnn_lp_models_layout_for(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,
                                          int32_t mode, int32_t n_models, const int32_t* model_of_snapshot, gcnn_lp_models_layout* L) {
-    return lpm_layout(n, dims, n_forced, n_forced_entries, mode, n_models, model_of_snapshot, L, nullptr);
+    return layout_out(L, [&](gcnn_lp_models_layout* l) { return lpm_layout(n, dims, n_forced, n_forced_entries, mode, n_models, model_of_snapshot, l, nullptr); });
 }
 
 extern "C" int gcnn_lp_models_fill_table(int32_t n, const gcnn_lp_dims* dims, const int32_t* n_forced, const int32_t* n_forced_entries,

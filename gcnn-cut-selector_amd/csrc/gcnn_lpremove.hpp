@@ -77,7 +77,7 @@ static int lpd_layout(const gcnn_lp_dims* d, const gcnn_lp_remove_dims* m, const
 }
 extern "C" int gcnn_lp_remove_layout_for(const gcnn_lp_dims* d, const gcnn_lp_remove_dims* m, const gcnn_lp_append_dims* b, int32_t present,
                                          int32_t n_forced, int32_t n_forced_entries, gcnn_lp_remove_layout* L) {
-    return lpd_layout(d, m, b, present, n_forced, n_forced_entries, L);
+    return layout_out(L, [&](gcnn_lp_remove_layout* l) { return lpd_layout(d, m, b, present, n_forced, n_forced_entries, l); });
 }
 
 // Byte spans of device memory -- of a set of derived arrays or of the raw rows for given sizes, or single buffers -- and whether any

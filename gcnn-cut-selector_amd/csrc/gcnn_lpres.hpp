@@ -18,7 +18,9 @@ static int lpr_rows_layout(const gcnn_lp_dims* d, gcnn_lp_rows_layout* L) {
     L->bytes = c.off;
     return 0;
 }
-extern "C" int gcnn_lp_rows_layout_for(const gcnn_lp_dims* d, gcnn_lp_rows_layout* L) { return lpr_rows_layout(d, L); }
+extern "C" int gcnn_lp_rows_layout_for(const gcnn_lp_dims* d, gcnn_lp_rows_layout* L) {
+    return layout_out(L, [&](gcnn_lp_rows_layout* l) { return lpr_rows_layout(d, l); });
+}
 
 extern "C" int gcnn_lp_rows_build(const gcnn_lp_dims* d, const int32_t* row_ptr, const int32_t* row_col, const double* row_val,
                                   const double* row_lhs, const double* row_rhs, const double* col_obj, void* derived,
@@ -92,7 +94,7 @@ static int lpr_round_layout(const gcnn_lp_dims* d, int32_t present, int32_t n_fo
 }
 extern "C" int gcnn_lp_round_layout_for(const gcnn_lp_dims* d, int32_t present, int32_t n_forced, int32_t n_forced_entries,
                                         gcnn_lp_round_layout* L) {
-    return lpr_round_layout(d, present, n_forced, n_forced_entries, L);
+    return layout_out(L, [&](gcnn_lp_round_layout* l) { return lpr_round_layout(d, present, n_forced, n_forced_entries, l); });
 }
 
 // want_order: 1 ranking, 0 scores only, -1 the state only (no forward pass; the download carries the flags and cut_index)

@@ -12,7 +12,7 @@ static bool lp_dims_ok(const gcnn_lp_dims* d) {
     if (!(d->infinity > 0.0) || !(d->sum_epsilon > 0.0) || !(d->obj_norm > 0.0) || d->obj_norm - d->obj_norm != 0.0) return false;
     return true;
 }
-static inline int lp_chunks(int n) { return (n + LP_NT - 1) / LP_NT; }
+static inline int lp_chunks(int n) { return (int)(((long long)n + LP_NT - 1) / LP_NT); }   // any n >= 0 a layout query may hold
 static gcnn_dims lp_state_dims(const gcnn_lp_dims* d) {
     return gcnn_dims{d->n_state_rows, d->n_cols, d->n_cuts, d->n_state_edges, d->cut_nnz};
 }
@@ -64,7 +64,7 @@ static int lp_layout(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_e
 }
 
 extern "C" int gcnn_lp_layout_for(const gcnn_lp_dims* d, int32_t n_forced, int32_t n_forced_entries, gcnn_lp_layout* L) {
-    return lp_layout(d, n_forced, n_forced_entries, L);
+    return layout_out(L, [&](gcnn_lp_layout* l) { return lp_layout(d, n_forced, n_forced_entries, l); });
 }
 
 // snap: the packed snapshot in device memory (offsets snap_off); the seven state arrays, cut_index and flags as given

@@ -70,17 +70,19 @@ static int mbatch_layout(int n_states, const gcnn_dims* dims, const int32_t* n_f
 extern "C" int gcnn_infer_models_layout_for(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
                                             const int32_t* n_forced_entries, int32_t mode, int32_t n_models,
                                             const int32_t* model_of_state, gcnn_mbatch_layout* layout) {
-    return mbatch_layout(n_states, dims, n_forced, n_forced_entries, mode, n_models, model_of_state, layout);
+    return layout_out(layout, [&](gcnn_mbatch_layout* l) { return mbatch_layout(n_states, dims, n_forced, n_forced_entries, mode, n_models, model_of_state, l); });
 }
 
 extern "C" int gcnn_infer_models_fill_table(int32_t n_states, const gcnn_dims* dims, const int32_t* n_forced,
                                             const int32_t* n_forced_entries, int32_t n_models, const int32_t* model_of_state,
                                             int32_t* table) {
     if (!table) return GCNN_E_BADARG;
-    int rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, table);
+    // (checked in full before the first word is written: a refused call leaves the table as it was)
+    int rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, nullptr);
     if (rc) return rc;
     MbModels mm;
     if ((rc = mbatch_models(n_states, dims, n_models, model_of_state, &mm))) return rc;
+    if ((rc = ibatch_sums(n_states, dims, n_forced, n_forced_entries, GCNN_IBATCH_SELECT, nullptr, table))) return rc;
     int32_t* mod = table + IB_COLS * IB_TS;
     memset(mod, 0, sizeof(int32_t) * (MB_HEAD + IB_MAX_STATES));
     mod[0] = n_models;

@@ -7,7 +7,7 @@
 #include "k_select.hpp"
 
 static size_t select_ws_bytes(int total_cuts, int total_forced, int max_cuts) {
-    const size_t words = (size_t)(std::max(max_cuts, 0) + 63) / 64;
+    const size_t words = ((size_t)std::max(max_cuts, 0) + 63) / 64;
     return std::max<size_t>(((size_t)std::max(total_cuts, 0) + (size_t)std::max(total_forced, 0)) * words * 16, 16);
 }
 
@@ -82,7 +82,7 @@ static int select_layout(const gcnn_dims* d, int32_t n_forced, int32_t n_forced_
 
 extern "C" int gcnn_infer_select_layout_for(const gcnn_dims* d, int32_t n_forced, int32_t n_forced_entries,
                                             gcnn_select_layout* L) {
-    return select_layout(d, n_forced, n_forced_entries, L);
+    return layout_out(L, [&](gcnn_select_layout* l) { return select_layout(d, n_forced, n_forced_entries, l); });
 }
 
 // What every call that uploads from pinned memory into a caller-owned arena refuses: a missing pointer, an arena shorter than the

@@ -396,6 +396,8 @@ class GCNN:
     # ---- workspaces --------------------------------------------------------------------------------------------
     def _take_workspace(self, batch):
         need = _lib.lib().gcnn_workspace_floats(C.byref(batch.dims))
+        if need == 0:   # the size function's refusal (a negative count): no workspace is sized from it
+            raise _lib.GcnnError(f"gcnn_workspace_floats refused the batch's sizes {tuple(getattr(batch.dims, f) for f, _ in _lib.Dims._fields_)}")
         best = None
         for i, ws in enumerate(self._ws_pool):
             if ws.numel() >= need and (best is None or ws.numel() < self._ws_pool[best].numel()):

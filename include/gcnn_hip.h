@@ -6,7 +6,8 @@
  * arithmetic it replaces.  All pointers are DEVICE pointers unless marked "host"; all matrices are row-major fp32,
  * indices int32; `stream` is a hipStream_t passed as void*.  Every function returns 0 on success, a negative
  * GCNN_E_* code on bad arguments and a positive hipError_t on a HIP failure; no function allocates device memory
- * (workspaces are passed in), synchronises the device or throws.
+ * (workspaces are passed in), synchronises the device or throws.  A *_layout_for or *_fill_table that returns a GCNN_E_* code has
+ * written nothing: the caller's struct or table is as it was.
  */
 #ifndef GCNN_HIP_H
 #define GCNN_HIP_H
@@ -152,7 +153,9 @@ int gcnn_conv_edge_bwd_send(const int32_t* seg_ptr, const int32_t* oth, const fl
  * have nothing between them but the PreNorm scale (model.py:503), so the pass multiplies by their product
  * M = s2*Wf*W1a (made once per call); save_for_backward = 2 runs the two-layer form instead and also stores the tensor between
  * them (the scatter-sum output A = post_conv_module's input) -- what gcnn_prenorm_stats reads for layers 6, 8 and 10.
- * scores: [n_cuts] (model.py:300). */
+ * scores: [n_cuts] (model.py:300).
+ * gcnn_workspace_floats returns 0 for a null dims or a negative count (every valid size is > 0); any count >= 0 is sized exactly,
+ * in size_t (the calls themselves refuse more than 2^24 rows of a kind). */
 size_t gcnn_workspace_floats(const gcnn_dims* dims);
 int gcnn_forward(const gcnn_dims* dims, const float* params, const float* cons_feats, const float* var_feats,
                  const float* cut_feats, const gcnn_graph* cons_graph, const gcnn_graph* cut_graph,
@@ -195,7 +198,8 @@ int gcnn_infer(const gcnn_dims* dims, const float* params, const void* host_in, 
  * (utils.py:102-104), other producers may not -- is brought into row order while it is packed into the staging buffer: a stable
  * counting sort (entries of a row keep their input order), O(E + n_left), a few tens of microseconds for a few 10^4 entries.
  * rows / cols / vals: the list (host); out_inds [2,E] and out_vals [E] (host, e.g. inside host_in); scratch: n_left + 1 ints (host).
- * Returns 0, or GCNN_E_BADARG when a row id lies outside [0, n_left) (nothing is written then: the device check reports it). */
+ * Returns 0, or GCNN_E_BADARG when a row id lies outside [0, n_left) (nothing is written then: the device check reports it).
+ * n_edges = 0 returns 0 and touches no pointer: all of them may be null then. */
 int gcnn_host_sort_edges_by_row(const int32_t* rows, const int32_t* cols, const float* vals, int32_t n_edges, int32_t n_left,
                                 int32_t* out_inds, float* out_vals, int32_t* scratch);
 /* The packing step itself, same arguments: copies the list into the staging buffer and checks its order on the way (one pass, no

@@ -87,6 +87,39 @@ def device_build() -> DeviceBuild:
     return _result
 
 
+HOSTSAN = os.path.join(ROOT, "tests", "hostsan")
+HOSTSAN_FLAGS = ("-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-Xarch_host", "-fsanitize=address,undefined,implicit-conversion", "-Xarch_host",
+                 "-fno-omit-frame-pointer", "-Xarch_host", f"-fsanitize-ignorelist={os.path.join(HOSTSAN, 'ubsan_ignorelist.txt')}")
+
+
+def _run_hostsan_hipcc(out: str) -> subprocess.CompletedProcess:
+    # host code alone is instrumented (-Xarch_host); the device code is compiled as always and never runs
+    return subprocess.run([HIPCC, *HOSTSAN_FLAGS, f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}", "-o", out,
+                           os.path.join(HOSTSAN, "hostsan_main.hip")], capture_output=True, text=True, timeout=600)
+
+
+_hostsan = None   # the program's path, or the text every caller of a failed compile fails with
+
+
+def host_sanitizer_build() -> str:
+    """The path of tests/hostsan's stand-alone program: gcnn_capi.hip's host code under ASan and UBSan, compiled once per Python
+    process as device_build() compiles the device code -- skipped only without hipcc, a failed compile fails every caller."""
+    global _hostsan
+    if not os.path.exists(HIPCC):
+        pytest.skip(f"the cross-compiler {HIPCC} is not installed: the sanitized host program cannot be built here")
+    if _hostsan is None:
+        tmp = tempfile.mkdtemp(prefix="gcnn_hostsan_build_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        out = os.path.join(tmp, "hostsan")
+        try:
+            p = _run_hostsan_hipcc(out)
+            _hostsan = out if p.returncode == 0 and os.path.exists(out) else "hostsan compile failed:\n" + p.stderr[-2000:]
+        except subprocess.TimeoutExpired as e:
+            _hostsan = f"hostsan compile failed: {e}"
+    assert not _hostsan.startswith("hostsan compile failed"), _hostsan
+    return _hostsan
+
+
 def declared_everywhere(symbols) -> str:
     """Every symbol is declared in the header, has a signature in the binding and is exported by the built library, and both
     sides are at ABI 13.  Returns the header's text for the caller's own checks of it."""

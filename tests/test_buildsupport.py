@@ -81,3 +81,39 @@ def test_a_failed_compile_is_remembered(monkeypatch):
         with pytest.raises(AssertionError, match="expected unqualified-id"):
             buildsupport.device_build()
     assert len(calls) == 1
+
+
+def _fake_host_compiler(monkeypatch, returncode, stderr):
+    calls = []
+
+    def run(out):
+        calls.append(out)
+        if returncode == 0:
+            open(out, "w").write("#!/bin/sh\n")
+        return subprocess.CompletedProcess([], returncode, "", stderr)
+
+    monkeypatch.setattr(buildsupport, "HIPCC", sys.executable)
+    monkeypatch.setattr(buildsupport, "_run_hostsan_hipcc", run)
+    monkeypatch.setattr(buildsupport, "_hostsan", None)          # the session's real program comes back afterwards
+    return calls
+
+
+def test_one_sanitizer_compile_serves_every_caller(monkeypatch):
+    calls = _fake_host_compiler(monkeypatch, 0, "")
+    first = buildsupport.host_sanitizer_build()
+    assert buildsupport.host_sanitizer_build() == first == calls[0] and len(calls) == 1
+
+
+def test_a_failed_sanitizer_compile_is_remembered(monkeypatch):
+    calls = _fake_host_compiler(monkeypatch, 1, "hostsan_main.hip:1:1: error: expected unqualified-id")
+    for _ in range(2):
+        with pytest.raises(AssertionError, match="expected unqualified-id"):
+            buildsupport.host_sanitizer_build()
+    assert len(calls) == 1
+
+
+def test_the_sanitizer_build_instruments_host_code_only():
+    flags = buildsupport.HOSTSAN_FLAGS
+    at = [i for i, f in enumerate(flags) if f.startswith("-fsanitize") or f == "-fno-omit-frame-pointer"]
+    assert len(at) == 3 and all(flags[i - 1] == "-Xarch_host" for i in at)
+    assert [f for f in flags if f.startswith("--offload-arch")] == ["--offload-arch=gfx950"]     # the plain target, no feature suffix
